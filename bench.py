@@ -22,6 +22,7 @@ rate is the mean rate of the whole solve (config.solve.iterations_per_sec_whole_
 [W, W + K) at small depths - `--window-at-warmup` restores that, config.value_is says which one a line carries).
 
   python bench.py --gpus 1 --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank per GPU)
+  --dump-outputs DIR: after the timed window, psi and the residual history of the window run as DIR/*.npy (float64, <= 32 MB).
 
 Prints ONE JSON line (rank 0) with `roofline` (dRdW^T.psi SpMV, HIP-event timed on the launch stream), `roofline_pc`,
 `roofline_iteration` and `cpu_baseline`: the oracle's OpenMP C port (oracle/csrc/oracle_krylov_omp.c; threads = the container's CPU
@@ -45,6 +46,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 NORM = {"U": 10.0, "p": 50.0, "nuTilda": 1e-3, "phi": 1.0}  # reference tests/runRegTests_AeroOpt.py:83
 NORM_RHO = {"U": 50.0, "p": 1.0e5, "T": 300.0, "nuTilda": 1e-3, "phi": 1.0}  # compressible solvers (the tier's NORM_STATES_RHO)
+DUMP_MAX_ENTRIES = 1 << 21  # --dump-outputs: psi entries written (float64 values + float64 indices: 32 MB at most)
 
 
 def parse():
@@ -110,7 +112,13 @@ def parse():
     ap.add_argument("--dump-psi", default=None, metavar="FILE.npy", help="after the solve to tolerance: rank 0 writes psi in the GLOBAL state ordering (owned entries of every rank gathered, "
                     "face states back in the global face orientation) - psi of an N-rank run against psi of the 1-rank run")
     ap.add_argument("--amd", action="append", default=[], metavar="KEY=VALUE", help="experiments: any amd.* option, e.g. --amd gradFaceParallel=0 (listed in config.pc_options_passed_by_bench)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed window: rank 0 writes what the timed solve returned to DIR/<name>.npy - psi "
+                    "(in the global state ordering for N > 1; a fixed seeded sample of at most %d entries, with its indices, when larger) and the residual history "
+                    "of the window run; the same arguments give the same inputs, so two builds can be compared output for output" % DUMP_MAX_ENTRIES)
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def pmc_traffic(op_nnz, kernel):
@@ -471,6 +479,23 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    def global_solution():
+        """sol on rank 0 (None elsewhere; collective): N > 1 wing - the owned entries of every rank in the GLOBAL state ordering, face states back
+        in the global face orientation; otherwise rank 0's own vector."""
+        x_h = sol.cpu().numpy()
+        if sharded is not None and hasattr(sharded, "info"):
+            own_m = sharded.owned
+            mine = (sharded.key[own_m], x_h[own_m] * sharded.info["state_sign"][own_m])
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(mine, parts, dst=0)
+            if rank == 0:
+                psi_g = np.full(sum(p_[0].size for p_ in parts), np.nan)
+                for kk, vv in parts:
+                    psi_g[kk] = vv
+                return psi_g
+            return None
+        return x_h if rank == 0 else None
+
     # ---- solve to tolerance: the reference's defaults gmresRestart = gmresMaxIters = 1000 (pyDAFoam.py:526-548) --------------------
     # (N > 1: the same calls on every rank - ONE global solve, collective inside the library)
     solve = None
@@ -515,19 +540,9 @@ def main():
                  "iterations_per_sec_whole_solve": its / t_solve}
         stage(f"solve: {its} iterations, {t_solve:.1f} s, fail {fail}")
         if a.dump_psi:
-            x_h = sol.cpu().numpy()
-            if sharded is not None and hasattr(sharded, "info"):
-                own_m = sharded.owned
-                mine = (sharded.key[own_m], x_h[own_m] * sharded.info["state_sign"][own_m])
-                parts = [None] * world if rank == 0 else None
-                dist.gather_object(mine, parts, dst=0)
-                if rank == 0:
-                    psi_g = np.full(sum(p_[0].size for p_ in parts), np.nan)
-                    for kk, vv in parts:
-                        psi_g[kk] = vv
-                    np.save(a.dump_psi, psi_g)
-            elif rank == 0:
-                np.save(a.dump_psi, x_h)
+            psi_g = global_solution()
+            if rank == 0:
+                np.save(a.dump_psi, psi_g)
 
     # ---- timed window (driver contract): W' untimed iterations, then EXACTLY K timed, inside ONE Arnoldi cycle.  W' = the mean basis
     # depth of the full solve minus K/2 (>= --warmup): the window rate is then the mean per-iteration rate of the whole solve ----------
@@ -557,6 +572,10 @@ def main():
     spmv_cnt = L.das_timer_count(h, b"spmv")
     pc_ms = L.das_timer_avg_ms(h, b"pc")
     win_info = ksp.info()
+    if a.dump_outputs:
+        psi_out = global_solution()  # collective for N > 1
+        if rank == 0:
+            dump_outputs(a.dump_outputs, psi_out, ksp.history())
     tmax = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -743,6 +762,20 @@ def main():
     if world > 1:
         dist.destroy_process_group()
     return out
+
+
+def dump_outputs(d, psi, hist):
+    """--dump-outputs: what the timed solve hands its caller - psi (whole, or a fixed seeded sample of DUMP_MAX_ENTRIES entries plus their
+    indices) and the residual history of the window run - as float64 .npy files."""
+    os.makedirs(d, exist_ok=True)
+    psi = np.asarray(psi, dtype=np.float64)
+    if psi.size > DUMP_MAX_ENTRIES:
+        idx = np.sort(np.random.default_rng(0).choice(psi.size, DUMP_MAX_ENTRIES, replace=False))
+        np.save(os.path.join(d, "psi_sample.npy"), psi[idx])
+        np.save(os.path.join(d, "psi_sample_index.npy"), idx.astype(np.float64))
+    else:
+        np.save(os.path.join(d, "psi.npy"), psi)
+    np.save(os.path.join(d, "residual_history.npy"), np.asarray(hist, dtype=np.float64))
 
 
 def _cpu_threads():
