@@ -1,0 +1,76 @@
+// Cell-set objectives (reference DAFunctionVariableVolSum.C, DAFunctionVariance.C mode "field"): F = coef * sum_t w_t g(x_t) over
+// the terms t of a fixed cell set, one term per (cell, component):
+//   x_t = src[idx_t] - d_t      src = the states (or the betaFINuTilda field), d_t = reference data (variance; 0 otherwise)
+//   g   = x^2 (isSquare / variance) or x
+//   w_t = V_cell (multiplyVol / useGeoWeight) or 1
+// coef = scale / (totalVol | sum of weights | number of terms) is set by the host from the current metrics.
+#pragma once
+#include "das_common.hpp"
+#include "das_dual.hpp"
+
+namespace das {
+
+#define DAS_CELLFN_MAX_BLOCKS 1024
+
+struct CellFnView {
+    long long nt;
+    const int* cell;        // nt: the cell of each term
+    const long long* idx;   // nt: index of the term's value in src
+    const double* data;     // nt: reference values, may be null
+    int square, mv;
+};
+
+DAS_HD inline double cellfn_x(const CellFnView& f, const double* src, long long t) { return src[f.idx[t]] - (f.data ? f.data[t] : 0.0); }
+
+// value, stage 1: per-workgroup partial sums (grid-stride loop over the terms, wave64 shuffles, 4 waves through LDS); the grid size
+// depends on nt only, so the partials - and the final sum - are the same bits on every call
+__global__ __launch_bounds__(256) void k_cellfn_value(CellFnView f, const CellGeom* __restrict__ cg, const double* __restrict__ src, double* __restrict__ part) {
+    double acc = 0.0;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < f.nt; t += (long long)gridDim.x * blockDim.x) {
+        const double x = cellfn_x(f, src, t);
+        acc += (f.mv ? cg[f.cell[t]].V : 1.0) * (f.square ? x * x : x);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    __shared__ double sh[4];
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+// value, stage 2: ONE workgroup adds the nb partials in a fixed order; out[0] = coef * sum
+__global__ __launch_bounds__(256) void k_cellfn_sum(int nb, const double* __restrict__ part, double coef, double* __restrict__ out) {
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nb; i += 256) acc += part[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    __shared__ double sh[4];
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) out[0] = coef * ((sh[0] + sh[1]) + (sh[2] + sh[3]));
+}
+// gradient: out[idx_t] = g * w_t * dg/dx * sc[idx_t]   (g = seed x coef x outer derivative; sc = state scales or null).  The terms
+// of one function address distinct entries, so the stores do not collide; the caller zeroes out first.
+__global__ __launch_bounds__(256) void k_cellfn_grad(CellFnView f, const CellGeom* __restrict__ cg, const double* __restrict__ src, const double* __restrict__ sc,
+                                                     double g, double* __restrict__ out) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= f.nt) return;
+    const long long i = f.idx[t];
+    const double dx = f.square ? 2.0 * cellfn_x(f, src, t) : 1.0;
+    out[i] = g * (f.mv ? cg[f.cell[t]].V : 1.0) * dx * (sc ? sc[i] : 1.0);
+}
+// volCoord product (dual-point pass): per-cell tangent t_c = a V_c'  (the -N/T^2 part of divByTotalVol over all cells; a = 0 clears)
+__global__ __launch_bounds__(256) void k_vc_cellfn_all(int nC, const CellGeomT<Dual<1>>* __restrict__ cg, double a, double* __restrict__ tc) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < nC) tc[c] = a * cg[c].V.d[0];
+}
+// ... plus b g(x_t) V_c' on the cells of the set (multiplyVol; one term per cell)
+__global__ __launch_bounds__(256) void k_vc_cellfn_terms(CellFnView f, const CellGeomT<Dual<1>>* __restrict__ cg, const double* __restrict__ src, double b,
+                                                         double* __restrict__ tc) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= f.nt) return;
+    const int c = f.cell[t];
+    const double x = cellfn_x(f, src, t);
+    tc[c] += b * (f.square ? x * x : x) * cg[c].V.d[0];
+}
+
+}  // namespace das

@@ -25,6 +25,7 @@
 #include "das_opmat.hpp"
 #include "das_graph.hpp"
 #include "das_volcoord.hpp"
+#include "das_cellfn.hpp"
 #include "das_simple.hpp"
 
 #include <omp.h>
@@ -1215,11 +1216,34 @@ struct das_solver {
         bool isMoment = false;
         double vecA[3] = {0, 0, 0}, vecB[3] = {0, 0, 0}, scale = 1.0;
         long long geomVersion = -1;
+        // patchMean / variance (surface): calcRefVar F <- (F - ref)^2; variance weights |Sf| (useGeoWeight) or 1, over their
+        // sum or the number of reference points; no reference data: all weights 0
+        bool refVar = false, geoWeight = false, hasData = true;
+        double ref = 0.0;
+        int ncomp = 1;
         FaceFnView view(const double* w) const {
             return FaceFnView{d_faces.p, d_group.p, w, dir.empty() ? nullptr : d_dir.p, (int)faces.size(), kind, gammaFn, RFn};
         }
     };
     std::map<std::string, FaceFn> functions;
+    struct CellFn {  // a cell-set objective (see das_cellfn.hpp)
+        bool variance = false, square = false, multiplyVol = true, divByTotalVol = false, refVar = false, geoWeight = false, hasData = true;
+        bool field = false;  // src = betaFINuTilda instead of the states
+        double scale = 1.0, ref = 0.0;
+        double coef = 0.0, totalVol = 1.0;  // from the metrics of geomVersion
+        long long geomVersion = -1;
+        std::vector<int> cell;
+        std::vector<long long> idx;
+        std::vector<double> data;
+        DevBuf<int> d_cell;
+        DevBuf<long long> d_idx;
+        DevBuf<double> d_data, d_part, d_unit;  // d_unit: betaFINuTilda = 1 while no field has been set
+        bool uploaded = false;
+        CellFnView view() const {
+            return CellFnView{(long long)cell.size(), d_cell.p, d_idx.p, data.empty() ? nullptr : d_data.p, (int)square, (int)multiplyVol};
+        }
+    };
+    std::map<std::string, CellFn> cellFunctions;
     int colorRounds = 0;        // rounds of the speculative device colouring (0: another algorithm ran)
     DevBuf<double> d_betaFI, d_dBetaFI;  // `field` input betaFINuTilda and its tangent (das_set_field / das_calc_dfield_product)
     long long geomVersion = 0;  // bumped by das_update_of_mesh
@@ -4588,6 +4612,9 @@ static void build_function_geometry(das_solver* s, das_solver::FaceFn& fn) {
             fn.w0[k] = fn.scale;
         } else if (fn.kind == DAS_FN_MASSFLOW) fn.w0[k] = fn.scale;
         else if (fn.kind == DAS_FN_TOTALPRESSURE) fn.w0[k] = fn.scale * g.magSf / area[0];  // area average, DAFunctionTotalPressure.C:77
+        else if (DAS_FN_BASE(fn.kind) == DAS_FN_PATCHMEAN) fn.w0[k] = fn.scale * g.magSf / area[0];  // DAFunctionPatchMean.C:55-80
+        else if (DAS_FN_BASE(fn.kind) == DAS_FN_VARIANCE)  // DAFunctionVariance.C: geoWeightTotal adds |Sf| once per component
+            fn.w0[k] = !fn.hasData ? 0.0 : fn.geoWeight ? fn.scale * g.magSf / (fn.ncomp * area[0]) : fn.scale / (double)(fn.ncomp * nf);
         else fn.w0[k] = g.magSf / area[fn.group[k]];                                          // TTIn / TTOut area averages
     }
     fn.geomVersion = s->geomVersion;
@@ -4636,12 +4663,187 @@ int das_define_face_function(das_solver_t* s, const char* name, const char* type
     fn.scale = scale;
     for (int d = 0; d < 3; d++) { fn.vecA[d] = vecA ? vecA[d] : 0.0; fn.vecB[d] = vecB ? vecB[d] : 0.0; }
     build_function_geometry(s, fn);
+    s->cellFunctions.erase(name);
     s->functions[name] = std::move(fn);
     return DAS_OK;
     DAS_CATCH
 }
 int das_define_force_function(das_solver_t* s, const char* name, const int* patch_ids, int npatch, const double* direction, double scale) {
     return das_define_face_function(s, name, "force", patch_ids, nullptr, npatch, direction, nullptr, scale, 0.0);
+}
+// ---- field-valued objectives (reference DAFunctionVariableVolSum.C, DAFunctionPatchMean.C, DAFunctionVariance.C) ----------
+// variable id of a cell state (0 U, 1 p, 2 nuTilda, 3 T) and whether this solver has it; "betaFINuTilda" is 4 (cell sets only)
+static int field_var_id(das_solver* s, const char* var, bool allowField) {
+    const std::string v = var ? var : "";
+    const bool flow = s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver);
+    const bool hasT = DAS_IS_COMPRESSIBLE(s->cp.solver) || s->cp.hasT || s->cp.solver == DAS_SOLVER_SCALARTRANSPORTFOAM;
+    const std::string supported = std::string(flow ? "U, p, nuTilda" : "") + (hasT ? (flow ? ", T" : "T") : "") + (allowField && flow ? ", betaFINuTilda" : "");
+    int id = -1;
+    if (v == "U" && flow) id = 0;
+    else if (v == "p" && flow) id = 1;
+    else if (v == "nuTilda" && flow) id = 2;
+    else if (v == "T" && hasT) id = 3;
+    else if (v == "betaFINuTilda" && flow && allowField) id = 4;
+    DAS_CHECK(id >= 0, DAS_ERR_ARG, "varName " + v + " is not supported by this solver; supported: " + supported);
+    return id;
+}
+static void check_comps(int vid, const int* comps, int ncomp) {
+    DAS_CHECK(comps && ncomp >= 1 && ncomp <= 3, DAS_ERR_ARG, "1 to 3 components expected");
+    int mask = 0;
+    for (int i = 0; i < ncomp; i++) {
+        DAS_CHECK(comps[i] >= 0 && comps[i] < (vid == 0 ? 3 : 1), DAS_ERR_ARG, "component index out of range for this varType");
+        DAS_CHECK(!((mask >> comps[i]) & 1), DAS_ERR_ARG, "repeated component index");
+        mask |= 1 << comps[i];
+    }
+}
+int das_define_patch_field_function(das_solver_t* s, const char* name, const char* type, const int* patch_ids, int npatch, const char* var,
+                                    const int* comps, int ncomp, const double* data, int flags, double scale, double ref) {
+    DAS_TRY
+    DAS_CHECK(s && name && type && patch_ids && npatch > 0, DAS_ERR_ARG, "bad argument");
+    DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "patchMean / variance functions run on an undecomposed solver");
+    DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver), DAS_ERR_ARG, "function needs a flow solver");
+    const std::string ty = type;
+    DAS_CHECK(ty == "patchMean" || ty == "variance", DAS_ERR_ARG, "patch field function type not valid: " + ty);
+    const int vid = field_var_id(s, var, false);
+    check_comps(vid, comps, ncomp);
+    DAS_CHECK(ty == "variance" || ncomp == 1, DAS_ERR_ARG, "patchMean takes one component");
+    das_solver::FaceFn fn;
+    int mask = 0;
+    for (int i = 0; i < ncomp; i++) mask |= 1 << comps[i];
+    fn.kind = (ty == "patchMean" ? DAS_FN_PATCHMEAN : DAS_FN_VARIANCE) | (vid << 4) | (mask << 8);
+    for (int k = 0; k < npatch; k++) {
+        const int p = patch_ids[k];
+        DAS_CHECK(p >= 0 && p < s->mesh.nPatch, DAS_ERR_ARG, "patch id out of range");
+        DAS_CHECK(s->mesh.patch_type[p] != DAS_PATCH_CYCLIC, DAS_ERR_ARG, "functions cannot be defined on cyclic patches");
+        for (int q = 0; q < s->mesh.patch_size[p]; q++) {
+            fn.faces.push_back(s->mesh.patch_start[p] + q);
+            fn.group.push_back(0);
+        }
+    }
+    DAS_CHECK(!fn.faces.empty(), DAS_ERR_ARG, "the patches of function " + std::string(name) + " have no faces");
+    fn.scale = scale;
+    fn.refVar = ty == "patchMean" && (flags & 8);
+    fn.ref = ref;
+    fn.geoWeight = (flags & 16) != 0;
+    fn.ncomp = ncomp;
+    if (ty == "variance") {  // the reference values of face k go into its direction slot: dir[3 k + component]
+        fn.hasData = data != nullptr;
+        fn.dir.assign(3 * fn.faces.size(), 0.0);
+        if (data)
+            for (size_t k = 0; k < fn.faces.size(); k++)
+                for (int i = 0; i < ncomp; i++) fn.dir[3 * k + comps[i]] = data[k * ncomp + i];
+    }
+    build_function_geometry(s, fn);
+    s->cellFunctions.erase(name);
+    s->functions[name] = std::move(fn);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_define_cell_function(das_solver_t* s, const char* name, const char* type, const int* cells, int ncells, const char* var, const int* comps,
+                             int ncomp, const double* data, int flags, double scale, double ref) {
+    DAS_TRY
+    DAS_CHECK(s && name && type && (cells || ncells == 0) && ncells >= 0, DAS_ERR_ARG, "bad argument");
+    DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "variableVolSum / variance functions run on an undecomposed solver");
+    const std::string ty = type;
+    DAS_CHECK(ty == "variableVolSum" || ty == "variance", DAS_ERR_ARG, "cell function type not valid: " + ty);
+    const int vid = field_var_id(s, var, ty == "variableVolSum");
+    check_comps(vid, comps, ncomp);
+    DAS_CHECK(ty == "variance" || ncomp == 1, DAS_ERR_ARG, "variableVolSum takes one component");
+    das_solver::CellFn fn;
+    fn.variance = ty == "variance";
+    fn.field = vid == 4;
+    fn.square = fn.variance || (flags & 1);
+    fn.multiplyVol = fn.variance ? (flags & 16) != 0 : (flags & 2) != 0;
+    fn.divByTotalVol = !fn.variance && (flags & 4);
+    fn.refVar = !fn.variance && (flags & 8);
+    fn.geoWeight = fn.variance && (flags & 16);
+    fn.hasData = !fn.variance || data != nullptr;
+    fn.scale = scale;
+    fn.ref = ref;
+    const ResParams prm = make_params(s->cp, s->opt, 0);
+    const long long N = s->mesh.nC;
+    const long long off = vid == 1 ? prm.offP * N : vid == 2 ? prm.offN * N : vid == 3 ? prm.offT * N : 0;
+    for (int k = 0; k < ncells; k++) {
+        const int c = cells[k];
+        DAS_CHECK(c >= 0 && c < s->mesh.nC, DAS_ERR_ARG, "cell index out of range");
+        for (int i = 0; i < ncomp; i++) {
+            fn.cell.push_back(c);
+            fn.idx.push_back(vid == 0 ? 3LL * c + comps[i] : off + c);
+        }
+    }
+    {  // one term per state: the gradient scatter stores without collisions
+        std::vector<unsigned char> seen(N, 0);
+        for (int k = 0; k < ncells; k++) { DAS_CHECK(!seen[cells[k]], DAS_ERR_ARG, "repeated cell in the cell set"); seen[cells[k]] = 1; }
+    }
+    if (fn.variance && data) fn.data.assign(data, data + fn.cell.size());
+    s->functions.erase(name);
+    s->cellFunctions[name] = std::move(fn);
+    return DAS_OK;
+    DAS_CATCH
+}
+static das_solver::CellFn* find_cell_function(das_solver* s, const char* name) {
+    auto it = s->cellFunctions.find(name ? name : "");
+    if (it == s->cellFunctions.end()) return nullptr;
+    das_solver::CellFn& fn = it->second;
+    if (fn.geomVersion != s->geomVersion) {  // the cell set is fixed; its weights follow the metrics
+        const Mesh& m = s->mesh;
+        double norm = 1.0;
+        if (fn.variance) {
+            norm = (double)fn.cell.size();
+            if (fn.geoWeight) { norm = 0.0; for (int c : fn.cell) norm += m.cg[c].V; }
+        } else if (fn.divByTotalVol) {
+            for (int c = 0; c < m.nC; c++) norm += m.cg[c].V;  // totalVol starts at 1 (DAFunctionVariableVolSum.C:60-70)
+        }
+        fn.totalVol = norm;
+        fn.coef = (!fn.hasData || fn.cell.empty()) ? 0.0 : fn.scale / norm;
+        fn.geomVersion = s->geomVersion;
+    }
+    if (!fn.uploaded && s->inited) {
+        fn.d_cell.upload(fn.cell);
+        fn.d_idx.upload(fn.idx);
+        if (!fn.data.empty()) fn.d_data.upload(fn.data);
+        fn.d_part.alloc(DAS_CELLFN_MAX_BLOCKS);
+        fn.uploaded = true;
+    }
+    return &fn;
+}
+// the values the terms read: the states or the betaFINuTilda field (1 everywhere until das_set_field; the solver's field state
+// is left as it is)
+static const double* cell_function_src(das_solver* s, das_solver::CellFn& fn) {
+    if (!fn.field) return s->d_W.p;
+    if (!s->cp.beta_fi.empty()) return s->d_betaFI.p;
+    if (fn.d_unit.n != (size_t)s->mesh.nC) fn.d_unit.upload(std::vector<double>(s->mesh.nC, 1.0));
+    return fn.d_unit.p;
+}
+static int cell_function_blocks(const das_solver::CellFn& fn) {
+    return std::max(1, std::min(DAS_CELLFN_MAX_BLOCKS, nblk((long long)fn.cell.size(), 256)));
+}
+// F0 = coef sum_t w_t g(x_t) (before calcRefVar)
+static double cell_function_base_value(das_solver* s, das_solver::CellFn& fn) {
+    if (fn.coef == 0.0) return 0.0;
+    const int nb = cell_function_blocks(fn);
+    hipLaunchKernelGGL(k_cellfn_value, dim3(nb), dim3(256), 0, s->stream, fn.view(), (const CellGeom*)s->d_cg.p, cell_function_src(s, fn), fn.d_part.p);
+    hipLaunchKernelGGL(k_cellfn_sum, dim3(1), dim3(256), 0, s->stream, nb, (const double*)fn.d_part.p, fn.coef, s->d_tmp1.p);
+    DAS_HIP(hipGetLastError());
+    double v = 0.0;
+    DAS_HIP(hipMemcpyAsync(&v, s->d_tmp1.p, sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    return v;
+}
+// dF/dF0: 2 (F0 - ref) under calcRefVar (DAFunction::calcRefVar), else 1
+static double cell_function_outer(das_solver* s, das_solver::CellFn& fn) {
+    return fn.refVar ? 2.0 * (cell_function_base_value(s, fn) - fn.ref) : 1.0;
+}
+// out[0..len) = 0, then seed dF/dsrc_i (x s_i for the states) on the entries of the terms
+static void cell_function_gradient(das_solver* s, das_solver::CellFn& fn, double seed, bool stateScaled, double* out, long long len) {
+    const double g = seed * cell_function_outer(s, fn) * fn.coef;
+    DAS_HIP(hipMemsetAsync(s->d_tmp2.p, 0, len * sizeof(double), s->stream));
+    if (g != 0.0 && !fn.cell.empty())
+        hipLaunchKernelGGL(k_cellfn_grad, dim3(nblk((long long)fn.cell.size(), 256)), dim3(256), 0, s->stream, fn.view(), (const CellGeom*)s->d_cg.p,
+                           cell_function_src(s, fn), stateScaled ? (const double*)s->d_scale.p : (const double*)nullptr, g, s->d_tmp2.p);
+    DAS_HIP(hipGetLastError());
+    DAS_HIP(hipMemcpyAsync(out, s->d_tmp2.p, len * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
 }
 static das_solver::FaceFn& get_function(das_solver* s, const char* name) {
     auto it = s->functions.find(name ? name : "");
@@ -4678,6 +4880,15 @@ static void function_sums(das_solver* s, das_solver::FaceFn& fn, double S[2]) {
 }
 // effective per-face weights of the derivative passes: the base weights, times the quotient rule for ratio functions
 static void function_effective_weights(das_solver* s, das_solver::FaceFn& fn) {
+    if (fn.refVar) {  // F = (S - ref)^2: dF = 2 (S - ref) dS
+        double S[2];
+        function_sums(s, fn, S);
+        const double a = 2.0 * (S[0] + S[1] - fn.ref);
+        std::vector<double> w(fn.w0.size());
+        for (size_t k = 0; k < w.size(); k++) w[k] = fn.w0[k] * a;
+        fn.d_weff.upload(w);
+        return;
+    }
     if (!fn.ratio) {
         DAS_HIP(hipMemcpyAsync(fn.d_weff.p, fn.d_w0.p, fn.w0.size() * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
         return;
@@ -4693,16 +4904,27 @@ int das_calc_function(das_solver_t* s, const char* name, double* value) {
     DAS_TRY
     need_init(s);
     DAS_CHECK(value, DAS_ERR_ARG, "null output");
+    if (das_solver::CellFn* cf = find_cell_function(s, name)) {
+        const double F0 = cell_function_base_value(s, *cf);
+        *value = cf->refVar ? (F0 - cf->ref) * (F0 - cf->ref) : F0;
+        return DAS_OK;
+    }
     das_solver::FaceFn& fn = get_function(s, name);
     double S[2];
     function_sums(s, fn, S);
     *value = fn.ratio ? S[1] / S[0] : S[0] + S[1];
+    if (fn.refVar) *value = (*value - fn.ref) * (*value - fn.ref);
     return DAS_OK;
     DAS_CATCH
 }
 // product_j = seed * s_j dF/dW_j : coloured forward-mode gradient of the objective (one k_grad + one k_force per colour)
 static void function_gradient(das_solver* s, const char* name, double seed, double* product) {
     need_init(s);
+    if (das_solver::CellFn* cf = find_cell_function(s, name)) {  // local and analytic: one elementwise pass, no colouring
+        if (cf->field) std::fill(product, product + s->n, 0.0);
+        else cell_function_gradient(s, *cf, seed, true, product, s->n);
+        return;
+    }
     das_solver::FaceFn& fn = get_function(s, name);
     ensure_con_dev(s, 0);
     function_effective_weights(s, fn);
@@ -4835,6 +5057,9 @@ int das_calc_dbc_product(das_solver_t* s, const int* patches, int np, const char
         hipLaunchKernelGGL(k_tangent_dot, dim3(1024), dim3(256), 0, st, n, s->d_Rd.p, s->d_tmp2.p, part.p);
         hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, st, 1024LL, (const unsigned char*)nullptr, (const double*)part.p, s->d_tmp1.p);
         DAS_HIP(hipStreamSynchronize(st));  // part goes out of scope
+    } else if (find_cell_function(s, outputName)) {  // cell-set functions read no boundary value
+        product[0] = 0.0;
+        return DAS_OK;
     } else {
         das_solver::FaceFn& fn = get_function(s, outputName);
         function_effective_weights(s, fn);
@@ -4901,6 +5126,12 @@ int das_calc_dfield_product(das_solver_t* s, const char* fieldName, const char* 
     const std::string ot = outputType;
     DAS_CHECK(ot == "residual" || ot == "function", DAS_ERR_ARG, "outputType not supported on this path: " + ot);
     const long long N = s->mesh.nC, n = s->n;
+    if (ot == "function" && find_cell_function(s, outputName)) {
+        das_solver::CellFn& cf = *find_cell_function(s, outputName);
+        if (cf.field) cell_function_gradient(s, cf, seeds[0], false, product, N);  // dF/dbeta_c, unscaled like the field itself
+        else std::fill(product, product + N, 0.0);
+        return DAS_OK;
+    }
     if (ot == "function") {  // the patch-integral functions do not see the production term
         (void)get_function(s, outputName);
         std::fill(product, product + N, 0.0);
@@ -5032,7 +5263,7 @@ int das_point_influence_get(das_solver_t* s, int* colors, long long* ptr, int* c
 }
 // exact mode of the product (amd.volCoordMode "dual", the default): Dual<1> points -> Dual<1> metrics -> Dual<1> residual
 static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool areaAvg, const double* cN, const double* cA, const double* seeds,
-                                  double* product, double* info4) {
+                                  double* product, double* info4, das_solver::CellFn* cfn = nullptr) {
     typedef Dual<1> D;
     const Mesh& m = s->mesh;
     das_solver::VolCoord& v = s->vc;
@@ -5042,8 +5273,17 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
     const int B = 256;
     const long long n = s->n;
     const size_t n3 = 3 * (size_t)m.nP;
-    const bool isFn = fn != nullptr;
+    const bool isFn = fn != nullptr, isCell = cfn != nullptr;
     const bool rho = DAS_IS_COMPRESSIBLE(s->cp.solver);
+    // cell-set functions (variableVolSum): F0 = N / T with N = coef T sum_S w g, T = totalVol, so dF/dV_c = dF/dF0 ( [c in S, multiplyVol]
+    // scale g_c / T - [divByTotalVol] F0 / T ): cellA multiplies V_c' on every cell, cellB g_c V_c' on the cells of the set
+    double cellA = 0.0, cellB = 0.0;
+    if (isCell) {
+        const double F0 = cell_function_base_value(s, *cfn);
+        const double outer = seeds[0] * (cfn->refVar ? 2.0 * (F0 - cfn->ref) : 1.0);
+        cellA = cfn->divByTotalVol ? -outer * F0 / cfn->totalVol : 0.0;
+        cellB = cfn->multiplyVol ? outer * cfn->coef : 0.0;
+    }
     DevBuf<double> d_X0, d_out(n3), d_tc((size_t)m.nC), d_seeds, d_fvd;
     DevBuf<D> d_XD(n3), d_Wd((size_t)n), d_Rd;
     DevBuf<FaceGeomT<D>> d_fgD((size_t)m.nF);
@@ -5063,7 +5303,8 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
     ResParams prm0 = make_params(s->cp, s->opt, 0);
     RowLayout L{};
     int nf = 0;
-    if (!isFn) {
+    if (isCell) {
+    } else if (!isFn) {
         const Stencil stn = make_stencil(s->cp.solver, m.nC, m.nF, s->opt, false, s->cp.hasT != 0);
         DAS_CHECK(stn.states.size() <= 8, DAS_ERR_INTERNAL, "more than 8 state blocks");
         L.nb = (int)stn.states.size();
@@ -5092,7 +5333,12 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
             hipLaunchKernelGGL(k_geom_face<D>, dim3(nblk(t.nF, B)), dim3(B), 0, st, t, (const D*)d_XD.p, d_fgD.p);
             hipLaunchKernelGGL(k_geom_cell<D>, dim3(nblk(t.nC, B)), dim3(B), 0, st, t, (const FaceGeomT<D>*)d_fgD.p, d_cgD.p, v.d_bad.p);
             hipLaunchKernelGGL(k_geom_weights<D>, dim3(nblk(t.nF, B)), dim3(B), 0, st, t, (const CellGeomT<D>*)d_cgD.p, d_fgD.p);
-            if (!isFn) {
+            if (isCell) {
+                hipLaunchKernelGGL(k_vc_cellfn_all, dim3(nblk(m.nC, B)), dim3(B), 0, st, m.nC, (const CellGeomT<D>*)d_cgD.p, cellA, d_tc.p);
+                if (cellB != 0.0 && !cfn->cell.empty())
+                    hipLaunchKernelGGL(k_vc_cellfn_terms, dim3(nblk((long long)cfn->cell.size(), B)), dim3(B), 0, st, cfn->view(), (const CellGeomT<D>*)d_cgD.p,
+                                       cell_function_src(s, *cfn), cellB, d_tc.p);
+            } else if (!isFn) {
                 eval_residual<D, D>(dmD, s->cp, prm0, d_Wd.p, d_Rd.p, s->wk1, s->d_phiF.p, s->d_Told.p, st);
                 hipLaunchKernelGGL(k_vc_rows_dual, dim3(nblk(m.nC, B)), dim3(B), 0, st, s->dm, L, (const double*)d_seeds.p, (const D*)d_Rd.p, d_tc.p);
             } else {
@@ -5139,18 +5385,28 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
     DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "the volCoord product runs on an undecomposed mesh (sharded solvers: use calcVolCoordDirectionalProduct)");
     const Mesh& m = s->mesh;
     const bool isFn = ot == "function";
+    if (isFn) {
+        if (das_solver::CellFn* cf = find_cell_function(s, outputName)) {
+            DAS_CHECK(!cf->variance, DAS_ERR_ARG, std::string("volCoord input is not supported for the variance function ") + outputName);
+            ensure_point_influence(s);
+            volcoord_product_dual(s, nullptr, false, nullptr, nullptr, seeds, product, info4, cf);
+            return DAS_OK;
+        }
+    }
     das_solver::FaceFn* fn = nullptr;
     if (isFn) fn = &get_function(s, outputName);
+    DAS_CHECK(!fn || DAS_FN_BASE(fn->kind) != DAS_FN_VARIANCE, DAS_ERR_ARG, std::string("volCoord input is not supported for the variance function ") + outputName);
     // area-averaged functions: coefficients of the linearised functional (k_fn_area_avg) from the group sums at the base mesh
     double cN[2] = {0.0, 0.0}, cA[2] = {0.0, 0.0};
-    const bool areaAvg = isFn && (fn->kind == DAS_FN_TOTALPRESSURE || fn->kind == DAS_FN_TOTALTEMPERATURE);
+    const bool areaAvg = isFn && (fn->kind == DAS_FN_TOTALPRESSURE || fn->kind == DAS_FN_TOTALTEMPERATURE || DAS_FN_BASE(fn->kind) == DAS_FN_PATCHMEAN);
     if (areaAvg) {
         double S[2], A[2] = {0.0, 0.0};
         function_sums(s, *fn, S);  // S_g = sum of w0 q: totalPressure scale N0 / A0 (one group), ratio functions N_g / A_g
         for (size_t q = 0; q < fn->faces.size(); q++) A[fn->group[q]] += m.fg[fn->faces[q]].magSf;
         if (!fn->ratio) {
-            cN[0] = fn->scale / A[0];
-            cA[0] = -S[0] / A[0];
+            const double outer = fn->refVar ? 2.0 * (S[0] + S[1] - fn->ref) : 1.0;  // patchMean calcRefVar
+            cN[0] = outer * fn->scale / A[0];
+            cA[0] = -outer * S[0] / A[0];
         } else {
             const double F = S[1] / S[0];  // F = (N1 / A1) / (N0 / A0)
             cN[1] = F / (S[1] * A[1]); cA[1] = -F / A[1];

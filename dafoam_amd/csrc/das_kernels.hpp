@@ -1121,6 +1121,13 @@ DAS_HD T body_force(int f, const DevMeshT<G>& m, const ResParams& prm, const T* 
 #define DAS_FN_MASSFLOW 1
 #define DAS_FN_TOTALPRESSURE 2
 #define DAS_FN_TOTALTEMPERATURE 3
+//   kind 4  patchMean        component of the boundary value  b_v,i                    DAFunctionPatchMean.C:36-110
+//   kind 5  variance         sum_i (b_v,i - d_f,i)^2 over the selected components, d_f = dir (the reference data of the face)
+//                                                                       DAFunctionVariance.C (mode surface)
+//   (kinds 4, 5: bits 4-7 = variable v (0 U, 1 p, 2 nuTilda, 3 T), bits 8-10 = component mask)
+#define DAS_FN_PATCHMEAN 4
+#define DAS_FN_VARIANCE 5
+#define DAS_FN_BASE(kind) ((kind) & 15)
 template <class T, bool RHO, class G, class DV>
 DAS_HD T body_facefn(int f, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* nut, const T* gradU, int kind, const DV* dir,
                      double gammaFn, double RFn) {
@@ -1130,12 +1137,27 @@ DAS_HD T body_facefn(int f, const DevMeshT<G>& m, const ResParams& prm, const T*
     const int c = m.owner[f];
     T Uc[3] = {W[3LL * c], W[3LL * c + 1], W[3LL * c + 2]};
     T pc = W[prm.offP * N + c], nc = W[prm.offN * N + c];
-    T Tc = RHO ? W[prm.offT * N + c] : T(0.0);
+    T Tc = (RHO || prm.hasT) ? W[prm.offT * N + c] : T(0.0);
     BFace<T, G> b;
     eval_bface<T, RHO>(m.bc[m.bpatch[f - m.nIF]], g, m.cg[c], prm, Uc, pc, Tc, nc, nut[c], val(W[prm.offPhi * N + f]), b);
     T U2 = b.U.xb[0] * b.U.xb[0] + b.U.xb[1] * b.U.xb[1] + b.U.xb[2] * b.U.xb[2];
     if (kind == DAS_FN_MASSFLOW) return b.rho_b * (b.U.xb[0] * g.Sf[0] + b.U.xb[1] * g.Sf[1] + b.U.xb[2] * g.Sf[2]);
     if (kind == DAS_FN_TOTALPRESSURE) return b.p.xb + 0.5 * b.rho_b * U2;
+    if (DAS_FN_BASE(kind) == DAS_FN_PATCHMEAN || DAS_FN_BASE(kind) == DAS_FN_VARIANCE) {
+        const int v = (kind >> 4) & 15, mask = (kind >> 8) & 7;
+        T q(0.0);
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            if (!((mask >> i) & 1)) continue;
+            T x = v == 0 ? b.U.xb[i] : v == 1 ? b.p.xb : v == 2 ? b.n.xb : b.Tt.xb;
+            if (DAS_FN_BASE(kind) == DAS_FN_VARIANCE) {
+                x = x - dir[i];
+                x = x * x;
+            }
+            q = q + x;
+        }
+        return q;
+    }
     // total temperature (compressible solvers only; the caller checks)
     return b.Tt.xb + (0.5 * (gammaFn - 1.0) / (gammaFn * RFn)) * U2;
 }

@@ -523,7 +523,47 @@ def read_case(case_dir, solver_name="DASimpleFoam", time="0", y_wall=None, stric
                     if cnt == pt.size:
                         phi[sl] = np.array(body.split(), dtype=np.float64)
     case.states = np.concatenate([U.ravel(), p, nuT, phi])
+    case.ref_data = read_ref_data(case_dir, mesh, time, g.Sf, phi)
     return apply_system_dicts(case, case_dir, strict=strict_schemes)
+
+
+REF_DATA_FIELDS = (("UData", 3), ("pData", 1), ("nuTildaData", 1), ("TData", 1))
+
+
+def read_ref_data(case_dir, mesh, time, Sf, phi):
+    """0/<var>Data of the variance functions (DAFunctionVariance.C reads them with READ_IF_PRESENT): {name: {"internal": (N[, 3]),
+    "boundary": (nBF[, 3])}} for the files that exist.  Boundary values follow the patch type like the state fields': fixedValue /
+    noSlip the patch value, zeroGradient / calculated the cell value, symmetry the tangential part of the cell value (vectors),
+    inletOutlet the inlet value where the flux enters and the cell value elsewhere."""
+    out = {}
+    N, nIF = mesh.n_cells, mesh.n_internal_faces
+    for name, ncomp in REF_DATA_FIELDS:
+        path = os.path.join(case_dir, time, name)
+        if not os.path.exists(path):
+            continue
+        internal, bfield = read_field(path, N, ncomp)
+        vec = ncomp == 3
+        bvals = np.zeros((mesh.n_faces - nIF, 3) if vec else mesh.n_faces - nIF)
+        for pt in mesh.patches:
+            if not pt.size:
+                continue
+            sl = slice(pt.start - nIF, pt.start - nIF + pt.size)
+            cells = mesh.owner[pt.start : pt.start + pt.size]
+            code, val = _bc_entry(bfield.get(pt.name, {"type": "zeroGradient"}), vec)
+            cv = internal[cells]
+            if code == BC_FIXED_VALUE:
+                bvals[sl] = np.asarray(val, dtype=np.float64)
+            elif code == BC_SYMMETRY and vec:
+                n = Sf[pt.start : pt.start + pt.size]
+                n = n / np.linalg.norm(n, axis=1)[:, None]
+                bvals[sl] = cv - np.einsum("ij,ij->i", cv, n)[:, None] * n
+            elif code == BC_INLET_OUTLET:
+                inflow = phi[pt.start : pt.start + pt.size] < 0.0
+                bvals[sl] = np.where(inflow[:, None] if vec else inflow, np.asarray(val, dtype=np.float64), cv)
+            else:
+                bvals[sl] = cv
+        out[name] = {"internal": internal, "boundary": bvals}
+    return out
 
 
 def write_case(case_dir, case: FoamCase, time="0"):

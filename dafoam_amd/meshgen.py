@@ -101,6 +101,9 @@ class FoamCase:
     # DASimpleFoam with the optional passive T field (0/T present; Pr, Prt from transportProperties -> thermo["Pr"/"Prt"]):
     # states [U | p | T | nuTilda | phi]
     has_T: bool = False
+    # reference data of the variance functions, 0/<var>Data: {"pData": {"internal": (N,) | (N, 3), "boundary": (nBF,) | (nBF, 3)}}
+    # (boundary = the boundary faces in face order; read by foam_io.read_case when the files exist)
+    ref_data: Dict[str, dict] = field(default_factory=dict)
 
 
 def hex_block(

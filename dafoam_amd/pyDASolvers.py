@@ -746,6 +746,9 @@ class pyDASolvers:
         L = lib()
         for fname, fd in (functions or {}).items():
             ftype = fd.get("type")
+            if ftype in ("variableVolSum", "patchMean", "variance"):
+                self._define_field_function(fname, fd)
+                continue
             if ftype not in ("force", "moment", "massFlowRate", "totalPressure", "totalTemperatureRatio"):
                 raise NotImplementedError(f"function type {ftype} is outside the GPU hot path")
             ids = np.array([names.index(p) for p in fd["patches"]], dtype=np.int32)
@@ -779,6 +782,89 @@ class pyDASolvers:
                 self._h, fname.encode(), ftype.encode(), ids.ctypes.data_as(_capi.c_int_p),
                 grp.ctypes.data_as(_capi.c_int_p) if grp is not None else None, ids.size,
                 dptr(vecA) if vecA is not None else None, dptr(vecB) if vecB is not None else None, float(fd.get("scale", 1.0)), gamma))
+
+    def _function_cells(self, fname, fd):
+        """cellSources of a cell-set function (DAFunction.C): "allCells", or "boxToCell" = the cells whose centre lies in the
+        closed box min/max.  Selected once, at definition (a later updateOFMesh does not reselect)."""
+        src = fd.get("source", "allCells")
+        N = self._case.mesh.n_cells
+        if src == "allCells":
+            return np.arange(N, dtype=np.int32)
+        if src == "boxToCell":
+            if "min" not in fd or "max" not in fd:
+                raise _capi.DASError(f"function {fname}: boxToCell needs min and max")
+            C = self.geometry()["C"].reshape(-1, 3)  # the library's cell centres (OpenFOAM's boxToCell tests mesh.C())
+            lo, hi = np.asarray(fd["min"], dtype=np.float64), np.asarray(fd["max"], dtype=np.float64)
+            return np.nonzero(np.all((C >= lo) & (C <= hi), axis=1))[0].astype(np.int32)
+        raise _capi.DASError(f"function {fname}: source {src} not supported (allCells, boxToCell)")
+
+    def _define_field_function(self, fname, fd):
+        """variableVolSum (DAFunctionVariableVolSum.C), patchMean (DAFunctionPatchMean.C), variance (DAFunctionVariance.C; modes
+        field and surface) with the reference's keys and defaults.  timeOp / nStepsFrac / timeOpMaxMode mean nothing for a
+        steady solve and are ignored."""
+        ftype = fd["type"]
+        var = fd.get("varName")
+        vtype = fd.get("varType")
+        if ftype == "variance":
+            mode = fd.get("mode")
+            if mode not in ("field", "surface"):
+                raise _capi.DASError(f"variance {fname}: mode {mode} is not supported (field, surface; probePoint is not implemented)")
+            if fd.get("timeDependentRefData", False):
+                raise _capi.DASError(f"variance {fname}: timeDependentRefData is not supported (steady solvers)")
+            if var in ("wallShearStress", "wallHeatFlux"):
+                raise _capi.DASError(f"variance {fname}: varName {var} is not supported")
+        if vtype not in ("scalar", "vector"):
+            raise _capi.DASError(f"function {fname}: varType {vtype} not supported! Options are: scalar or vector")
+        if ftype == "variance":
+            if vtype == "vector" and "indices" not in fd:
+                raise _capi.DASError(f"variance {fname}: a vector variable needs indices")
+            comps = [int(i) for i in fd["indices"]] if vtype == "vector" else [0]
+        else:
+            comps = [int(fd.get("index", 0))] if vtype == "vector" else [0]
+        comps = np.array(comps, dtype=np.int32)
+        if (vtype == "vector") != (var == "U"):
+            raise _capi.DASError(f"function {fname}: varType {vtype} does not match varName {var}")
+        flags = (int(fd.get("isSquare", 0)) and 1) | (int(fd.get("multiplyVol", 1)) and 2) | (int(fd.get("divByTotalVol", 0)) and 4)
+        ref = 0.0
+        if ftype != "variance" and int(fd.get("calcRefVar", 0)):
+            flags |= 8
+            ref = float(np.atleast_1d(fd["ref"])[0])
+        if int(fd.get("useGeoWeight", 0)):
+            flags |= 16
+        scale = float(fd.get("scale", 1.0))
+        data = None
+        surface = ftype == "patchMean" or (ftype == "variance" and fd["mode"] == "surface")
+        if ftype == "variance":
+            d = self._case.ref_data.get(var + "Data")
+            if d is None:
+                print(f"WARNING! Can't find data files or can't find valid values in data files for the variance function {var}")
+            else:
+                m = self._case.mesh
+                if surface:
+                    rows = np.concatenate([np.arange(p.start, p.start + p.size) for p in self._patches_of(fd)]) - m.n_internal_faces
+                    vals = np.asarray(d["boundary"], dtype=np.float64)[rows]
+                else:
+                    vals = np.asarray(d["internal"], dtype=np.float64)
+                data = vals.reshape(vals.shape[0], -1)
+        L = lib()
+        if surface:
+            ids = np.array([self._case.mesh.patches.index(p) for p in self._patches_of(fd)], dtype=np.int32)
+            if data is not None:
+                data = np.ascontiguousarray(data[:, comps] if vtype == "vector" else data[:, :1])
+            check(L.das_define_patch_field_function(self._h, fname.encode(), ftype.encode(), ids.ctypes.data_as(_capi.c_int_p), ids.size, str(var).encode(),
+                                                    comps.ctypes.data_as(_capi.c_int_p), comps.size, dptr(data) if data is not None else None, flags, scale, ref))
+            return
+        cells = self._function_cells(fname, fd)
+        if data is not None:
+            data = np.ascontiguousarray(data[cells][:, comps] if vtype == "vector" else data[cells][:, :1])
+        check(L.das_define_cell_function(self._h, fname.encode(), ftype.encode(), cells.ctypes.data_as(_capi.c_int_p), cells.size, str(var).encode(),
+                                         comps.ctypes.data_as(_capi.c_int_p), comps.size, dptr(data) if data is not None else None, flags, scale, ref))
+
+    def _patches_of(self, fd):
+        if fd.get("source", "patchToFace") != "patchToFace":
+            raise _capi.DASError(f"source {fd.get('source')} not valid for a boundary-value function (patchToFace)")
+        by_name = {p.name: p for p in self._case.mesh.patches}
+        return [by_name[p] for p in fd["patches"]]
 
     def _flow_direction(self, meta, deriv=False):
         """force direction of parallelToFlow / normalToFlow at the current AoA (deriv: d/dAoA[deg])"""

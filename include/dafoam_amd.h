@@ -302,6 +302,32 @@ int das_define_force_function(das_solver_t* s, const char* name, const int* patc
  * das_calc_jac_t_vec_product / das_calc_dbc_product like the force. */
 int das_define_face_function(das_solver_t* s, const char* name, const char* type, const int* patch_ids, const int* patch_group, int npatch,
                              const double* vecA, const double* vecB, double scale, double gammaFn);
+/* das_define_patch_field_function <- the boundary-value entries of the "function" option dict (flow solvers):
+ *   type "patchMean"  area average of component comps[0] of the boundary value of var, * scale   DAFunctionPatchMean.C:36-110
+ *        "variance"   mode surface: sum w_f scale (b_f,i - d_f,i)^2 / W over the faces and the components comps[ncomp],
+ *                     w_f = |Sf| (flags & 16: useGeoWeight) or 1, W = sum of w_f per component or the number of points
+ *                                                                                             DAFunctionVariance.C
+ * var: "U" (comps in 0..2), "p", "nuTilda", "T" (comps = {0}); the boundary value follows each patch's condition like the
+ * residual's.  data[nfaces * ncomp] (variance: the reference values face-major over the patches in the given order; NULL = no
+ * reference data: F = 0 with zero derivatives).  flags & 8: calcRefVar, F <- (F - ref)^2 (patchMean).  Values and derivatives
+ * go through das_calc_function / das_calc_jac_t_vec_product / das_calc_dbc_product / das_calc_dvolcoord_product (patchMean) like
+ * the face functions above; variance rejects the volCoord product.  Sharded solvers (owned-cell mask) return DAS_ERR_ARG. */
+int das_define_patch_field_function(das_solver_t* s, const char* name, const char* type, const int* patch_ids, int npatch, const char* var,
+                                    const int* comps, int ncomp, const double* data, int flags, double scale, double ref);
+/* das_define_cell_function <- the cell-set entries of the "function" option dict (every solver):
+ *   type "variableVolSum"  scale sum_c (V_c | 1) q_c^(1|2) / T over cells[ncells]; flags & 1 isSquare, & 2 multiplyVol,
+ *                          & 4 divByTotalVol (T = 1 + the volume of ALL cells, else T = 1), & 8 calcRefVar (F <- (F - ref)^2)
+ *                                                                                             DAFunctionVariableVolSum.C:43-135
+ *        "variance"        mode field: sum w_t scale (q_t - d_t)^2 / W over (cell, component) terms, w = V_c (flags & 16:
+ *                          useGeoWeight) or 1, W = sum of w or the number of terms            DAFunctionVariance.C
+ * The cell set (allCells / boxToCell, chosen by the caller) is fixed here; the volumes follow das_update_of_mesh.
+ * var: a cell state of the solver ("U", "p", "nuTilda", "T") or "betaFINuTilda" (variableVolSum on the SA solvers).
+ * data[ncells * ncomp] (variance, cell-major; NULL = no reference data: F = 0).  The value is a two-stage deterministic reduction
+ * (bitwise repeatable); dF/dW is one elementwise pass (no colouring); das_calc_dfield_product gives dF/dbeta for
+ * var = betaFINuTilda (0 otherwise); das_calc_dbc_product gives 0; das_calc_dvolcoord_product differentiates the volumes
+ * (variableVolSum; variance rejects it).  Sharded solvers (owned-cell mask) return DAS_ERR_ARG. */
+int das_define_cell_function(das_solver_t* s, const char* name, const char* type, const int* cells, int ncells, const char* var, const int* comps,
+                             int ncomp, const double* data, int flags, double scale, double ref);
 int das_calc_function(das_solver_t* s, const char* name, double* value);
 
 /* das_calc_jac_t_vec_product <- calcJacTVecProduct(inputName,inputType,inputs,outputName,outputType,seeds,product)
