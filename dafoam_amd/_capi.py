@@ -301,6 +301,18 @@ _SIGS = {
     "das_get_elapsed_cpu_time": (C.c_double, [_VP]),
     "das_timer_avg_ms": (C.c_double, [_VP, C.c_char_p]),
     "das_debug_orth_bench": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    # test-only entries (tests/test_gpu_krylov_kernels.py): the Krylov kernels on caller data, never called by the bindings
+    "das_debug_krylov_dots2": (C.c_int, [C.c_longlong, C.c_int, C.c_int, _VP, C.c_longlong, c_double_p, c_double_p]),
+    "das_debug_krylov_dcgs2_update": (C.c_int, [C.c_longlong, C.c_int, C.c_int, _VP, C.c_longlong, C.c_int, c_double_p, C.c_double, C.c_double, c_double_p]),
+    "das_debug_krylov_multidot": (C.c_int, [C.c_longlong, C.c_int, C.c_int, _VP, C.c_longlong, c_double_p, c_double_p]),
+    "das_debug_krylov_multiaxpy": (C.c_int, [C.c_longlong, C.c_int, C.c_int, _VP, C.c_longlong, c_double_p, C.c_int, _VP, C.c_longlong]),
+    "das_debug_krylov_lincomb": (C.c_int, [C.c_longlong, C.c_int, C.c_int, _VP, C.c_longlong, c_double_p, c_double_p, C.c_longlong]),
+    "das_debug_krylov_scale_to": (C.c_int, [C.c_longlong, C.c_double, C.c_int, _VP, _VP, C.c_longlong]),
+    "das_debug_krylov_block_tn": (C.c_int, [C.c_longlong, C.c_int, C.c_int, c_double_p, C.c_longlong, C.c_longlong, c_double_p, C.c_longlong, c_double_p]),
+    "das_debug_krylov_block_nn_sub": (C.c_int, [C.c_longlong, C.c_int, C.c_int, c_double_p, C.c_longlong, c_double_p, c_double_p, C.c_longlong]),
+    "das_debug_krylov_block_right_mult": (C.c_int, [C.c_longlong, C.c_int, c_double_p, C.c_longlong, c_double_p]),
+    "das_debug_krylov_block_lincomb": (C.c_int, [C.c_longlong, C.c_int, C.c_int, c_double_p, C.c_longlong, c_double_p, c_double_p, C.c_longlong]),
+    "das_debug_krylov_block_spmm": (C.c_int, [C.c_longlong, C.c_int, c_ll_p, c_int_p, c_double_p, c_double_p, C.c_longlong, c_double_p, C.c_longlong]),
     "das_timer_count": (C.c_longlong, [_VP, C.c_char_p]),
     "das_timer_reset": (None, [_VP]),
     "das_timer_enable": (None, [_VP, C.c_int]),

@@ -672,6 +672,94 @@ __global__ void k_scale_to(long long n, double a, const TI* __restrict__ x, TO* 
     y[k] = yh;
     if (ylo) ylo[k] = (float)(val - (double)yh);
 }
+// ---- launch helpers of the Krylov vector kernels --------------------------------------------------------------------------
+// The one place that holds the grid arithmetic of these kernels: they take (stream, n, ...) and no solver handle, so that the
+// solver (gmres_iter_t, gmres_iter_dcgs2, DrDeviceOps) and the test-only entries das_debug_krylov_* run the SAME launches.
+static inline size_t multidot_partial_size(long long n, int m) { return (size_t)(m + 1) * nblk(n, MD_CHUNK); }
+// out[0..m) = V^T w, out[m] = w.w
+template <class VT>
+static void launch_multidot(hipStream_t st, long long n, int m, const VT* V, long long ldv, const double* w, double* partial, double* out) {
+    const int nb = nblk(n, MD_CHUNK);
+    hipLaunchKernelGGL(k_multidot, dim3(nb), dim3(256), 0, st, n, m, V, ldv, w, partial, nb);
+    hipLaunchKernelGGL(k_reduce, dim3(m + 1), dim3(256), 0, st, nb, (const double*)partial, out);
+}
+template <int ROWS>
+static inline long long multidot2_nbw(long long n) { return 4LL * nblk(n, 256 * ROWS); }
+static inline size_t multidot2_partial_size(long long n, int K) { return (size_t)2 * K * (size_t)multidot2_nbw<MD2_ROWS>(n); }
+// the inner-product pass alone (the tuning hook times it for several ROWS)
+template <int ROWS, class VT>
+static void launch_multidot2_pass(hipStream_t st, long long n, int K, const VT* V, long long ldv, const VT* u, const double* v, double* partial) {
+    hipLaunchKernelGGL((k_multidot2<ROWS, VT, VT>), dim3(nblk(n, 256 * ROWS)), dim3(256), 0, st, n, K, V, ldv, u, v, partial, multidot2_nbw<ROWS>(n));
+}
+// out[0..K) = V^T u, out[K..2K) = V^T v
+template <class VT>
+static void launch_multidot2(hipStream_t st, long long n, int K, const VT* V, long long ldv, const VT* u, const double* v, double* partial, double* out) {
+    launch_multidot2_pass<MD2_ROWS, VT>(st, n, K, V, ldv, u, v, partial);
+    hipLaunchKernelGGL(k_reduce, dim3(2 * K), dim3(256), 0, st, (int)multidot2_nbw<MD2_ROWS>(n), (const double*)partial, out);
+}
+template <int UNROLL, int RPT, class VT>
+static void launch_dcgs2_update(hipStream_t st, long long n, int j, VT* V, long long ldv, const double* sc, double gamma, double ralpha, const double* v,
+                                float* Vlo) {
+    hipLaunchKernelGGL((k_dcgs2_update<UNROLL, RPT, VT>), dim3(nblk(n, 256 * RPT)), dim3(256), 0, st, n, j, V, ldv, sc, gamma, ralpha, v, Vlo);
+}
+template <class VT, class WT>
+static void launch_multiaxpy(hipStream_t st, long long n, int m, const VT* V, long long ldv, const double* h, WT* w, const float* Vlo) {
+    hipLaunchKernelGGL(k_multiaxpy, dim3(nblk(n, 256)), dim3(256), 0, st, n, m, V, ldv, h, w, Vlo);
+}
+template <class VT>
+static void launch_lincomb(hipStream_t st, long long n, int m, const VT* V, long long ldv, const double* c, double* y, const float* Vlo) {
+    hipLaunchKernelGGL(k_lincomb, dim3(nblk(n, 256)), dim3(256), 0, st, n, m, V, ldv, c, y, Vlo);
+}
+template <class TI, class TO>
+static void launch_scale_to(hipStream_t st, long long n, double a, const TI* x, TO* y, const float* xlo, float* ylo) {
+    hipLaunchKernelGGL(k_scale_to, dim3(nblk(n, 256)), dim3(256), 0, st, n, a, x, y, xlo, ylo);
+}
+static constexpr int TSG_CHUNKS = 1024;  // row chunks of the TN product (one wave each per group of 64 basis vectors)
+// ---- launch helpers of the block kernels (das_block.hpp): like the vector ones above they hold the grid arithmetic once, take
+// (stream, n, ..., leading dimensions) and serve both the block solver and the test-only entries das_debug_krylov_block_*
+static inline int tsgemm_kpad(int K) { return (K + 16 * TSG_TILES - 1) / (16 * TSG_TILES) * (16 * TSG_TILES); }
+static inline size_t tsgemm_partial_size(int K) { return (size_t)TSG_CHUNKS * tsgemm_kpad(K) * 16; }
+// C (K x sv, row-major, device) = V^T W; partial: tsgemm_partial_size(K) doubles
+static void launch_tsgemm_tn(hipStream_t st, long long n, int K, int sv, const double* V, long long ldv, const double* W, long long ldw, double* partial,
+                             double* C) {
+    long long rpc = (n + TSG_CHUNKS - 1) / TSG_CHUNKS;
+    rpc = (rpc + 15) / 16 * 16;
+    const int Kpad = tsgemm_kpad(K);
+    const int gy = Kpad / (16 * TSG_TILES);
+    // even leading dimensions select the 16-byte loads of k_tsgemm_tn: they need 16-byte aligned blocks (every block of the solver
+    // starts a multiple of its leading dimension into a fresh allocation)
+    DAS_CHECK((((ldv | ldw) & 1) != 0) || ((((uintptr_t)V | (uintptr_t)W) & 15) == 0), DAS_ERR_ARG,
+              "block V^T W: even leading dimensions need 16-byte aligned blocks");
+    hipLaunchKernelGGL(k_tsgemm_tn, dim3(TSG_CHUNKS / TSG_WAVES, gy), dim3(64 * TSG_WAVES), 0, st, n, K, sv, V, ldv, W, ldw, rpc, Kpad, partial);
+    hipLaunchKernelGGL(k_tsgemm_reduce, dim3(nblk((long long)K * sv, 4)), dim3(256), 0, st, K, sv, Kpad, (long long)TSG_CHUNKS, (const double*)partial, C);
+}
+// W -= V C  (C = K x sv, row-major, device)
+static void launch_tsgemm_nn_sub(hipStream_t st, long long n, int K, int sv, const double* V, long long ldv, const double* C, double* W, long long ldw) {
+    hipLaunchKernelGGL(k_tsgemm_nn_sub, dim3(nblk(n, 256)), dim3(256), 0, st, n, K, sv, V, ldv, C, W, ldw);
+}
+static void launch_block_right_mult(hipStream_t st, long long n, int sv, double* W, long long ldw, const double* T) {
+    hipLaunchKernelGGL(k_block_right_mult, dim3(nblk(n, 256)), dim3(256), 0, st, n, sv, W, ldw, T);
+}
+static void launch_block_lincomb(hipStream_t st, long long n, int K, int sv, const double* V, long long ldv, const double* C, double* Y, long long ldy) {
+    hipLaunchKernelGGL(k_block_lincomb, dim3(nblk(n, 256)), dim3(256), 0, st, n, K, sv, V, ldv, C, Y, ldy);
+}
+// the sparse product for sv vectors runs at the template width 2, 4 or 8; Xr (n x width, row-major) is its gather layout
+static inline int spmm_width(int sv) { return sv <= 2 ? 2 : (sv <= 4 ? 4 : 8); }
+static void launch_block_to_rows(hipStream_t st, long long n, int sv, const double* X, long long ldx, double* Xr) {
+    switch (spmm_width(sv)) {
+        case 2: hipLaunchKernelGGL(k_block_to_rows<2>, dim3(nblk(n, 256)), dim3(256), 0, st, n, sv, X, ldx, Xr); break;
+        case 4: hipLaunchKernelGGL(k_block_to_rows<4>, dim3(nblk(n, 256)), dim3(256), 0, st, n, sv, X, ldx, Xr); break;
+        default: hipLaunchKernelGGL(k_block_to_rows<8>, dim3(nblk(n, 256)), dim3(256), 0, st, n, sv, X, ldx, Xr); break;
+    }
+}
+static void launch_spmm_wave(hipStream_t st, long long nrows, int sv, const long long* rp, const int* ci, const double* val, const double* Xr, double* Y,
+                             long long ldy) {
+    switch (spmm_width(sv)) {
+        case 2: hipLaunchKernelGGL(k_spmm_wave<2>, dim3(nblk(nrows, 16)), dim3(256), 0, st, nrows, sv, rp, ci, val, Xr, Y, ldy); break;
+        case 4: hipLaunchKernelGGL(k_spmm_wave<4>, dim3(nblk(nrows, 16)), dim3(256), 0, st, nrows, sv, rp, ci, val, Xr, Y, ldy); break;
+        default: hipLaunchKernelGGL(k_spmm_wave<8>, dim3(nblk(nrows, 16)), dim3(256), 0, st, nrows, sv, rp, ci, val, Xr, Y, ldy); break;
+    }
+}
 __global__ void k_axpby(long long n, double a, const double* __restrict__ x, double b, double* __restrict__ y) {
     long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) y[k] = a * x[k] + b * y[k];
@@ -2593,8 +2681,7 @@ static void gmres_ws(das_solver* s, das_ksp* k) {
         k->restart = (int)restart;
         k->w.alloc(n); k->z.alloc(n); k->r.alloc(n); k->xdev.alloc(n); k->bdev.alloc(n);
         k->z.zero();  // multi-GPU: ghost entries are never written by the PC and must stay zero
-        int nb = nblk(n, MD_CHUNK);
-        k->partial.alloc(std::max<size_t>((size_t)(restart + 2) * nb, (size_t)2 * (restart + 2) * 4 * (size_t)nblk(n, MD2_CHUNK)));
+        k->partial.alloc(std::max<size_t>(multidot_partial_size(n, (int)restart + 1), multidot2_partial_size(n, (int)restart + 2)));
         k->hdev.alloc(4 * (restart + 3));
     }
 }
@@ -2617,10 +2704,7 @@ static inline float* basis_lo(das_solver* s, das_ksp* k, long long j) { return k
 // dev_out[0..m) = V^T w (V = m vectors of stride n starting at Vbase), dev_out[m] = w.w; summed over the ranks
 template <class VT>
 static void multidot_dev(das_solver* s, das_ksp* k, const VT* Vbase, int m, const double* w, double* dev_out) {
-    const long long n = s->n;
-    int nb = nblk(n, MD_CHUNK);
-    hipLaunchKernelGGL(k_multidot, dim3(nb), dim3(256), 0, s->stream, n, m, Vbase, basis_ld(s, k), w, k->partial.p, nb);
-    hipLaunchKernelGGL(k_reduce, dim3(m + 1), dim3(256), 0, s->stream, nb, k->partial.p, dev_out);
+    launch_multidot<VT>(s->stream, s->n, m, Vbase, basis_ld(s, k), w, k->partial.p, dev_out);
     if (!(s->halo.active && s->halo.allreduce(dev_out, m + 1, s->stream)) && s->allreduce_cb) s->allreduce_cb(dev_out, m + 1, s->comm_user);
 }
 // h[0..m) = V^T w, h[m] = w.w  (device result in k->hdev, copied to host)
@@ -2854,8 +2938,8 @@ static void gmres_cycle_start(das_solver* s, das_ksp* k) {
     GmresRun& G = *k->run;
     const long long n = s->n;
     DAS_CHECK(gmres_map_basis(s, k, 3), DAS_ERR_INTERNAL, "GMRES: no device memory for three Krylov vectors (" + k->V.workerError + ")");
-    if (k->vf32) hipLaunchKernelGGL(k_scale_to, dim3(nblk(n, 256)), dim3(256), 0, s->stream, n, 1.0 / G.beta, (const double*)k->r.p, basis_slot<float>(s, k, 0), (const float*)nullptr, basis_lo(s, k, 0));
-    else hipLaunchKernelGGL(k_scale_to, dim3(nblk(n, 256)), dim3(256), 0, s->stream, n, 1.0 / G.beta, (const double*)k->r.p, k->V.p, (const float*)nullptr, (float*)nullptr);
+    if (k->vf32) launch_scale_to(s->stream, n, 1.0 / G.beta, (const double*)k->r.p, basis_slot<float>(s, k, 0), (const float*)nullptr, basis_lo(s, k, 0));
+    else launch_scale_to(s->stream, n, 1.0 / G.beta, (const double*)k->r.p, (double*)k->V.p, (const float*)nullptr, (float*)nullptr);
     std::fill(G.g.begin(), G.g.end(), 0.0);
     G.g[0] = G.beta;
     G.j = 0;
@@ -2868,7 +2952,7 @@ static void gmres_cycle_start(das_solver* s, das_ksp* k) {
 template <class VT>
 static const double* basis_as_double(das_solver* s, das_ksp* k, long long j) {
     if (sizeof(VT) == sizeof(double)) return reinterpret_cast<const double*>(basis_slot<VT>(s, k, j));
-    hipLaunchKernelGGL(k_scale_to, dim3(nblk(s->n, 256)), dim3(256), 0, s->stream, s->n, 1.0, (const VT*)basis_slot<VT>(s, k, j), k->ustage.p, (const float*)basis_lo(s, k, j), (float*)nullptr);
+    launch_scale_to(s->stream, s->n, 1.0, (const VT*)basis_slot<VT>(s, k, j), (double*)k->ustage.p, (const float*)basis_lo(s, k, j), (float*)nullptr);
     return k->ustage.p;
 }
 // one Arnoldi step; returns the recurrence residual norm
@@ -2896,7 +2980,7 @@ static double gmres_iter_t(das_solver* s, das_ksp* k) {
         for (int i = 0; i <= j; i++) {
             multidot_dev<VT>(s, k, Vb + (long long)i * ld, 1, k->w.p, k->hdev.p);
             DAS_HIP(hipMemcpyAsync(hcol + i, k->hdev.p, sizeof(double), hipMemcpyDeviceToDevice, st));
-            hipLaunchKernelGGL(k_multiaxpy, dim3(nblk(n, B)), dim3(B), 0, st, n, 1, (const VT*)(Vb + (long long)i * ld), ld, (const double*)k->hdev.p, k->w.p, (const float*)basis_lo(s, k, i));
+            launch_multiaxpy(st, n, 1, (const VT*)(Vb + (long long)i * ld), ld, (const double*)k->hdev.p, (double*)k->w.p, (const float*)basis_lo(s, k, i));
         }
         multidot_dev<VT>(s, k, Vb, 0, k->w.p, k->hdev.p);
         DAS_HIP(hipMemcpyAsync(hcol + j + 1, k->hdev.p, sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -2908,14 +2992,14 @@ static double gmres_iter_t(das_solver* s, das_ksp* k) {
         // KSP_GMRES_CGS_REFINE_IFNEEDED, DALinearEqn.C:160): refine when the projected vector keeps less than half
         // of its squared norm, i.e. ||w - V h||^2 (= w.w - h.h) < h.h
         multidot<VT>(s, k, j + 1, k->w.p, hh.data());
-        hipLaunchKernelGGL(k_multiaxpy, dim3(nblk(n, B)), dim3(B), 0, st, n, j + 1, (const VT*)Vb, ld, (const double*)k->hdev.p, k->w.p, (const float*)basis_lo(s, k, 0));
+        launch_multiaxpy(st, n, j + 1, (const VT*)Vb, ld, (const double*)k->hdev.p, (double*)k->w.p, (const float*)basis_lo(s, k, 0));
         double hsq = 0.0;
         for (int i = 0; i <= j; i++) hsq += hh[i] * hh[i];
         const double ww = hh[j + 1];
         const double est = ww - hsq;
         if (alwaysRefine || !(est > hsq) || !(est > 0.0)) {
             multidot<VT>(s, k, j + 1, k->w.p, h2.data());
-            hipLaunchKernelGGL(k_multiaxpy, dim3(nblk(n, B)), dim3(B), 0, st, n, j + 1, (const VT*)Vb, ld, (const double*)k->hdev.p, k->w.p, (const float*)basis_lo(s, k, 0));
+            launch_multiaxpy(st, n, j + 1, (const VT*)Vb, ld, (const double*)k->hdev.p, (double*)k->w.p, (const float*)basis_lo(s, k, 0));
             double hn2;
             multidot<VT>(s, k, 0, k->w.p, &hn2);
             hn = std::sqrt(std::max(hn2, 0.0));
@@ -2927,7 +3011,7 @@ static double gmres_iter_t(das_solver* s, das_ksp* k) {
     if (!mgs && !(hn > GMRES_BREAKDOWN_TOL * std::sqrt(std::max(hh[j + 1], 0.0)))) { hn = 0.0; G.nBreakdown++; }  // happy breakdown (hh[j+1] = |A M^-1 v_j|^2)
     for (int i = 0; i <= j; i++) H[(size_t)i * m + j] = hh[i] + h2[i];
     H[(size_t)(j + 1) * m + j] = hn;
-    if (hn > 0.0) hipLaunchKernelGGL(k_scale_to, dim3(nblk(n, B)), dim3(B), 0, st, n, 1.0 / hn, (const double*)k->w.p, Vb + (long long)(j + 1) * ld, (const float*)nullptr, basis_lo(s, k, j + 1));
+    if (hn > 0.0) launch_scale_to(st, n, 1.0 / hn, (const double*)k->w.p, Vb + (long long)(j + 1) * ld, (const float*)nullptr, basis_lo(s, k, j + 1));
     for (int i = 0; i < j; i++) {
         double a = H[(size_t)i * m + j], b2 = H[(size_t)(i + 1) * m + j];
         H[(size_t)i * m + j] = cs[i] * a + sn[i] * b2;
@@ -2998,9 +3082,7 @@ static double gmres_iter_dcgs2(das_solver* s, das_ksp* k) {
     pc_apply_full(s, k, basis_as_double<VT>(s, k, j), k->z.p);
     apply_operator(s, k->z.p, k->w.p);
     const int K = j + 1;
-    const long long nbw = 4LL * nblk(n, MD2_CHUNK);
-    hipLaunchKernelGGL((k_multidot2<MD2_ROWS, VT, VT>), dim3(nblk(n, MD2_CHUNK)), dim3(256), 0, st, n, K, (const VT*)Vb, ld, (const VT*)u, (const double*)k->w.p, k->partial.p, nbw);
-    hipLaunchKernelGGL(k_reduce, dim3(2 * K), dim3(256), 0, st, (int)nbw, k->partial.p, k->hdev.p);
+    launch_multidot2<VT>(st, n, K, (const VT*)Vb, ld, (const VT*)u, (const double*)k->w.p, k->partial.p, k->hdev.p);
     if (!(s->halo.active && s->halo.allreduce(k->hdev.p, 2 * K, st)) && s->allreduce_cb) s->allreduce_cb(k->hdev.p, 2 * K, s->comm_user);
     std::vector<double>& o = G.hh;
     DAS_HIP(hipMemcpyAsync(o.data(), k->hdev.p, 2 * K * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -3024,13 +3106,12 @@ static double gmres_iter_dcgs2(das_solver* s, das_ksp* k) {
         if (k->split) {
             // u is stored split: project its fp64 value (staging vector) with the hi + lo basis, store it split again
             const double* ud = basis_as_double<VT>(s, k, j);
-            hipLaunchKernelGGL(k_multiaxpy, dim3(nblk(n, 256)), dim3(256), 0, st, n, j, (const VT*)Vb, ld, (const double*)dsc, const_cast<double*>(ud), (const float*)basis_lo(s, k, 0));
-            hipLaunchKernelGGL(k_scale_to, dim3(nblk(n, 256)), dim3(256), 0, st, n, 1.0, ud, u, (const float*)nullptr, basis_lo(s, k, j));
+            launch_multiaxpy(st, n, j, (const VT*)Vb, ld, (const double*)dsc, const_cast<double*>(ud), (const float*)basis_lo(s, k, 0));
+            launch_scale_to(st, n, 1.0, ud, u, (const float*)nullptr, basis_lo(s, k, j));
         } else {
-            hipLaunchKernelGGL(k_multiaxpy, dim3(nblk(n, 256)), dim3(256), 0, st, n, j, (const VT*)Vb, ld, (const double*)dsc, u);
+            launch_multiaxpy(st, n, j, (const VT*)Vb, ld, (const double*)dsc, u, (const float*)nullptr);
         }
-        hipLaunchKernelGGL((k_multidot2<MD2_ROWS, VT, VT>), dim3(nblk(n, MD2_CHUNK)), dim3(256), 0, st, n, 1, (const VT*)u, n, (const VT*)u, (const double*)k->w.p, k->partial.p, nbw);
-        hipLaunchKernelGGL(k_reduce, dim3(2), dim3(256), 0, st, (int)nbw, k->partial.p, k->hdev.p);
+        launch_multidot2<VT>(st, n, 1, (const VT*)u, ld, (const VT*)u, (const double*)k->w.p, k->partial.p, k->hdev.p);  // K = 1: the leading dimension is not used
         if (!(s->halo.active && s->halo.allreduce(k->hdev.p, 2, st)) && s->allreduce_cb) s->allreduce_cb(k->hdev.p, 2, s->comm_user);
         double cc[2] = {0.0, 0.0};
         DAS_HIP(hipMemcpyAsync(cc, k->hdev.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -3073,7 +3154,7 @@ static double gmres_iter_dcgs2(das_solver* s, das_ksp* k) {
     for (int i = 0; i < j; i++) { co[i] = sv[i]; co[j + i] = tv[i] - gam * sv[i]; }
     double* dco = k->hdev.p + 2 * (m + 3);
     if (j > 0) DAS_HIP(hipMemcpyAsync(dco, co.data(), 2 * j * sizeof(double), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL((k_dcgs2_update<DCGS2_UNROLL, DCGS2_RPT, VT>), dim3(nblk(n, 256 * DCGS2_RPT)), dim3(256), 0, st, n, j, Vb, ld, (const double*)dco, gam, 1.0 / al, (const double*)k->w.p, basis_lo(s, k, 0));
+    launch_dcgs2_update<DCGS2_UNROLL, DCGS2_RPT, VT>(st, n, j, Vb, ld, (const double*)dco, gam, 1.0 / al, (const double*)k->w.p, basis_lo(s, k, 0));
     // first-projection coefficients of the new pending vector: (t - H_jj s) / alpha, gamma - s_{j-1}
     for (int i = 0; i < j; i++) {
         double a = tv[i];
@@ -3097,7 +3178,7 @@ static void gmres_cycle_end_t(das_solver* s, das_ksp* k) {
         G.y[i] = sacc / G.H[(size_t)i * m + i];
     }
     DAS_HIP(hipMemcpyAsync(k->hdev.p, G.y.data(), j * sizeof(double), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_lincomb, dim3(nblk(n, B)), dim3(B), 0, st, n, j, (const VT*)basis_slot<VT>(s, k, 0), basis_ld(s, k), (const double*)k->hdev.p, k->w.p, (const float*)basis_lo(s, k, 0));
+    launch_lincomb(st, n, j, (const VT*)basis_slot<VT>(s, k, 0), basis_ld(s, k), (const double*)k->hdev.p, (double*)k->w.p, (const float*)basis_lo(s, k, 0));
     pc_apply_full(s, k, k->w.p, k->z.p);
     hipLaunchKernelGGL(k_axpby, dim3(nblk(n, B)), dim3(B), 0, st, n, 1.0, k->z.p, 1.0, G.d_x);
     const double recRes = k->hist.back();
@@ -3400,7 +3481,7 @@ struct DrDeviceOps {
     das_solver* s; das_ksp* k; GmresRun* G; int kdefMax;
     DevBuf<double> scratch, Cdev;
     void start(double beta) {
-        hipLaunchKernelGGL(k_scale_to, dim3(nblk(s->n, 256)), dim3(256), 0, s->stream, s->n, 1.0 / beta, k->r.p, k->V.p);
+        launch_scale_to(s->stream, s->n, 1.0 / beta, (const double*)k->r.p, (double*)k->V.p, (const float*)nullptr, (float*)nullptr);
     }
     void arnoldi(int j, double* h, double& ww, double& hn) {
         const long long n = s->n;
@@ -3408,9 +3489,9 @@ struct DrDeviceOps {
         pc_apply_full(s, k, k->V.p + (long long)j * n, k->z.p);
         apply_operator(s, k->z.p, k->w.p);
         multidot(s, k, j + 1, k->w.p, G->hh.data());
-        hipLaunchKernelGGL(k_multiaxpy, dim3(nblk(n, 256)), dim3(256), 0, st, n, j + 1, k->V.p, n, k->hdev.p, k->w.p);
+        launch_multiaxpy(st, n, j + 1, (const double*)k->V.p, n, (const double*)k->hdev.p, (double*)k->w.p, (const float*)nullptr);
         multidot(s, k, j + 1, k->w.p, G->h2.data());
-        hipLaunchKernelGGL(k_multiaxpy, dim3(nblk(n, 256)), dim3(256), 0, st, n, j + 1, k->V.p, n, k->hdev.p, k->w.p);
+        launch_multiaxpy(st, n, j + 1, (const double*)k->V.p, n, (const double*)k->hdev.p, (double*)k->w.p, (const float*)nullptr);
         double hn2 = 0.0;
         multidot(s, k, 0, k->w.p, &hn2);
         k->nrefine++;
@@ -3418,14 +3499,14 @@ struct DrDeviceOps {
         ww = G->hh[j + 1];
         hn = std::sqrt(std::max(hn2, 0.0));
         if (hn > GMRES_BREAKDOWN_TOL * std::sqrt(std::max(ww, 0.0)))
-            hipLaunchKernelGGL(k_scale_to, dim3(nblk(n, 256)), dim3(256), 0, st, n, 1.0 / hn, k->w.p, k->V.p + (long long)(j + 1) * n);
+            launch_scale_to(st, n, 1.0 / hn, (const double*)k->w.p, (double*)k->V.p + (long long)(j + 1) * n, (const float*)nullptr, (float*)nullptr);
     }
     void update(int j, const double* y) {
         const long long n = s->n;
         hipStream_t st = s->stream;
         DAS_HIP(hipMemcpyAsync(k->hdev.p, y, j * sizeof(double), hipMemcpyHostToDevice, st));
         DAS_HIP(hipStreamSynchronize(st));  // y is the caller's host vector
-        hipLaunchKernelGGL(k_lincomb, dim3(nblk(n, 256)), dim3(256), 0, st, n, j, k->V.p, n, k->hdev.p, k->w.p);
+        launch_lincomb(st, n, j, (const double*)k->V.p, n, (const double*)k->hdev.p, (double*)k->w.p, (const float*)nullptr);
         pc_apply_full(s, k, k->w.p, k->z.p);
         hipLaunchKernelGGL(k_axpby, dim3(nblk(n, 256)), dim3(256), 0, st, n, 1.0, k->z.p, 1.0, G->d_x);
     }
@@ -3441,7 +3522,7 @@ struct DrDeviceOps {
             Cblk.assign((size_t)(m + 1) * sv, 0.0);
             for (int i = 0; i <= m; i++) for (int r = 0; r < sv; r++) Cblk[(size_t)i * sv + r] = P1[(size_t)i * (kk + 1) + c0 + r];
             DAS_HIP(hipMemcpyAsync(Cdev.p, Cblk.data(), Cblk.size() * sizeof(double), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_block_lincomb, dim3(nblk(n, 256)), dim3(256), 0, st, n, m + 1, sv, k->V.p, n, Cdev.p, scratch.p + (long long)c0 * n, n);
+            launch_block_lincomb(st, n, m + 1, sv, k->V.p, n, Cdev.p, scratch.p + (long long)c0 * n, n);
             DAS_HIP(hipStreamSynchronize(st));  // Cblk / Cdev are reused by the next group
         }
         DAS_HIP(hipMemcpyAsync(k->V.p, scratch.p, (size_t)(kk + 1) * n * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -3558,21 +3639,12 @@ struct BlockWork {
     DevBuf<double> V, W, Z, R, Xr, partial, Cdev, Tdev;
     int s = 0, m = 0;
 };
-static constexpr int TSG_CHUNKS = 1024;  // row chunks of the TN product (one wave each per group of 64 basis vectors)
-
 // C_host (K x sv, row-major) = V^T W  (V: K vectors, W: sv vectors, both column-major with leading dimension n)
 static void block_tn(das_solver* s, BlockWork& bw, const double* V, int K, const double* W, int sv, double* C_host) {
-    const long long n = s->n;
-    long long rpc = (n + TSG_CHUNKS - 1) / TSG_CHUNKS;
-    rpc = (rpc + 15) / 16 * 16;
-    const int gy = (K + 16 * TSG_TILES - 1) / (16 * TSG_TILES);
-    const int Kpad = gy * 16 * TSG_TILES;
-    const size_t need = (size_t)TSG_CHUNKS * Kpad * 16;
+    const size_t need = tsgemm_partial_size(K);
     if (bw.partial.n < need) bw.partial.alloc(need);
     if (bw.Cdev.n < (size_t)K * sv) bw.Cdev.alloc((size_t)K * sv + 1024);
-    hipLaunchKernelGGL(k_tsgemm_tn, dim3(TSG_CHUNKS / TSG_WAVES, gy), dim3(64 * TSG_WAVES), 0, s->stream, n, K, sv, V, n, W, n, rpc, Kpad, bw.partial.p);
-    hipLaunchKernelGGL(k_tsgemm_reduce, dim3(nblk((long long)K * sv, 4)), dim3(256), 0, s->stream, K, sv, Kpad, (long long)TSG_CHUNKS, bw.partial.p,
-                       bw.Cdev.p);
+    launch_tsgemm_tn(s->stream, s->n, K, sv, V, s->n, W, s->n, bw.partial.p, bw.Cdev.p);
     DAS_HIP(hipMemcpyAsync(C_host, bw.Cdev.p, (size_t)K * sv * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     DAS_HIP(hipStreamSynchronize(s->stream));
 }
@@ -3580,7 +3652,7 @@ static void block_tn(das_solver* s, BlockWork& bw, const double* V, int K, const
 static void block_nn_sub(das_solver* s, BlockWork& bw, const double* V, int K, const double* C_host, double* W, int sv) {
     if (bw.Cdev.n < (size_t)K * sv) bw.Cdev.alloc((size_t)K * sv + 1024);
     DAS_HIP(hipMemcpyAsync(bw.Cdev.p, C_host, (size_t)K * sv * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    hipLaunchKernelGGL(k_tsgemm_nn_sub, dim3(nblk(s->n, 256)), dim3(256), 0, s->stream, s->n, K, sv, V, s->n, bw.Cdev.p, W, s->n);
+    launch_tsgemm_nn_sub(s->stream, s->n, K, sv, V, s->n, bw.Cdev.p, W, s->n);
 }
 // W = Q S with Q^T Q = I (CholQR applied twice); S (sv x sv upper triangular, row-major) returned on the host
 static void block_cholqr2(das_solver* s, BlockWork& bw, double* W, int sv, std::vector<double>& S) {
@@ -3613,25 +3685,19 @@ static void block_cholqr2(das_solver* s, BlockWork& bw, double* W, int sv, std::
             }
         }
         DAS_HIP(hipMemcpyAsync(bw.Tdev.p, T.data(), (size_t)sv * sv * sizeof(double), hipMemcpyHostToDevice, s->stream));
-        hipLaunchKernelGGL(k_block_right_mult, dim3(nblk(s->n, 256)), dim3(256), 0, s->stream, s->n, sv, W, s->n, bw.Tdev.p);
+        launch_block_right_mult(s->stream, s->n, sv, W, s->n, bw.Tdev.p);
         std::vector<double>& Sp = pass == 0 ? S1 : S2;
         for (int i = 0; i < sv; i++) for (int j = i; j < sv; j++) Sp[(size_t)i * sv + j] = L[(size_t)j * sv + i];  // L^T
     }
     S.assign((size_t)sv * sv, 0.0);  // W = Q2 S2 S1
     for (int i = 0; i < sv; i++) for (int j = i; j < sv; j++) { double a = 0.0; for (int q = i; q <= j; q++) a += S2[(size_t)i * sv + q] * S1[(size_t)q * sv + j]; S[(size_t)i * sv + j] = a; }
 }
-template <int S>
-static void block_spmm_t(das_solver* s, BlockWork& bw, const Mat& A, const double* X, double* Y, int sv) {
-    hipLaunchKernelGGL(k_block_to_rows<S>, dim3(nblk(s->n, 256)), dim3(256), 0, s->stream, s->n, sv, X, s->n, bw.Xr.p);
+static void block_spmm(das_solver* s, BlockWork& bw, const Mat& A, const double* X, double* Y, int sv) {
+    launch_block_to_rows(s->stream, s->n, sv, X, s->n, bw.Xr.p);
     hipEvent_t ev = nullptr;
     s->timer.begin("spmm", s->stream, ev);
-    hipLaunchKernelGGL(k_spmm_wave<S>, dim3(nblk(A.n, 16)), dim3(256), 0, s->stream, A.n, sv, A.rowptr.p, A.col.p, A.val.p, bw.Xr.p, Y, s->n);
+    launch_spmm_wave(s->stream, A.n, sv, A.rowptr.p, A.col.p, A.val.p, bw.Xr.p, Y, s->n);
     s->timer.end("spmm", s->stream, ev);
-}
-static void block_spmm(das_solver* s, BlockWork& bw, const Mat& A, const double* X, double* Y, int sv) {
-    if (sv <= 2) block_spmm_t<2>(s, bw, A, X, Y, sv);
-    else if (sv <= 4) block_spmm_t<4>(s, bw, A, X, Y, sv);
-    else block_spmm_t<8>(s, bw, A, X, Y, sv);
 }
 
 static int run_block_gmres(das_solver* s, das_ksp* k, int sv, const double* d_B, double* d_X) {
@@ -3745,7 +3811,7 @@ static int run_block_gmres(das_solver* s, das_ksp* k, int sv, const double* d_B,
             }
         if (bw.Cdev.n < (size_t)K * sv) bw.Cdev.alloc((size_t)K * sv + 1024);
         DAS_HIP(hipMemcpyAsync(bw.Cdev.p, Y.data(), (size_t)K * sv * sizeof(double), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_block_lincomb, dim3(nblk(n, B)), dim3(B), 0, st, n, K, sv, bw.V.p, n, bw.Cdev.p, bw.W.p, n);
+        launch_block_lincomb(st, n, K, sv, bw.V.p, n, bw.Cdev.p, bw.W.p, n);
         pc_apply_block(s, k, bw.W.p, bw.Z.p, sv);
         hipLaunchKernelGGL(k_axpby, dim3(nblk((long long)sv * n, B)), dim3(B), 0, st, (long long)sv * n, 1.0, bw.Z.p, 1.0, d_X);
         // true residuals
@@ -3840,7 +3906,7 @@ static int run_newton_primal(das_solver* s, int maxSteps, double relTol, double 
     auto residual_at = [&](const double* W, double* R) { eval_residual<double>(s->dm, s->cp, prm, W, R, s->wk, s->d_phiF.p, s->d_Told.p, st); };
     // a scratch KSP just for norms before the first preconditioner exists
     std::unique_ptr<das_ksp> scratch(new das_ksp);
-    scratch->partial.alloc((size_t)2 * nblk(n, MD_CHUNK));
+    scratch->partial.alloc(multidot_partial_size(n, 1));
     scratch->hdev.alloc(8);
     residual_at(s->d_W.p, Rc.p);
     double rn = device_norm2(s, scratch.get(), Rc.p);
@@ -3875,7 +3941,7 @@ static int run_newton_primal(das_solver* s, int maxSteps, double relTol, double 
         sincePC++;
         s->fwd.on = true;
         s->fwd.invTau = 1.0 / tau;
-        hipLaunchKernelGGL(k_scale_to, dim3(nblk(n, B)), dim3(B), 0, st, n, -1.0, Rc.p, rhs.p);
+        launch_scale_to(st, n, -1.0, (const double*)Rc.p, (double*)rhs.p, (const float*)nullptr, (float*)nullptr);
         run_gmres(s, k.get(), rhs.p, dw.p, 0);
         s->fwd.on = false;
         info.linIters += k->iters;
@@ -3932,11 +3998,98 @@ static int run_newton_primal(das_solver* s, int maxSteps, double relTol, double 
 // launch helpers of the tuning hook das_debug_orth_bench (templates cannot sit inside the extern "C" block)
 template <int ROWS>
 static void orth_bench_dots(long long n, int K, const double* V, const double* w, double* partial) {
-    hipLaunchKernelGGL((k_multidot2<ROWS, double, double>), dim3(nblk(n, 256 * ROWS)), dim3(256), 0, 0, n, K, (const double*)V, n, (const double*)(V + (long long)(K - 1) * n), (const double*)w, partial, 4LL * nblk(n, 256 * ROWS));
+    launch_multidot2_pass<ROWS, double>(0, n, K, V, n, V + (long long)(K - 1) * n, w, partial);
 }
 template <int UNROLL, int RPT>
 static void orth_bench_update(long long n, int j, double* V, const double* sc, const double* w) {
-    hipLaunchKernelGGL((k_dcgs2_update<UNROLL, RPT>), dim3(nblk(n, 256 * RPT)), dim3(256), 0, 0, n, j, V, n, sc, 0.5, 1.0, w);
+    launch_dcgs2_update<UNROLL, RPT, double>(0, n, j, V, n, sc, 0.5, 1.0, w, (float*)nullptr);
+}
+
+// ---- bodies of the test-only entries das_debug_krylov_* (tests/test_gpu_krylov_kernels.py) --------------------------------
+// They upload the caller's arrays, run the launch helpers the solver runs (null stream) and download the result.  Nothing in the
+// product path calls them.  Basis formats: 0 = fp64, 1 = fp32, 2 = split (float hi, the lo array n floats further inside a slot).
+enum { KRY_FP64 = 0, KRY_FP32 = 1, KRY_SPLIT = 2 };
+static void krylov_check_basis(const std::string& who, long long n, long long nvec, int fmt, const void* V, long long ld) {
+    DAS_CHECK(n > 0 && nvec > 0, DAS_ERR_ARG, who + ": sizes must be positive");
+    DAS_CHECK(fmt == KRY_FP64 || fmt == KRY_FP32 || fmt == KRY_SPLIT, DAS_ERR_ARG, who + ": fmt is 0 (fp64), 1 (fp32) or 2 (split)");
+    DAS_CHECK(V, DAS_ERR_ARG, who + ": null basis");
+    DAS_CHECK(ld >= (fmt == KRY_SPLIT ? 2 * n : n), DAS_ERR_ARG, who + ": leading dimension below n (split: below 2 n)");
+}
+static void krylov_check_block(const std::string& who, long long n, int K, int sv) {
+    DAS_CHECK(n > 0 && K > 0, DAS_ERR_ARG, who + ": sizes must be positive");
+    DAS_CHECK(sv >= 1 && sv <= 8, DAS_ERR_ARG, who + ": 1 to 8 right-hand sides");
+}
+static void krylov_debug_sync() {
+    DAS_HIP(hipGetLastError());
+    DAS_HIP(hipStreamSynchronize(0));
+}
+template <class VT>
+static float* krylov_lo(VT* V, long long n, bool split) { return split ? reinterpret_cast<float*>(V) + n : nullptr; }
+template <class VT>
+static void debug_krylov_dots2(long long n, int K, const void* V, long long ld, const double* v, double* out) {
+    DevBuf<VT> dV;
+    dV.upload((const VT*)V, (size_t)K * ld);
+    DevBuf<double> dv, partial(multidot2_partial_size(n, K)), dout((size_t)2 * K);
+    dv.upload(v, n);
+    launch_multidot2<VT>(0, n, K, (const VT*)dV.p, ld, (const VT*)(dV.p + (long long)(K - 1) * ld), (const double*)dv.p, partial.p, dout.p);
+    krylov_debug_sync();
+    dout.download(out, (size_t)2 * K);
+}
+template <class VT>
+static void debug_krylov_dcgs2_update(long long n, int j, bool split, void* V, long long ld, int nslots, const double* sc, double gamma, double ralpha,
+                                      const double* v) {
+    DevBuf<VT> dV;
+    dV.upload((const VT*)V, (size_t)nslots * ld);
+    DevBuf<double> dsc((size_t)std::max(1, 2 * j)), dv;
+    if (j > 0) dsc.upload(sc, (size_t)2 * j);
+    dv.upload(v, n);
+    launch_dcgs2_update<DCGS2_UNROLL, DCGS2_RPT, VT>(0, n, j, dV.p, ld, (const double*)dsc.p, gamma, ralpha, (const double*)dv.p, krylov_lo(dV.p, n, split));
+    krylov_debug_sync();
+    dV.download((VT*)V, (size_t)nslots * ld);
+}
+template <class VT>
+static void debug_krylov_multidot(long long n, int m, const void* V, long long ld, const double* w, double* out) {
+    DevBuf<VT> dV((size_t)std::max<long long>(1, m * ld));
+    if (m > 0) dV.upload((const VT*)V, (size_t)m * ld);
+    DevBuf<double> dw, partial(multidot_partial_size(n, m)), dout((size_t)m + 1);
+    dw.upload(w, n);
+    launch_multidot<VT>(0, n, m, (const VT*)dV.p, ld, (const double*)dw.p, partial.p, dout.p);
+    krylov_debug_sync();
+    dout.download(out, (size_t)m + 1);
+}
+template <class VT, class WT>
+static void debug_krylov_multiaxpy(long long n, int m, bool split, const void* V, long long ld, const double* h, void* w, long long wlen) {
+    DevBuf<VT> dV;
+    dV.upload((const VT*)V, (size_t)m * ld);
+    DevBuf<double> dh;
+    dh.upload(h, m);
+    DevBuf<WT> dw;
+    dw.upload((const WT*)w, (size_t)wlen);
+    launch_multiaxpy(0, n, m, (const VT*)dV.p, ld, (const double*)dh.p, dw.p, (const float*)krylov_lo(dV.p, n, split));
+    krylov_debug_sync();
+    dw.download((WT*)w, (size_t)wlen);
+}
+template <class VT>
+static void debug_krylov_lincomb(long long n, int m, bool split, const void* V, long long ld, const double* c, double* y, long long ylen) {
+    DevBuf<VT> dV;
+    dV.upload((const VT*)V, (size_t)m * ld);
+    DevBuf<double> dc, dy;
+    dc.upload(c, m);
+    dy.upload(y, (size_t)ylen);
+    launch_lincomb(0, n, m, (const VT*)dV.p, ld, (const double*)dc.p, dy.p, (const float*)krylov_lo(dV.p, n, split));
+    krylov_debug_sync();
+    dy.download(y, (size_t)ylen);
+}
+// xsplit / ysplit: the lo array sits n floats after the hi array, as in a basis slot
+template <class TI, class TO>
+static void debug_krylov_scale_to(long long n, double a, bool xsplit, bool ysplit, const void* x, void* y, long long ylen) {
+    DevBuf<TI> dx;
+    dx.upload((const TI*)x, (size_t)(xsplit ? 2 * n : n));
+    DevBuf<TO> dy;
+    dy.upload((const TO*)y, (size_t)ylen);
+    launch_scale_to(0, n, a, (const TI*)dx.p, dy.p, (const float*)krylov_lo(dx.p, n, xsplit), krylov_lo(dy.p, n, ysplit));
+    krylov_debug_sync();
+    dy.download((TO*)y, (size_t)ylen);
 }
 
 extern "C" {
@@ -6094,6 +6247,159 @@ int das_debug_orth_bench(long long n, int K, int reps, int rows, int unroll, int
     DAS_UPD(4, 1); DAS_UPD(8, 1); DAS_UPD(16, 1); DAS_UPD(4, 2); DAS_UPD(8, 2); DAS_UPD(4, 4); DAS_UPD(8, 4);
 #undef DAS_UPD
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    return DAS_OK;
+    DAS_CATCH
+}
+
+// Test-only entries (tests/test_gpu_krylov_kernels.py): every Krylov kernel of the GMRES engine on caller data through the launch
+// helpers the solver uses.  No solver handle, nothing in the product path calls them.
+int das_debug_krylov_dots2(long long n, int K, int fmt, const void* V, long long ld, const double* v, double* out) {
+    DAS_TRY
+    krylov_check_basis("das_debug_krylov_dots2", n, K, fmt, V, ld);
+    DAS_CHECK(v && out, DAS_ERR_ARG, "das_debug_krylov_dots2: null pointer");
+    if (fmt == KRY_FP64) debug_krylov_dots2<double>(n, K, V, ld, v, out);
+    else debug_krylov_dots2<float>(n, K, V, ld, v, out);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_krylov_dcgs2_update(long long n, int j, int fmt, void* V, long long ld, int nslots, const double* sc, double gamma, double ralpha,
+                                  const double* v) {
+    DAS_TRY
+    DAS_CHECK(j >= 0, DAS_ERR_ARG, "das_debug_krylov_dcgs2_update: j must not be negative");
+    krylov_check_basis("das_debug_krylov_dcgs2_update", n, nslots, fmt, V, ld);
+    DAS_CHECK(nslots >= j + 2, DAS_ERR_ARG, "das_debug_krylov_dcgs2_update: the basis needs slots 0 .. j + 1");
+    DAS_CHECK(v && (sc || j == 0), DAS_ERR_ARG, "das_debug_krylov_dcgs2_update: null pointer");
+    if (fmt == KRY_FP64) debug_krylov_dcgs2_update<double>(n, j, false, V, ld, nslots, sc, gamma, ralpha, v);
+    else debug_krylov_dcgs2_update<float>(n, j, fmt == KRY_SPLIT, V, ld, nslots, sc, gamma, ralpha, v);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_krylov_multidot(long long n, int m, int fmt, const void* V, long long ld, const double* w, double* out) {
+    DAS_TRY
+    DAS_CHECK(m >= 0, DAS_ERR_ARG, "das_debug_krylov_multidot: m must not be negative");
+    krylov_check_basis("das_debug_krylov_multidot", n, std::max(m, 1), fmt, m > 0 ? V : (const void*)w, ld);
+    DAS_CHECK(w && out, DAS_ERR_ARG, "das_debug_krylov_multidot: null pointer");
+    if (fmt == KRY_FP64) debug_krylov_multidot<double>(n, m, V, ld, w, out);
+    else debug_krylov_multidot<float>(n, m, V, ld, w, out);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_krylov_multiaxpy(long long n, int m, int fmt, const void* V, long long ld, const double* h, int wfloat, void* w, long long wlen) {
+    DAS_TRY
+    krylov_check_basis("das_debug_krylov_multiaxpy", n, m, fmt, V, ld);
+    DAS_CHECK(h && w, DAS_ERR_ARG, "das_debug_krylov_multiaxpy: null pointer");
+    DAS_CHECK(wlen >= n, DAS_ERR_ARG, "das_debug_krylov_multiaxpy: w shorter than n");
+    DAS_CHECK(!wfloat || fmt == KRY_FP32, DAS_ERR_ARG, "das_debug_krylov_multiaxpy: a float w goes with the fp32 basis only");
+    if (fmt == KRY_FP64) debug_krylov_multiaxpy<double, double>(n, m, false, V, ld, h, w, wlen);
+    else if (wfloat) debug_krylov_multiaxpy<float, float>(n, m, false, V, ld, h, w, wlen);
+    else debug_krylov_multiaxpy<float, double>(n, m, fmt == KRY_SPLIT, V, ld, h, w, wlen);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_krylov_lincomb(long long n, int m, int fmt, const void* V, long long ld, const double* c, double* y, long long ylen) {
+    DAS_TRY
+    krylov_check_basis("das_debug_krylov_lincomb", n, m, fmt, V, ld);
+    DAS_CHECK(c && y, DAS_ERR_ARG, "das_debug_krylov_lincomb: null pointer");
+    DAS_CHECK(ylen >= n, DAS_ERR_ARG, "das_debug_krylov_lincomb: y shorter than n");
+    if (fmt == KRY_FP64) debug_krylov_lincomb<double>(n, m, false, V, ld, c, y, ylen);
+    else debug_krylov_lincomb<float>(n, m, fmt == KRY_SPLIT, V, ld, c, y, ylen);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_krylov_scale_to(long long n, double a, int use, const void* x, void* y, long long ylen) {
+    DAS_TRY
+    DAS_CHECK(n > 0, DAS_ERR_ARG, "das_debug_krylov_scale_to: n must be positive");
+    DAS_CHECK(use >= 0 && use <= 4, DAS_ERR_ARG, "das_debug_krylov_scale_to: use is 0 (double -> double), 1 (double -> float), 2 (double -> split), 3 (split -> double) or 4 (float -> double)");
+    DAS_CHECK(x && y, DAS_ERR_ARG, "das_debug_krylov_scale_to: null pointer");
+    DAS_CHECK(ylen >= (use == 2 ? 2 * n : n), DAS_ERR_ARG, "das_debug_krylov_scale_to: y shorter than n (split: 2 n)");
+    if (use == 0) debug_krylov_scale_to<double, double>(n, a, false, false, x, y, ylen);
+    else if (use == 1) debug_krylov_scale_to<double, float>(n, a, false, false, x, y, ylen);
+    else if (use == 2) debug_krylov_scale_to<double, float>(n, a, false, true, x, y, ylen);
+    else if (use == 3) debug_krylov_scale_to<float, double>(n, a, true, false, x, y, ylen);
+    else debug_krylov_scale_to<float, double>(n, a, false, false, x, y, ylen);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_krylov_block_tn(long long n, int K, int s, const double* V, long long ldv, long long voff, const double* W, long long ldw, double* C) {
+    DAS_TRY
+    krylov_check_block("das_debug_krylov_block_tn", n, K, s);
+    DAS_CHECK(V && W && C, DAS_ERR_ARG, "das_debug_krylov_block_tn: null pointer");
+    DAS_CHECK(ldv >= n && ldw >= n && voff >= 0, DAS_ERR_ARG, "das_debug_krylov_block_tn: leading dimension below n or negative offset");
+    DevBuf<double> dV, dW, partial(tsgemm_partial_size(K)), dC((size_t)K * s);
+    dV.upload(V, (size_t)(voff + (long long)K * ldv));
+    dW.upload(W, (size_t)s * ldw);
+    launch_tsgemm_tn(0, n, K, s, dV.p + voff, ldv, dW.p, ldw, partial.p, dC.p);
+    krylov_debug_sync();
+    dC.download(C, (size_t)K * s);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_krylov_block_nn_sub(long long n, int K, int s, const double* V, long long ldv, const double* C, double* W, long long ldw) {
+    DAS_TRY
+    krylov_check_block("das_debug_krylov_block_nn_sub", n, K, s);
+    DAS_CHECK(V && W && C, DAS_ERR_ARG, "das_debug_krylov_block_nn_sub: null pointer");
+    DAS_CHECK(ldv >= n && ldw >= n, DAS_ERR_ARG, "das_debug_krylov_block_nn_sub: leading dimension below n");
+    DevBuf<double> dV, dW, dC;
+    dV.upload(V, (size_t)K * ldv);
+    dW.upload(W, (size_t)s * ldw);
+    dC.upload(C, (size_t)K * s);
+    launch_tsgemm_nn_sub(0, n, K, s, dV.p, ldv, dC.p, dW.p, ldw);
+    krylov_debug_sync();
+    dW.download(W, (size_t)s * ldw);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_krylov_block_right_mult(long long n, int s, double* W, long long ldw, const double* T) {
+    DAS_TRY
+    krylov_check_block("das_debug_krylov_block_right_mult", n, 1, s);
+    DAS_CHECK(W && T, DAS_ERR_ARG, "das_debug_krylov_block_right_mult: null pointer");
+    DAS_CHECK(ldw >= n, DAS_ERR_ARG, "das_debug_krylov_block_right_mult: leading dimension below n");
+    DevBuf<double> dW, dT;
+    dW.upload(W, (size_t)s * ldw);
+    dT.upload(T, (size_t)s * s);
+    launch_block_right_mult(0, n, s, dW.p, ldw, dT.p);
+    krylov_debug_sync();
+    dW.download(W, (size_t)s * ldw);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_krylov_block_lincomb(long long n, int K, int s, const double* V, long long ldv, const double* C, double* Y, long long ldy) {
+    DAS_TRY
+    krylov_check_block("das_debug_krylov_block_lincomb", n, K, s);
+    DAS_CHECK(V && C && Y, DAS_ERR_ARG, "das_debug_krylov_block_lincomb: null pointer");
+    DAS_CHECK(ldv >= n && ldy >= n, DAS_ERR_ARG, "das_debug_krylov_block_lincomb: leading dimension below n");
+    DevBuf<double> dV, dC, dY;
+    dV.upload(V, (size_t)K * ldv);
+    dC.upload(C, (size_t)K * s);
+    dY.upload(Y, (size_t)s * ldy);
+    launch_block_lincomb(0, n, K, s, dV.p, ldv, dC.p, dY.p, ldy);
+    krylov_debug_sync();
+    dY.download(Y, (size_t)s * ldy);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_krylov_block_spmm(long long n, int s, const long long* rp, const int* ci, const double* val, const double* X, long long ldx, double* Y,
+                                long long ldy) {
+    DAS_TRY
+    krylov_check_block("das_debug_krylov_block_spmm", n, 1, s);
+    DAS_CHECK(rp && X && Y, DAS_ERR_ARG, "das_debug_krylov_block_spmm: null pointer");
+    DAS_CHECK(ldx >= n && ldy >= n, DAS_ERR_ARG, "das_debug_krylov_block_spmm: leading dimension below n");
+    DAS_CHECK(rp[0] == 0, DAS_ERR_ARG, "das_debug_krylov_block_spmm: rowptr[0] must be 0");
+    for (long long i = 0; i < n; i++) DAS_CHECK(rp[i + 1] >= rp[i], DAS_ERR_ARG, "das_debug_krylov_block_spmm: rowptr decreases");
+    const long long nnz = rp[n];
+    DAS_CHECK(nnz == 0 || (ci && val), DAS_ERR_ARG, "das_debug_krylov_block_spmm: null pointer");
+    for (long long k = 0; k < nnz; k++) DAS_CHECK(ci[k] >= 0 && ci[k] < n, DAS_ERR_ARG, "das_debug_krylov_block_spmm: column index out of range");
+    DevBuf<long long> drp;
+    drp.upload(rp, (size_t)n + 1);
+    DevBuf<int> dci((size_t)std::max<long long>(1, nnz));
+    DevBuf<double> dval((size_t)std::max<long long>(1, nnz)), dX, dY, dXr((size_t)n * spmm_width(s));
+    if (nnz > 0) { dci.upload(ci, (size_t)nnz); dval.upload(val, (size_t)nnz); }
+    dX.upload(X, (size_t)s * ldx);
+    dY.upload(Y, (size_t)s * ldy);
+    launch_block_to_rows(0, n, s, dX.p, ldx, dXr.p);
+    launch_spmm_wave(0, n, s, drp.p, dci.p, dval.p, dXr.p, dY.p, ldy);
+    krylov_debug_sync();
+    dY.download(Y, (size_t)s * ldy);
     return DAS_OK;
     DAS_CATCH
 }

@@ -488,6 +488,40 @@ double das_timer_avg_ms(das_solver_t* s, const char* name);
  * `rows` rows per thread; update with `unroll` basis vectors in flight and `rpt` rows per thread) on synthetic vectors of
  * length n against K basis vectors; -1 for a variant that is not compiled in */
 int das_debug_orth_bench(long long n, int K, int reps, int rows, int unroll, int rpt, double* ms_dots, double* ms_update);
+/* ---- TEST-ONLY entries (tests/test_gpu_krylov_kernels.py).  Nothing in the product path calls them and no binding should: they exist
+ * so that every Krylov kernel of the GMRES engine can be compared with a high-precision reference on caller data, one kernel at a
+ * time.  They need the device but no solver handle: host arrays are uploaded, the launch helper THE SOLVER USES is run on the null
+ * stream, the result is downloaded.  Bad arguments (sizes <= 0, s outside 1..8, a leading dimension below n, null pointers) return
+ * DAS_ERR_ARG with a message.
+ * Basis storage `fmt`: 0 = fp64 (V: double, slot stride ld >= n), 1 = fp32 (V: float, ld >= n), 2 = split (V: float, slot = hi
+ * array followed by the lo array n floats further, ld >= 2 n).  Arrays that a kernel writes are uploaded and downloaded whole, so
+ * that the caller can put a sentinel around the written range and find it untouched. */
+/* k_multidot2 + k_reduce: out[0..K) = V^T u, out[K..2K) = V^T v with u = slot K - 1 (split: its hi array) */
+int das_debug_krylov_dots2(long long n, int K, int fmt, const void* V, long long ld, const double* v, double* out);
+/* k_dcgs2_update on slots 0..j+1 of V (nslots >= j + 2 slots, in place): sc = [s (j); c (j)] */
+int das_debug_krylov_dcgs2_update(long long n, int j, int fmt, void* V, long long ld, int nslots, const double* sc, double gamma, double ralpha,
+                                  const double* v);
+/* k_multidot + k_reduce: out[0..m) = V^T w, out[m] = w.w (m >= 0; fp32 and split read the hi array) */
+int das_debug_krylov_multidot(long long n, int m, int fmt, const void* V, long long ld, const double* w, double* out);
+/* k_multiaxpy: w -= sum_i h_i V_i in place on wlen >= n entries (wfloat: w is float, fp32 basis only) */
+int das_debug_krylov_multiaxpy(long long n, int m, int fmt, const void* V, long long ld, const double* h, int wfloat, void* w, long long wlen);
+/* k_lincomb: y[0..n) = sum_i c_i V_i, y holds ylen >= n entries */
+int das_debug_krylov_lincomb(long long n, int m, int fmt, const void* V, long long ld, const double* c, double* y, long long ylen);
+/* k_scale_to, y = a x: use 0 double -> double, 1 double -> float, 2 double -> split (lo at y + n), 3 split -> double (lo at x + n),
+ * 4 float -> double; y holds ylen >= n (use 2: 2 n) entries of its type */
+int das_debug_krylov_scale_to(long long n, double a, int use, const void* x, void* y, long long ylen);
+/* block_tn (k_tsgemm_tn + k_tsgemm_reduce): C (K x s row-major) = V^T W; the block V starts voff doubles into the uploaded array
+ * (voff + K ldv doubles); even leading dimensions with an odd voff are rejected (16-byte loads) */
+int das_debug_krylov_block_tn(long long n, int K, int s, const double* V, long long ldv, long long voff, const double* W, long long ldw, double* C);
+/* block_nn_sub (k_tsgemm_nn_sub): W -= V C in place */
+int das_debug_krylov_block_nn_sub(long long n, int K, int s, const double* V, long long ldv, const double* C, double* W, long long ldw);
+/* k_block_right_mult: W <- W T (T: s x s row-major) in place */
+int das_debug_krylov_block_right_mult(long long n, int s, double* W, long long ldw, const double* T);
+/* k_block_lincomb: Y_r = sum_i V_i C[i s + r] */
+int das_debug_krylov_block_lincomb(long long n, int K, int s, const double* V, long long ldv, const double* C, double* Y, long long ldy);
+/* block_spmm (k_block_to_rows<S> + k_spmm_wave<S>, S = 2, 4 or 8 chosen from s): Y_r = A X_r for a square CSR matrix */
+int das_debug_krylov_block_spmm(long long n, int s, const long long* rowptr, const int* colidx, const double* vals, const double* X, long long ldx,
+                                double* Y, long long ldy);
 long long das_timer_count(das_solver_t* s, const char* name);
 void das_timer_reset(das_solver_t* s);
 void das_timer_enable(das_solver_t* s, int on);
