@@ -301,6 +301,9 @@ _SIGS = {
     "das_get_elapsed_cpu_time": (C.c_double, [_VP]),
     "das_timer_avg_ms": (C.c_double, [_VP, C.c_char_p]),
     "das_debug_orth_bench": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "das_debug_orth_bench_split": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "das_debug_set_orth_wide": (C.c_int, [C.c_int, C.POINTER(C.c_int)]),
+    "das_debug_krylov_wide_eligible": (C.c_int, [C.c_longlong, C.c_int, C.c_longlong, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     # test-only entries (tests/test_gpu_krylov_kernels.py): the Krylov kernels on caller data, never called by the bindings
     "das_debug_krylov_dots2": (C.c_int, [C.c_longlong, C.c_int, C.c_int, _VP, C.c_longlong, c_double_p, c_double_p]),
     "das_debug_krylov_dcgs2_update": (C.c_int, [C.c_longlong, C.c_int, C.c_int, _VP, C.c_longlong, C.c_int, c_double_p, C.c_double, C.c_double, c_double_p]),

@@ -650,6 +650,214 @@ __global__ __launch_bounds__(256) void k_dcgs2_update(long long n, int j, VT* __
         if (Vlo) { Vlo[(long long)j * ldv + k] = (float)(qj - (double)qh); Vlo[(long long)(j + 1) * ldv + k] = (float)(un - (double)uh); }
     }
 }
+// ---- 16-byte-load variants of the two kernels above for the float basis (fp32 and split storage) -------------------------------
+// A lane owns groups of 4 consecutive rows and reads the hi (and lo) floats of a group as ONE 16-byte load: 1 KiB per wave
+// instruction, a quarter of the load instructions of the one-dword-per-lane kernels.  The vector's start is uniform and stepped by
+// ldv from vector to vector; the lane's part of the address is a 32-bit byte offset computed once (n < 2^30).  A workgroup whose
+// rows all exist (FULL) uses the 16-byte loads and stores; the last one goes element by element with clamped loads (row n - 1 of the
+// same vector: real data, never the padding behind row n) and masked sums / stores.  They need 16-byte aligned V, Vlo, u, v and
+// ldv % 4 == 0 (orth_wide_ok); everything else runs the kernels above.  Sums in fp64 as above; only the order of the rows differs.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+template <bool FULL, bool NT>
+__device__ __forceinline__ f32x4 ld_group(const float* __restrict__ vec, const unsigned (&bo)[4]) {
+    const char* b = reinterpret_cast<const char*>(vec);
+    if (FULL) {
+        const f32x4* p = reinterpret_cast<const f32x4*>(b + bo[0]);
+        return NT ? __builtin_nontemporal_load(p) : *p;
+    }
+    f32x4 r;
+    r.x = *reinterpret_cast<const float*>(b + bo[0]);
+    r.y = *reinterpret_cast<const float*>(b + bo[1]);
+    r.z = *reinterpret_cast<const float*>(b + bo[2]);
+    r.w = *reinterpret_cast<const float*>(b + bo[3]);
+    return r;
+}
+// byte offsets of the 4 rows of the group that starts at row k (clamped to row n - 1 unless FULL)
+template <bool FULL>
+__device__ __forceinline__ void group_offsets(long long k, long long n, unsigned (&bo)[4]) {
+#pragma unroll
+    for (int e = 0; e < 4; e++) bo[e] = (unsigned)((FULL ? k + e : min(k + e, n - 1)) * 4);
+}
+// R4 groups of 4 rows per lane (group t of a lane starts at row 4 (256 (R4 blockIdx + t) + threadIdx)); partial sums as k_multidot2
+template <int R4, bool FULL, bool NT>
+__device__ __forceinline__ void multidot2w_body(long long n, int K, const float* __restrict__ V, long long ldv, const float* __restrict__ u,
+                                                const double* __restrict__ v, double* __restrict__ partial, long long nbw) {
+    const int lane = threadIdx.x & 63, g = lane >> 3;
+    const long long base = ((long long)blockIdx.x * (256 * R4) + threadIdx.x) * 4;
+    const long long slot = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    unsigned bo[R4][4];
+    float ur[R4][4];
+    double vr[R4][4];
+#pragma unroll
+    for (int t = 0; t < R4; t++) {
+        const long long k = base + 1024LL * t;
+        group_offsets<FULL>(k, n, bo[t]);
+        const f32x4 uu = ld_group<FULL, false>(u, bo[t]);
+        ur[t][0] = uu.x; ur[t][1] = uu.y; ur[t][2] = uu.z; ur[t][3] = uu.w;
+        if (FULL) {
+            const f64x2 a = *reinterpret_cast<const f64x2*>(v + k), b = *reinterpret_cast<const f64x2*>(v + k + 2);
+            vr[t][0] = a.x; vr[t][1] = a.y; vr[t][2] = b.x; vr[t][3] = b.y;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const bool in = k + e < n;
+                vr[t][e] = in ? v[min(k + e, n - 1)] : 0.0;
+                ur[t][e] = in ? ur[t][e] : 0.f;
+            }
+        }
+    }
+    const float* v0 = V;  // start of vector i0 (uniform)
+    for (int i0 = 0; i0 < K; i0 += 4, v0 += 4 * ldv) {
+        f32x4 x[4][R4];
+        double acc[8];
+        // all 4 x R4 loads are issued before the first use (two loops, as in multidot2_body)
+#pragma unroll
+        for (int ii = 0; ii < 4; ii++) {
+            const float* vi = v0 + (long long)min(ii, K - 1 - i0) * ldv;  // beyond K - 1: vector K - 1 again, its sums are not stored
+#pragma unroll
+            for (int t = 0; t < R4; t++) x[ii][t] = ld_group<FULL, NT>(vi, bo[t]);
+        }
+#pragma unroll
+        for (int ii = 0; ii < 4; ii++) {
+            double a = 0.0, b = 0.0;
+#pragma unroll
+            for (int t = 0; t < R4; t++) {
+                const double x0 = (double)x[ii][t].x, x1 = (double)x[ii][t].y, x2 = (double)x[ii][t].z, x3 = (double)x[ii][t].w;
+                a += x0 * (double)ur[t][0]; b += x0 * vr[t][0];
+                a += x1 * (double)ur[t][1]; b += x1 * vr[t][1];
+                a += x2 * (double)ur[t][2]; b += x2 * vr[t][2];
+                a += x3 * (double)ur[t][3]; b += x3 * vr[t][3];
+            }
+            acc[2 * ii] = a;
+            acc[2 * ii + 1] = b;
+        }
+        double a4[4], a2[2], a1;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const double snd = (g & 4) ? acc[i] : acc[i + 4], keep = (g & 4) ? acc[i + 4] : acc[i];
+            a4[i] = keep + __shfl_xor(snd, 32, 64);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const double snd = (g & 2) ? a4[i] : a4[i + 2], keep = (g & 2) ? a4[i + 2] : a4[i];
+            a2[i] = keep + __shfl_xor(snd, 16, 64);
+        }
+        {
+            const double snd = (g & 1) ? a2[0] : a2[1], keep = (g & 1) ? a2[1] : a2[0];
+            a1 = keep + __shfl_xor(snd, 8, 64);
+        }
+        a1 += __shfl_xor(a1, 1, 64);
+        a1 += __shfl_xor(a1, 2, 64);
+        a1 += __shfl_xor(a1, 4, 64);  // lane group g: the wave's sum number g = 2 ii + r
+        const int i = i0 + (g >> 1);
+        if ((lane & 7) == 0 && i < K) partial[((long long)(g & 1) * K + i) * nbw + slot] = a1;
+    }
+}
+template <int R4, bool NT>
+__global__ __launch_bounds__(256) void k_multidot2w(long long n, int K, const float* __restrict__ V, long long ldv, const float* __restrict__ u,
+                                                    const double* __restrict__ v, double* __restrict__ partial, long long nbw) {
+    if ((long long)(blockIdx.x + 1) * (1024 * R4) <= n) multidot2w_body<R4, true, NT>(n, K, V, ldv, u, v, partial, nbw);
+    else multidot2w_body<R4, false, NT>(n, K, V, ldv, u, v, partial, nbw);
+}
+// the fused update with RPT4 groups of 4 rows per lane and UNROLL basis vectors (hi and lo: 2 x UNROLL x RPT4 16-byte loads) in flight
+template <int UNROLL, int RPT4, bool FULL, bool NT>
+__device__ __forceinline__ void dcgs2w_body(long long n, int j, float* __restrict__ V, long long ldv, const double* __restrict__ sc, double gamma,
+                                            double ralpha, const double* __restrict__ v, float* __restrict__ Vlo) {
+    const long long base = ((long long)blockIdx.x * (256 * RPT4) + threadIdx.x) * 4;
+    const double* s = sc;
+    const double* c = sc + j;
+    unsigned bo[RPT4][4];
+    double as[RPT4][4], ac[RPT4][4];
+#pragma unroll
+    for (int r = 0; r < RPT4; r++) {
+        group_offsets<FULL>(base + 1024LL * r, n, bo[r]);
+#pragma unroll
+        for (int e = 0; e < 4; e++) { as[r][e] = 0.0; ac[r][e] = 0.0; }
+    }
+    const float* h0 = V;    // start of vector i (uniform), hi and lo
+    const float* l0 = Vlo;
+    for (int i = 0; i < j; i += UNROLL, h0 += UNROLL * ldv, l0 += (Vlo ? UNROLL * ldv : 0)) {
+        f32x4 qh[UNROLL][RPT4], ql[UNROLL][RPT4];
+        // beyond j - 1: vector j - 1 again with zero coefficients (never slot j, which this kernel writes)
+#pragma unroll
+        for (int t = 0; t < UNROLL; t++) {
+            const float* hv = h0 + (long long)min(t, j - 1 - i) * ldv;
+#pragma unroll
+            for (int r = 0; r < RPT4; r++) qh[t][r] = ld_group<FULL, NT>(hv, bo[r]);
+        }
+        if (Vlo) {
+#pragma unroll
+            for (int t = 0; t < UNROLL; t++) {
+                const float* lv = l0 + (long long)min(t, j - 1 - i) * ldv;
+#pragma unroll
+                for (int r = 0; r < RPT4; r++) ql[t][r] = ld_group<FULL, NT>(lv, bo[r]);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < UNROLL; t++) {
+            const bool in = i + t < j;
+            const double st = in ? s[min(i + t, j - 1)] : 0.0, ct = in ? c[min(i + t, j - 1)] : 0.0;
+#pragma unroll
+            for (int r = 0; r < RPT4; r++) {
+                double q[4] = {(double)qh[t][r].x, (double)qh[t][r].y, (double)qh[t][r].z, (double)qh[t][r].w};
+                if (Vlo) { q[0] += (double)ql[t][r].x; q[1] += (double)ql[t][r].y; q[2] += (double)ql[t][r].z; q[3] += (double)ql[t][r].w; }
+#pragma unroll
+                for (int e = 0; e < 4; e++) { as[r][e] += st * q[e]; ac[r][e] += ct * q[e]; }
+            }
+        }
+    }
+    float* uh = V + (long long)j * ldv;
+    float* nh = uh + ldv;
+    float* ul = Vlo ? Vlo + (long long)j * ldv : nullptr;
+    float* nl = Vlo ? ul + ldv : nullptr;
+#pragma unroll
+    for (int r = 0; r < RPT4; r++) {
+        const long long k = base + 1024LL * r;
+        if (k >= n) continue;
+        const f32x4 u4 = ld_group<FULL, false>(uh, bo[r]);
+        double u[4] = {(double)u4.x, (double)u4.y, (double)u4.z, (double)u4.w}, vv[4];
+        if (Vlo) {
+            const f32x4 l4 = ld_group<FULL, false>(ul, bo[r]);
+            u[0] += (double)l4.x; u[1] += (double)l4.y; u[2] += (double)l4.z; u[3] += (double)l4.w;
+        }
+        if (FULL) {
+            const f64x2 a = *reinterpret_cast<const f64x2*>(v + k), b = *reinterpret_cast<const f64x2*>(v + k + 2);
+            vv[0] = a.x; vv[1] = a.y; vv[2] = b.x; vv[3] = b.y;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++) vv[e] = v[min(k + e, n - 1)];
+        }
+        float qh[4], qlo[4], nhh[4], nlo[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const double qj = (u[e] - as[r][e]) * ralpha, un = (vv[e] - gamma * u[e] - ac[r][e]) * ralpha;
+            qh[e] = (float)qj; nhh[e] = (float)un;
+            qlo[e] = (float)(qj - (double)qh[e]); nlo[e] = (float)(un - (double)nhh[e]);
+        }
+        if (FULL) {
+            *reinterpret_cast<f32x4*>(uh + k) = f32x4{qh[0], qh[1], qh[2], qh[3]};
+            *reinterpret_cast<f32x4*>(nh + k) = f32x4{nhh[0], nhh[1], nhh[2], nhh[3]};
+            if (Vlo) {
+                *reinterpret_cast<f32x4*>(ul + k) = f32x4{qlo[0], qlo[1], qlo[2], qlo[3]};
+                *reinterpret_cast<f32x4*>(nl + k) = f32x4{nlo[0], nlo[1], nlo[2], nlo[3]};
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                if (k + e >= n) continue;
+                uh[k + e] = qh[e]; nh[k + e] = nhh[e];
+                if (Vlo) { ul[k + e] = qlo[e]; nl[k + e] = nlo[e]; }
+            }
+        }
+    }
+}
+template <int UNROLL, int RPT4, bool NT>
+__global__ __launch_bounds__(256) void k_dcgs2w_update(long long n, int j, float* __restrict__ V, long long ldv, const double* __restrict__ sc,
+                                                       double gamma, double ralpha, const double* __restrict__ v, float* __restrict__ Vlo) {
+    if ((long long)(blockIdx.x + 1) * (1024 * RPT4) <= n) dcgs2w_body<UNROLL, RPT4, true, NT>(n, j, V, ldv, sc, gamma, ralpha, v, Vlo);
+    else dcgs2w_body<UNROLL, RPT4, false, NT>(n, j, V, ldv, sc, gamma, ralpha, v, Vlo);
+}
 // y = sum_i c_i V_i
 template <class VT>
 __global__ __launch_bounds__(256) void k_lincomb(long long n, int m, const VT* __restrict__ V, long long ldv, const double* __restrict__ c,
@@ -685,21 +893,74 @@ static void launch_multidot(hipStream_t st, long long n, int m, const VT* V, lon
 }
 template <int ROWS>
 static inline long long multidot2_nbw(long long n) { return 4LL * nblk(n, 256 * ROWS); }
-static inline size_t multidot2_partial_size(long long n, int K) { return (size_t)2 * K * (size_t)multidot2_nbw<MD2_ROWS>(n); }
+// Shapes of the 16-byte-load kernels (k_multidot2w, k_dcgs2w_update) and whether the launch helpers pick them for an eligible
+// float basis.  MEASURED ON THE FLOAT INSTANTIATIONS (split layout, n = 16 172 600, K = 150 and 352) with das_debug_orth_bench_split /
+// tools/orth_bench.py --split - not inherited from the fp64 shapes above; the table is in profiles/orth_wide_loads_split_basis.md.
+// At K = 352: inner products 3.81 ms (4.30 with k_multidot2<16, float>), non-temporal loads 0.4 ms better than plain ones (u, v stay in
+// the cache); update 7.67 ms (8.95 with k_dcgs2_update<4, 2, float>), plain loads better than non-temporal ones.
+#ifndef MD2W_R4
+#define MD2W_R4 4  // groups of 4 rows per lane of the inner products (16 rows: 184 VGPRs, 2 waves per SIMD)
+#endif
+#ifndef MD2W_NT
+#define MD2W_NT 1  // non-temporal loads of the basis stream in the inner products
+#endif
+#ifndef DCGS2W_UNROLL
+#define DCGS2W_UNROLL 4  // basis vectors in flight in the update
+#endif
+#ifndef DCGS2W_RPT4
+#define DCGS2W_RPT4 2  // groups of 4 rows per lane of the update (8 rows x 4 vectors x hi, lo: 220 VGPRs, 2 waves per SIMD)
+#endif
+#ifndef DCGS2W_NT
+#define DCGS2W_NT 0  // non-temporal loads of the basis stream in the update
+#endif
+#ifndef ORTH_WIDE_DEFAULT
+#define ORTH_WIDE_DEFAULT 1
+#endif
+static int g_orth_wide = ORTH_WIDE_DEFAULT;  // das_debug_set_orth_wide: the tests and the timing tool run both paths of one build
+// the 16-byte path of the float basis: every pointer 16-byte aligned, vectors a multiple of 16 bytes apart, 32-bit byte offsets in a vector
+static inline bool orth_wide_ok(long long n, const void* V, const void* Vlo, long long ldv, const void* u, const void* v) {
+    return n >= 4 && n < (1LL << 30) && (ldv & 3) == 0 && ((((uintptr_t)V | (uintptr_t)Vlo | (uintptr_t)u | (uintptr_t)v) & 15) == 0);
+}
+static inline long long multidot2w_nbw(long long n, int r4) { return 4LL * nblk(n, 1024 * r4); }
+static inline size_t multidot2_partial_size(long long n, int K) {
+    return (size_t)2 * K * (size_t)std::max(multidot2_nbw<MD2_ROWS>(n), multidot2w_nbw(n, MD2W_R4));
+}
 // the inner-product pass alone (the tuning hook times it for several ROWS)
 template <int ROWS, class VT>
 static void launch_multidot2_pass(hipStream_t st, long long n, int K, const VT* V, long long ldv, const VT* u, const double* v, double* partial) {
     hipLaunchKernelGGL((k_multidot2<ROWS, VT, VT>), dim3(nblk(n, 256 * ROWS)), dim3(256), 0, st, n, K, V, ldv, u, v, partial, multidot2_nbw<ROWS>(n));
 }
 // out[0..K) = V^T u, out[K..2K) = V^T v
+template <int R4, bool NT>
+static void launch_multidot2w_pass(hipStream_t st, long long n, int K, const float* V, long long ldv, const float* u, const double* v, double* partial) {
+    hipLaunchKernelGGL((k_multidot2w<R4, NT>), dim3(nblk(n, 1024 * R4)), dim3(256), 0, st, n, K, V, ldv, u, v, partial, multidot2w_nbw(n, R4));
+}
+template <int UNROLL, int RPT4, bool NT>
+static void launch_dcgs2w_update(hipStream_t st, long long n, int j, float* V, long long ldv, const double* sc, double gamma, double ralpha,
+                                 const double* v, float* Vlo) {
+    hipLaunchKernelGGL((k_dcgs2w_update<UNROLL, RPT4, NT>), dim3(nblk(n, 1024 * RPT4)), dim3(256), 0, st, n, j, V, ldv, sc, gamma, ralpha, v, Vlo);
+}
 template <class VT>
 static void launch_multidot2(hipStream_t st, long long n, int K, const VT* V, long long ldv, const VT* u, const double* v, double* partial, double* out) {
+    if constexpr (std::is_same<VT, float>::value) {
+        if (g_orth_wide && orth_wide_ok(n, V, nullptr, ldv, u, v)) {
+            launch_multidot2w_pass<MD2W_R4, MD2W_NT != 0>(st, n, K, V, ldv, u, v, partial);
+            hipLaunchKernelGGL(k_reduce, dim3(2 * K), dim3(256), 0, st, (int)multidot2w_nbw(n, MD2W_R4), (const double*)partial, out);
+            return;
+        }
+    }
     launch_multidot2_pass<MD2_ROWS, VT>(st, n, K, V, ldv, u, v, partial);
     hipLaunchKernelGGL(k_reduce, dim3(2 * K), dim3(256), 0, st, (int)multidot2_nbw<MD2_ROWS>(n), (const double*)partial, out);
 }
 template <int UNROLL, int RPT, class VT>
 static void launch_dcgs2_update(hipStream_t st, long long n, int j, VT* V, long long ldv, const double* sc, double gamma, double ralpha, const double* v,
                                 float* Vlo) {
+    if constexpr (std::is_same<VT, float>::value) {
+        if (g_orth_wide && orth_wide_ok(n, V, Vlo, ldv, nullptr, v)) {
+            launch_dcgs2w_update<DCGS2W_UNROLL, DCGS2W_RPT4, DCGS2W_NT != 0>(st, n, j, V, ldv, sc, gamma, ralpha, v, Vlo);
+            return;
+        }
+    }
     hipLaunchKernelGGL((k_dcgs2_update<UNROLL, RPT, VT>), dim3(nblk(n, 256 * RPT)), dim3(256), 0, st, n, j, V, ldv, sc, gamma, ralpha, v, Vlo);
 }
 template <class VT, class WT>
@@ -2631,7 +2892,8 @@ static void gmres_ws(das_solver* s, das_ksp* k) {
     long long budget = (long long)(32.0 * 1024 * 1024 * 1024);
     auto it = s->opt.i.find("amd.maxKrylovBytes");
     if (it != s->opt.i.end()) budget = it->second;
-    const long long maxVec = std::max<long long>(3, budget / (8 * n));  // vectors the budget holds (restart + 2 of them are needed)
+    const long long nr = (n + 3) / 4 * 4;  // fp64 elements a basis vector occupies at most (float storage pads its rows to a multiple of 4: basis_ld)
+    const long long maxVec = std::max<long long>(3, budget / (8 * nr));  // vectors the budget holds (restart + 2 of them are needed)
     restart = std::max<long long>(1, std::min<long long>(restart, maxVec - 2));
     // the basis: address range for the larger of this restart and what the reference's default restart (1000) would need inside
     // the budget - reserved ONCE, so that a later solve with another restart never frees and re-allocates it; physical memory is
@@ -2639,9 +2901,9 @@ static void gmres_ws(das_solver* s, das_ksp* k) {
     long long wantVec = std::max<long long>(restart + 2, std::min<long long>(maxVec, 1002));
     // the over-reservation is free only on the virtual-memory path (>= 4 GB, VmBuf::reserve); below that the range is one hipMalloc of
     // real memory: then exactly what this restart needs (~2.8 GB per KSP on small cases otherwise)
-    if ((size_t)wantVec * (size_t)n * sizeof(double) < ((size_t)4 << 30) || getenv("DAS_NO_VMM")) wantVec = restart + 2;
-    if (k->V.n < (size_t)((restart + 2) * n) || k->Vn != n) {
-        k->V.reserve((size_t)(wantVec * n));  // (sized for fp64 vectors whatever the storage type of this solve: switching needs no new range)
+    if ((size_t)wantVec * (size_t)nr * sizeof(double) < ((size_t)4 << 30) || getenv("DAS_NO_VMM")) wantVec = restart + 2;
+    if (k->V.n < (size_t)((restart + 2) * nr) || k->Vn != n) {
+        k->V.reserve((size_t)(wantVec * nr));  // (sized for fp64 vectors whatever the storage type of this solve: switching needs no new range)
         k->Vn = n;
     }
     {   // storage type of the basis.  "auto" (default): split (hi + lo floats) for the delayed re-orthogonalisation when the basis is >= 1 GB,
@@ -2685,21 +2947,24 @@ static void gmres_ws(das_solver* s, das_ksp* k) {
         k->hdev.alloc(4 * (restart + 3));
     }
 }
+// distance between consecutive basis vectors in elements of the storage type (split: hi and lo floats of a vector are adjacent)
+// float storage: the rows of a vector are padded to a multiple of 4 (n4), so that every slot and every lo half starts 16-byte aligned
+// and the 16-byte-load kernels always apply (orth_wide_ok); nothing reads or relies on the padding
+static inline long long basis_n4(das_solver* s) { return (s->n + 3) / 4 * 4; }
+static inline long long basis_ld(das_solver* s, das_ksp* k) { return k->split ? 2 * basis_n4(s) : (k->vf32 ? basis_n4(s) : s->n); }
 // basis slots [0, nvec) are about to be written / read: map them (a no-op once mapped; milliseconds per new 2 GB chunk)
 // the helper thread of the buffer maps 64 vectors ahead of the iteration; the solver waits only if it catches up
 // false: the device cannot hold that many vectors (gmres_advance then closes the cycle: the mapped part is the restart length)
 static inline bool gmres_map_basis(das_solver* s, das_ksp* k, long long nvec) {
-    const long long per = (k->vf32 && !k->split) ? (s->n + 1) / 2 : s->n;  // fp64 elements of the range one basis vector occupies
+    const long long per = basis_ld(s, k) / (k->vf32 ? 2 : 1);  // fp64 elements of the range one basis vector occupies
     k->V.request((size_t)((nvec + 64) * per));
     return k->V.try_ensure((size_t)(nvec * per));
 }
 // slot j of the basis in its storage type
-// distance between consecutive basis vectors in elements of the storage type (split: hi and lo floats of a vector are adjacent)
-static inline long long basis_ld(das_solver* s, das_ksp* k) { return k->split ? 2 * s->n : s->n; }
 template <class VT>
 static inline VT* basis_slot(das_solver* s, das_ksp* k, long long j) { return reinterpret_cast<VT*>(k->V.p) + j * basis_ld(s, k); }
 // the lo half of slot j (split storage), or null
-static inline float* basis_lo(das_solver* s, das_ksp* k, long long j) { return k->split ? reinterpret_cast<float*>(k->V.p) + j * basis_ld(s, k) + s->n : nullptr; }
+static inline float* basis_lo(das_solver* s, das_ksp* k, long long j) { return k->split ? reinterpret_cast<float*>(k->V.p) + j * basis_ld(s, k) + basis_n4(s) : nullptr; }
 
 // dev_out[0..m) = V^T w (V = m vectors of stride n starting at Vbase), dev_out[m] = w.w; summed over the ranks
 template <class VT>
@@ -4003,6 +4268,24 @@ static void orth_bench_dots(long long n, int K, const double* V, const double* w
 template <int UNROLL, int RPT>
 static void orth_bench_update(long long n, int j, double* V, const double* sc, const double* w) {
     launch_dcgs2_update<UNROLL, RPT, double>(0, n, j, V, n, sc, 0.5, 1.0, w, (float*)nullptr);
+}
+
+// the same for das_debug_orth_bench_split: the float instantiations the solver runs (lo = null: fp32 storage)
+template <int ROWS>
+static void orth_bench_dots_f(long long n, int K, const float* V, long long ld, const double* w, double* partial) {
+    launch_multidot2_pass<ROWS, float>(0, n, K, V, ld, V + (long long)(K - 1) * ld, w, partial);
+}
+template <int UNROLL, int RPT>
+static void orth_bench_update_f(long long n, int j, float* V, long long ld, float* lo, const double* sc, const double* w) {
+    hipLaunchKernelGGL((k_dcgs2_update<UNROLL, RPT, float>), dim3(nblk(n, 256 * RPT)), dim3(256), 0, 0, n, j, V, ld, sc, 0.5, 1.0, w, lo);
+}
+template <int R4, bool NT>
+static void orth_bench_dots_w(long long n, int K, const float* V, long long ld, const double* w, double* partial) {
+    launch_multidot2w_pass<R4, NT>(0, n, K, V, ld, V + (long long)(K - 1) * ld, w, partial);
+}
+template <int UNROLL, int RPT4, bool NT>
+static void orth_bench_update_w(long long n, int j, float* V, long long ld, float* lo, const double* sc, const double* w) {
+    launch_dcgs2w_update<UNROLL, RPT4, NT>(0, n, j, V, ld, sc, 0.5, 1.0, w, lo);
 }
 
 // ---- bodies of the test-only entries das_debug_krylov_* (tests/test_gpu_krylov_kernels.py) --------------------------------
@@ -6031,7 +6314,7 @@ int das_ksp_get_basis_info(das_ksp_t* k, int* fp32, double* mappedBytes, double*
     DAS_CHECK(k, DAS_ERR_ARG, "null argument");
     if (fp32) *fp32 = ((k->vf32 && !k->split) ? 1 : 0) | (k->split ? 2 : 0);
     if (mappedBytes) *mappedBytes = (double)k->V.mappedBytes;
-    if (bytesPerVector) *bytesPerVector = (double)k->Vn * ((k->vf32 && !k->split) ? 4.0 : 8.0);
+    if (bytesPerVector) *bytesPerVector = k->vf32 ? (double)((k->Vn + 3) / 4 * 4) * (k->split ? 8.0 : 4.0) : (double)k->Vn * 8.0;  // basis_ld
     return DAS_OK;
     DAS_CATCH
 }
@@ -6247,6 +6530,70 @@ int das_debug_orth_bench(long long n, int K, int reps, int rows, int unroll, int
     DAS_UPD(4, 1); DAS_UPD(8, 1); DAS_UPD(16, 1); DAS_UPD(4, 2); DAS_UPD(8, 2); DAS_UPD(4, 4); DAS_UPD(8, 4);
 #undef DAS_UPD
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    return DAS_OK;
+    DAS_CATCH
+}
+
+// The same for the float basis the solver runs by default (tools/orth_bench.py --split): synthetic buffers in the solver's layout
+// (fmt 2 = split: ld = 2 n4, lo n4 floats into a slot; fmt 1 = fp32: ld = n4, no lo array; n4 = n rounded up to a multiple of 4).
+// variant 0: the one-dword-per-lane kernels (rows 4 | 8 | 16; unroll, rpt as above); 1: the 16-byte-load kernels (rows = groups of 4
+// rows per lane 1 | 2 | 4; (unroll, rpt) = (vectors in flight, groups of 4 rows per lane)); 2: the same with non-temporal loads.
+// rows = 0 / unroll = 0 skips that kernel; a combination that is not compiled returns -1 ms.
+int das_debug_orth_bench_split(long long n, int K, int reps, int fmt, int variant, int rows, int unroll, int rpt, double* ms_dots, double* ms_update) {
+    DAS_TRY
+    DAS_CHECK(n > 0 && n < (1LL << 30) && K > 1 && reps > 0 && ms_dots && ms_update, DAS_ERR_ARG, "das_debug_orth_bench_split: bad arguments");
+    DAS_CHECK((fmt == KRY_FP32 || fmt == KRY_SPLIT) && variant >= 0 && variant <= 2, DAS_ERR_ARG, "das_debug_orth_bench_split: fmt 1 | 2, variant 0 | 1 | 2");
+    const long long n4 = (n + 3) / 4 * 4, ld = fmt == KRY_SPLIT ? 2 * n4 : n4;
+    DevBuf<float> V((size_t)(K + 2) * ld);
+    DevBuf<double> w(n4), partial((size_t)2 * K * 4 * nblk(n, 1024)), sc(2 * (size_t)K);
+    V.zero(); w.zero(); sc.zero();
+    float* lo = fmt == KRY_SPLIT ? V.p + n4 : nullptr;
+    hipEvent_t e0, e1;
+    DAS_HIP(hipEventCreate(&e0)); DAS_HIP(hipEventCreate(&e1));
+    auto timed = [&](auto&& launch) {
+        launch();  // warm-up
+        DAS_HIP(hipEventRecord(e0, 0));
+        for (int r = 0; r < reps; r++) launch();
+        DAS_HIP(hipEventRecord(e1, 0));
+        DAS_HIP(hipEventSynchronize(e1));
+        DAS_HIP(hipGetLastError());
+        float ms = 0.f;
+        DAS_HIP(hipEventElapsedTime(&ms, e0, e1));
+        return (double)ms / reps;
+    };
+    *ms_dots = -1.0; *ms_update = -1.0;
+    const int j = K - 1;
+#define DAS_DOT(R) if (rows == R) *ms_dots = timed([&] { orth_bench_dots_f<R>(n, K, V.p, ld, w.p, partial.p); })
+#define DAS_UPD(U, R) if (unroll == U && rpt == R) *ms_update = timed([&] { orth_bench_update_f<U, R>(n, j, V.p, ld, lo, sc.p, w.p); })
+    if (variant == 0) { DAS_DOT(4); DAS_DOT(8); DAS_DOT(16); DAS_UPD(4, 1); DAS_UPD(8, 1); DAS_UPD(4, 2); DAS_UPD(8, 2); DAS_UPD(4, 4); }
+#undef DAS_DOT
+#undef DAS_UPD
+#define DAS_DOT(R, NT) if (rows == R) *ms_dots = timed([&] { orth_bench_dots_w<R, NT>(n, K, V.p, ld, w.p, partial.p); })
+#define DAS_UPD(U, R, NT) if (unroll == U && rpt == R) *ms_update = timed([&] { orth_bench_update_w<U, R, NT>(n, j, V.p, ld, lo, sc.p, w.p); })
+    if (variant == 1) { DAS_DOT(1, false); DAS_DOT(2, false); DAS_DOT(4, false); DAS_UPD(2, 1, false); DAS_UPD(4, 1, false); DAS_UPD(8, 1, false); DAS_UPD(2, 2, false); DAS_UPD(4, 2, false); }
+    if (variant == 2) { DAS_DOT(1, true); DAS_DOT(2, true); DAS_DOT(4, true); DAS_UPD(2, 1, true); DAS_UPD(4, 1, true); DAS_UPD(8, 1, true); DAS_UPD(2, 2, true); DAS_UPD(4, 2, true); }
+#undef DAS_DOT
+#undef DAS_UPD
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    return DAS_OK;
+    DAS_CATCH
+}
+// the 16-byte-load path of the float basis on (1) / off (0) for every later launch of this process; *previous: what it was.  The tests
+// and the timing tool run both paths of one build with it; the solver never calls it.
+int das_debug_set_orth_wide(int on, int* previous) {
+    if (previous) *previous = g_orth_wide;
+    g_orth_wide = on ? 1 : 0;
+    return DAS_OK;
+}
+// would das_debug_krylov_dots2 / das_debug_krylov_dcgs2_update on a basis of this shape (their uploads are allocation-aligned) run the
+// 16-byte-load kernels?  The launch helpers' own predicate on stand-in pointers.
+int das_debug_krylov_wide_eligible(long long n, int fmt, long long ld, int* dots, int* update) {
+    DAS_TRY
+    DAS_CHECK(dots && update, DAS_ERR_ARG, "das_debug_krylov_wide_eligible: null pointer");
+    const float* base = reinterpret_cast<const float*>((uintptr_t)1 << 20);
+    const bool f = fmt == KRY_FP32 || fmt == KRY_SPLIT;
+    *dots = (f && g_orth_wide && orth_wide_ok(n, base, nullptr, ld, base + ld, base)) ? 1 : 0;
+    *update = (f && g_orth_wide && orth_wide_ok(n, base, fmt == KRY_SPLIT ? base + n : nullptr, ld, nullptr, base)) ? 1 : 0;
     return DAS_OK;
     DAS_CATCH
 }

@@ -488,6 +488,13 @@ double das_timer_avg_ms(das_solver_t* s, const char* name);
  * `rows` rows per thread; update with `unroll` basis vectors in flight and `rpt` rows per thread) on synthetic vectors of
  * length n against K basis vectors; -1 for a variant that is not compiled in */
 int das_debug_orth_bench(long long n, int K, int reps, int rows, int unroll, int rpt, double* ms_dots, double* ms_update);
+/* the same for the float basis in the solver's layout (fmt 1 = fp32, 2 = split): variant 0 = the one-dword-per-lane kernels,
+   1 = the 16-byte-load kernels (rows and rpt count groups of 4 rows per lane), 2 = 1 with non-temporal loads */
+int das_debug_orth_bench_split(long long n, int K, int reps, int fmt, int variant, int rows, int unroll, int rpt, double* ms_dots, double* ms_update);
+/* 16-byte-load path of the float basis on / off for the later launches of this process (tests, timing tool) */
+int das_debug_set_orth_wide(int on, int* previous);
+/* does a basis of this shape, uploaded by das_debug_krylov_dots2 / _dcgs2_update, take the 16-byte-load kernels? */
+int das_debug_krylov_wide_eligible(long long n, int fmt, long long ld, int* dots, int* update);
 /* ---- TEST-ONLY entries (tests/test_gpu_krylov_kernels.py).  Nothing in the product path calls them and no binding should: they exist
  * so that every Krylov kernel of the GMRES engine can be compared with a high-precision reference on caller data, one kernel at a
  * time.  They need the device but no solver handle: host arrays are uploaded, the launch helper THE SOLVER USES is run on the null
