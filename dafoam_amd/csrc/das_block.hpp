@@ -199,4 +199,51 @@ __global__ void k_block_lincomb(long long n, int K, int s, const double* __restr
     for (int r = 0; r < s; r++) Y[(long long)r * ldy + i] = acc[r];
 }
 
+// ---- launch helpers of the block kernels: like the vector ones (das_krylov.hpp) they hold the grid arithmetic once, take
+// (stream, n, ..., leading dimensions) and serve both the block solver and the test-only entries das_debug_krylov_block_*
+static constexpr int TSG_CHUNKS = 1024;  // row chunks of the TN product (one wave each per group of 64 basis vectors)
+static inline int tsgemm_kpad(int K) { return (K + 16 * TSG_TILES - 1) / (16 * TSG_TILES) * (16 * TSG_TILES); }
+static inline size_t tsgemm_partial_size(int K) { return (size_t)TSG_CHUNKS * tsgemm_kpad(K) * 16; }
+// C (K x sv, row-major, device) = V^T W; partial: tsgemm_partial_size(K) doubles
+static void launch_tsgemm_tn(hipStream_t st, long long n, int K, int sv, const double* V, long long ldv, const double* W, long long ldw, double* partial,
+                             double* C) {
+    long long rpc = (n + TSG_CHUNKS - 1) / TSG_CHUNKS;
+    rpc = (rpc + 15) / 16 * 16;
+    const int Kpad = tsgemm_kpad(K);
+    const int gy = Kpad / (16 * TSG_TILES);
+    // even leading dimensions select the 16-byte loads of k_tsgemm_tn: they need 16-byte aligned blocks (every block of the solver
+    // starts a multiple of its leading dimension into a fresh allocation)
+    DAS_CHECK((((ldv | ldw) & 1) != 0) || ((((uintptr_t)V | (uintptr_t)W) & 15) == 0), DAS_ERR_ARG,
+              "block V^T W: even leading dimensions need 16-byte aligned blocks");
+    hipLaunchKernelGGL(k_tsgemm_tn, dim3(TSG_CHUNKS / TSG_WAVES, gy), dim3(64 * TSG_WAVES), 0, st, n, K, sv, V, ldv, W, ldw, rpc, Kpad, partial);
+    hipLaunchKernelGGL(k_tsgemm_reduce, dim3(nblk((long long)K * sv, 4)), dim3(256), 0, st, K, sv, Kpad, (long long)TSG_CHUNKS, (const double*)partial, C);
+}
+// W -= V C  (C = K x sv, row-major, device)
+static void launch_tsgemm_nn_sub(hipStream_t st, long long n, int K, int sv, const double* V, long long ldv, const double* C, double* W, long long ldw) {
+    hipLaunchKernelGGL(k_tsgemm_nn_sub, dim3(nblk(n, 256)), dim3(256), 0, st, n, K, sv, V, ldv, C, W, ldw);
+}
+static void launch_block_right_mult(hipStream_t st, long long n, int sv, double* W, long long ldw, const double* T) {
+    hipLaunchKernelGGL(k_block_right_mult, dim3(nblk(n, 256)), dim3(256), 0, st, n, sv, W, ldw, T);
+}
+static void launch_block_lincomb(hipStream_t st, long long n, int K, int sv, const double* V, long long ldv, const double* C, double* Y, long long ldy) {
+    hipLaunchKernelGGL(k_block_lincomb, dim3(nblk(n, 256)), dim3(256), 0, st, n, K, sv, V, ldv, C, Y, ldy);
+}
+// the sparse product for sv vectors runs at the template width 2, 4 or 8; Xr (n x width, row-major) is its gather layout
+static inline int spmm_width(int sv) { return sv <= 2 ? 2 : (sv <= 4 ? 4 : 8); }
+static void launch_block_to_rows(hipStream_t st, long long n, int sv, const double* X, long long ldx, double* Xr) {
+    switch (spmm_width(sv)) {
+        case 2: hipLaunchKernelGGL(k_block_to_rows<2>, dim3(nblk(n, 256)), dim3(256), 0, st, n, sv, X, ldx, Xr); break;
+        case 4: hipLaunchKernelGGL(k_block_to_rows<4>, dim3(nblk(n, 256)), dim3(256), 0, st, n, sv, X, ldx, Xr); break;
+        default: hipLaunchKernelGGL(k_block_to_rows<8>, dim3(nblk(n, 256)), dim3(256), 0, st, n, sv, X, ldx, Xr); break;
+    }
+}
+static void launch_spmm_wave(hipStream_t st, long long nrows, int sv, const long long* rp, const int* ci, const double* val, const double* Xr, double* Y,
+                             long long ldy) {
+    switch (spmm_width(sv)) {
+        case 2: hipLaunchKernelGGL(k_spmm_wave<2>, dim3(nblk(nrows, 16)), dim3(256), 0, st, nrows, sv, rp, ci, val, Xr, Y, ldy); break;
+        case 4: hipLaunchKernelGGL(k_spmm_wave<4>, dim3(nblk(nrows, 16)), dim3(256), 0, st, nrows, sv, rp, ci, val, Xr, Y, ldy); break;
+        default: hipLaunchKernelGGL(k_spmm_wave<8>, dim3(nblk(nrows, 16)), dim3(256), 0, st, nrows, sv, rp, ci, val, Xr, Y, ldy); break;
+    }
+}
+
 }  // namespace das

@@ -41,6 +41,9 @@ struct Error : std::runtime_error {
         if (!(cond)) throw das::Error((code), (msg)); \
     } while (0)
 
+// workgroups of b items that cover n items
+static inline int nblk(long long n, int b) { return (int)((n + b - 1) / b); }
+
 // ---- host threads ---------------------------------------------------------------------------
 // CPUs this process may really use: the affinity mask AND the container's CFS quota (cgroup v2 cpu.max, v1 cpu.cfs_quota_us).  The
 // round-4 bench host shows 256 CPUs to a container whose quota is 16: OpenMP regions with 256 threads then run throttled (host

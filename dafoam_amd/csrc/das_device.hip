@@ -20,7 +20,9 @@
 #include "das_jaccon.hpp"
 #include "das_bilu.hpp"
 #include "das_comm.hpp"
+#include "das_krylov.hpp"
 #include "das_block.hpp"
+#include "das_krylov_debug.hpp"
 #include "das_color.hpp"
 #include "das_opmat.hpp"
 #include "das_graph.hpp"
@@ -254,8 +256,6 @@ struct ResWork {
     }
 };
 
-static inline int nblk(long long n, int b) { return (int)((n + b - 1) / b); }
-
 // the gradient launch of DASimpleFoam: face-parallel k_grad_fp where it applies (no T field, double metrics, amd.gradFaceParallel), else k_grad
 template <class T, class G>
 static void launch_grad_simple(const DevMeshT<G>& dm, const ResParams& prm, const T* W, ResWork<T>& wk, hipStream_t st) {
@@ -461,566 +461,6 @@ __global__ __launch_bounds__(256) void k_spmv_wave(long long n, const long long*
 }
 #define SPMV_GRID(n) dim3(nblk((n), 256 / SPMV_LANES))
 
-// partial[i*nb + blk] = sum over this block's chunk of V_i . w   (i < m); last slot (i == m) = w . w
-// Split storage of the Krylov basis (amd.krylovBasisPrecision "split"): a basis entry x is kept as hi = (float)x and lo = (float)(x - hi) in
-// TWO float arrays (8 bytes per entry like fp64; hi + lo carries 48 mantissa bits).  The inner-product pass of the delayed
-// re-orthogonalisation reads only the hi array (4 bytes per entry), the update pass reads and writes both - every consumer that builds
-// vectors (updates, the solution update, the preconditioner input) uses hi + lo, so the Arnoldi relation holds to 2^-48, while the
-// Gram-Schmidt coefficients carry fp32-level errors, which only cost orthogonality (1e-7).  Kernels below take the lo array as an optional
-// pointer next to a float basis: null = plain fp32 storage (amd.krylovBasisPrecision "fp32").
-// (VT: storage type of the Krylov basis - double, or float for the compressed basis of amd.krylovBasisPrecision; all sums in fp64)
-#define MD_CHUNK 1024
-template <class VT>
-__global__ __launch_bounds__(256) void k_multidot(long long n, int m, const VT* __restrict__ V, long long ldv, const double* __restrict__ w,
-                                                  double* __restrict__ partial, int nb) {
-    __shared__ double red[4];
-    long long base = (long long)blockIdx.x * MD_CHUNK;
-    double wr[4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-        long long k = base + threadIdx.x + 256 * t;
-        wr[t] = k < n ? w[k] : 0.0;
-    }
-    for (int i = 0; i <= m; i++) {
-        double s = 0.0;
-        if (i < m) {
-            const VT* vi = V + (long long)i * ldv;
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                long long k = base + threadIdx.x + 256 * t;
-                if (k < n) s += (double)vi[k] * wr[t];
-            }
-        } else {
-#pragma unroll
-            for (int t = 0; t < 4; t++) s += wr[t] * wr[t];
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) partial[(long long)i * nb + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-        __syncthreads();
-    }
-}
-__global__ __launch_bounds__(256) void k_reduce(int nb, const double* __restrict__ partial, double* __restrict__ out) {
-    __shared__ double red[4];
-    const double* p = partial + (long long)blockIdx.x * nb;
-    double s = 0.0;
-    for (int k = threadIdx.x; k < nb; k += 256) s += p[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-// w -= sum_i h_i V_i
-template <class VT, class WT>
-__global__ __launch_bounds__(256) void k_multiaxpy(long long n, int m, const VT* __restrict__ V, long long ldv, const double* __restrict__ h,
-                                                   WT* __restrict__ w, const float* __restrict__ Vlo = nullptr) {
-    long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    double s = (double)w[k];
-    if (Vlo) for (int i = 0; i < m; i++) s -= h[i] * ((double)V[(long long)i * ldv + k] + (double)Vlo[(long long)i * ldv + k]);
-    else for (int i = 0; i < m; i++) s -= h[i] * (double)V[(long long)i * ldv + k];
-    w[k] = (WT)s;
-}
-// Two right-hand sides against K basis vectors in ONE pass over the basis (the fused inner products of the delayed
-// re-orthogonalisation, gmres_iter_dcgs2): partial[(r K + i) nbw + slot] = this wave's part of V_i . (r == 0 ? u : v).
-// A thread keeps MD2_ROWS rows of u and v in registers (16: 5.9 TB/s, 8: 5.6, 4: 4.7 on synthetic vectors, tools/orth_bench.py); four basis vectors at a time give 8 sums per lane, which one
-// reduce-scatter over the wave (10 exchanges for 8 sums instead of 48) leaves in the 8 lane groups.
-#ifndef MD2_ROWS
-#define MD2_ROWS 16
-#endif
-#define MD2_CHUNK (256 * MD2_ROWS)
-template <int ROWS, bool FULL, class QT, class VT>
-__device__ __forceinline__ void multidot2_body(long long n, int K, const QT* __restrict__ V, long long ldv, const VT* __restrict__ u,
-                                               const double* __restrict__ v, double* __restrict__ partial, long long nbw) {
-    const int lane = threadIdx.x & 63, g = lane >> 3;
-    const long long base = (long long)blockIdx.x * (256 * ROWS) + threadIdx.x;
-    const long long slot = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    double ur[ROWS], vr[ROWS];
-#pragma unroll
-    for (int t = 0; t < ROWS; t++) {
-        const long long k = FULL ? base + 256 * t : min(base + 256 * t, n - 1);  // clamped loads, masked below: no branches
-        const double m = (FULL || base + 256 * t < n) ? 1.0 : 0.0;
-        ur[t] = m * (double)u[k];
-        vr[t] = m * v[k];
-    }
-    for (int i0 = 0; i0 < K; i0 += 4) {
-        double acc[8], x[4][ROWS];
-        // all 4 x ROWS loads are issued before the first use (written as two loops: the scheduler otherwise trades the
-        // loads in flight for registers and waits after every load)
-#pragma unroll
-        for (int ii = 0; ii < 4; ii++) {
-            const QT* vi = V + (long long)min(i0 + ii, K - 1) * ldv;
-#pragma unroll
-            for (int t = 0; t < ROWS; t++) x[ii][t] = (double)vi[FULL ? base + 256 * t : min(base + 256 * t, n - 1)];  // ur, vr are zero beyond n
-        }
-#pragma unroll
-        for (int ii = 0; ii < 4; ii++) {
-            double a = 0.0, b = 0.0;
-#pragma unroll
-            for (int t = 0; t < ROWS; t++) {
-                a += x[ii][t] * ur[t];
-                b += x[ii][t] * vr[t];
-            }
-            acc[2 * ii] = a;
-            acc[2 * ii + 1] = b;
-        }
-        double a4[4], a2[2], a1;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const double snd = (g & 4) ? acc[i] : acc[i + 4], keep = (g & 4) ? acc[i + 4] : acc[i];
-            a4[i] = keep + __shfl_xor(snd, 32, 64);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const double snd = (g & 2) ? a4[i] : a4[i + 2], keep = (g & 2) ? a4[i + 2] : a4[i];
-            a2[i] = keep + __shfl_xor(snd, 16, 64);
-        }
-        {
-            const double snd = (g & 1) ? a2[0] : a2[1], keep = (g & 1) ? a2[1] : a2[0];
-            a1 = keep + __shfl_xor(snd, 8, 64);
-        }
-        a1 += __shfl_xor(a1, 1, 64);
-        a1 += __shfl_xor(a1, 2, 64);
-        a1 += __shfl_xor(a1, 4, 64);  // lane group g: the wave's sum number g = 2 ii + r
-        const int i = i0 + (g >> 1);
-        if ((lane & 7) == 0 && i < K) partial[((long long)(g & 1) * K + i) * nbw + slot] = a1;
-    }
-}
-template <int ROWS, class QT, class VT>
-__global__ __launch_bounds__(256) void k_multidot2(long long n, int K, const QT* __restrict__ V, long long ldv, const VT* __restrict__ u,
-                                                   const double* __restrict__ v, double* __restrict__ partial, long long nbw) {
-    if ((long long)(blockIdx.x + 1) * (256 * ROWS) <= n) multidot2_body<ROWS, true, QT, VT>(n, K, V, ldv, u, v, partial, nbw);
-    else multidot2_body<ROWS, false, QT, VT>(n, K, V, ldv, u, v, partial, nbw);
-}
-// The fused update of the delayed re-orthogonalisation, one pass over the basis: with Q = the j final vectors, u = slot j
-// (projected once), v = the operator applied to u:   q_j = (u - Q s) / alpha  -> slot j,
-//                                                     u' = (v - gamma u - Q c) / alpha -> slot j + 1
-#ifndef DCGS2_UNROLL
-#define DCGS2_UNROLL 4
-#endif
-#ifndef DCGS2_RPT
-#define DCGS2_RPT 2
-#endif
-template <int UNROLL, int RPT, class VT>
-__global__ __launch_bounds__(256) void k_dcgs2_update(long long n, int j, VT* __restrict__ V, long long ldv, const double* __restrict__ sc,
-                                                      double gamma, double ralpha, const double* __restrict__ v, float* __restrict__ Vlo = nullptr) {
-    const long long k0 = ((long long)blockIdx.x * RPT) * blockDim.x + threadIdx.x;  // rows k0 + r * blockDim.x
-    const double* s = sc;
-    const double* c = sc + j;
-    double as[RPT], ac[RPT];
-    long long kk[RPT];
-#pragma unroll
-    for (int r = 0; r < RPT; r++) { as[r] = 0.0; ac[r] = 0.0; kk[r] = min(k0 + (long long)r * blockDim.x, n - 1); }
-    int i = 0;
-    for (; i + UNROLL <= j; i += UNROLL) {
-        double q[UNROLL][RPT];
-#pragma unroll
-        for (int t = 0; t < UNROLL; t++)
-#pragma unroll
-            for (int r = 0; r < RPT; r++) q[t][r] = (double)V[(long long)(i + t) * ldv + kk[r]];
-        if (Vlo) {
-#pragma unroll
-            for (int t = 0; t < UNROLL; t++)
-#pragma unroll
-                for (int r = 0; r < RPT; r++) q[t][r] += (double)Vlo[(long long)(i + t) * ldv + kk[r]];
-        }
-#pragma unroll
-        for (int t = 0; t < UNROLL; t++)
-#pragma unroll
-            for (int r = 0; r < RPT; r++) { as[r] += s[i + t] * q[t][r]; ac[r] += c[i + t] * q[t][r]; }
-    }
-    for (; i < j; i++)
-#pragma unroll
-        for (int r = 0; r < RPT; r++) {
-            const double q = (double)V[(long long)i * ldv + kk[r]] + (Vlo ? (double)Vlo[(long long)i * ldv + kk[r]] : 0.0);
-            as[r] += s[i] * q; ac[r] += c[i] * q;
-        }
-#pragma unroll
-    for (int r = 0; r < RPT; r++) {
-        const long long k = k0 + (long long)r * blockDim.x;
-        if (k >= n) continue;
-        const double u = (double)V[(long long)j * ldv + k] + (Vlo ? (double)Vlo[(long long)j * ldv + k] : 0.0);
-        const double qj = (u - as[r]) * ralpha, un = (v[k] - gamma * u - ac[r]) * ralpha;
-        const VT qh = (VT)qj, uh = (VT)un;
-        V[(long long)j * ldv + k] = qh;
-        V[(long long)(j + 1) * ldv + k] = uh;
-        if (Vlo) { Vlo[(long long)j * ldv + k] = (float)(qj - (double)qh); Vlo[(long long)(j + 1) * ldv + k] = (float)(un - (double)uh); }
-    }
-}
-// ---- 16-byte-load variants of the two kernels above for the float basis (fp32 and split storage) -------------------------------
-// A lane owns groups of 4 consecutive rows and reads the hi (and lo) floats of a group as ONE 16-byte load: 1 KiB per wave
-// instruction, a quarter of the load instructions of the one-dword-per-lane kernels.  The vector's start is uniform and stepped by
-// ldv from vector to vector; the lane's part of the address is a 32-bit byte offset computed once (n < 2^30).  A workgroup whose
-// rows all exist (FULL) uses the 16-byte loads and stores; the last one goes element by element with clamped loads (row n - 1 of the
-// same vector: real data, never the padding behind row n) and masked sums / stores.  They need 16-byte aligned V, Vlo, u, v and
-// ldv % 4 == 0 (orth_wide_ok); everything else runs the kernels above.  Sums in fp64 as above; only the order of the rows differs.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-template <bool FULL, bool NT>
-__device__ __forceinline__ f32x4 ld_group(const float* __restrict__ vec, const unsigned (&bo)[4]) {
-    const char* b = reinterpret_cast<const char*>(vec);
-    if (FULL) {
-        const f32x4* p = reinterpret_cast<const f32x4*>(b + bo[0]);
-        return NT ? __builtin_nontemporal_load(p) : *p;
-    }
-    f32x4 r;
-    r.x = *reinterpret_cast<const float*>(b + bo[0]);
-    r.y = *reinterpret_cast<const float*>(b + bo[1]);
-    r.z = *reinterpret_cast<const float*>(b + bo[2]);
-    r.w = *reinterpret_cast<const float*>(b + bo[3]);
-    return r;
-}
-// byte offsets of the 4 rows of the group that starts at row k (clamped to row n - 1 unless FULL)
-template <bool FULL>
-__device__ __forceinline__ void group_offsets(long long k, long long n, unsigned (&bo)[4]) {
-#pragma unroll
-    for (int e = 0; e < 4; e++) bo[e] = (unsigned)((FULL ? k + e : min(k + e, n - 1)) * 4);
-}
-// R4 groups of 4 rows per lane (group t of a lane starts at row 4 (256 (R4 blockIdx + t) + threadIdx)); partial sums as k_multidot2
-template <int R4, bool FULL, bool NT>
-__device__ __forceinline__ void multidot2w_body(long long n, int K, const float* __restrict__ V, long long ldv, const float* __restrict__ u,
-                                                const double* __restrict__ v, double* __restrict__ partial, long long nbw) {
-    const int lane = threadIdx.x & 63, g = lane >> 3;
-    const long long base = ((long long)blockIdx.x * (256 * R4) + threadIdx.x) * 4;
-    const long long slot = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    unsigned bo[R4][4];
-    float ur[R4][4];
-    double vr[R4][4];
-#pragma unroll
-    for (int t = 0; t < R4; t++) {
-        const long long k = base + 1024LL * t;
-        group_offsets<FULL>(k, n, bo[t]);
-        const f32x4 uu = ld_group<FULL, false>(u, bo[t]);
-        ur[t][0] = uu.x; ur[t][1] = uu.y; ur[t][2] = uu.z; ur[t][3] = uu.w;
-        if (FULL) {
-            const f64x2 a = *reinterpret_cast<const f64x2*>(v + k), b = *reinterpret_cast<const f64x2*>(v + k + 2);
-            vr[t][0] = a.x; vr[t][1] = a.y; vr[t][2] = b.x; vr[t][3] = b.y;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const bool in = k + e < n;
-                vr[t][e] = in ? v[min(k + e, n - 1)] : 0.0;
-                ur[t][e] = in ? ur[t][e] : 0.f;
-            }
-        }
-    }
-    const float* v0 = V;  // start of vector i0 (uniform)
-    for (int i0 = 0; i0 < K; i0 += 4, v0 += 4 * ldv) {
-        f32x4 x[4][R4];
-        double acc[8];
-        // all 4 x R4 loads are issued before the first use (two loops, as in multidot2_body)
-#pragma unroll
-        for (int ii = 0; ii < 4; ii++) {
-            const float* vi = v0 + (long long)min(ii, K - 1 - i0) * ldv;  // beyond K - 1: vector K - 1 again, its sums are not stored
-#pragma unroll
-            for (int t = 0; t < R4; t++) x[ii][t] = ld_group<FULL, NT>(vi, bo[t]);
-        }
-#pragma unroll
-        for (int ii = 0; ii < 4; ii++) {
-            double a = 0.0, b = 0.0;
-#pragma unroll
-            for (int t = 0; t < R4; t++) {
-                const double x0 = (double)x[ii][t].x, x1 = (double)x[ii][t].y, x2 = (double)x[ii][t].z, x3 = (double)x[ii][t].w;
-                a += x0 * (double)ur[t][0]; b += x0 * vr[t][0];
-                a += x1 * (double)ur[t][1]; b += x1 * vr[t][1];
-                a += x2 * (double)ur[t][2]; b += x2 * vr[t][2];
-                a += x3 * (double)ur[t][3]; b += x3 * vr[t][3];
-            }
-            acc[2 * ii] = a;
-            acc[2 * ii + 1] = b;
-        }
-        double a4[4], a2[2], a1;
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const double snd = (g & 4) ? acc[i] : acc[i + 4], keep = (g & 4) ? acc[i + 4] : acc[i];
-            a4[i] = keep + __shfl_xor(snd, 32, 64);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const double snd = (g & 2) ? a4[i] : a4[i + 2], keep = (g & 2) ? a4[i + 2] : a4[i];
-            a2[i] = keep + __shfl_xor(snd, 16, 64);
-        }
-        {
-            const double snd = (g & 1) ? a2[0] : a2[1], keep = (g & 1) ? a2[1] : a2[0];
-            a1 = keep + __shfl_xor(snd, 8, 64);
-        }
-        a1 += __shfl_xor(a1, 1, 64);
-        a1 += __shfl_xor(a1, 2, 64);
-        a1 += __shfl_xor(a1, 4, 64);  // lane group g: the wave's sum number g = 2 ii + r
-        const int i = i0 + (g >> 1);
-        if ((lane & 7) == 0 && i < K) partial[((long long)(g & 1) * K + i) * nbw + slot] = a1;
-    }
-}
-template <int R4, bool NT>
-__global__ __launch_bounds__(256) void k_multidot2w(long long n, int K, const float* __restrict__ V, long long ldv, const float* __restrict__ u,
-                                                    const double* __restrict__ v, double* __restrict__ partial, long long nbw) {
-    if ((long long)(blockIdx.x + 1) * (1024 * R4) <= n) multidot2w_body<R4, true, NT>(n, K, V, ldv, u, v, partial, nbw);
-    else multidot2w_body<R4, false, NT>(n, K, V, ldv, u, v, partial, nbw);
-}
-// the fused update with RPT4 groups of 4 rows per lane and UNROLL basis vectors (hi and lo: 2 x UNROLL x RPT4 16-byte loads) in flight
-template <int UNROLL, int RPT4, bool FULL, bool NT>
-__device__ __forceinline__ void dcgs2w_body(long long n, int j, float* __restrict__ V, long long ldv, const double* __restrict__ sc, double gamma,
-                                            double ralpha, const double* __restrict__ v, float* __restrict__ Vlo) {
-    const long long base = ((long long)blockIdx.x * (256 * RPT4) + threadIdx.x) * 4;
-    const double* s = sc;
-    const double* c = sc + j;
-    unsigned bo[RPT4][4];
-    double as[RPT4][4], ac[RPT4][4];
-#pragma unroll
-    for (int r = 0; r < RPT4; r++) {
-        group_offsets<FULL>(base + 1024LL * r, n, bo[r]);
-#pragma unroll
-        for (int e = 0; e < 4; e++) { as[r][e] = 0.0; ac[r][e] = 0.0; }
-    }
-    const float* h0 = V;    // start of vector i (uniform), hi and lo
-    const float* l0 = Vlo;
-    for (int i = 0; i < j; i += UNROLL, h0 += UNROLL * ldv, l0 += (Vlo ? UNROLL * ldv : 0)) {
-        f32x4 qh[UNROLL][RPT4], ql[UNROLL][RPT4];
-        // beyond j - 1: vector j - 1 again with zero coefficients (never slot j, which this kernel writes)
-#pragma unroll
-        for (int t = 0; t < UNROLL; t++) {
-            const float* hv = h0 + (long long)min(t, j - 1 - i) * ldv;
-#pragma unroll
-            for (int r = 0; r < RPT4; r++) qh[t][r] = ld_group<FULL, NT>(hv, bo[r]);
-        }
-        if (Vlo) {
-#pragma unroll
-            for (int t = 0; t < UNROLL; t++) {
-                const float* lv = l0 + (long long)min(t, j - 1 - i) * ldv;
-#pragma unroll
-                for (int r = 0; r < RPT4; r++) ql[t][r] = ld_group<FULL, NT>(lv, bo[r]);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < UNROLL; t++) {
-            const bool in = i + t < j;
-            const double st = in ? s[min(i + t, j - 1)] : 0.0, ct = in ? c[min(i + t, j - 1)] : 0.0;
-#pragma unroll
-            for (int r = 0; r < RPT4; r++) {
-                double q[4] = {(double)qh[t][r].x, (double)qh[t][r].y, (double)qh[t][r].z, (double)qh[t][r].w};
-                if (Vlo) { q[0] += (double)ql[t][r].x; q[1] += (double)ql[t][r].y; q[2] += (double)ql[t][r].z; q[3] += (double)ql[t][r].w; }
-#pragma unroll
-                for (int e = 0; e < 4; e++) { as[r][e] += st * q[e]; ac[r][e] += ct * q[e]; }
-            }
-        }
-    }
-    float* uh = V + (long long)j * ldv;
-    float* nh = uh + ldv;
-    float* ul = Vlo ? Vlo + (long long)j * ldv : nullptr;
-    float* nl = Vlo ? ul + ldv : nullptr;
-#pragma unroll
-    for (int r = 0; r < RPT4; r++) {
-        const long long k = base + 1024LL * r;
-        if (k >= n) continue;
-        const f32x4 u4 = ld_group<FULL, false>(uh, bo[r]);
-        double u[4] = {(double)u4.x, (double)u4.y, (double)u4.z, (double)u4.w}, vv[4];
-        if (Vlo) {
-            const f32x4 l4 = ld_group<FULL, false>(ul, bo[r]);
-            u[0] += (double)l4.x; u[1] += (double)l4.y; u[2] += (double)l4.z; u[3] += (double)l4.w;
-        }
-        if (FULL) {
-            const f64x2 a = *reinterpret_cast<const f64x2*>(v + k), b = *reinterpret_cast<const f64x2*>(v + k + 2);
-            vv[0] = a.x; vv[1] = a.y; vv[2] = b.x; vv[3] = b.y;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; e++) vv[e] = v[min(k + e, n - 1)];
-        }
-        float qh[4], qlo[4], nhh[4], nlo[4];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-            const double qj = (u[e] - as[r][e]) * ralpha, un = (vv[e] - gamma * u[e] - ac[r][e]) * ralpha;
-            qh[e] = (float)qj; nhh[e] = (float)un;
-            qlo[e] = (float)(qj - (double)qh[e]); nlo[e] = (float)(un - (double)nhh[e]);
-        }
-        if (FULL) {
-            *reinterpret_cast<f32x4*>(uh + k) = f32x4{qh[0], qh[1], qh[2], qh[3]};
-            *reinterpret_cast<f32x4*>(nh + k) = f32x4{nhh[0], nhh[1], nhh[2], nhh[3]};
-            if (Vlo) {
-                *reinterpret_cast<f32x4*>(ul + k) = f32x4{qlo[0], qlo[1], qlo[2], qlo[3]};
-                *reinterpret_cast<f32x4*>(nl + k) = f32x4{nlo[0], nlo[1], nlo[2], nlo[3]};
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                if (k + e >= n) continue;
-                uh[k + e] = qh[e]; nh[k + e] = nhh[e];
-                if (Vlo) { ul[k + e] = qlo[e]; nl[k + e] = nlo[e]; }
-            }
-        }
-    }
-}
-template <int UNROLL, int RPT4, bool NT>
-__global__ __launch_bounds__(256) void k_dcgs2w_update(long long n, int j, float* __restrict__ V, long long ldv, const double* __restrict__ sc,
-                                                       double gamma, double ralpha, const double* __restrict__ v, float* __restrict__ Vlo) {
-    if ((long long)(blockIdx.x + 1) * (1024 * RPT4) <= n) dcgs2w_body<UNROLL, RPT4, true, NT>(n, j, V, ldv, sc, gamma, ralpha, v, Vlo);
-    else dcgs2w_body<UNROLL, RPT4, false, NT>(n, j, V, ldv, sc, gamma, ralpha, v, Vlo);
-}
-// y = sum_i c_i V_i
-template <class VT>
-__global__ __launch_bounds__(256) void k_lincomb(long long n, int m, const VT* __restrict__ V, long long ldv, const double* __restrict__ c,
-                                                 double* __restrict__ y, const float* __restrict__ Vlo = nullptr) {
-    long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    double s = 0.0;
-    if (Vlo) for (int i = 0; i < m; i++) s += c[i] * ((double)V[(long long)i * ldv + k] + (double)Vlo[(long long)i * ldv + k]);
-    else for (int i = 0; i < m; i++) s += c[i] * (double)V[(long long)i * ldv + k];
-    y[k] = s;
-}
-// y = a x; xlo: x is stored split (x = x + xlo); ylo: y is stored split (y = (TO) value, ylo = the fp32 rest)
-template <class TI, class TO>
-__global__ void k_scale_to(long long n, double a, const TI* __restrict__ x, TO* __restrict__ y, const float* __restrict__ xlo = nullptr,
-                           float* __restrict__ ylo = nullptr) {
-    long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const double val = a * ((double)x[k] + (xlo ? (double)xlo[k] : 0.0));
-    const TO yh = (TO)val;
-    y[k] = yh;
-    if (ylo) ylo[k] = (float)(val - (double)yh);
-}
-// ---- launch helpers of the Krylov vector kernels --------------------------------------------------------------------------
-// The one place that holds the grid arithmetic of these kernels: they take (stream, n, ...) and no solver handle, so that the
-// solver (gmres_iter_t, gmres_iter_dcgs2, DrDeviceOps) and the test-only entries das_debug_krylov_* run the SAME launches.
-static inline size_t multidot_partial_size(long long n, int m) { return (size_t)(m + 1) * nblk(n, MD_CHUNK); }
-// out[0..m) = V^T w, out[m] = w.w
-template <class VT>
-static void launch_multidot(hipStream_t st, long long n, int m, const VT* V, long long ldv, const double* w, double* partial, double* out) {
-    const int nb = nblk(n, MD_CHUNK);
-    hipLaunchKernelGGL(k_multidot, dim3(nb), dim3(256), 0, st, n, m, V, ldv, w, partial, nb);
-    hipLaunchKernelGGL(k_reduce, dim3(m + 1), dim3(256), 0, st, nb, (const double*)partial, out);
-}
-template <int ROWS>
-static inline long long multidot2_nbw(long long n) { return 4LL * nblk(n, 256 * ROWS); }
-// Shapes of the 16-byte-load kernels (k_multidot2w, k_dcgs2w_update) and whether the launch helpers pick them for an eligible
-// float basis.  MEASURED ON THE FLOAT INSTANTIATIONS (split layout, n = 16 172 600, K = 150 and 352) with das_debug_orth_bench_split /
-// tools/orth_bench.py --split - not inherited from the fp64 shapes above; the table is in profiles/orth_wide_loads_split_basis.md.
-// At K = 352: inner products 3.81 ms (4.30 with k_multidot2<16, float>), non-temporal loads 0.4 ms better than plain ones (u, v stay in
-// the cache); update 7.67 ms (8.95 with k_dcgs2_update<4, 2, float>), plain loads better than non-temporal ones.
-#ifndef MD2W_R4
-#define MD2W_R4 4  // groups of 4 rows per lane of the inner products (16 rows: 184 VGPRs, 2 waves per SIMD)
-#endif
-#ifndef MD2W_NT
-#define MD2W_NT 1  // non-temporal loads of the basis stream in the inner products
-#endif
-#ifndef DCGS2W_UNROLL
-#define DCGS2W_UNROLL 4  // basis vectors in flight in the update
-#endif
-#ifndef DCGS2W_RPT4
-#define DCGS2W_RPT4 2  // groups of 4 rows per lane of the update (8 rows x 4 vectors x hi, lo: 220 VGPRs, 2 waves per SIMD)
-#endif
-#ifndef DCGS2W_NT
-#define DCGS2W_NT 0  // non-temporal loads of the basis stream in the update
-#endif
-#ifndef ORTH_WIDE_DEFAULT
-#define ORTH_WIDE_DEFAULT 1
-#endif
-static int g_orth_wide = ORTH_WIDE_DEFAULT;  // das_debug_set_orth_wide: the tests and the timing tool run both paths of one build
-// the 16-byte path of the float basis: every pointer 16-byte aligned, vectors a multiple of 16 bytes apart, 32-bit byte offsets in a vector
-static inline bool orth_wide_ok(long long n, const void* V, const void* Vlo, long long ldv, const void* u, const void* v) {
-    return n >= 4 && n < (1LL << 30) && (ldv & 3) == 0 && ((((uintptr_t)V | (uintptr_t)Vlo | (uintptr_t)u | (uintptr_t)v) & 15) == 0);
-}
-static inline long long multidot2w_nbw(long long n, int r4) { return 4LL * nblk(n, 1024 * r4); }
-static inline size_t multidot2_partial_size(long long n, int K) {
-    return (size_t)2 * K * (size_t)std::max(multidot2_nbw<MD2_ROWS>(n), multidot2w_nbw(n, MD2W_R4));
-}
-// the inner-product pass alone (the tuning hook times it for several ROWS)
-template <int ROWS, class VT>
-static void launch_multidot2_pass(hipStream_t st, long long n, int K, const VT* V, long long ldv, const VT* u, const double* v, double* partial) {
-    hipLaunchKernelGGL((k_multidot2<ROWS, VT, VT>), dim3(nblk(n, 256 * ROWS)), dim3(256), 0, st, n, K, V, ldv, u, v, partial, multidot2_nbw<ROWS>(n));
-}
-// out[0..K) = V^T u, out[K..2K) = V^T v
-template <int R4, bool NT>
-static void launch_multidot2w_pass(hipStream_t st, long long n, int K, const float* V, long long ldv, const float* u, const double* v, double* partial) {
-    hipLaunchKernelGGL((k_multidot2w<R4, NT>), dim3(nblk(n, 1024 * R4)), dim3(256), 0, st, n, K, V, ldv, u, v, partial, multidot2w_nbw(n, R4));
-}
-template <int UNROLL, int RPT4, bool NT>
-static void launch_dcgs2w_update(hipStream_t st, long long n, int j, float* V, long long ldv, const double* sc, double gamma, double ralpha,
-                                 const double* v, float* Vlo) {
-    hipLaunchKernelGGL((k_dcgs2w_update<UNROLL, RPT4, NT>), dim3(nblk(n, 1024 * RPT4)), dim3(256), 0, st, n, j, V, ldv, sc, gamma, ralpha, v, Vlo);
-}
-template <class VT>
-static void launch_multidot2(hipStream_t st, long long n, int K, const VT* V, long long ldv, const VT* u, const double* v, double* partial, double* out) {
-    if constexpr (std::is_same<VT, float>::value) {
-        if (g_orth_wide && orth_wide_ok(n, V, nullptr, ldv, u, v)) {
-            launch_multidot2w_pass<MD2W_R4, MD2W_NT != 0>(st, n, K, V, ldv, u, v, partial);
-            hipLaunchKernelGGL(k_reduce, dim3(2 * K), dim3(256), 0, st, (int)multidot2w_nbw(n, MD2W_R4), (const double*)partial, out);
-            return;
-        }
-    }
-    launch_multidot2_pass<MD2_ROWS, VT>(st, n, K, V, ldv, u, v, partial);
-    hipLaunchKernelGGL(k_reduce, dim3(2 * K), dim3(256), 0, st, (int)multidot2_nbw<MD2_ROWS>(n), (const double*)partial, out);
-}
-template <int UNROLL, int RPT, class VT>
-static void launch_dcgs2_update(hipStream_t st, long long n, int j, VT* V, long long ldv, const double* sc, double gamma, double ralpha, const double* v,
-                                float* Vlo) {
-    if constexpr (std::is_same<VT, float>::value) {
-        if (g_orth_wide && orth_wide_ok(n, V, Vlo, ldv, nullptr, v)) {
-            launch_dcgs2w_update<DCGS2W_UNROLL, DCGS2W_RPT4, DCGS2W_NT != 0>(st, n, j, V, ldv, sc, gamma, ralpha, v, Vlo);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((k_dcgs2_update<UNROLL, RPT, VT>), dim3(nblk(n, 256 * RPT)), dim3(256), 0, st, n, j, V, ldv, sc, gamma, ralpha, v, Vlo);
-}
-template <class VT, class WT>
-static void launch_multiaxpy(hipStream_t st, long long n, int m, const VT* V, long long ldv, const double* h, WT* w, const float* Vlo) {
-    hipLaunchKernelGGL(k_multiaxpy, dim3(nblk(n, 256)), dim3(256), 0, st, n, m, V, ldv, h, w, Vlo);
-}
-template <class VT>
-static void launch_lincomb(hipStream_t st, long long n, int m, const VT* V, long long ldv, const double* c, double* y, const float* Vlo) {
-    hipLaunchKernelGGL(k_lincomb, dim3(nblk(n, 256)), dim3(256), 0, st, n, m, V, ldv, c, y, Vlo);
-}
-template <class TI, class TO>
-static void launch_scale_to(hipStream_t st, long long n, double a, const TI* x, TO* y, const float* xlo, float* ylo) {
-    hipLaunchKernelGGL(k_scale_to, dim3(nblk(n, 256)), dim3(256), 0, st, n, a, x, y, xlo, ylo);
-}
-static constexpr int TSG_CHUNKS = 1024;  // row chunks of the TN product (one wave each per group of 64 basis vectors)
-// ---- launch helpers of the block kernels (das_block.hpp): like the vector ones above they hold the grid arithmetic once, take
-// (stream, n, ..., leading dimensions) and serve both the block solver and the test-only entries das_debug_krylov_block_*
-static inline int tsgemm_kpad(int K) { return (K + 16 * TSG_TILES - 1) / (16 * TSG_TILES) * (16 * TSG_TILES); }
-static inline size_t tsgemm_partial_size(int K) { return (size_t)TSG_CHUNKS * tsgemm_kpad(K) * 16; }
-// C (K x sv, row-major, device) = V^T W; partial: tsgemm_partial_size(K) doubles
-static void launch_tsgemm_tn(hipStream_t st, long long n, int K, int sv, const double* V, long long ldv, const double* W, long long ldw, double* partial,
-                             double* C) {
-    long long rpc = (n + TSG_CHUNKS - 1) / TSG_CHUNKS;
-    rpc = (rpc + 15) / 16 * 16;
-    const int Kpad = tsgemm_kpad(K);
-    const int gy = Kpad / (16 * TSG_TILES);
-    // even leading dimensions select the 16-byte loads of k_tsgemm_tn: they need 16-byte aligned blocks (every block of the solver
-    // starts a multiple of its leading dimension into a fresh allocation)
-    DAS_CHECK((((ldv | ldw) & 1) != 0) || ((((uintptr_t)V | (uintptr_t)W) & 15) == 0), DAS_ERR_ARG,
-              "block V^T W: even leading dimensions need 16-byte aligned blocks");
-    hipLaunchKernelGGL(k_tsgemm_tn, dim3(TSG_CHUNKS / TSG_WAVES, gy), dim3(64 * TSG_WAVES), 0, st, n, K, sv, V, ldv, W, ldw, rpc, Kpad, partial);
-    hipLaunchKernelGGL(k_tsgemm_reduce, dim3(nblk((long long)K * sv, 4)), dim3(256), 0, st, K, sv, Kpad, (long long)TSG_CHUNKS, (const double*)partial, C);
-}
-// W -= V C  (C = K x sv, row-major, device)
-static void launch_tsgemm_nn_sub(hipStream_t st, long long n, int K, int sv, const double* V, long long ldv, const double* C, double* W, long long ldw) {
-    hipLaunchKernelGGL(k_tsgemm_nn_sub, dim3(nblk(n, 256)), dim3(256), 0, st, n, K, sv, V, ldv, C, W, ldw);
-}
-static void launch_block_right_mult(hipStream_t st, long long n, int sv, double* W, long long ldw, const double* T) {
-    hipLaunchKernelGGL(k_block_right_mult, dim3(nblk(n, 256)), dim3(256), 0, st, n, sv, W, ldw, T);
-}
-static void launch_block_lincomb(hipStream_t st, long long n, int K, int sv, const double* V, long long ldv, const double* C, double* Y, long long ldy) {
-    hipLaunchKernelGGL(k_block_lincomb, dim3(nblk(n, 256)), dim3(256), 0, st, n, K, sv, V, ldv, C, Y, ldy);
-}
-// the sparse product for sv vectors runs at the template width 2, 4 or 8; Xr (n x width, row-major) is its gather layout
-static inline int spmm_width(int sv) { return sv <= 2 ? 2 : (sv <= 4 ? 4 : 8); }
-static void launch_block_to_rows(hipStream_t st, long long n, int sv, const double* X, long long ldx, double* Xr) {
-    switch (spmm_width(sv)) {
-        case 2: hipLaunchKernelGGL(k_block_to_rows<2>, dim3(nblk(n, 256)), dim3(256), 0, st, n, sv, X, ldx, Xr); break;
-        case 4: hipLaunchKernelGGL(k_block_to_rows<4>, dim3(nblk(n, 256)), dim3(256), 0, st, n, sv, X, ldx, Xr); break;
-        default: hipLaunchKernelGGL(k_block_to_rows<8>, dim3(nblk(n, 256)), dim3(256), 0, st, n, sv, X, ldx, Xr); break;
-    }
-}
-static void launch_spmm_wave(hipStream_t st, long long nrows, int sv, const long long* rp, const int* ci, const double* val, const double* Xr, double* Y,
-                             long long ldy) {
-    switch (spmm_width(sv)) {
-        case 2: hipLaunchKernelGGL(k_spmm_wave<2>, dim3(nblk(nrows, 16)), dim3(256), 0, st, nrows, sv, rp, ci, val, Xr, Y, ldy); break;
-        case 4: hipLaunchKernelGGL(k_spmm_wave<4>, dim3(nblk(nrows, 16)), dim3(256), 0, st, nrows, sv, rp, ci, val, Xr, Y, ldy); break;
-        default: hipLaunchKernelGGL(k_spmm_wave<8>, dim3(nblk(nrows, 16)), dim3(256), 0, st, nrows, sv, rp, ci, val, Xr, Y, ldy); break;
-    }
-}
 __global__ void k_axpby(long long n, double a, const double* __restrict__ x, double b, double* __restrict__ y) {
     long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) y[k] = a * x[k] + b * y[k];
@@ -1652,6 +1092,11 @@ static int fail(const std::exception& e) {
 static void need_init(das_solver* s) {
     DAS_CHECK(s, DAS_ERR_ARG, "null solver handle");
     DAS_CHECK(s->inited, DAS_ERR_STATE, "das_init_solver has not been called (or failed): no GPU path available");
+}
+
+// sum of a small device buffer over the ranks: the native all-reduce in stream order, else the legacy host callback (single rank: nothing)
+static void rank_allreduce(das_solver* s, double* p, long long cnt, hipStream_t st) {
+    if (!(s->halo.active && s->halo.allreduce(p, (int)cnt, st)) && s->allreduce_cb) s->allreduce_cb(p, (int)cnt, s->comm_user);
 }
 
 // state scaling s_j (reference DAPartDeriv.C:210-315, DASolver.C:2356-2455)
@@ -2754,7 +2199,7 @@ static void coarse_build_operator(das_solver* s, das_ksp* k, int naggG, int aggO
                        (C.off < k->shiftEnd && !(C.off >= k->shiftExLo && C.off < k->shiftExHi)) ? k->pcDiagScale : 1.0);
     if (C.global) {
         DAS_CHECK(!k->pcTranspose, DAS_ERR_ARG, "global coarse space: adjoint preconditioner only");
-        if (!(s->halo.active && s->halo.allreduce(E.p, naggG * naggG, s->stream)) && s->allreduce_cb) s->allreduce_cb(E.p, naggG * naggG, s->comm_user);
+        rank_allreduce(s, E.p, naggG * naggG, s->stream);
     }
     // E^-1 on the device (Gauss-Jordan, partial pivoting)
     {
@@ -2849,7 +2294,7 @@ static void coarse_solve(das_solver* s, das_ksp* k, const double* r) {
     das_ksp::CoarsePC& C = k->coarse;
     if (C.global) DAS_HIP(hipMemsetAsync(C.t.p, 0, (size_t)C.naggG * sizeof(double), s->stream));
     if (C.nagg > 0) hipLaunchKernelGGL(k_coarse_restrict, dim3(C.nagg), dim3(256), 0, s->stream, C.aptr.p, C.cells.p, C.off, r, C.t.p + C.aggOff);
-    if (C.global && !(s->halo.active && s->halo.allreduce(C.t.p, C.naggG, s->stream)) && s->allreduce_cb) s->allreduce_cb(C.t.p, C.naggG, s->comm_user);
+    if (C.global) rank_allreduce(s, C.t.p, C.naggG, s->stream);
     hipLaunchKernelGGL(k_coarse_solve, dim3(nblk(C.naggG, 64)), dim3(64), 0, s->stream, C.naggG, C.Einv.p, C.t.p, C.u.p);
 }
 
@@ -2931,7 +2376,7 @@ static void gmres_ws(das_solver* s, das_ksp* k) {
             DevBuf<double> f(1);
             const double fv = big ? 1.0 : 0.0;
             DAS_HIP(hipMemcpyAsync(f.p, &fv, sizeof(double), hipMemcpyHostToDevice, s->stream));
-            if (!(s->halo.active && s->halo.allreduce(f.p, 1, s->stream)) && s->allreduce_cb) s->allreduce_cb(f.p, 1, s->comm_user);
+            rank_allreduce(s, f.p, 1, s->stream);
             DAS_HIP(hipStreamSynchronize(s->stream));
             big = f.to_host()[0] > 0.5;
         }
@@ -2970,7 +2415,7 @@ static inline float* basis_lo(das_solver* s, das_ksp* k, long long j) { return k
 template <class VT>
 static void multidot_dev(das_solver* s, das_ksp* k, const VT* Vbase, int m, const double* w, double* dev_out) {
     launch_multidot<VT>(s->stream, s->n, m, Vbase, basis_ld(s, k), w, k->partial.p, dev_out);
-    if (!(s->halo.active && s->halo.allreduce(dev_out, m + 1, s->stream)) && s->allreduce_cb) s->allreduce_cb(dev_out, m + 1, s->comm_user);
+    rank_allreduce(s, dev_out, m + 1, s->stream);
 }
 // h[0..m) = V^T w, h[m] = w.w  (device result in k->hdev, copied to host)
 template <class VT = double>
@@ -3007,7 +2452,7 @@ static bool coarse_az_ready(das_solver* s, das_ksp* k) {
         DevBuf<double> f(1);
         const double fv = ovfAny ? 1.0 : 0.0;
         DAS_HIP(hipMemcpyAsync(f.p, &fv, sizeof(double), hipMemcpyHostToDevice, st));
-        if (!(s->halo.active && s->halo.allreduce(f.p, 1, st)) && s->allreduce_cb) s->allreduce_cb(f.p, 1, s->comm_user);
+        rank_allreduce(s, f.p, 1, st);
         DAS_HIP(hipStreamSynchronize(st));
         ovfAny = f.to_host()[0] > 0.5 ? 1 : 0;
     }
@@ -3348,7 +2793,7 @@ static double gmres_iter_dcgs2(das_solver* s, das_ksp* k) {
     apply_operator(s, k->z.p, k->w.p);
     const int K = j + 1;
     launch_multidot2<VT>(st, n, K, (const VT*)Vb, ld, (const VT*)u, (const double*)k->w.p, k->partial.p, k->hdev.p);
-    if (!(s->halo.active && s->halo.allreduce(k->hdev.p, 2 * K, st)) && s->allreduce_cb) s->allreduce_cb(k->hdev.p, 2 * K, s->comm_user);
+    rank_allreduce(s, k->hdev.p, 2 * K, st);
     std::vector<double>& o = G.hh;
     DAS_HIP(hipMemcpyAsync(o.data(), k->hdev.p, 2 * K * sizeof(double), hipMemcpyDeviceToHost, st));
     DAS_HIP(hipStreamSynchronize(st));
@@ -3377,7 +2822,7 @@ static double gmres_iter_dcgs2(das_solver* s, das_ksp* k) {
             launch_multiaxpy(st, n, j, (const VT*)Vb, ld, (const double*)dsc, u, (const float*)nullptr);
         }
         launch_multidot2<VT>(st, n, 1, (const VT*)u, ld, (const VT*)u, (const double*)k->w.p, k->partial.p, k->hdev.p);  // K = 1: the leading dimension is not used
-        if (!(s->halo.active && s->halo.allreduce(k->hdev.p, 2, st)) && s->allreduce_cb) s->allreduce_cb(k->hdev.p, 2, s->comm_user);
+        rank_allreduce(s, k->hdev.p, 2, st);
         double cc[2] = {0.0, 0.0};
         DAS_HIP(hipMemcpyAsync(cc, k->hdev.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
         DAS_HIP(hipStreamSynchronize(st));
@@ -4260,121 +3705,6 @@ static int run_newton_primal(das_solver* s, int maxSteps, double relTol, double 
 // =====================================================================================================
 // C-ABI
 // =====================================================================================================
-// launch helpers of the tuning hook das_debug_orth_bench (templates cannot sit inside the extern "C" block)
-template <int ROWS>
-static void orth_bench_dots(long long n, int K, const double* V, const double* w, double* partial) {
-    launch_multidot2_pass<ROWS, double>(0, n, K, V, n, V + (long long)(K - 1) * n, w, partial);
-}
-template <int UNROLL, int RPT>
-static void orth_bench_update(long long n, int j, double* V, const double* sc, const double* w) {
-    launch_dcgs2_update<UNROLL, RPT, double>(0, n, j, V, n, sc, 0.5, 1.0, w, (float*)nullptr);
-}
-
-// the same for das_debug_orth_bench_split: the float instantiations the solver runs (lo = null: fp32 storage)
-template <int ROWS>
-static void orth_bench_dots_f(long long n, int K, const float* V, long long ld, const double* w, double* partial) {
-    launch_multidot2_pass<ROWS, float>(0, n, K, V, ld, V + (long long)(K - 1) * ld, w, partial);
-}
-template <int UNROLL, int RPT>
-static void orth_bench_update_f(long long n, int j, float* V, long long ld, float* lo, const double* sc, const double* w) {
-    hipLaunchKernelGGL((k_dcgs2_update<UNROLL, RPT, float>), dim3(nblk(n, 256 * RPT)), dim3(256), 0, 0, n, j, V, ld, sc, 0.5, 1.0, w, lo);
-}
-template <int R4, bool NT>
-static void orth_bench_dots_w(long long n, int K, const float* V, long long ld, const double* w, double* partial) {
-    launch_multidot2w_pass<R4, NT>(0, n, K, V, ld, V + (long long)(K - 1) * ld, w, partial);
-}
-template <int UNROLL, int RPT4, bool NT>
-static void orth_bench_update_w(long long n, int j, float* V, long long ld, float* lo, const double* sc, const double* w) {
-    launch_dcgs2w_update<UNROLL, RPT4, NT>(0, n, j, V, ld, sc, 0.5, 1.0, w, lo);
-}
-
-// ---- bodies of the test-only entries das_debug_krylov_* (tests/test_gpu_krylov_kernels.py) --------------------------------
-// They upload the caller's arrays, run the launch helpers the solver runs (null stream) and download the result.  Nothing in the
-// product path calls them.  Basis formats: 0 = fp64, 1 = fp32, 2 = split (float hi, the lo array n floats further inside a slot).
-enum { KRY_FP64 = 0, KRY_FP32 = 1, KRY_SPLIT = 2 };
-static void krylov_check_basis(const std::string& who, long long n, long long nvec, int fmt, const void* V, long long ld) {
-    DAS_CHECK(n > 0 && nvec > 0, DAS_ERR_ARG, who + ": sizes must be positive");
-    DAS_CHECK(fmt == KRY_FP64 || fmt == KRY_FP32 || fmt == KRY_SPLIT, DAS_ERR_ARG, who + ": fmt is 0 (fp64), 1 (fp32) or 2 (split)");
-    DAS_CHECK(V, DAS_ERR_ARG, who + ": null basis");
-    DAS_CHECK(ld >= (fmt == KRY_SPLIT ? 2 * n : n), DAS_ERR_ARG, who + ": leading dimension below n (split: below 2 n)");
-}
-static void krylov_check_block(const std::string& who, long long n, int K, int sv) {
-    DAS_CHECK(n > 0 && K > 0, DAS_ERR_ARG, who + ": sizes must be positive");
-    DAS_CHECK(sv >= 1 && sv <= 8, DAS_ERR_ARG, who + ": 1 to 8 right-hand sides");
-}
-static void krylov_debug_sync() {
-    DAS_HIP(hipGetLastError());
-    DAS_HIP(hipStreamSynchronize(0));
-}
-template <class VT>
-static float* krylov_lo(VT* V, long long n, bool split) { return split ? reinterpret_cast<float*>(V) + n : nullptr; }
-template <class VT>
-static void debug_krylov_dots2(long long n, int K, const void* V, long long ld, const double* v, double* out) {
-    DevBuf<VT> dV;
-    dV.upload((const VT*)V, (size_t)K * ld);
-    DevBuf<double> dv, partial(multidot2_partial_size(n, K)), dout((size_t)2 * K);
-    dv.upload(v, n);
-    launch_multidot2<VT>(0, n, K, (const VT*)dV.p, ld, (const VT*)(dV.p + (long long)(K - 1) * ld), (const double*)dv.p, partial.p, dout.p);
-    krylov_debug_sync();
-    dout.download(out, (size_t)2 * K);
-}
-template <class VT>
-static void debug_krylov_dcgs2_update(long long n, int j, bool split, void* V, long long ld, int nslots, const double* sc, double gamma, double ralpha,
-                                      const double* v) {
-    DevBuf<VT> dV;
-    dV.upload((const VT*)V, (size_t)nslots * ld);
-    DevBuf<double> dsc((size_t)std::max(1, 2 * j)), dv;
-    if (j > 0) dsc.upload(sc, (size_t)2 * j);
-    dv.upload(v, n);
-    launch_dcgs2_update<DCGS2_UNROLL, DCGS2_RPT, VT>(0, n, j, dV.p, ld, (const double*)dsc.p, gamma, ralpha, (const double*)dv.p, krylov_lo(dV.p, n, split));
-    krylov_debug_sync();
-    dV.download((VT*)V, (size_t)nslots * ld);
-}
-template <class VT>
-static void debug_krylov_multidot(long long n, int m, const void* V, long long ld, const double* w, double* out) {
-    DevBuf<VT> dV((size_t)std::max<long long>(1, m * ld));
-    if (m > 0) dV.upload((const VT*)V, (size_t)m * ld);
-    DevBuf<double> dw, partial(multidot_partial_size(n, m)), dout((size_t)m + 1);
-    dw.upload(w, n);
-    launch_multidot<VT>(0, n, m, (const VT*)dV.p, ld, (const double*)dw.p, partial.p, dout.p);
-    krylov_debug_sync();
-    dout.download(out, (size_t)m + 1);
-}
-template <class VT, class WT>
-static void debug_krylov_multiaxpy(long long n, int m, bool split, const void* V, long long ld, const double* h, void* w, long long wlen) {
-    DevBuf<VT> dV;
-    dV.upload((const VT*)V, (size_t)m * ld);
-    DevBuf<double> dh;
-    dh.upload(h, m);
-    DevBuf<WT> dw;
-    dw.upload((const WT*)w, (size_t)wlen);
-    launch_multiaxpy(0, n, m, (const VT*)dV.p, ld, (const double*)dh.p, dw.p, (const float*)krylov_lo(dV.p, n, split));
-    krylov_debug_sync();
-    dw.download((WT*)w, (size_t)wlen);
-}
-template <class VT>
-static void debug_krylov_lincomb(long long n, int m, bool split, const void* V, long long ld, const double* c, double* y, long long ylen) {
-    DevBuf<VT> dV;
-    dV.upload((const VT*)V, (size_t)m * ld);
-    DevBuf<double> dc, dy;
-    dc.upload(c, m);
-    dy.upload(y, (size_t)ylen);
-    launch_lincomb(0, n, m, (const VT*)dV.p, ld, (const double*)dc.p, dy.p, (const float*)krylov_lo(dV.p, n, split));
-    krylov_debug_sync();
-    dy.download(y, (size_t)ylen);
-}
-// xsplit / ysplit: the lo array sits n floats after the hi array, as in a basis slot
-template <class TI, class TO>
-static void debug_krylov_scale_to(long long n, double a, bool xsplit, bool ysplit, const void* x, void* y, long long ylen) {
-    DevBuf<TI> dx;
-    dx.upload((const TI*)x, (size_t)(xsplit ? 2 * n : n));
-    DevBuf<TO> dy;
-    dy.upload((const TO*)y, (size_t)ylen);
-    launch_scale_to(0, n, a, (const TI*)dx.p, dy.p, (const float*)krylov_lo(dx.p, n, xsplit), krylov_lo(dy.p, n, ysplit));
-    krylov_debug_sync();
-    dy.download((TO*)y, (size_t)ylen);
-}
-
 extern "C" {
 
 const char* das_last_error(void) { return g_err.c_str(); }
@@ -6501,35 +5831,34 @@ int das_set_stream(das_solver_t* s, void* hip_stream) {
     DAS_CATCH
 }
 
+// One timed shape of the two tuning entries below (das_debug_orth_bench*): they name n, K, reps, j = K - 1, the basis V (leading dimension ld, lo array or null),
+// u = its slot K - 1, w, sc and the empty buffer partial, which every inner-product shape sizes for its own slots.
+#define DAS_DOT(VT, R) do { if (rows == R) { partial.alloc((size_t)2 * K * multidot2_nbw<R>(n)); \
+    *ms_dots = orth_bench_ms(reps, [&] { launch_multidot2_pass<R, VT>(0, n, K, V.p, ld, u, w.p, partial.p); }); } } while (0)
+#define DAS_UPD(VT, U, R) do { if (unroll == U && rpt == R) \
+    *ms_update = orth_bench_ms(reps, [&] { launch_dcgs2_update_pass<U, R, VT>(0, n, j, V.p, ld, sc.p, 0.5, 1.0, w.p, lo); }); } while (0)
+#define DAS_DOTW(R, NT) do { if (rows == R) { partial.alloc((size_t)2 * K * multidot2w_nbw(n, R)); \
+    *ms_dots = orth_bench_ms(reps, [&] { launch_multidot2w_pass<R, NT>(0, n, K, V.p, ld, u, w.p, partial.p); }); } } while (0)
+#define DAS_UPDW(U, R, NT) do { if (unroll == U && rpt == R) \
+    *ms_update = orth_bench_ms(reps, [&] { launch_dcgs2w_update<U, R, NT>(0, n, j, V.p, ld, sc.p, 0.5, 1.0, w.p, lo); }); } while (0)
+#define DAS_WIDE(NT) do { DAS_DOTW(1, NT); DAS_DOTW(2, NT); DAS_DOTW(4, NT); \
+    DAS_UPDW(2, 1, NT); DAS_UPDW(4, 1, NT); DAS_UPDW(8, 1, NT); DAS_UPDW(2, 2, NT); DAS_UPDW(4, 2, NT); } while (0)
 // Tuning hook (tools/orth_bench.py): times the two kernels of the delayed re-orthogonalisation on synthetic vectors of length n
 // against K basis vectors, for the compiled variants (rows per thread of the inner products; unroll / rows per thread of
 // the update).  No solver handle: it only needs the device.
 int das_debug_orth_bench(long long n, int K, int reps, int rows, int unroll, int rpt, double* ms_dots, double* ms_update) {
     DAS_TRY
     DAS_CHECK(n > 0 && K > 1 && reps > 0 && ms_dots && ms_update, DAS_ERR_ARG, "das_debug_orth_bench: bad arguments");
-    DevBuf<double> V((size_t)(K + 2) * n), w(n), partial((size_t)2 * K * 4 * nblk(n, 256 * 4)), sc(2 * (size_t)K);
+    const long long ld = n;
+    DevBuf<double> V((size_t)(K + 2) * ld), w(n), partial, sc(2 * (size_t)K);
     V.zero(); w.zero(); sc.zero();
-    hipEvent_t e0, e1;
-    DAS_HIP(hipEventCreate(&e0)); DAS_HIP(hipEventCreate(&e1));
-    auto timed = [&](auto&& launch) {
-        launch();  // warm-up
-        DAS_HIP(hipEventRecord(e0, 0));
-        for (int r = 0; r < reps; r++) launch();
-        DAS_HIP(hipEventRecord(e1, 0));
-        DAS_HIP(hipEventSynchronize(e1));
-        DAS_HIP(hipGetLastError());
-        float ms = 0.f;
-        DAS_HIP(hipEventElapsedTime(&ms, e0, e1));
-        return (double)ms / reps;
-    };
+    float* lo = nullptr;
+    const double* u = V.p + (long long)(K - 1) * ld;
     *ms_dots = -1.0; *ms_update = -1.0;
-    if (rows == 4) *ms_dots = timed([&] { orth_bench_dots<4>(n, K, V.p, w.p, partial.p); });
-    else if (rows == 8) *ms_dots = timed([&] { orth_bench_dots<8>(n, K, V.p, w.p, partial.p); });
-    else if (rows == 16) *ms_dots = timed([&] { orth_bench_dots<16>(n, K, V.p, w.p, partial.p); });
-#define DAS_UPD(U, R) if (unroll == U && rpt == R) *ms_update = timed([&] { orth_bench_update<U, R>(n, K - 1, V.p, sc.p, w.p); })
-    DAS_UPD(4, 1); DAS_UPD(8, 1); DAS_UPD(16, 1); DAS_UPD(4, 2); DAS_UPD(8, 2); DAS_UPD(4, 4); DAS_UPD(8, 4);
-#undef DAS_UPD
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    const int j = K - 1;
+    DAS_DOT(double, 4); DAS_DOT(double, 8); DAS_DOT(double, 16);
+    DAS_UPD(double, 4, 1); DAS_UPD(double, 8, 1); DAS_UPD(double, 16, 1); DAS_UPD(double, 4, 2); DAS_UPD(double, 8, 2); DAS_UPD(double, 4, 4);
+    DAS_UPD(double, 8, 4);
     return DAS_OK;
     DAS_CATCH
 }
@@ -6545,39 +5874,26 @@ int das_debug_orth_bench_split(long long n, int K, int reps, int fmt, int varian
     DAS_CHECK((fmt == KRY_FP32 || fmt == KRY_SPLIT) && variant >= 0 && variant <= 2, DAS_ERR_ARG, "das_debug_orth_bench_split: fmt 1 | 2, variant 0 | 1 | 2");
     const long long n4 = (n + 3) / 4 * 4, ld = fmt == KRY_SPLIT ? 2 * n4 : n4;
     DevBuf<float> V((size_t)(K + 2) * ld);
-    DevBuf<double> w(n4), partial((size_t)2 * K * 4 * nblk(n, 1024)), sc(2 * (size_t)K);
+    DevBuf<double> w(n4), partial, sc(2 * (size_t)K);
     V.zero(); w.zero(); sc.zero();
     float* lo = fmt == KRY_SPLIT ? V.p + n4 : nullptr;
-    hipEvent_t e0, e1;
-    DAS_HIP(hipEventCreate(&e0)); DAS_HIP(hipEventCreate(&e1));
-    auto timed = [&](auto&& launch) {
-        launch();  // warm-up
-        DAS_HIP(hipEventRecord(e0, 0));
-        for (int r = 0; r < reps; r++) launch();
-        DAS_HIP(hipEventRecord(e1, 0));
-        DAS_HIP(hipEventSynchronize(e1));
-        DAS_HIP(hipGetLastError());
-        float ms = 0.f;
-        DAS_HIP(hipEventElapsedTime(&ms, e0, e1));
-        return (double)ms / reps;
-    };
+    const float* u = V.p + (long long)(K - 1) * ld;
     *ms_dots = -1.0; *ms_update = -1.0;
     const int j = K - 1;
-#define DAS_DOT(R) if (rows == R) *ms_dots = timed([&] { orth_bench_dots_f<R>(n, K, V.p, ld, w.p, partial.p); })
-#define DAS_UPD(U, R) if (unroll == U && rpt == R) *ms_update = timed([&] { orth_bench_update_f<U, R>(n, j, V.p, ld, lo, sc.p, w.p); })
-    if (variant == 0) { DAS_DOT(4); DAS_DOT(8); DAS_DOT(16); DAS_UPD(4, 1); DAS_UPD(8, 1); DAS_UPD(4, 2); DAS_UPD(8, 2); DAS_UPD(4, 4); }
-#undef DAS_DOT
-#undef DAS_UPD
-#define DAS_DOT(R, NT) if (rows == R) *ms_dots = timed([&] { orth_bench_dots_w<R, NT>(n, K, V.p, ld, w.p, partial.p); })
-#define DAS_UPD(U, R, NT) if (unroll == U && rpt == R) *ms_update = timed([&] { orth_bench_update_w<U, R, NT>(n, j, V.p, ld, lo, sc.p, w.p); })
-    if (variant == 1) { DAS_DOT(1, false); DAS_DOT(2, false); DAS_DOT(4, false); DAS_UPD(2, 1, false); DAS_UPD(4, 1, false); DAS_UPD(8, 1, false); DAS_UPD(2, 2, false); DAS_UPD(4, 2, false); }
-    if (variant == 2) { DAS_DOT(1, true); DAS_DOT(2, true); DAS_DOT(4, true); DAS_UPD(2, 1, true); DAS_UPD(4, 1, true); DAS_UPD(8, 1, true); DAS_UPD(2, 2, true); DAS_UPD(4, 2, true); }
-#undef DAS_DOT
-#undef DAS_UPD
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (variant == 0) {
+        DAS_DOT(float, 4); DAS_DOT(float, 8); DAS_DOT(float, 16);
+        DAS_UPD(float, 4, 1); DAS_UPD(float, 8, 1); DAS_UPD(float, 4, 2); DAS_UPD(float, 8, 2); DAS_UPD(float, 4, 4);
+    }
+    if (variant == 1) DAS_WIDE(false);
+    if (variant == 2) DAS_WIDE(true);
     return DAS_OK;
     DAS_CATCH
 }
+#undef DAS_DOT
+#undef DAS_UPD
+#undef DAS_DOTW
+#undef DAS_UPDW
+#undef DAS_WIDE
 // the 16-byte-load path of the float basis on (1) / off (0) for every later launch of this process; *previous: what it was.  The tests
 // and the timing tool run both paths of one build with it; the solver never calls it.
 int das_debug_set_orth_wide(int on, int* previous) {
@@ -6672,12 +5988,7 @@ int das_debug_krylov_block_tn(long long n, int K, int s, const double* V, long l
     krylov_check_block("das_debug_krylov_block_tn", n, K, s);
     DAS_CHECK(V && W && C, DAS_ERR_ARG, "das_debug_krylov_block_tn: null pointer");
     DAS_CHECK(ldv >= n && ldw >= n && voff >= 0, DAS_ERR_ARG, "das_debug_krylov_block_tn: leading dimension below n or negative offset");
-    DevBuf<double> dV, dW, partial(tsgemm_partial_size(K)), dC((size_t)K * s);
-    dV.upload(V, (size_t)(voff + (long long)K * ldv));
-    dW.upload(W, (size_t)s * ldw);
-    launch_tsgemm_tn(0, n, K, s, dV.p + voff, ldv, dW.p, ldw, partial.p, dC.p);
-    krylov_debug_sync();
-    dC.download(C, (size_t)K * s);
+    debug_krylov_block_tn(n, K, s, V, ldv, voff, W, ldw, C);
     return DAS_OK;
     DAS_CATCH
 }
@@ -6686,13 +5997,7 @@ int das_debug_krylov_block_nn_sub(long long n, int K, int s, const double* V, lo
     krylov_check_block("das_debug_krylov_block_nn_sub", n, K, s);
     DAS_CHECK(V && W && C, DAS_ERR_ARG, "das_debug_krylov_block_nn_sub: null pointer");
     DAS_CHECK(ldv >= n && ldw >= n, DAS_ERR_ARG, "das_debug_krylov_block_nn_sub: leading dimension below n");
-    DevBuf<double> dV, dW, dC;
-    dV.upload(V, (size_t)K * ldv);
-    dW.upload(W, (size_t)s * ldw);
-    dC.upload(C, (size_t)K * s);
-    launch_tsgemm_nn_sub(0, n, K, s, dV.p, ldv, dC.p, dW.p, ldw);
-    krylov_debug_sync();
-    dW.download(W, (size_t)s * ldw);
+    debug_krylov_block_nn_sub(n, K, s, V, ldv, C, W, ldw);
     return DAS_OK;
     DAS_CATCH
 }
@@ -6701,12 +6006,7 @@ int das_debug_krylov_block_right_mult(long long n, int s, double* W, long long l
     krylov_check_block("das_debug_krylov_block_right_mult", n, 1, s);
     DAS_CHECK(W && T, DAS_ERR_ARG, "das_debug_krylov_block_right_mult: null pointer");
     DAS_CHECK(ldw >= n, DAS_ERR_ARG, "das_debug_krylov_block_right_mult: leading dimension below n");
-    DevBuf<double> dW, dT;
-    dW.upload(W, (size_t)s * ldw);
-    dT.upload(T, (size_t)s * s);
-    launch_block_right_mult(0, n, s, dW.p, ldw, dT.p);
-    krylov_debug_sync();
-    dW.download(W, (size_t)s * ldw);
+    debug_krylov_block_right_mult(n, s, W, ldw, T);
     return DAS_OK;
     DAS_CATCH
 }
@@ -6715,13 +6015,7 @@ int das_debug_krylov_block_lincomb(long long n, int K, int s, const double* V, l
     krylov_check_block("das_debug_krylov_block_lincomb", n, K, s);
     DAS_CHECK(V && C && Y, DAS_ERR_ARG, "das_debug_krylov_block_lincomb: null pointer");
     DAS_CHECK(ldv >= n && ldy >= n, DAS_ERR_ARG, "das_debug_krylov_block_lincomb: leading dimension below n");
-    DevBuf<double> dV, dC, dY;
-    dV.upload(V, (size_t)K * ldv);
-    dC.upload(C, (size_t)K * s);
-    dY.upload(Y, (size_t)s * ldy);
-    launch_block_lincomb(0, n, K, s, dV.p, ldv, dC.p, dY.p, ldy);
-    krylov_debug_sync();
-    dY.download(Y, (size_t)s * ldy);
+    debug_krylov_block_lincomb(n, K, s, V, ldv, C, Y, ldy);
     return DAS_OK;
     DAS_CATCH
 }
@@ -6736,17 +6030,7 @@ int das_debug_krylov_block_spmm(long long n, int s, const long long* rp, const i
     const long long nnz = rp[n];
     DAS_CHECK(nnz == 0 || (ci && val), DAS_ERR_ARG, "das_debug_krylov_block_spmm: null pointer");
     for (long long k = 0; k < nnz; k++) DAS_CHECK(ci[k] >= 0 && ci[k] < n, DAS_ERR_ARG, "das_debug_krylov_block_spmm: column index out of range");
-    DevBuf<long long> drp;
-    drp.upload(rp, (size_t)n + 1);
-    DevBuf<int> dci((size_t)std::max<long long>(1, nnz));
-    DevBuf<double> dval((size_t)std::max<long long>(1, nnz)), dX, dY, dXr((size_t)n * spmm_width(s));
-    if (nnz > 0) { dci.upload(ci, (size_t)nnz); dval.upload(val, (size_t)nnz); }
-    dX.upload(X, (size_t)s * ldx);
-    dY.upload(Y, (size_t)s * ldy);
-    launch_block_to_rows(0, n, s, dX.p, ldx, dXr.p);
-    launch_spmm_wave(0, n, s, drp.p, dci.p, dval.p, dXr.p, dY.p, ldy);
-    krylov_debug_sync();
-    dY.download(Y, (size_t)s * ldy);
+    debug_krylov_block_spmm(n, s, rp, ci, val, X, ldx, Y, ldy);
     return DAS_OK;
     DAS_CATCH
 }

@@ -19,11 +19,10 @@ import __graft_entry__ as ge
 ge.build()
 from dafoam_amd import _capi
 L = _capi.lib()
-FP64_DOTS = (16,) if a.quick else (4, 8, 16)
-FP64_UPD = ((4, 2),) if a.quick else ((4, 1), (8, 1), (16, 1), (4, 2), (8, 2), (4, 4), (8, 4))
-SCALAR_DOTS, SCALAR_UPD = (8, 16), ((4, 1), (8, 1), (4, 2), (8, 2), (4, 4))
-WIDE_DOTS, WIDE_UPD = (1, 2, 4), ((2, 1), (4, 1), (8, 1), (2, 2), (4, 2))
-VARIANT = {0: "scalar", 1: "wide", 2: "wide-nt"}
+from dafoam_amd import orth_bench_shapes as S
+FP64_DOTS = S.FP64_DOTS_QUICK if a.quick else S.FP64_DOTS
+FP64_UPD = S.FP64_UPD_QUICK if a.quick else S.FP64_UPD
+VARIANT = S.VARIANT
 
 
 def line(K, what, ms, gb):
@@ -46,12 +45,13 @@ for K in a.K:
             continue
         gb_d = 4.0 * (K + 2) * a.n / 1e9  # 4 B per basis entry (K vectors), u and v on top
         gb_u = (8.0 if fmt == 2 else 4.0) * (K + 2) * a.n / 1e9
-        for variant in (0, 1, 2):
-            for rows in (SCALAR_DOTS if variant == 0 else WIDE_DOTS):
+        for variant in VARIANT:
+            dots, upd = S.split_shapes(variant)
+            for rows in dots:
                 d, u = C.c_double(-1), C.c_double(-1)
                 _capi.check(L.das_debug_orth_bench_split(a.n, K, a.reps, fmt, variant, rows, 0, 0, C.byref(d), C.byref(u)))
                 line(K, f"{name} {VARIANT[variant]} multidot2 rows/lane {rows if variant == 0 else 4 * rows}", d.value, gb_d)
-            for unroll, rpt in (SCALAR_UPD if variant == 0 else WIDE_UPD):
+            for unroll, rpt in upd:
                 d, u = C.c_double(-1), C.c_double(-1)
                 _capi.check(L.das_debug_orth_bench_split(a.n, K, a.reps, fmt, variant, 0, unroll, rpt, C.byref(d), C.byref(u)))
                 line(K, f"{name} {VARIANT[variant]} dcgs2_update unroll {unroll} rows/lane {rpt if variant == 0 else 4 * rpt}", u.value, gb_u)
