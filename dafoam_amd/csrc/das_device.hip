@@ -28,6 +28,7 @@
 #include "das_graph.hpp"
 #include "das_volcoord.hpp"
 #include "das_cellfn.hpp"
+#include "das_facefn.hpp"
 #include "das_simple.hpp"
 
 #include <omp.h>
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(256) void k_fn_value(DevMesh m, ResParams prm, cons
     if (k >= fn.nf) return;
     double dir[3] = {0.0, 0.0, 0.0};
     if (fn.dir) { dir[0] = fn.dir[3 * k]; dir[1] = fn.dir[3 * k + 1]; dir[2] = fn.dir[3 * k + 2]; }
-    fv[k] = fn.w[k] * body_facefn<double, RHO>(fn.faces[k], m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn);
+    fv[k] = fn.w[k] * body_facefn<double, RHO>(fn.faces[k], m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc);
 }
 // out2[g] = sum of fv[k] over the entries of group g (group == nullptr: everything is group 0); one workgroup, fixed order
 __global__ __launch_bounds__(256) void k_group_sum(long long cnt, const unsigned char* __restrict__ group, const double* __restrict__ fv, double* __restrict__ out2) {
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(256) void k_fn_tangent(DevMesh m, ResParams prm, co
     if (k >= fn.nf) return;
     double dir[3] = {0.0, 0.0, 0.0};
     if (fn.dir) { dir[0] = fn.dir[3 * k]; dir[1] = fn.dir[3 * k + 1]; dir[2] = fn.dir[3 * k + 2]; }
-    Dual<1> v = body_facefn<Dual<1>, RHO>(fn.faces[k], m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn);
+    Dual<1> v = body_facefn<Dual<1>, RHO>(fn.faces[k], m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc);
     fv[k] = seed * fn.w[k] * v.d[0];
 }
 // part[b] = sum over the block's rows of psi_i * dR_i  (dR = tangent part of a dual residual); k_group_sum adds the parts
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(256) void k_fn_grad(DevMesh m, ResParams prm, const
     double dir[3] = {0.0, 0.0, 0.0};
     if (fn.dir) { dir[0] = fn.dir[3 * k]; dir[1] = fn.dir[3 * k + 1]; dir[2] = fn.dir[3 * k + 2]; }
     const int f = fn.faces[k];
-    Dual<1> v = body_facefn<Dual<1>, RHO>(f, m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn);
+    Dual<1> v = body_facefn<Dual<1>, RHO>(f, m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc);
     if (v.d[0] == 0.0) return;
     const double g = seed * fn.w[k] * v.d[0];
     const long long N = m.nC;
@@ -1010,8 +1011,14 @@ struct das_solver {
         bool refVar = false, geoWeight = false, hasData = true;
         double ref = 0.0;
         int ncomp = 1;
+        // wallHeatFlux: byUnitArea (area average) or the plain sum; location: axis / center, the KS modes (F = log sum exp(coeffKS a_f) /
+        // coeffKS, das_facefn.hpp; d_ks = {m, S} of the last value, d_kpart = the block partials) or maxRadius (one face, chosen at definition)
+        bool byUnitArea = true, ks = false;
+        double coeffKS = 1.0, loc[6] = {1, 0, 0, 0, 0, 0};
+        DevBuf<double> d_ks, d_kpart;
         FaceFnView view(const double* w) const {
-            return FaceFnView{d_faces.p, d_group.p, w, dir.empty() ? nullptr : d_dir.p, (int)faces.size(), kind, gammaFn, RFn};
+            return FaceFnView{d_faces.p, d_group.p, w, dir.empty() ? nullptr : d_dir.p, (int)faces.size(), kind, gammaFn, RFn,
+                              {loc[0], loc[1], loc[2], loc[3], loc[4], loc[5]}};
         }
     };
     std::map<std::string, FaceFn> functions;
@@ -4381,7 +4388,10 @@ static void build_function_geometry(das_solver* s, das_solver::FaceFn& fn) {
         else if (DAS_FN_BASE(fn.kind) == DAS_FN_PATCHMEAN) fn.w0[k] = fn.scale * g.magSf / area[0];  // DAFunctionPatchMean.C:55-80
         else if (DAS_FN_BASE(fn.kind) == DAS_FN_VARIANCE)  // DAFunctionVariance.C: geoWeightTotal adds |Sf| once per component
             fn.w0[k] = !fn.hasData ? 0.0 : fn.geoWeight ? fn.scale * g.magSf / (fn.ncomp * area[0]) : fn.scale / (double)(fn.ncomp * nf);
-        else fn.w0[k] = g.magSf / area[fn.group[k]];                                          // TTIn / TTOut area averages
+        else if (DAS_FN_BASE(fn.kind) == DAS_FN_WALLHEATFLUX)  // DAFunctionWallHeatFlux.C:264-295: area average, or the total through the surface
+            fn.w0[k] = fn.byUnitArea ? fn.scale * g.magSf / area[0] : fn.scale * g.magSf;
+        else if (DAS_FN_BASE(fn.kind) == DAS_FN_LOCATION) fn.w0[k] = 1.0;  // the value pass stores a_f itself
+        else fn.w0[k] = g.magSf / area[fn.group[k]];                                          // TTIn / TTOut, TPIn / TPOut area averages
     }
     fn.geomVersion = s->geomVersion;
     fn.uploaded = false;
@@ -4391,15 +4401,23 @@ static void build_function_geometry(das_solver* s, das_solver::FaceFn& fn) {
 //      DAFunctionTotalPressure, DAFunctionTotalTemperatureRatio) ------------------------------------------------------
 int das_define_face_function(das_solver_t* s, const char* name, const char* type, const int* patch_ids, const int* patch_group, int npatch,
                              const double* vecA, const double* vecB, double scale, double gammaFn) {
+    return das_define_face_function_ex(s, name, type, patch_ids, patch_group, npatch, vecA, vecB, scale, gammaFn, 1, 0.0);
+}
+int das_define_face_function_ex(das_solver_t* s, const char* name, const char* type, const int* patch_ids, const int* patch_group, int npatch,
+                                const double* vecA, const double* vecB, double scale, double gammaFn, int flags, double ref) {
     DAS_TRY
     DAS_CHECK(s && name && type && patch_ids && npatch > 0, DAS_ERR_ARG, "bad argument");
-    DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver), DAS_ERR_ARG, "function needs a flow solver");
     const std::string ty = type;
+    DAS_CHECK(ty != "wallHeatFlux" || DAS_IS_COMPRESSIBLE(s->cp.solver) || (s->cp.solver == DAS_SOLVER_SIMPLEFOAM && s->cp.hasT), DAS_ERR_ARG,
+              std::string("wallHeatFlux function ") + name + " needs a T field (DASimpleFoam with T, DARhoSimpleFoam, DATurboFoam)");
+    DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver), DAS_ERR_ARG, "function needs a flow solver");
     das_solver::FaceFn fn;
     if (ty == "force" || ty == "moment") fn.kind = DAS_FN_FORCE;
     else if (ty == "massFlowRate") fn.kind = DAS_FN_MASSFLOW;
     else if (ty == "totalPressure") fn.kind = DAS_FN_TOTALPRESSURE;
     else if (ty == "totalTemperatureRatio") { fn.kind = DAS_FN_TOTALTEMPERATURE; fn.ratio = true; }
+    else if (ty == "totalPressureRatio") { fn.kind = DAS_FN_TOTALPRESSURERATIO; fn.ratio = true; }
+    else if (ty == "wallHeatFlux") { fn.kind = DAS_FN_WALLHEATFLUX | ((flags & 2) ? 16 : 0); fn.byUnitArea = (flags & 1) != 0; }
     else throw Error(DAS_ERR_ARG, "function type not implemented on the GPU path: " + ty);
     if (fn.kind == DAS_FN_FORCE) {
         DAS_CHECK(vecA, DAS_ERR_ARG, "force / moment need a direction / axis");
@@ -4409,9 +4427,9 @@ int das_define_face_function(das_solver_t* s, const char* name, const char* type
         DAS_CHECK(ty == "force" || vecB, DAS_ERR_ARG, "moment needs a center");
     }
     if (fn.ratio) {
-        DAS_CHECK(DAS_IS_COMPRESSIBLE(s->cp.solver), DAS_ERR_ARG, "totalTemperatureRatio needs a compressible solver");
-        DAS_CHECK(patch_group, DAS_ERR_ARG, "totalTemperatureRatio needs the inlet (0) / outlet (1) group of every patch");
-        DAS_CHECK(gammaFn > 1.0, DAS_ERR_ARG, "totalTemperatureRatio needs gamma > 1");
+        DAS_CHECK(DAS_IS_COMPRESSIBLE(s->cp.solver), DAS_ERR_ARG, ty + " needs a compressible solver");
+        DAS_CHECK(patch_group, DAS_ERR_ARG, ty + " needs the inlet (0) / outlet (1) group of every patch");
+        DAS_CHECK(gammaFn > 1.0, DAS_ERR_ARG, ty + " needs gamma > 1");
         fn.gammaFn = gammaFn;
         fn.RFn = s->cp.Cp - s->cp.Cp / gammaFn;  // DAFunctionTotalTemperatureRatio.C:98
     }
@@ -4426,8 +4444,53 @@ int das_define_face_function(das_solver_t* s, const char* name, const char* type
         }
     }
     fn.isMoment = ty == "moment";
-    fn.scale = scale;
+    fn.scale = fn.kind == DAS_FN_TOTALPRESSURERATIO ? 1.0 : scale;  // DAFunctionTotalPressureRatio.C applies no scale
+    // calcRefVar (DAFunction::calcRefVar) of the kinds this entry adds; the earlier kinds keep their meaning under das_define_face_function
+    fn.refVar = (flags & 8) && (fn.kind == DAS_FN_TOTALPRESSURERATIO || DAS_FN_BASE(fn.kind) == DAS_FN_WALLHEATFLUX);
+    fn.ref = ref;
     for (int d = 0; d < 3; d++) { fn.vecA[d] = vecA ? vecA[d] : 0.0; fn.vecB[d] = vecB ? vecB[d] : 0.0; }
+    build_function_geometry(s, fn);
+    s->cellFunctions.erase(name);
+    s->functions[name] = std::move(fn);
+    return DAS_OK;
+    DAS_CATCH
+}
+// location (reference DAFunctionLocation.C): mode maxRadiusKS / maxInverseRadiusKS / maxRadius over the faces of the patches.  The axis is
+// normalised here (:40-46).  maxRadius keeps the ONE face that has the largest radius now (the first on ties, :83-126); a later
+// das_update_of_mesh does not choose again.  flags & 8: calcRefVar.  No scale is applied (:153-295).
+int das_define_location_function(das_solver_t* s, const char* name, const char* mode, const int* patch_ids, int npatch, const double* axis,
+                                 const double* center, double coeffKS, int flags, double ref) {
+    DAS_TRY
+    DAS_CHECK(s && name && mode && patch_ids && npatch > 0 && axis && center, DAS_ERR_ARG, "bad argument");
+    DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver), DAS_ERR_ARG, "function needs a flow solver");
+    const std::string md = mode;
+    DAS_CHECK(md == "maxRadiusKS" || md == "maxInverseRadiusKS" || md == "maxRadius", DAS_ERR_ARG,
+              "mode: " + md + " not supported! Options are: maxRadiusKS, maxInverseRadiusKS, maxRadius");
+    const double mag = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
+    DAS_CHECK(mag > 0.0, DAS_ERR_ARG, std::string("the axis of location function ") + name + " has zero length");
+    das_solver::FaceFn fn;
+    fn.kind = DAS_FN_LOCATION | (md == "maxInverseRadiusKS" ? 16 : 0);
+    fn.ks = md != "maxRadius";
+    fn.coeffKS = coeffKS;
+    DAS_CHECK(!fn.ks || coeffKS != 0.0, DAS_ERR_ARG, std::string("coeffKS of location function ") + name + " is zero");
+    for (int d = 0; d < 3; d++) { fn.loc[d] = axis[d] / mag; fn.loc[3 + d] = center[d]; }
+    fn.refVar = (flags & 8) != 0;
+    fn.ref = ref;
+    int best = -1;
+    double maxR = -100000.0;
+    for (int k = 0; k < npatch; k++) {
+        const int p = patch_ids[k];
+        DAS_CHECK(p >= 0 && p < s->mesh.nPatch, DAS_ERR_ARG, "patch id out of range");
+        DAS_CHECK(s->mesh.patch_type[p] != DAS_PATCH_CYCLIC, DAS_ERR_ARG, "functions cannot be defined on cyclic patches");
+        for (int q = 0; q < s->mesh.patch_size[p]; q++) {
+            const int f = s->mesh.patch_start[p] + q;
+            if (fn.ks) { fn.faces.push_back(f); fn.group.push_back(0); continue; }
+            const double r = location_radius<double>(s->mesh.fg[f], fn.loc, false);
+            if (r > maxR) { maxR = r; best = f; }
+        }
+    }
+    if (!fn.ks && best >= 0) { fn.faces.push_back(best); fn.group.push_back(0); }
+    DAS_CHECK(!fn.faces.empty(), DAS_ERR_ARG, "the patches of function " + std::string(name) + " have no faces");
     build_function_geometry(s, fn);
     s->cellFunctions.erase(name);
     s->functions[name] = std::move(fn);
@@ -4629,9 +4692,19 @@ static das_solver::FaceFn& get_function(das_solver* s, const char* name) {
 // group sums S[0], S[1] of w0_f q_f at the current states (k_grad + k_fn_value)
 static void function_sums(das_solver* s, das_solver::FaceFn& fn, double S[2]) {
     const bool rho = DAS_IS_COMPRESSIBLE(s->cp.solver);
-    ResParams prm = s->wk.bind(s->cp.solver, s->dm.nC, s->dm.nF, make_params(s->cp, s->opt, 0));
     const int B = 256, nf = (int)fn.faces.size();
     if (fn.d_fv.n != (size_t)nf) fn.d_fv.alloc(nf);
+    if (DAS_FN_BASE(fn.kind) == DAS_FN_LOCATION) {  // geometry only: no gradients, no states
+        hipLaunchKernelGGL((k_fn_value<false>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, make_params(s->cp, s->opt, 0), s->d_W.p, (const double*)nullptr,
+                           (const double*)nullptr, fn.view(fn.d_w0.p), fn.d_fv.p);
+        if (fn.ks) { DAS_HIP(hipGetLastError()); S[0] = S[1] = 0.0; return; }  // the KS reduction reads fn.d_fv (location_ks_value)
+        hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, s->stream, (long long)nf, (const unsigned char*)fn.d_group.p, (const double*)fn.d_fv.p, s->d_tmp1.p);
+        DAS_HIP(hipGetLastError());
+        DAS_HIP(hipMemcpyAsync(S, s->d_tmp1.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        DAS_HIP(hipStreamSynchronize(s->stream));
+        return;
+    }
+    ResParams prm = s->wk.bind(s->cp.solver, s->dm.nC, s->dm.nF, make_params(s->cp, s->opt, 0));
     if (rho) {
         hipLaunchKernelGGL((k_grad<double, true>), dim3(nblk(s->dm.nC, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, s->wk.gP.p, s->wk.gN.p, s->wk.gH.p);
         hipLaunchKernelGGL((k_fn_value<true>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn.view(fn.d_w0.p), fn.d_fv.p);
@@ -4644,8 +4717,58 @@ static void function_sums(das_solver* s, das_solver::FaceFn& fn, double S[2]) {
     DAS_HIP(hipMemcpyAsync(S, s->d_tmp1.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     DAS_HIP(hipStreamSynchronize(s->stream));
 }
+// the KS aggregate F0 = (m + log S) / coeffKS of the per-face values (das_facefn.hpp); {m, S} stay in fn.d_ks for k_ks_weights.
+// The reference stops when its running sum of exp(coeffKS a_f) passes 1e200 (DAFunctionLocation.C:195-199); the sum only grows, so
+// that is the total m + log S passing log(1e200) - the same guard, with no exponential that could overflow.
+static double location_ks_value(das_solver* s, das_solver::FaceFn& fn) {
+    double unused[2];
+    function_sums(s, fn, unused);  // a_f -> fn.d_fv
+    const long long nf = (long long)fn.faces.size();
+    const int nb = std::max(1, std::min(DAS_FACEFN_MAX_BLOCKS, nblk(nf, 256)));
+    if (fn.d_ks.n != 2) { fn.d_ks.alloc(2); fn.d_kpart.alloc(DAS_FACEFN_MAX_BLOCKS); }
+    hipLaunchKernelGGL(k_ks_max, dim3(nb), dim3(256), 0, s->stream, nf, (const double*)fn.d_fv.p, fn.coeffKS, fn.d_kpart.p);
+    hipLaunchKernelGGL(k_ks_max_final, dim3(1), dim3(256), 0, s->stream, nb, (const double*)fn.d_kpart.p, fn.d_ks.p);
+    hipLaunchKernelGGL(k_ks_expsum, dim3(nb), dim3(256), 0, s->stream, nf, (const double*)fn.d_fv.p, fn.coeffKS, (const double*)fn.d_ks.p, fn.d_kpart.p);
+    hipLaunchKernelGGL(k_ks_sum_final, dim3(1), dim3(256), 0, s->stream, nb, (const double*)fn.d_kpart.p, fn.d_ks.p);
+    DAS_HIP(hipGetLastError());
+    double ms[2];
+    DAS_HIP(hipMemcpyAsync(ms, fn.d_ks.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    const double lg = ms[0] + std::log(ms[1]);
+    DAS_CHECK(lg <= std::log(1e200), DAS_ERR_ARG, "KS function summation term too large! Reduce coeffKS!");
+    return lg / fn.coeffKS;
+}
+// the function before calcRefVar: the sum or the quotient of the group sums, or the KS aggregate
+static double function_base_value(das_solver* s, das_solver::FaceFn& fn) {
+    if (fn.ks) return location_ks_value(s, fn);
+    double S[2];
+    function_sums(s, fn, S);
+    return fn.ratio ? S[1] / S[0] : S[0] + S[1];
+}
 // effective per-face weights of the derivative passes: the base weights, times the quotient rule for ratio functions
 static void function_effective_weights(das_solver* s, das_solver::FaceFn& fn) {
+    if (DAS_FN_BASE(fn.kind) == DAS_FN_LOCATION) {  // dF/da_f: the softmax of the KS modes, 1 on the one face of maxRadius
+        const double F0 = function_base_value(s, fn);
+        const double outer = fn.refVar ? 2.0 * (F0 - fn.ref) : 1.0;
+        const long long nf = (long long)fn.faces.size();
+        if (fn.ks) {
+            hipLaunchKernelGGL(k_ks_weights, dim3(nblk(nf, 256)), dim3(256), 0, s->stream, nf, (const double*)fn.d_fv.p, fn.coeffKS, (const double*)fn.d_ks.p, outer, fn.d_weff.p);
+            DAS_HIP(hipGetLastError());
+        } else {
+            fn.d_weff.upload(std::vector<double>(fn.w0.size(), outer));
+        }
+        return;
+    }
+    if (fn.refVar && fn.ratio) {  // F = (S1 / S0 - ref)^2
+        double S[2];
+        function_sums(s, fn, S);
+        const double a = 2.0 * (S[1] / S[0] - fn.ref);
+        const double c[2] = {-a * S[1] / (S[0] * S[0]), a / S[0]};
+        std::vector<double> w(fn.w0.size());
+        for (size_t k = 0; k < w.size(); k++) w[k] = fn.w0[k] * c[fn.group[k]];
+        fn.d_weff.upload(w);
+        return;
+    }
     if (fn.refVar) {  // F = (S - ref)^2: dF = 2 (S - ref) dS
         double S[2];
         function_sums(s, fn, S);
@@ -4676,9 +4799,7 @@ int das_calc_function(das_solver_t* s, const char* name, double* value) {
         return DAS_OK;
     }
     das_solver::FaceFn& fn = get_function(s, name);
-    double S[2];
-    function_sums(s, fn, S);
-    *value = fn.ratio ? S[1] / S[0] : S[0] + S[1];
+    *value = function_base_value(s, fn);
     if (fn.refVar) *value = (*value - fn.ref) * (*value - fn.ref);
     return DAS_OK;
     DAS_CATCH
@@ -4692,6 +4813,10 @@ static void function_gradient(das_solver* s, const char* name, double seed, doub
         return;
     }
     das_solver::FaceFn& fn = get_function(s, name);
+    if (DAS_FN_BASE(fn.kind) == DAS_FN_LOCATION) {  // geometry only: dF/dW = 0 exactly, no coloured pass
+        std::fill(product, product + s->n, 0.0);
+        return;
+    }
     ensure_con_dev(s, 0);
     function_effective_weights(s, fn);
     ResParams prm = s->wk1.bind(s->cp.solver, s->dm.nC, s->dm.nF, make_params(s->cp, s->opt, 0));
@@ -4824,6 +4949,9 @@ int das_calc_dbc_product(das_solver_t* s, const int* patches, int np, const char
         hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, st, 1024LL, (const unsigned char*)nullptr, (const double*)part.p, s->d_tmp1.p);
         DAS_HIP(hipStreamSynchronize(st));  // part goes out of scope
     } else if (find_cell_function(s, outputName)) {  // cell-set functions read no boundary value
+        product[0] = 0.0;
+        return DAS_OK;
+    } else if (DAS_FN_BASE(get_function(s, outputName).kind) == DAS_FN_LOCATION) {  // geometry only
         product[0] = 0.0;
         return DAS_OK;
     } else {
@@ -5109,13 +5237,14 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
                 hipLaunchKernelGGL(k_vc_rows_dual, dim3(nblk(m.nC, B)), dim3(B), 0, st, s->dm, L, (const double*)d_seeds.p, (const D*)d_Rd.p, d_tc.p);
             } else {
                 const ResParams prm = s->wk1.bind(s->cp.solver, s->dm.nC, s->dm.nF, prm0);
-                const FaceFnView fv = fn->view(fn->d_w0.p);
+                const bool isLoc = DAS_FN_BASE(fn->kind) == DAS_FN_LOCATION;  // the linearised functional sum w_eff a_f; no state is read
+                const FaceFnView fv = fn->view(isLoc ? fn->d_weff.p : fn->d_w0.p);
                 if (rho) {
-                    hipLaunchKernelGGL((k_grad<D, true, D>), dim3(nblk(m.nC, B)), dim3(B), 0, st, dmD, prm, (const D*)d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, s->wk1.gP.p, s->wk1.gN.p, s->wk1.gH.p);
+                    if (!isLoc) hipLaunchKernelGGL((k_grad<D, true, D>), dim3(nblk(m.nC, B)), dim3(B), 0, st, dmD, prm, (const D*)d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, s->wk1.gP.p, s->wk1.gN.p, s->wk1.gH.p);
                     hipLaunchKernelGGL((k_fn_dual<true>), dim3(nblk(nf, B)), dim3(B), 0, st, dmD, prm, (const D*)d_Wd.p, (const D*)s->wk1.nut.p, (const D*)s->wk1.gU.p, fv,
                                        (int)fn->isMoment, fn->vecA[0], fn->vecA[1], fn->vecA[2], fn->vecB[0], fn->vecB[1], fn->vecB[2], (int)areaAvg, cN[0], cN[1], cA[0], cA[1], d_fvd.p);
                 } else {
-                    hipLaunchKernelGGL((k_grad<D, false, D>), dim3(nblk(m.nC, B)), dim3(B), 0, st, dmD, prm, (const D*)d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, s->wk1.gP.p, s->wk1.gN.p, s->wk1.gH.p);
+                    if (!isLoc) hipLaunchKernelGGL((k_grad<D, false, D>), dim3(nblk(m.nC, B)), dim3(B), 0, st, dmD, prm, (const D*)d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, s->wk1.gP.p, s->wk1.gN.p, s->wk1.gH.p);
                     hipLaunchKernelGGL((k_fn_dual<false>), dim3(nblk(nf, B)), dim3(B), 0, st, dmD, prm, (const D*)d_Wd.p, (const D*)s->wk1.nut.p, (const D*)s->wk1.gU.p, fv,
                                        (int)fn->isMoment, fn->vecA[0], fn->vecA[1], fn->vecA[2], fn->vecB[0], fn->vecB[1], fn->vecB[2], (int)areaAvg, cN[0], cN[1], cA[0], cA[1], d_fvd.p);
                 }
@@ -5164,17 +5293,27 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
     DAS_CHECK(!fn || DAS_FN_BASE(fn->kind) != DAS_FN_VARIANCE, DAS_ERR_ARG, std::string("volCoord input is not supported for the variance function ") + outputName);
     // area-averaged functions: coefficients of the linearised functional (k_fn_area_avg) from the group sums at the base mesh
     double cN[2] = {0.0, 0.0}, cA[2] = {0.0, 0.0};
-    const bool areaAvg = isFn && (fn->kind == DAS_FN_TOTALPRESSURE || fn->kind == DAS_FN_TOTALTEMPERATURE || DAS_FN_BASE(fn->kind) == DAS_FN_PATCHMEAN);
+    const int base = isFn ? DAS_FN_BASE(fn->kind) : -1;
+    const bool isLoc = base == DAS_FN_LOCATION;
+    // functions whose weights carry |Sf| (the area averages; wallHeatFlux also as the plain sum scale |Sf| q)
+    const bool areaAvg = isFn && (fn->kind == DAS_FN_TOTALPRESSURE || fn->kind == DAS_FN_TOTALTEMPERATURE || base == DAS_FN_PATCHMEAN
+                                  || base == DAS_FN_TOTALPRESSURERATIO || base == DAS_FN_WALLHEATFLUX);
+    if (isLoc) function_effective_weights(s, *fn);  // location: the linearised functional sum w_eff a_f (softmax weights at the base mesh)
     if (areaAvg) {
         double S[2], A[2] = {0.0, 0.0};
         function_sums(s, *fn, S);  // S_g = sum of w0 q: totalPressure scale N0 / A0 (one group), ratio functions N_g / A_g
         for (size_t q = 0; q < fn->faces.size(); q++) A[fn->group[q]] += m.fg[fn->faces[q]].magSf;
         if (!fn->ratio) {
-            const double outer = fn->refVar ? 2.0 * (S[0] + S[1] - fn->ref) : 1.0;  // patchMean calcRefVar
-            cN[0] = outer * fn->scale / A[0];
-            cA[0] = -outer * S[0] / A[0];
+            const double outer = fn->refVar ? 2.0 * (S[0] + S[1] - fn->ref) : 1.0;  // calcRefVar
+            if (base == DAS_FN_WALLHEATFLUX && !fn->byUnitArea) {  // F = scale sum |Sf| q
+                cN[0] = outer * fn->scale;
+            } else {
+                cN[0] = outer * fn->scale / A[0];
+                cA[0] = -outer * S[0] / A[0];
+            }
         } else {
-            const double F = S[1] / S[0];  // F = (N1 / A1) / (N0 / A0)
+            const double F0 = S[1] / S[0];  // F0 = (N1 / A1) / (N0 / A0)
+            const double F = (fn->refVar ? 2.0 * (F0 - fn->ref) : 1.0) * F0;
             cN[1] = F / (S[1] * A[1]); cA[1] = -F / A[1];
             cN[0] = -F / (S[0] * A[0]); cA[0] = F / A[0];
         }
@@ -5245,6 +5384,11 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
     auto output_pass = [&](double* Rout, double* fvOut) {
         if (!isFn) {
             eval_residual<double>(s->dm, s->cp, prm0, s->d_W.p, Rout, s->wk, s->d_phiF.p, s->d_Told.p, st);
+            return;
+        }
+        if (isLoc) {
+            hipLaunchKernelGGL((k_fn_value<false>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm0, s->d_W.p, (const double*)nullptr, (const double*)nullptr,
+                               fn->view(fn->d_weff.p), fvOut);
             return;
         }
         const ResParams prm = s->wk.bind(s->cp.solver, s->dm.nC, s->dm.nF, prm0);

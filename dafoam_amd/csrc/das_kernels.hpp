@@ -277,6 +277,14 @@ DAS_HD void eval_bface(const PatchBC& bc, const FaceGeomT<G>& g, const CellGeomT
     }
 }
 
+// alphaEff of the energy equation and of the wall heat flux: compressible mu alphaFac + rho nut / Prt (alphaFac = 1 / Pr, or the
+// modified Eucken factor under Sutherland transport); DASimpleFoam T field nu / Pr + nut / Prt (DAResidualSimpleFoam.C:226)
+template <class T, bool RHO>
+DAS_HD T alpha_eff(const ResParams& prm, const T& mu, const T& rho, const T& nut) {
+    if (RHO) return mu * prm.alphaFac + rho * nut * (1.0 / prm.Prt);
+    return prm.nu / prm.Pr + nut * (1.0 / prm.Prt);
+}
+
 // q = Teff . U with Teff = muEff dev(twoSymm(grad U))  (= -devRhoReff, symmetric); g[3*i+j] = d_i U_j
 template <class T>
 DAS_HD void teff_dot_u(const T* g, const T& muEff, const T* U, T* q) {
@@ -426,8 +434,7 @@ DAS_HD void body_cell(int c, const DevMeshT<G>& m, const ResParams& prm, const T
     T Dn_c = rho_c * (nc + nu_c) * (1.0 / SA_SIGMA);
     // energy (RHO)
     T he_c = RHO ? prm.Cp * (Tc - DAS_TREF) : Tc;
-    // alphaEff: compressible mu/Pr + rho nut/Prt ; DASimpleFoam T field nu/Pr + nut/Prt (DAResidualSimpleFoam.C:226)
-    T aEff_c = RHO ? mu_c * prm.alphaFac + rho_c * nut_c * (1.0 / prm.Prt) : prm.nu / prm.Pr + nut_c * (1.0 / prm.Prt);
+    T aEff_c = alpha_eff<T, RHO>(prm, mu_c, rho_c, nut_c);
     T K_c = RHO ? 0.5 * (Uc[0] * Uc[0] + Uc[1] * Uc[1] + Uc[2] * Uc[2]) : T(0.0);
 
     const bool turbo = RHO && prm.turbo;
@@ -540,7 +547,7 @@ DAS_HD void body_cell(int c, const DevMeshT<G>& m, const ResParams& prm, const T
             //      (DASimpleFoam T field: div(phi,T) bounded upwind - laplacian(alphaEff, T), no K)
             if (energy) {
                 T he_o = RHO ? prm.Cp * (T_o - DAS_TREF) : T_o;
-                T aEff_o = RHO ? (rho_o * nu_o) * prm.alphaFac + rho_o * nut_o * (1.0 / prm.Prt) : prm.nu / prm.Pr + nut_o * (1.0 / prm.Prt);
+                T aEff_o = alpha_eff<T, RHO>(prm, rho_o * nu_o, rho_o, nut_o);
                 T ga = (wc * aEff_c + wo * aEff_o) * g.magSf;
                 T cde = ga * g.nod;
                 dE += dcoef + cde;
@@ -619,7 +626,7 @@ DAS_HD void body_cell(int c, const DevMeshT<G>& m, const ResParams& prm, const T
             bdN += phi * b.n.vic - gn_b * b.n.gic;
             bsN += gn_b * b.n.gbc - phi * b.n.vbc;
             if (energy) {
-                T ga_b = (RHO ? b.mu_b * prm.alphaFac + b.rho_b * b.nut_b * (1.0 / prm.Prt) : prm.nu / prm.Pr + b.nut_b * (1.0 / prm.Prt)) * g.magSf;
+                T ga_b = alpha_eff<T, RHO>(prm, b.mu_b, b.rho_b, b.nut_b) * g.magSf;
                 bdE += phi * b.he.vic - ga_b * b.he.gic;
                 bsE += ga_b * b.he.gbc - phi * b.he.vbc;
                 T Kb = 0.5 * (b.U.xb[0] * b.U.xb[0] + b.U.xb[1] * b.U.xb[1] + b.U.xb[2] * b.U.xb[2]);
@@ -1127,11 +1134,36 @@ DAS_HD T body_force(int f, const DevMeshT<G>& m, const ResParams& prm, const T* 
 //   (kinds 4, 5: bits 4-7 = variable v (0 U, 1 p, 2 nuTilda, 3 T), bits 8-10 = component mask)
 #define DAS_FN_PATCHMEAN 4
 #define DAS_FN_VARIANCE 5
+//   kind 6  totalPressureRatio  p_b (1 + 0.5 (gamma-1) Ma^2)^(gamma/(gamma-1)), Ma^2 and R as for kind 3 (a ratio function: group 0 the
+//                            inlet, group 1 the outlet)                 DAFunctionTotalPressureRatio.C:50-139
+//   kind 7  wallHeatFlux     alphaEff_b snGrad(he)_f (compressible), Cp alphaEff_b snGrad(T)_f (DASimpleFoam with the T field); alphaEff_b
+//                            is alpha_eff above, the energy rows' own.  snGrad: the patch field's gic x_c + gbc (wallDistanceMethod
+//                            default), or bit 4 set: (x_b - x_c) / |C_f - C_c| (daCustom)  DAFunctionWallHeatFlux.C:115-304 (fluid branches)
+//   kind 8  location         r_f = |c - (c o axis)|, c = C_f - center, or bit 4 set: 1 / (r_f + 1e-12).  "o" is the COMPONENT-WISE product:
+//                            the reference applies the diagonal tensor diag(c) to the axis (DAFunctionLocation.C:183-191), which is not
+//                            the projection of c onto the axis; it is restated as written.  Geometry only: no state is read.
+//                            loc = axis (unit), center                  DAFunctionLocation.C:153-295
+#define DAS_FN_TOTALPRESSURERATIO 6
+#define DAS_FN_WALLHEATFLUX 7
+#define DAS_FN_LOCATION 8
 #define DAS_FN_BASE(kind) ((kind) & 15)
+template <class G>
+DAS_HD G location_radius(const FaceGeomT<G>& g, const double* loc, bool inverse) {
+    G r2(0.0);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const G c = g.Cf[i] - loc[3 + i];
+        const G cr = c - c * loc[i];
+        r2 += cr * cr;
+    }
+    const G r = dsqrt(r2);
+    return inverse ? G(1.0 / (r + 1e-12)) : r;
+}
 template <class T, bool RHO, class G, class DV>
 DAS_HD T body_facefn(int f, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* nut, const T* gradU, int kind, const DV* dir,
-                     double gammaFn, double RFn) {
+                     double gammaFn, double RFn, const double* loc = nullptr) {
     if (kind == DAS_FN_FORCE) return body_force<T, RHO>(f, m, prm, W, nut, gradU, dir, 1.0);
+    if (DAS_FN_BASE(kind) == DAS_FN_LOCATION) return T(location_radius<G>(m.fg[f], loc, (kind >> 4) & 1));
     const long long N = m.nC;
     const FaceGeomT<G>& g = m.fg[f];
     const int c = m.owner[f];
@@ -1158,7 +1190,21 @@ DAS_HD T body_facefn(int f, const DevMeshT<G>& m, const ResParams& prm, const T*
         }
         return q;
     }
-    // total temperature (compressible solvers only; the caller checks)
+    if (DAS_FN_BASE(kind) == DAS_FN_WALLHEATFLUX) {  // a solver with a T field (the caller checks)
+        const T xc = RHO ? prm.Cp * (Tc - DAS_TREF) : Tc;
+        T sn;
+        if ((kind >> 4) & 1) {
+            const G d0 = g.Cf[0] - m.cg[c].C[0], d1 = g.Cf[1] - m.cg[c].C[1], d2 = g.Cf[2] - m.cg[c].C[2];
+            sn = (b.he.xb - xc) / dsqrt(d0 * d0 + d1 * d1 + d2 * d2);
+        } else {
+            sn = b.he.gic * xc + b.he.gbc;
+        }
+        const T q = alpha_eff<T, RHO>(prm, b.mu_b, b.rho_b, b.nut_b) * sn;
+        return RHO ? q : prm.Cp * q;
+    }
+    // total temperature / total pressure of the ratio functions (compressible solvers only; the caller checks)
+    const T Ma2 = U2 / ((gammaFn * RFn) * b.Tt.xb);
+    if (kind == DAS_FN_TOTALPRESSURERATIO) return b.p.xb * dpow(1.0 + (0.5 * (gammaFn - 1.0)) * Ma2, gammaFn / (gammaFn - 1.0));
     return b.Tt.xb + (0.5 * (gammaFn - 1.0) / (gammaFn * RFn)) * U2;
 }
 
@@ -1245,6 +1291,7 @@ struct FaceFnView {
     const double* dir;           // 3 per face (force / moment), may be null for the other kinds
     int nf, kind;
     double gammaFn, RFn;
+    double loc[6];               // location: axis (unit), center
 };
 
 }  // namespace das

@@ -301,6 +301,7 @@ class pyDASolvers:
         self._checkMeshThreshold = dict(pyOptions.get("checkMeshThreshold") or {}) if isinstance(pyOptions, dict) else {}
         self._patchVelocity = [0.0, 0.0]  # DAGlobalVar::patchVelocity = [UMag, AoA(deg)], set by DAInputPatchVelocity::run
         self._flowdir_fns = {}
+        self._wallDistanceMethod = pyOptions.get("wallDistanceMethod", "default") if isinstance(pyOptions, dict) else "default"
         self._define_functions(pyOptions.get("function") if isinstance(pyOptions, dict) else None)
         if case.states is not None:  # FoamCase.states is always in "state" ordering (input data)
             check(lib().das_update_of_fields(self._h, dptr(np.ascontiguousarray(case.states, dtype=np.float64))))
@@ -741,7 +742,8 @@ class pyDASolvers:
     # -- objective functions ------------------------------------------------------------------------
     def _define_functions(self, functions):
         """"function" option dict (reference pyDAFoam.py DAOPTION.function): the patch-integral types force (directionMode
-        fixedDirection), moment, massFlowRate, totalPressure and totalTemperatureRatio are on this path."""
+        fixedDirection), moment, massFlowRate, totalPressure, totalTemperatureRatio, totalPressureRatio, wallHeatFlux and
+        location are on this path, as are the field-valued variableVolSum, patchMean and variance."""
         names = [p.name for p in self._case.mesh.patches]
         L = lib()
         for fname, fd in (functions or {}).items():
@@ -749,9 +751,17 @@ class pyDASolvers:
             if ftype in ("variableVolSum", "patchMean", "variance"):
                 self._define_field_function(fname, fd)
                 continue
-            if ftype not in ("force", "moment", "massFlowRate", "totalPressure", "totalTemperatureRatio"):
+            if ftype not in ("force", "moment", "massFlowRate", "totalPressure", "totalTemperatureRatio", "totalPressureRatio", "wallHeatFlux",
+                             "location"):
                 raise NotImplementedError(f"function type {ftype} is outside the GPU hot path")
             ids = np.array([names.index(p) for p in fd["patches"]], dtype=np.int32)
+            # calcRefVar / ref (DAFunction.C:44-49, 204-224; steady: the one reference value)
+            flags, ref = 0, 0.0
+            if int(fd.get("calcRefVar", 0)):
+                flags, ref = 8, float(np.atleast_1d(fd["ref"])[0])
+            if ftype == "location":
+                self._define_location(fname, fd, ids, flags, ref)
+                continue
             dmode = fd.get("directionMode", "fixedDirection") if ftype == "force" else None
             if dmode in ("parallelToFlow", "normalToFlow"):
                 # the direction follows the angle of attack of a patchVelocity input (DAFunctionForce.C:45-61,92-113)
@@ -771,17 +781,42 @@ class pyDASolvers:
             elif ftype == "moment":
                 vecA = np.ascontiguousarray(fd["axis"], dtype=np.float64)
                 vecB = np.ascontiguousarray(fd["center"], dtype=np.float64)
-            elif ftype == "totalTemperatureRatio":
+            elif ftype in ("totalTemperatureRatio", "totalPressureRatio"):
+                if ftype == "totalPressureRatio" and self._case.solver_name not in ("DARhoSimpleFoam", "DATurboFoam"):
+                    raise _capi.DASError(f"totalPressureRatio function {fname} needs a compressible solver, not {self._case.solver_name}")
                 inl, out = fd["inletPatches"], fd["outletPatches"]
                 for p in fd["patches"]:
                     if p not in inl and p not in out:
                         raise _capi.DASError("inlet/outletPatches names are not in patches")
                 grp = np.array([1 if p in out else 0 for p in fd["patches"]], dtype=np.int32)
                 gamma = float(self._case.thermo.get("gamma", 1.4))
+            elif ftype == "wallHeatFlux":
+                # DAFunctionWallHeatFlux.C:44-52: the distance method is the top-level option, byUnitArea the function's own key
+                wdm = self._wallDistanceMethod
+                if wdm not in ("default", "daCustom"):
+                    raise _capi.DASError(f"wallDistanceMethod: {wdm} not supported! Options are: default and daCustom.")
+                flags |= (1 if bool(fd.get("byUnitArea", True)) else 0) | (2 if wdm == "daCustom" else 0)
+            if ftype in ("totalPressureRatio", "wallHeatFlux"):
+                check(L.das_define_face_function_ex(
+                    self._h, fname.encode(), ftype.encode(), ids.ctypes.data_as(_capi.c_int_p),
+                    grp.ctypes.data_as(_capi.c_int_p) if grp is not None else None, ids.size, None, None, float(fd.get("scale", 1.0)), gamma, flags, ref))
+                continue
             check(L.das_define_face_function(
                 self._h, fname.encode(), ftype.encode(), ids.ctypes.data_as(_capi.c_int_p),
                 grp.ctypes.data_as(_capi.c_int_p) if grp is not None else None, ids.size,
                 dptr(vecA) if vecA is not None else None, dptr(vecB) if vecB is not None else None, float(fd.get("scale", 1.0)), gamma))
+
+    def _define_location(self, fname, fd, ids, flags, ref):
+        """location (DAFunctionLocation.C:19-127): mode is required; coeffKS 1, axis (1, 0, 0) and center (0, 0, 0) are the reference's
+        defaults.  snapCenter2Cell is not implemented."""
+        if int(fd.get("snapCenter2Cell", 0)):
+            raise _capi.DASError(f"location function {fname}: snapCenter2Cell is not implemented")
+        if "mode" not in fd:
+            raise _capi.DASError(f"location function {fname}: mode is required")
+        axis = np.ascontiguousarray(fd.get("axis", [1.0, 0.0, 0.0]), dtype=np.float64)
+        center = np.ascontiguousarray(fd.get("center", [0.0, 0.0, 0.0]), dtype=np.float64)
+        check(lib().das_define_location_function(self._h, fname.encode(), str(fd["mode"]).encode(), ids.ctypes.data_as(_capi.c_int_p), ids.size,
+                                                 dptr(axis), dptr(center), float(fd.get("coeffKS", 1.0)), flags, ref))
 
     def _function_cells(self, fname, fd):
         """cellSources of a cell-set function (DAFunction.C): "allCells", or "boxToCell" = the cells whose centre lies in the

@@ -302,6 +302,28 @@ int das_define_force_function(das_solver_t* s, const char* name, const int* patc
  * das_calc_jac_t_vec_product / das_calc_dbc_product like the force. */
 int das_define_face_function(das_solver_t* s, const char* name, const char* type, const int* patch_ids, const int* patch_group, int npatch,
                              const double* vecA, const double* vecB, double scale, double gammaFn);
+/* das_define_face_function_ex <- the same entries, plus the types that carry more options:
+ *   type "totalPressureRatio"   TP_out / TP_in (area averages), TP = p_b (1 + 0.5 (gamma-1) Ma^2)^(gamma/(gamma-1)); groups, gammaFn and R
+ *                               as for totalTemperatureRatio; no scale is applied            DAFunctionTotalPressureRatio.C:50-139
+ *        "wallHeatFlux"         sum scale w_f q_f, q_f = alphaEff_b snGrad(he)_f (compressible) or Cp alphaEff_b snGrad(T)_f (DASimpleFoam
+ *                               with the T field); w_f = |Sf| / sum |Sf| (flags & 1: byUnitArea) or |Sf|; snGrad from the patch field
+ *                               (wallDistanceMethod default) or (x_b - x_c) / |C_f - C_c| (flags & 2: daCustom).  Solvers without a T
+ *                               field return DAS_ERR_ARG                                    DAFunctionWallHeatFlux.C:115-304
+ * flags & 8: calcRefVar, F <- (F - ref)^2, for these two types.  das_define_face_function(...) is
+ * das_define_face_function_ex(..., flags = 1, ref = 0). */
+int das_define_face_function_ex(das_solver_t* s, const char* name, const char* type, const int* patch_ids, const int* patch_group, int npatch,
+                                const double* vecA, const double* vecB, double scale, double gammaFn, int flags, double ref);
+/* das_define_location_function <- {type: location, mode, coeffKS, axis, center} (DAFunctionLocation.C:153-295) over the faces of the patches:
+ *   r_f = |c - (c o axis)|, c = C_f - center, "o" the COMPONENT-WISE product as the reference writes it (not the projection onto the axis);
+ *   mode "maxRadiusKS"         log(sum exp(coeffKS r_f)) / coeffKS
+ *        "maxInverseRadiusKS"  log(sum exp(coeffKS / (r_f + 1e-12))) / coeffKS
+ *        "maxRadius"           r of the face that has the largest radius at definition (first on ties; kept after das_update_of_mesh)
+ * The KS sums are evaluated in log space, deterministically, over any number of faces; beyond the reference's guard (sum > 1e200)
+ * das_calc_function returns DAS_ERR_ARG "KS function summation term too large! Reduce coeffKS!".  axis is normalised here.
+ * flags & 8: calcRefVar.  State, boundary-value and field derivatives are exactly zero; das_calc_dvolcoord_product carries the
+ * softmax weights through the dual-point metrics. */
+int das_define_location_function(das_solver_t* s, const char* name, const char* mode, const int* patch_ids, int npatch, const double* axis,
+                                 const double* center, double coeffKS, int flags, double ref);
 /* das_define_patch_field_function <- the boundary-value entries of the "function" option dict (flow solvers):
  *   type "patchMean"  area average of component comps[0] of the boundary value of var, * scale   DAFunctionPatchMean.C:36-110
  *        "variance"   mode surface: sum w_f scale (b_f,i - d_f,i)^2 / W over the faces and the components comps[ncomp],
