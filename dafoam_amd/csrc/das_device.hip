@@ -4364,6 +4364,31 @@ int das_set_old_time_fields(das_solver_t* s, const double* phi_frozen, const dou
     DAS_CATCH
 }
 
+// ---- shared by the host paths of the objective functions ----------------------------------------------------------------------
+extern "C++" {  // templates: not under the C linkage of the entry points around them
+// f with the compressible switch as a compile-time tag: f(std::true_type{}) or f(std::false_type{})
+template <class F>
+static void with_rho(bool rho, F&& f) {
+    if (rho) f(std::true_type{});
+    else f(std::false_type{});
+}
+// the two launches of a function pass: the gradient fields of W into wk (k_grad; not for location, which reads no state: grad = false),
+// then the per-face kernel - `face` launches it and takes the same tag
+template <class T, class G, class F>
+static void launch_grad_and_faces(hipStream_t st, bool rho, const DevMeshT<G>& dm, const ResParams& prm, const T* W, ResWork<T>& wk, bool grad, F&& face) {
+    with_rho(rho, [&](auto R) {
+        if (grad) hipLaunchKernelGGL((k_grad<T, decltype(R)::value, G>), dim3(nblk(dm.nC, 256)), dim3(256), 0, st, dm, prm, W, wk.nut.p, wk.gU.p, wk.gP.p, wk.gN.p, wk.gH.p);
+        face(R);
+    });
+}
+}  // extern "C++"
+// calcRefVar (DAFunction::calcRefVar): F = (F0 - ref)^2, dF/dF0 = 2 (F0 - ref); without it F = F0
+static double ref_var_value(bool refVar, double ref, double F0) { return refVar ? (F0 - ref) * (F0 - ref) : F0; }
+static double ref_var_outer(bool refVar, double ref, double F0) { return refVar ? 2.0 * (F0 - ref) : 1.0; }
+static void need_flow_solver(das_solver* s) {
+    DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver), DAS_ERR_ARG, "function needs a flow solver");
+}
+
 // geometry-dependent part of a face function: per-face weights (scale, area fractions) and directions (moment arms)
 static void build_function_geometry(das_solver* s, das_solver::FaceFn& fn) {
     const size_t nf = fn.faces.size();
@@ -4397,8 +4422,31 @@ static void build_function_geometry(das_solver* s, das_solver::FaceFn& fn) {
     fn.uploaded = false;
 }
 
-// ---- objective functions (reference "function" option dict: DAFunctionForce, DAFunctionMoment, DAFunctionMassFlowRate,
-//      DAFunctionTotalPressure, DAFunctionTotalTemperatureRatio) ------------------------------------------------------
+// the faces of the patches, in patch order -> fn.faces / fn.group (group 1: patch_group[k] != 0; all 0 when patch_group is null)
+static void collect_patch_faces(das_solver* s, const int* patch_ids, const int* patch_group, int npatch, das_solver::FaceFn& fn) {
+    for (int k = 0; k < npatch; k++) {
+        const int p = patch_ids[k];
+        DAS_CHECK(p >= 0 && p < s->mesh.nPatch, DAS_ERR_ARG, "patch id out of range");
+        DAS_CHECK(s->mesh.patch_type[p] != DAS_PATCH_CYCLIC, DAS_ERR_ARG, "functions cannot be defined on cyclic patches");
+        const unsigned char grp = (patch_group && patch_group[k]) ? 1 : 0;
+        for (int q = 0; q < s->mesh.patch_size[p]; q++) {
+            fn.faces.push_back(s->mesh.patch_start[p] + q);
+            fn.group.push_back(grp);
+        }
+    }
+}
+// the tail of every face-function definition; needFaces: an empty face list is an error that names the function
+static void register_face_function(das_solver* s, const char* name, das_solver::FaceFn&& fn, bool needFaces) {
+    DAS_CHECK(!needFaces || !fn.faces.empty(), DAS_ERR_ARG, "the patches of function " + std::string(name) + " have no faces");
+    build_function_geometry(s, fn);
+    s->cellFunctions.erase(name);
+    s->functions[name] = std::move(fn);
+}
+
+// ---- objective functions (reference "function" option dict).  Face functions (das_define_face_function[_ex]): DAFunctionForce,
+//      DAFunctionMoment, DAFunctionMassFlowRate, DAFunctionTotalPressure, DAFunctionTotalTemperatureRatio, DAFunctionTotalPressureRatio,
+//      DAFunctionWallHeatFlux; das_define_location_function: DAFunctionLocation; das_define_patch_field_function / das_define_cell_function:
+//      DAFunctionPatchMean, DAFunctionVariance, DAFunctionVariableVolSum -------------------------------------------------------------
 int das_define_face_function(das_solver_t* s, const char* name, const char* type, const int* patch_ids, const int* patch_group, int npatch,
                              const double* vecA, const double* vecB, double scale, double gammaFn) {
     return das_define_face_function_ex(s, name, type, patch_ids, patch_group, npatch, vecA, vecB, scale, gammaFn, 1, 0.0);
@@ -4410,14 +4458,14 @@ int das_define_face_function_ex(das_solver_t* s, const char* name, const char* t
     const std::string ty = type;
     DAS_CHECK(ty != "wallHeatFlux" || DAS_IS_COMPRESSIBLE(s->cp.solver) || (s->cp.solver == DAS_SOLVER_SIMPLEFOAM && s->cp.hasT), DAS_ERR_ARG,
               std::string("wallHeatFlux function ") + name + " needs a T field (DASimpleFoam with T, DARhoSimpleFoam, DATurboFoam)");
-    DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver), DAS_ERR_ARG, "function needs a flow solver");
+    need_flow_solver(s);
     das_solver::FaceFn fn;
     if (ty == "force" || ty == "moment") fn.kind = DAS_FN_FORCE;
     else if (ty == "massFlowRate") fn.kind = DAS_FN_MASSFLOW;
     else if (ty == "totalPressure") fn.kind = DAS_FN_TOTALPRESSURE;
     else if (ty == "totalTemperatureRatio") { fn.kind = DAS_FN_TOTALTEMPERATURE; fn.ratio = true; }
     else if (ty == "totalPressureRatio") { fn.kind = DAS_FN_TOTALPRESSURERATIO; fn.ratio = true; }
-    else if (ty == "wallHeatFlux") { fn.kind = DAS_FN_WALLHEATFLUX | ((flags & 2) ? 16 : 0); fn.byUnitArea = (flags & 1) != 0; }
+    else if (ty == "wallHeatFlux") { fn.kind = DAS_FN_WALLHEATFLUX | ((flags & 2) ? DAS_FN_ALT_BIT : 0); fn.byUnitArea = (flags & 1) != 0; }
     else throw Error(DAS_ERR_ARG, "function type not implemented on the GPU path: " + ty);
     if (fn.kind == DAS_FN_FORCE) {
         DAS_CHECK(vecA, DAS_ERR_ARG, "force / moment need a direction / axis");
@@ -4433,25 +4481,14 @@ int das_define_face_function_ex(das_solver_t* s, const char* name, const char* t
         fn.gammaFn = gammaFn;
         fn.RFn = s->cp.Cp - s->cp.Cp / gammaFn;  // DAFunctionTotalTemperatureRatio.C:98
     }
-    for (int k = 0; k < npatch; k++) {
-        const int p = patch_ids[k];
-        DAS_CHECK(p >= 0 && p < s->mesh.nPatch, DAS_ERR_ARG, "patch id out of range");
-        DAS_CHECK(s->mesh.patch_type[p] != DAS_PATCH_CYCLIC, DAS_ERR_ARG, "functions cannot be defined on cyclic patches");
-        const int grp = (fn.ratio && patch_group[k]) ? 1 : 0;
-        for (int q = 0; q < s->mesh.patch_size[p]; q++) {
-            fn.faces.push_back(s->mesh.patch_start[p] + q);
-            fn.group.push_back((unsigned char)grp);
-        }
-    }
+    collect_patch_faces(s, patch_ids, fn.ratio ? patch_group : nullptr, npatch, fn);
     fn.isMoment = ty == "moment";
     fn.scale = fn.kind == DAS_FN_TOTALPRESSURERATIO ? 1.0 : scale;  // DAFunctionTotalPressureRatio.C applies no scale
     // calcRefVar (DAFunction::calcRefVar) of the kinds this entry adds; the earlier kinds keep their meaning under das_define_face_function
     fn.refVar = (flags & 8) && (fn.kind == DAS_FN_TOTALPRESSURERATIO || DAS_FN_BASE(fn.kind) == DAS_FN_WALLHEATFLUX);
     fn.ref = ref;
     for (int d = 0; d < 3; d++) { fn.vecA[d] = vecA ? vecA[d] : 0.0; fn.vecB[d] = vecB ? vecB[d] : 0.0; }
-    build_function_geometry(s, fn);
-    s->cellFunctions.erase(name);
-    s->functions[name] = std::move(fn);
+    register_face_function(s, name, std::move(fn), false);  // no faces: defined all the same, as before the entry points shared this tail
     return DAS_OK;
     DAS_CATCH
 }
@@ -4462,38 +4499,33 @@ int das_define_location_function(das_solver_t* s, const char* name, const char* 
                                  const double* center, double coeffKS, int flags, double ref) {
     DAS_TRY
     DAS_CHECK(s && name && mode && patch_ids && npatch > 0 && axis && center, DAS_ERR_ARG, "bad argument");
-    DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver), DAS_ERR_ARG, "function needs a flow solver");
+    need_flow_solver(s);
     const std::string md = mode;
     DAS_CHECK(md == "maxRadiusKS" || md == "maxInverseRadiusKS" || md == "maxRadius", DAS_ERR_ARG,
               "mode: " + md + " not supported! Options are: maxRadiusKS, maxInverseRadiusKS, maxRadius");
     const double mag = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
     DAS_CHECK(mag > 0.0, DAS_ERR_ARG, std::string("the axis of location function ") + name + " has zero length");
     das_solver::FaceFn fn;
-    fn.kind = DAS_FN_LOCATION | (md == "maxInverseRadiusKS" ? 16 : 0);
+    fn.kind = DAS_FN_LOCATION | (md == "maxInverseRadiusKS" ? DAS_FN_ALT_BIT : 0);
     fn.ks = md != "maxRadius";
     fn.coeffKS = coeffKS;
     DAS_CHECK(!fn.ks || coeffKS != 0.0, DAS_ERR_ARG, std::string("coeffKS of location function ") + name + " is zero");
     for (int d = 0; d < 3; d++) { fn.loc[d] = axis[d] / mag; fn.loc[3 + d] = center[d]; }
     fn.refVar = (flags & 8) != 0;
     fn.ref = ref;
-    int best = -1;
-    double maxR = -100000.0;
-    for (int k = 0; k < npatch; k++) {
-        const int p = patch_ids[k];
-        DAS_CHECK(p >= 0 && p < s->mesh.nPatch, DAS_ERR_ARG, "patch id out of range");
-        DAS_CHECK(s->mesh.patch_type[p] != DAS_PATCH_CYCLIC, DAS_ERR_ARG, "functions cannot be defined on cyclic patches");
-        for (int q = 0; q < s->mesh.patch_size[p]; q++) {
-            const int f = s->mesh.patch_start[p] + q;
-            if (fn.ks) { fn.faces.push_back(f); fn.group.push_back(0); continue; }
+    collect_patch_faces(s, patch_ids, nullptr, npatch, fn);
+    if (!fn.ks) {  // maxRadius: of the collected faces, the first of the largest radius
+        int best = -1;
+        double maxR = -100000.0;
+        for (int f : fn.faces) {
             const double r = location_radius<double>(s->mesh.fg[f], fn.loc, false);
             if (r > maxR) { maxR = r; best = f; }
         }
+        fn.faces.clear();
+        if (best >= 0) fn.faces.push_back(best);
+        fn.group.resize(fn.faces.size());
     }
-    if (!fn.ks && best >= 0) { fn.faces.push_back(best); fn.group.push_back(0); }
-    DAS_CHECK(!fn.faces.empty(), DAS_ERR_ARG, "the patches of function " + std::string(name) + " have no faces");
-    build_function_geometry(s, fn);
-    s->cellFunctions.erase(name);
-    s->functions[name] = std::move(fn);
+    register_face_function(s, name, std::move(fn), true);
     return DAS_OK;
     DAS_CATCH
 }
@@ -4530,7 +4562,7 @@ int das_define_patch_field_function(das_solver_t* s, const char* name, const cha
     DAS_TRY
     DAS_CHECK(s && name && type && patch_ids && npatch > 0, DAS_ERR_ARG, "bad argument");
     DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "patchMean / variance functions run on an undecomposed solver");
-    DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver), DAS_ERR_ARG, "function needs a flow solver");
+    need_flow_solver(s);
     const std::string ty = type;
     DAS_CHECK(ty == "patchMean" || ty == "variance", DAS_ERR_ARG, "patch field function type not valid: " + ty);
     const int vid = field_var_id(s, var, false);
@@ -4539,17 +4571,8 @@ int das_define_patch_field_function(das_solver_t* s, const char* name, const cha
     das_solver::FaceFn fn;
     int mask = 0;
     for (int i = 0; i < ncomp; i++) mask |= 1 << comps[i];
-    fn.kind = (ty == "patchMean" ? DAS_FN_PATCHMEAN : DAS_FN_VARIANCE) | (vid << 4) | (mask << 8);
-    for (int k = 0; k < npatch; k++) {
-        const int p = patch_ids[k];
-        DAS_CHECK(p >= 0 && p < s->mesh.nPatch, DAS_ERR_ARG, "patch id out of range");
-        DAS_CHECK(s->mesh.patch_type[p] != DAS_PATCH_CYCLIC, DAS_ERR_ARG, "functions cannot be defined on cyclic patches");
-        for (int q = 0; q < s->mesh.patch_size[p]; q++) {
-            fn.faces.push_back(s->mesh.patch_start[p] + q);
-            fn.group.push_back(0);
-        }
-    }
-    DAS_CHECK(!fn.faces.empty(), DAS_ERR_ARG, "the patches of function " + std::string(name) + " have no faces");
+    fn.kind = DAS_FN_FIELD_KIND(ty == "patchMean" ? DAS_FN_PATCHMEAN : DAS_FN_VARIANCE, vid, mask);
+    collect_patch_faces(s, patch_ids, nullptr, npatch, fn);
     fn.scale = scale;
     fn.refVar = ty == "patchMean" && (flags & 8);
     fn.ref = ref;
@@ -4562,9 +4585,7 @@ int das_define_patch_field_function(das_solver_t* s, const char* name, const cha
             for (size_t k = 0; k < fn.faces.size(); k++)
                 for (int i = 0; i < ncomp; i++) fn.dir[3 * k + comps[i]] = data[k * ncomp + i];
     }
-    build_function_geometry(s, fn);
-    s->cellFunctions.erase(name);
-    s->functions[name] = std::move(fn);
+    register_face_function(s, name, std::move(fn), true);
     return DAS_OK;
     DAS_CATCH
 }
@@ -4661,7 +4682,7 @@ static double cell_function_base_value(das_solver* s, das_solver::CellFn& fn) {
 }
 // dF/dF0: 2 (F0 - ref) under calcRefVar (DAFunction::calcRefVar), else 1
 static double cell_function_outer(das_solver* s, das_solver::CellFn& fn) {
-    return fn.refVar ? 2.0 * (cell_function_base_value(s, fn) - fn.ref) : 1.0;
+    return ref_var_outer(fn.refVar, fn.ref, fn.refVar ? cell_function_base_value(s, fn) : 0.0);  // the value pass runs only where it is read
 }
 // out[0..len) = 0, then seed dF/dsrc_i (x s_i for the states) on the entries of the terms
 static void cell_function_gradient(das_solver* s, das_solver::CellFn& fn, double seed, bool stateScaled, double* out, long long len) {
@@ -4698,19 +4719,11 @@ static void function_sums(das_solver* s, das_solver::FaceFn& fn, double S[2]) {
         hipLaunchKernelGGL((k_fn_value<false>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, make_params(s->cp, s->opt, 0), s->d_W.p, (const double*)nullptr,
                            (const double*)nullptr, fn.view(fn.d_w0.p), fn.d_fv.p);
         if (fn.ks) { DAS_HIP(hipGetLastError()); S[0] = S[1] = 0.0; return; }  // the KS reduction reads fn.d_fv (location_ks_value)
-        hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, s->stream, (long long)nf, (const unsigned char*)fn.d_group.p, (const double*)fn.d_fv.p, s->d_tmp1.p);
-        DAS_HIP(hipGetLastError());
-        DAS_HIP(hipMemcpyAsync(S, s->d_tmp1.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        DAS_HIP(hipStreamSynchronize(s->stream));
-        return;
-    }
-    ResParams prm = s->wk.bind(s->cp.solver, s->dm.nC, s->dm.nF, make_params(s->cp, s->opt, 0));
-    if (rho) {
-        hipLaunchKernelGGL((k_grad<double, true>), dim3(nblk(s->dm.nC, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, s->wk.gP.p, s->wk.gN.p, s->wk.gH.p);
-        hipLaunchKernelGGL((k_fn_value<true>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn.view(fn.d_w0.p), fn.d_fv.p);
     } else {
-        hipLaunchKernelGGL((k_grad<double, false>), dim3(nblk(s->dm.nC, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, s->wk.gP.p, s->wk.gN.p, s->wk.gH.p);
-        hipLaunchKernelGGL((k_fn_value<false>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn.view(fn.d_w0.p), fn.d_fv.p);
+        const ResParams prm = s->wk.bind(s->cp.solver, s->dm.nC, s->dm.nF, make_params(s->cp, s->opt, 0));
+        launch_grad_and_faces(s->stream, rho, s->dm, prm, (const double*)s->d_W.p, s->wk, true, [&](auto R) {
+            hipLaunchKernelGGL((k_fn_value<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn.view(fn.d_w0.p), fn.d_fv.p);
+        });
     }
     hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, s->stream, (long long)nf, (const unsigned char*)fn.d_group.p, (const double*)fn.d_fv.p, s->d_tmp1.p);
     DAS_HIP(hipGetLastError());
@@ -4749,7 +4762,7 @@ static double function_base_value(das_solver* s, das_solver::FaceFn& fn) {
 static void function_effective_weights(das_solver* s, das_solver::FaceFn& fn) {
     if (DAS_FN_BASE(fn.kind) == DAS_FN_LOCATION) {  // dF/da_f: the softmax of the KS modes, 1 on the one face of maxRadius
         const double F0 = function_base_value(s, fn);
-        const double outer = fn.refVar ? 2.0 * (F0 - fn.ref) : 1.0;
+        const double outer = ref_var_outer(fn.refVar, fn.ref, F0);
         const long long nf = (long long)fn.faces.size();
         if (fn.ks) {
             hipLaunchKernelGGL(k_ks_weights, dim3(nblk(nf, 256)), dim3(256), 0, s->stream, nf, (const double*)fn.d_fv.p, fn.coeffKS, (const double*)fn.d_ks.p, outer, fn.d_weff.p);
@@ -4759,32 +4772,22 @@ static void function_effective_weights(das_solver* s, das_solver::FaceFn& fn) {
         }
         return;
     }
-    if (fn.refVar && fn.ratio) {  // F = (S1 / S0 - ref)^2
-        double S[2];
-        function_sums(s, fn, S);
-        const double a = 2.0 * (S[1] / S[0] - fn.ref);
-        const double c[2] = {-a * S[1] / (S[0] * S[0]), a / S[0]};
-        std::vector<double> w(fn.w0.size());
-        for (size_t k = 0; k < w.size(); k++) w[k] = fn.w0[k] * c[fn.group[k]];
-        fn.d_weff.upload(w);
-        return;
-    }
-    if (fn.refVar) {  // F = (S - ref)^2: dF = 2 (S - ref) dS
-        double S[2];
-        function_sums(s, fn, S);
-        const double a = 2.0 * (S[0] + S[1] - fn.ref);
-        std::vector<double> w(fn.w0.size());
-        for (size_t k = 0; k < w.size(); k++) w[k] = fn.w0[k] * a;
-        fn.d_weff.upload(w);
-        return;
-    }
-    if (!fn.ratio) {
+    if (!fn.refVar && !fn.ratio) {  // F = S0 + S1: the base weights, no sums needed
         DAS_HIP(hipMemcpyAsync(fn.d_weff.p, fn.d_w0.p, fn.w0.size() * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
         return;
     }
-    double S[2];
+    double S[2], c[2];  // c[g] = dF/dS_g
     function_sums(s, fn, S);
-    const double c[2] = {-S[1] / (S[0] * S[0]), 1.0 / S[0]};  // F = S1/S0
+    if (!fn.ratio) {  // F = (S - ref)^2: dF = 2 (S - ref) dS
+        c[0] = c[1] = ref_var_outer(true, fn.ref, S[0] + S[1]);
+    } else if (fn.refVar) {  // F = (S1 / S0 - ref)^2; written out, not as the plain quotient rule times a: the rounding differs
+        const double a = ref_var_outer(true, fn.ref, S[1] / S[0]);
+        c[0] = -a * S[1] / (S[0] * S[0]);
+        c[1] = a / S[0];
+    } else {  // F = S1 / S0
+        c[0] = -S[1] / (S[0] * S[0]);
+        c[1] = 1.0 / S[0];
+    }
     std::vector<double> w(fn.w0.size());
     for (size_t k = 0; k < w.size(); k++) w[k] = fn.w0[k] * c[fn.group[k]];
     fn.d_weff.upload(w);
@@ -4794,13 +4797,11 @@ int das_calc_function(das_solver_t* s, const char* name, double* value) {
     need_init(s);
     DAS_CHECK(value, DAS_ERR_ARG, "null output");
     if (das_solver::CellFn* cf = find_cell_function(s, name)) {
-        const double F0 = cell_function_base_value(s, *cf);
-        *value = cf->refVar ? (F0 - cf->ref) * (F0 - cf->ref) : F0;
+        *value = ref_var_value(cf->refVar, cf->ref, cell_function_base_value(s, *cf));
         return DAS_OK;
     }
     das_solver::FaceFn& fn = get_function(s, name);
-    *value = function_base_value(s, fn);
-    if (fn.refVar) *value = (*value - fn.ref) * (*value - fn.ref);
+    *value = ref_var_value(fn.refVar, fn.ref, function_base_value(s, fn));
     return DAS_OK;
     DAS_CATCH
 }
@@ -4827,13 +4828,9 @@ static void function_gradient(das_solver* s, const char* name, double seed, doub
     const int B = 256, nf = (int)fn.faces.size();
     for (int col = 0; col < s->nColors; col++) {
         hipLaunchKernelGGL(k_seed<1>, dim3(nblk(n, B)), dim3(B), 0, s->stream, n, s->d_W.p, s->d_colors.p, s->d_scale.p, col, s->d_Wd.p);
-        if (rho) {
-            hipLaunchKernelGGL((k_grad<Dual<1>, true>), dim3(nblk(s->dm.nC, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, s->wk1.gP.p, s->wk1.gN.p, s->wk1.gH.p);
-            hipLaunchKernelGGL((k_fn_grad<true>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, fn.view(fn.d_weff.p), seed, s->d_colors.p, col, s->d_tmp2.p);
-        } else {
-            hipLaunchKernelGGL((k_grad<Dual<1>, false>), dim3(nblk(s->dm.nC, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, s->wk1.gP.p, s->wk1.gN.p, s->wk1.gH.p);
-            hipLaunchKernelGGL((k_fn_grad<false>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, fn.view(fn.d_weff.p), seed, s->d_colors.p, col, s->d_tmp2.p);
-        }
+        launch_grad_and_faces(s->stream, rho, s->dm, prm, (const Dual<1>*)s->d_Wd.p, s->wk1, true, [&](auto R) {
+            hipLaunchKernelGGL((k_fn_grad<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, fn.view(fn.d_weff.p), seed, s->d_colors.p, col, s->d_tmp2.p);
+        });
     }
     DAS_HIP(hipGetLastError());
     DAS_HIP(hipMemcpyAsync(product, s->d_tmp2.p, n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -4961,13 +4958,9 @@ int das_calc_dbc_product(das_solver_t* s, const int* patches, int np, const char
         prm = s->wk1.bind(s->cp.solver, s->dm.nC, s->dm.nF, prm);
         const int nf = (int)fn.faces.size();
         if (fn.d_fv.n != (size_t)nf) fn.d_fv.alloc(nf);
-        if (rho) {
-            hipLaunchKernelGGL((k_grad<Dual<1>, true>), dim3(nblk(s->dm.nC, B)), dim3(B), 0, st, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, s->wk1.gP.p, s->wk1.gN.p, s->wk1.gH.p);
-            hipLaunchKernelGGL((k_fn_tangent<true>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, fn.view(fn.d_weff.p), seeds[0], fn.d_fv.p);
-        } else {
-            hipLaunchKernelGGL((k_grad<Dual<1>, false>), dim3(nblk(s->dm.nC, B)), dim3(B), 0, st, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, s->wk1.gP.p, s->wk1.gN.p, s->wk1.gH.p);
-            hipLaunchKernelGGL((k_fn_tangent<false>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, fn.view(fn.d_weff.p), seeds[0], fn.d_fv.p);
-        }
+        launch_grad_and_faces(st, rho, s->dm, prm, (const Dual<1>*)s->d_Wd.p, s->wk1, true, [&](auto R) {
+            hipLaunchKernelGGL((k_fn_tangent<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, fn.view(fn.d_weff.p), seeds[0], fn.d_fv.p);
+        });
         hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, st, (long long)nf, (const unsigned char*)nullptr, (const double*)fn.d_fv.p, s->d_tmp1.p);
     }
     DAS_HIP(hipGetLastError());
@@ -5020,15 +5013,11 @@ int das_calc_dfield_product(das_solver_t* s, const char* fieldName, const char* 
     const std::string ot = outputType;
     DAS_CHECK(ot == "residual" || ot == "function", DAS_ERR_ARG, "outputType not supported on this path: " + ot);
     const long long N = s->mesh.nC, n = s->n;
-    if (ot == "function" && find_cell_function(s, outputName)) {
-        das_solver::CellFn& cf = *find_cell_function(s, outputName);
-        if (cf.field) cell_function_gradient(s, cf, seeds[0], false, product, N);  // dF/dbeta_c, unscaled like the field itself
+    if (ot == "function") {
+        das_solver::CellFn* cf = find_cell_function(s, outputName);
+        if (!cf) (void)get_function(s, outputName);  // the patch-integral functions do not see the production term
+        if (cf && cf->field) cell_function_gradient(s, *cf, seeds[0], false, product, N);  // dF/dbeta_c, unscaled like the field itself
         else std::fill(product, product + N, 0.0);
-        return DAS_OK;
-    }
-    if (ot == "function") {  // the patch-integral functions do not see the production term
-        (void)get_function(s, outputName);
-        std::fill(product, product + N, 0.0);
         return DAS_OK;
     }
     hipStream_t st = s->stream;
@@ -5155,6 +5144,38 @@ int das_point_influence_get(das_solver_t* s, int* colors, long long* ptr, int* c
     return DAS_OK;
     DAS_CATCH
 }
+// ---- shared by the two modes of the product -----------------------------------------------------------------------------------
+// cell -> slots of its function faces, as CSR
+static void function_face_slots(const Mesh& m, const das_solver::FaceFn& fn, std::vector<int>& cptr, std::vector<int>& cidx) {
+    const int nf = (int)fn.faces.size();
+    cptr.assign(m.nC + 1, 0);
+    cidx.resize(nf);
+    for (int k = 0; k < nf; k++) cptr[m.owner[fn.faces[k]] + 1]++;
+    for (int c = 0; c < m.nC; c++) cptr[c + 1] += cptr[c];
+    std::vector<int> pos(cptr.begin(), cptr.end() - 1);
+    for (int k = 0; k < nf; k++) cidx[pos[m.owner[fn.faces[k]]]++] = k;
+}
+// where the residual rows of each state block start (k_vc_rows / k_vc_rows_dual)
+static RowLayout residual_row_layout(das_solver* s) {
+    const Stencil stn = make_stencil(s->cp.solver, s->mesh.nC, s->mesh.nF, s->opt, false, s->cp.hasT != 0);
+    DAS_CHECK(stn.states.size() <= 8, DAS_ERR_INTERNAL, "more than 8 state blocks");
+    RowLayout L{};
+    L.nb = (int)stn.states.size();
+    for (int b = 0; b < L.nb; b++) { L.off[b] = stn.states[b].offset; L.kind[b] = (int)stn.states[b].kind; }
+    return L;
+}
+// the end of a product: the vector and the bad-volume flag come down, the timing goes into info4
+static void finish_volcoord(das_solver* s, const double* d_out, double* product, const char* badMessage, double t0, long long passes, double* info4) {
+    das_solver::VolCoord& v = s->vc;
+    int bad = 0;
+    DAS_HIP(hipMemcpyAsync(&bad, v.d_bad.p, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipMemcpyAsync(product, d_out, 3 * (size_t)s->mesh.nP * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    DAS_CHECK(!bad, DAS_ERR_INTERNAL, badMessage);
+    v.seconds = wall_seconds() - t0;
+    if (info4) { info4[0] = v.inf.nColors; info4[1] = (double)passes; info4[2] = v.seconds; info4[3] = v.buildSeconds; }
+}
+
 // exact mode of the product (amd.volCoordMode "dual", the default): Dual<1> points -> Dual<1> metrics -> Dual<1> residual
 static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool areaAvg, const double* cN, const double* cA, const double* seeds,
                                   double* product, double* info4, das_solver::CellFn* cfn = nullptr) {
@@ -5174,7 +5195,7 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
     double cellA = 0.0, cellB = 0.0;
     if (isCell) {
         const double F0 = cell_function_base_value(s, *cfn);
-        const double outer = seeds[0] * (cfn->refVar ? 2.0 * (F0 - cfn->ref) : 1.0);
+        const double outer = seeds[0] * ref_var_outer(cfn->refVar, cfn->ref, F0);
         cellA = cfn->divByTotalVol ? -outer * F0 / cfn->totalVol : 0.0;
         cellB = cfn->multiplyVol ? outer * cfn->coef : 0.0;
     }
@@ -5199,21 +5220,15 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
     int nf = 0;
     if (isCell) {
     } else if (!isFn) {
-        const Stencil stn = make_stencil(s->cp.solver, m.nC, m.nF, s->opt, false, s->cp.hasT != 0);
-        DAS_CHECK(stn.states.size() <= 8, DAS_ERR_INTERNAL, "more than 8 state blocks");
-        L.nb = (int)stn.states.size();
-        for (int b = 0; b < L.nb; b++) { L.off[b] = stn.states[b].offset; L.kind[b] = (int)stn.states[b].kind; }
+        L = residual_row_layout(s);
         d_Rd.alloc((size_t)n);
         d_seeds.upload(seeds, (size_t)n);
     } else {
-        DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || rho, DAS_ERR_ARG, "function needs a flow solver");
+        need_flow_solver(s);
         nf = (int)fn->faces.size();
         d_fvd.alloc((size_t)nf);
-        std::vector<int> cptr(m.nC + 1, 0), cidx(nf);
-        for (int k = 0; k < nf; k++) cptr[m.owner[fn->faces[k]] + 1]++;
-        for (int c = 0; c < m.nC; c++) cptr[c + 1] += cptr[c];
-        std::vector<int> pos(cptr.begin(), cptr.end() - 1);
-        for (int k = 0; k < nf; k++) cidx[pos[m.owner[fn->faces[k]]]++] = k;
+        std::vector<int> cptr, cidx;
+        function_face_slots(m, *fn, cptr, cidx);
         d_fnPtr.upload(cptr); d_fnIdx.upload(cidx);
     }
     const double t0 = wall_seconds();
@@ -5239,15 +5254,10 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
                 const ResParams prm = s->wk1.bind(s->cp.solver, s->dm.nC, s->dm.nF, prm0);
                 const bool isLoc = DAS_FN_BASE(fn->kind) == DAS_FN_LOCATION;  // the linearised functional sum w_eff a_f; no state is read
                 const FaceFnView fv = fn->view(isLoc ? fn->d_weff.p : fn->d_w0.p);
-                if (rho) {
-                    if (!isLoc) hipLaunchKernelGGL((k_grad<D, true, D>), dim3(nblk(m.nC, B)), dim3(B), 0, st, dmD, prm, (const D*)d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, s->wk1.gP.p, s->wk1.gN.p, s->wk1.gH.p);
-                    hipLaunchKernelGGL((k_fn_dual<true>), dim3(nblk(nf, B)), dim3(B), 0, st, dmD, prm, (const D*)d_Wd.p, (const D*)s->wk1.nut.p, (const D*)s->wk1.gU.p, fv,
+                launch_grad_and_faces(st, rho, dmD, prm, (const D*)d_Wd.p, s->wk1, !isLoc, [&](auto R) {
+                    hipLaunchKernelGGL((k_fn_dual<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, st, dmD, prm, (const D*)d_Wd.p, (const D*)s->wk1.nut.p, (const D*)s->wk1.gU.p, fv,
                                        (int)fn->isMoment, fn->vecA[0], fn->vecA[1], fn->vecA[2], fn->vecB[0], fn->vecB[1], fn->vecB[2], (int)areaAvg, cN[0], cN[1], cA[0], cA[1], d_fvd.p);
-                } else {
-                    if (!isLoc) hipLaunchKernelGGL((k_grad<D, false, D>), dim3(nblk(m.nC, B)), dim3(B), 0, st, dmD, prm, (const D*)d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, s->wk1.gP.p, s->wk1.gN.p, s->wk1.gH.p);
-                    hipLaunchKernelGGL((k_fn_dual<false>), dim3(nblk(nf, B)), dim3(B), 0, st, dmD, prm, (const D*)d_Wd.p, (const D*)s->wk1.nut.p, (const D*)s->wk1.gU.p, fv,
-                                       (int)fn->isMoment, fn->vecA[0], fn->vecA[1], fn->vecA[2], fn->vecB[0], fn->vecB[1], fn->vecB[2], (int)areaAvg, cN[0], cN[1], cA[0], cA[1], d_fvd.p);
-                }
+                });
                 hipLaunchKernelGGL(k_vc_fn_cells_dual, dim3(nblk(m.nC, B)), dim3(B), 0, st, m.nC, (const int*)d_fnPtr.p, (const int*)d_fnIdx.p, seeds[0],
                                    (const double*)d_fvd.p, d_tc.p);
             }
@@ -5258,13 +5268,7 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
         }
         DAS_HIP(hipGetLastError());
     }
-    int bad = 0;
-    DAS_HIP(hipMemcpyAsync(&bad, v.d_bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    DAS_HIP(hipMemcpyAsync(product, d_out.p, n3 * sizeof(double), hipMemcpyDeviceToHost, st));
-    DAS_HIP(hipStreamSynchronize(st));
-    DAS_CHECK(!bad, DAS_ERR_INTERNAL, "non-positive cell volume in the volCoord product");
-    v.seconds = wall_seconds() - t0;
-    if (info4) { info4[0] = I.nColors; info4[1] = (double)passes; info4[2] = v.seconds; info4[3] = v.buildSeconds; }
+    finish_volcoord(s, d_out.p, product, "non-positive cell volume in the volCoord product", t0, passes, info4);
 }
 
 // calcJacTVecProduct(volCoord -> residual | function), reference DASolver.C:1690-1839 + DAInputVolCoord: the full product vector
@@ -5304,7 +5308,7 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
         function_sums(s, *fn, S);  // S_g = sum of w0 q: totalPressure scale N0 / A0 (one group), ratio functions N_g / A_g
         for (size_t q = 0; q < fn->faces.size(); q++) A[fn->group[q]] += m.fg[fn->faces[q]].magSf;
         if (!fn->ratio) {
-            const double outer = fn->refVar ? 2.0 * (S[0] + S[1] - fn->ref) : 1.0;  // calcRefVar
+            const double outer = ref_var_outer(fn->refVar, fn->ref, S[0] + S[1]);
             if (base == DAS_FN_WALLHEATFLUX && !fn->byUnitArea) {  // F = scale sum |Sf| q
                 cN[0] = outer * fn->scale;
             } else {
@@ -5313,7 +5317,7 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
             }
         } else {
             const double F0 = S[1] / S[0];  // F0 = (N1 / A1) / (N0 / A0)
-            const double F = (fn->refVar ? 2.0 * (F0 - fn->ref) : 1.0) * F0;
+            const double F = ref_var_outer(fn->refVar, fn->ref, F0) * F0;
             cN[1] = F / (S[1] * A[1]); cA[1] = -F / A[1];
             cN[0] = -F / (S[0] * A[0]); cA[0] = F / A[0];
         }
@@ -5363,22 +5367,15 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
     RowLayout L{};
     int nf = 0;
     if (!isFn) {
-        const Stencil stn = make_stencil(s->cp.solver, m.nC, m.nF, s->opt, false, s->cp.hasT != 0);
-        DAS_CHECK(stn.states.size() <= 8, DAS_ERR_INTERNAL, "more than 8 state blocks");
-        L.nb = (int)stn.states.size();
-        for (int b = 0; b < L.nb; b++) { L.off[b] = stn.states[b].offset; L.kind[b] = (int)stn.states[b].kind; }
+        L = residual_row_layout(s);
         v.d_Rp.alloc(n); v.d_Rm.alloc(n);
         v.d_seeds.upload(seeds, n);
     } else {
-        DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || rho, DAS_ERR_ARG, "function needs a flow solver");
+        need_flow_solver(s);
         nf = (int)fn->faces.size();
         v.d_fvp.alloc(nf); v.d_fvm.alloc(nf);
-        // cell -> slots of its function faces
-        std::vector<int> cptr(m.nC + 1, 0), cidx(nf);
-        for (int k = 0; k < nf; k++) cptr[m.owner[fn->faces[k]] + 1]++;
-        for (int c = 0; c < m.nC; c++) cptr[c + 1] += cptr[c];
-        std::vector<int> pos(cptr.begin(), cptr.end() - 1);
-        for (int k = 0; k < nf; k++) cidx[pos[m.owner[fn->faces[k]]]++] = k;
+        std::vector<int> cptr, cidx;
+        function_face_slots(m, *fn, cptr, cidx);
         v.d_fnPtr.upload(cptr); v.d_fnIdx.upload(cidx);
     }
     auto output_pass = [&](double* Rout, double* fvOut) {
@@ -5395,15 +5392,10 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
         if (fn->isMoment)
             hipLaunchKernelGGL(k_fn_moment_dir, dim3(nblk(nf, B)), dim3(B), 0, st, nf, (const int*)fn->d_faces.p, (const FaceGeom*)s->d_fg.p, fn->vecA[0], fn->vecA[1],
                                fn->vecA[2], fn->vecB[0], fn->vecB[1], fn->vecB[2], fn->d_dir.p);
-        if (rho) {
-            hipLaunchKernelGGL((k_grad<double, true>), dim3(nblk(s->dm.nC, B)), dim3(B), 0, st, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, s->wk.gP.p, s->wk.gN.p, s->wk.gH.p);
-            if (areaAvg) hipLaunchKernelGGL((k_fn_area_avg<true>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn->view(fn->d_w0.p), cN[0], cN[1], cA[0], cA[1], fvOut);
-            else hipLaunchKernelGGL((k_fn_value<true>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn->view(fn->d_w0.p), fvOut);
-        } else {
-            hipLaunchKernelGGL((k_grad<double, false>), dim3(nblk(s->dm.nC, B)), dim3(B), 0, st, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, s->wk.gP.p, s->wk.gN.p, s->wk.gH.p);
-            if (areaAvg) hipLaunchKernelGGL((k_fn_area_avg<false>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn->view(fn->d_w0.p), cN[0], cN[1], cA[0], cA[1], fvOut);
-            else hipLaunchKernelGGL((k_fn_value<false>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn->view(fn->d_w0.p), fvOut);
-        }
+        launch_grad_and_faces(st, rho, s->dm, prm, (const double*)s->d_W.p, s->wk, true, [&](auto R) {
+            if (areaAvg) hipLaunchKernelGGL((k_fn_area_avg<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn->view(fn->d_w0.p), cN[0], cN[1], cA[0], cA[1], fvOut);
+            else hipLaunchKernelGGL((k_fn_value<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn->view(fn->d_w0.p), fvOut);
+        });
     };
     const double t0 = wall_seconds();
     long long passes = 0;
@@ -5431,13 +5423,8 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
         }
         DAS_HIP(hipGetLastError());
     }
-    int bad = 0;
-    DAS_HIP(hipMemcpyAsync(&bad, v.d_bad.p, sizeof(int), hipMemcpyDeviceToHost, st));
-    DAS_HIP(hipMemcpyAsync(product, v.d_out.p, n3 * sizeof(double), hipMemcpyDeviceToHost, st));
-    DAS_HIP(hipStreamSynchronize(st));
-    DAS_CHECK(!bad, DAS_ERR_INTERNAL, "a perturbed mesh of the volCoord product has a non-positive cell volume (amd.volCoordRelStep too large?)");
-    v.seconds = wall_seconds() - t0;
-    if (info4) { info4[0] = I.nColors; info4[1] = (double)passes; info4[2] = v.seconds; info4[3] = v.buildSeconds; }
+    finish_volcoord(s, v.d_out.p, product, "a perturbed mesh of the volCoord product has a non-positive cell volume (amd.volCoordRelStep too large?)", t0,
+                    passes, info4);
     return DAS_OK;
     DAS_CATCH
 }

@@ -1131,15 +1131,15 @@ DAS_HD T body_force(int f, const DevMeshT<G>& m, const ResParams& prm, const T* 
 //   kind 4  patchMean        component of the boundary value  b_v,i                    DAFunctionPatchMean.C:36-110
 //   kind 5  variance         sum_i (b_v,i - d_f,i)^2 over the selected components, d_f = dir (the reference data of the face)
 //                                                                       DAFunctionVariance.C (mode surface)
-//   (kinds 4, 5: bits 4-7 = variable v (0 U, 1 p, 2 nuTilda, 3 T), bits 8-10 = component mask)
+//   (kinds 4, 5: bits 4-7 = variable v (0 U, 1 p, 2 nuTilda, 3 T), bits 8-10 = component mask: DAS_FN_FIELD_KIND below)
 #define DAS_FN_PATCHMEAN 4
 #define DAS_FN_VARIANCE 5
 //   kind 6  totalPressureRatio  p_b (1 + 0.5 (gamma-1) Ma^2)^(gamma/(gamma-1)), Ma^2 and R as for kind 3 (a ratio function: group 0 the
 //                            inlet, group 1 the outlet)                 DAFunctionTotalPressureRatio.C:50-139
 //   kind 7  wallHeatFlux     alphaEff_b snGrad(he)_f (compressible), Cp alphaEff_b snGrad(T)_f (DASimpleFoam with the T field); alphaEff_b
 //                            is alpha_eff above, the energy rows' own.  snGrad: the patch field's gic x_c + gbc (wallDistanceMethod
-//                            default), or bit 4 set: (x_b - x_c) / |C_f - C_c| (daCustom)  DAFunctionWallHeatFlux.C:115-304 (fluid branches)
-//   kind 8  location         r_f = |c - (c o axis)|, c = C_f - center, or bit 4 set: 1 / (r_f + 1e-12).  "o" is the COMPONENT-WISE product:
+//                            default), or DAS_FN_ALT_BIT set: (x_b - x_c) / |C_f - C_c| (daCustom)  DAFunctionWallHeatFlux.C:115-304 (fluid branches)
+//   kind 8  location         r_f = |c - (c o axis)|, c = C_f - center, or DAS_FN_ALT_BIT set: 1 / (r_f + 1e-12).  "o" is the COMPONENT-WISE product:
 //                            the reference applies the diagonal tensor diag(c) to the axis (DAFunctionLocation.C:183-191), which is not
 //                            the projection of c onto the axis; it is restated as written.  Geometry only: no state is read.
 //                            loc = axis (unit), center                  DAFunctionLocation.C:153-295
@@ -1147,6 +1147,12 @@ DAS_HD T body_force(int f, const DevMeshT<G>& m, const ResParams& prm, const T* 
 #define DAS_FN_WALLHEATFLUX 7
 #define DAS_FN_LOCATION 8
 #define DAS_FN_BASE(kind) ((kind) & 15)
+// the kind word above its base: bit 4 selects the other form of kinds 7 and 8; kinds 4 and 5 keep their variable and component mask there
+#define DAS_FN_ALT_BIT 16
+#define DAS_FN_ALT(kind) (((kind) >> 4) & 1)
+#define DAS_FN_VAR(kind) (((kind) >> 4) & 15)
+#define DAS_FN_COMPMASK(kind) (((kind) >> 8) & 7)
+#define DAS_FN_FIELD_KIND(base, var, mask) ((base) | ((var) << 4) | ((mask) << 8))
 template <class G>
 DAS_HD G location_radius(const FaceGeomT<G>& g, const double* loc, bool inverse) {
     G r2(0.0);
@@ -1163,7 +1169,7 @@ template <class T, bool RHO, class G, class DV>
 DAS_HD T body_facefn(int f, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* nut, const T* gradU, int kind, const DV* dir,
                      double gammaFn, double RFn, const double* loc = nullptr) {
     if (kind == DAS_FN_FORCE) return body_force<T, RHO>(f, m, prm, W, nut, gradU, dir, 1.0);
-    if (DAS_FN_BASE(kind) == DAS_FN_LOCATION) return T(location_radius<G>(m.fg[f], loc, (kind >> 4) & 1));
+    if (DAS_FN_BASE(kind) == DAS_FN_LOCATION) return T(location_radius<G>(m.fg[f], loc, DAS_FN_ALT(kind)));
     const long long N = m.nC;
     const FaceGeomT<G>& g = m.fg[f];
     const int c = m.owner[f];
@@ -1176,7 +1182,7 @@ DAS_HD T body_facefn(int f, const DevMeshT<G>& m, const ResParams& prm, const T*
     if (kind == DAS_FN_MASSFLOW) return b.rho_b * (b.U.xb[0] * g.Sf[0] + b.U.xb[1] * g.Sf[1] + b.U.xb[2] * g.Sf[2]);
     if (kind == DAS_FN_TOTALPRESSURE) return b.p.xb + 0.5 * b.rho_b * U2;
     if (DAS_FN_BASE(kind) == DAS_FN_PATCHMEAN || DAS_FN_BASE(kind) == DAS_FN_VARIANCE) {
-        const int v = (kind >> 4) & 15, mask = (kind >> 8) & 7;
+        const int v = DAS_FN_VAR(kind), mask = DAS_FN_COMPMASK(kind);
         T q(0.0);
 #pragma unroll
         for (int i = 0; i < 3; i++) {
@@ -1193,7 +1199,7 @@ DAS_HD T body_facefn(int f, const DevMeshT<G>& m, const ResParams& prm, const T*
     if (DAS_FN_BASE(kind) == DAS_FN_WALLHEATFLUX) {  // a solver with a T field (the caller checks)
         const T xc = RHO ? prm.Cp * (Tc - DAS_TREF) : Tc;
         T sn;
-        if ((kind >> 4) & 1) {
+        if (DAS_FN_ALT(kind)) {
             const G d0 = g.Cf[0] - m.cg[c].C[0], d1 = g.Cf[1] - m.cg[c].C[1], d2 = g.Cf[2] - m.cg[c].C[2];
             sn = (b.he.xb - xc) / dsqrt(d0 * d0 + d1 * d1 + d2 * d2);
         } else {
@@ -1283,7 +1289,7 @@ DAS_HD void body_T(int c, const DevMeshT<G>& m, const ResParams& prm, const T* W
     R[c] = res;
 }
 
-// a face-integral objective as the kernels see it (k_fn_value / k_fn_grad / k_fn_face)
+// a face-integral objective as the kernels see it (k_fn_value / k_fn_tangent / k_fn_grad / k_fn_dual / k_fn_area_avg)
 struct FaceFnView {
     const int* faces;
     const unsigned char* group;  // 0 / 1: denominator / numerator set of ratio functions (all 0 otherwise)

@@ -225,6 +225,37 @@ def test_volcoord_location():
     check_volcoord(build_case("simpleT"), dict(LOCATION, RMaxRef=dict(LOCATION["RMaxKS"], calcRefVar=1, ref=[0.2])))
 
 
+FD_FNS = {
+    "totalPressure": {"type": "totalPressure", "source": "patchToFace", "patches": ["outlet"], "scale": 0.5},
+    "totalTemperatureRatio": {"type": "totalTemperatureRatio", "source": "patchToFace", "patches": ["inlet", "outlet"], "inletPatches": ["inlet"],
+                              "outletPatches": ["outlet"], "scale": 1.0},
+    "moment": {"type": "moment", "source": "patchToFace", "patches": WALLS, "axis": [0.0, 0.0, 1.0], "center": [0.5, 0.1, 0.0], "scale": 3.0},
+}
+
+
+@pytest.mark.parametrize("name", list(FD_FNS))
+def test_volcoord_fd_mode_agrees_with_dual_on_a_compressible_case(name):
+    """amd.volCoordMode "fd" against "dual" on the compressible case: an area average, a quotient of two area averages (both through the
+    linearised functional of the difference mode) and a moment (whose arms move with the points).  The bounds and the rule for the entries
+    next to a switch are those of test_volcoord_dual_and_difference_modes_agree_away_from_switches (tests/test_gpu_parity.py): half of the
+    entries within 1e-8 of the largest, 95 % within 1e-4, all within 5 %.  The same figures over the entries the function reaches at all
+    (the points far from its patches are exact zeros in both modes) are printed."""
+    case = build_case("rho")
+    X0 = case.mesh.points.ravel().copy()
+    out = {}
+    for mode in ("dual", "fd"):
+        D = make(case, function={name: FD_FNS[name]}, inputInfo={"x": {"type": "volCoord"}}, amd={"volCoordMode": mode})
+        out[mode] = np.zeros(X0.size)
+        D.solverAD.calcJacTVecProduct("x", "volCoord", X0, name, "function", np.ones(1), out[mode])
+    reached = (out["dual"] != 0.0) | (out["fd"] != 0.0)
+    scale = np.abs(out["dual"]).max()
+    err = np.abs(out["dual"] - out["fd"])
+    print(f"{name}: dual vs fd p50/p95/max", np.percentile(err, [50, 95, 100]) / scale, f" over the {int(reached.sum())} of {X0.size} entries reached:",
+          np.percentile(err[reached], [50, 95, 100]) / scale if reached.any() else None)
+    assert scale > 0 and np.percentile(err, 95) <= 1e-4 * scale and np.percentile(err, 50) <= 1e-8 * scale, (np.percentile(err, [50, 95, 100]), scale)
+    assert err.max() <= 5e-2 * scale
+
+
 # ---- 5: the reduction at size -------------------------------------------------------------------------------------------------------
 def test_ks_reduction_over_thousands_of_faces():
     """8000 wall faces: 32 workgroups of partials.  On the largest coeffKS: the guard the issue keeps from the reference, m + log S >
