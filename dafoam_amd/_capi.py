@@ -78,6 +78,35 @@ class das_case_t(C.Structure):
     ]
 
 
+class das_bilu_debug_t(C.Structure):
+    """input of the test-only entries das_debug_bilu_* (include/dafoam_amd.h)"""
+    _fields_ = [
+        ("nNodes", C.c_int),
+        ("nLevels", C.c_int),
+        ("nMaps", C.c_int),
+        ("fp32", C.c_int),
+        ("transpose", C.c_int),
+        ("n", C.c_longlong),
+        ("An", C.c_longlong),
+        ("nodeUnk", c_int_p),
+        ("nodeOut", c_int_p),
+        ("late", C.POINTER(C.c_ubyte)),
+        ("bptr", c_ll_p),
+        ("bdiag", c_ll_p),
+        ("bcol", c_int_p),
+        ("lvlPtr", c_int_p),
+        ("unkNode", c_int_p),
+        ("unkSlot", C.POINTER(C.c_ubyte)),
+        ("rp", c_ll_p),
+        ("ci", c_int_p),
+        ("val", c_double_p),
+        ("diagScale", C.c_double),
+        ("shiftExLo", C.c_longlong),
+        ("shiftExHi", C.c_longlong),
+        ("shiftEnd", C.c_longlong),
+    ]
+
+
 def _dp(a):
     return a.ctypes.data_as(c_double_p) if a is not None else None
 
@@ -318,6 +347,9 @@ _SIGS = {
     "das_debug_krylov_block_right_mult": (C.c_int, [C.c_longlong, C.c_int, c_double_p, C.c_longlong, c_double_p]),
     "das_debug_krylov_block_lincomb": (C.c_int, [C.c_longlong, C.c_int, C.c_int, c_double_p, C.c_longlong, c_double_p, c_double_p, C.c_longlong]),
     "das_debug_krylov_block_spmm": (C.c_int, [C.c_longlong, C.c_int, c_ll_p, c_int_p, c_double_p, c_double_p, C.c_longlong, c_double_p, C.c_longlong]),
+    # test-only entries (tests/test_gpu_bilu_kernels.py): the node-block ILU(0) on a caller-made structure, never called by the bindings
+    "das_debug_bilu_factor": (C.c_int, [C.POINTER(das_bilu_debug_t), c_ll_p, c_ll_p, c_int_p, c_int_p, _VP, _VP, c_double_p, c_int_p]),
+    "das_debug_bilu_apply": (C.c_int, [C.POINTER(das_bilu_debug_t), C.c_int, C.c_longlong, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p, c_int_p, c_int_p]),
     "das_timer_count": (C.c_longlong, [_VP, C.c_char_p]),
     "das_timer_reset": (None, [_VP]),
     "das_timer_enable": (None, [_VP, C.c_int]),

@@ -23,6 +23,7 @@
 #include "das_krylov.hpp"
 #include "das_block.hpp"
 #include "das_krylov_debug.hpp"
+#include "das_bilu_debug.hpp"
 #include "das_color.hpp"
 #include "das_opmat.hpp"
 #include "das_graph.hpp"
@@ -6162,6 +6163,29 @@ int das_debug_krylov_block_spmm(long long n, int s, const long long* rp, const i
     DAS_CHECK(nnz == 0 || (ci && val), DAS_ERR_ARG, "das_debug_krylov_block_spmm: null pointer");
     for (long long k = 0; k < nnz; k++) DAS_CHECK(ci[k] >= 0 && ci[k] < n, DAS_ERR_ARG, "das_debug_krylov_block_spmm: column index out of range");
     debug_krylov_block_spmm(n, s, rp, ci, val, X, ldx, Y, ldy);
+    return DAS_OK;
+    DAS_CATCH
+}
+
+// Test-only entries (tests/test_gpu_bilu_kernels.py): the node-block ILU(0) on a caller-made structure through the numeric setup and
+// the sweeps the solver uses (das_bilu_debug.hpp).  The structure is checked on the host before anything is launched.
+int das_debug_bilu_factor(const das_bilu_debug_t* in, long long* Lptr, long long* Uptr, int* Lcol, int* Ucol, void* Lval, void* Uval, double* invD,
+                          int* nshift) {
+    DAS_TRY
+    bilu_debug_check("das_debug_bilu_factor", in);
+    DAS_CHECK(Lptr && Uptr && Lcol && Ucol && Lval && Uval && invD && nshift, DAS_ERR_ARG, "das_debug_bilu_factor: null pointer");
+    debug_bilu_factor(*in, Lptr, Uptr, Lcol, Ucol, Lval, Uval, invD, nshift);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_bilu_apply(const das_bilu_debug_t* in, int nrhs, long long ld, const double* b, double* out, int twice, double* y, double* z,
+                         int* abortFlag, int* info) {
+    DAS_TRY
+    bilu_debug_check("das_debug_bilu_apply", in);
+    DAS_CHECK(nrhs >= 1 && nrhs <= 8, DAS_ERR_ARG, "das_debug_bilu_apply: 1 to 8 right-hand sides");
+    DAS_CHECK(ld >= in->n, DAS_ERR_ARG, "das_debug_bilu_apply: leading dimension below n");
+    DAS_CHECK(b && out && y && z && abortFlag && info, DAS_ERR_ARG, "das_debug_bilu_apply: null pointer");
+    debug_bilu_apply(*in, nrhs, ld, b, out, twice, y, z, abortFlag, info);
     return DAS_OK;
     DAS_CATCH
 }

@@ -551,6 +551,44 @@ int das_debug_krylov_block_lincomb(long long n, int K, int s, const double* V, l
 /* block_spmm (k_block_to_rows<S> + k_spmm_wave<S>, S = 2, 4 or 8 chosen from s): Y_r = A X_r for a square CSR matrix */
 int das_debug_krylov_block_spmm(long long n, int s, const long long* rowptr, const int* colidx, const double* vals, const double* X, long long ldx,
                                 double* Y, long long ldy);
+/* ---- TEST-ONLY entries (tests/test_gpu_bilu_kernels.py): the node-block ILU(0) preconditioner on a caller-made node structure and
+ * scalar CSR matrix, kernel by kernel.  No mesh, no solver handle; the numeric setup and the sweeps THE SOLVER USES run on the null
+ * stream.  The structure is checked on the host before anything is launched, and DAS_ERR_ARG is returned for a null pointer (nodeOut
+ * alone may be null: nodeOut = nodeUnk), sizes <= 0, An > n, and for anything that is not a valid level-ordered structure: bptr not
+ * monotone, block columns of a row not ascending, out of range or without the diagonal at bdiag, a pattern that is not symmetric,
+ * lvlPtr not covering [0, nNodes], an entry J < p of row p with level(J) >= level(p), slots >= 8, unkNode outside [-1, nNodes), CSR
+ * columns >= An, nodeUnk / nodeOut outside [-1, n).  Matrix entries outside the node pattern that are not late-late couplings stay the
+ * DAS_ERR_INTERNAL of the solver's setup. */
+typedef struct {
+    int nNodes, nLevels, nMaps; /* nodes in processing order, levels, (unkNode, unkSlot) maps (one per block of a multi-block factor) */
+    int fp32, transpose;        /* factor stored as float; factorise the transposed matrix */
+    long long n, An;            /* length of a vector of unknowns; rows (= columns) of the CSR matrix, An <= n */
+    const int* nodeUnk;         /* nNodes*8: unknown of a slot or -1 */
+    const int* nodeOut;         /* nNodes*8 or null: where the slot's solution is written, -1 for an overlap copy */
+    const unsigned char* late;  /* nNodes */
+    const long long* bptr;      /* nNodes+1 */
+    const long long* bdiag;     /* nNodes: position of the diagonal block */
+    const int* bcol;            /* bptr[nNodes] */
+    const int* lvlPtr;          /* nLevels+1 */
+    const int* unkNode;         /* nMaps*An: node of an unknown or -1 */
+    const unsigned char* unkSlot; /* nMaps*An */
+    const long long* rp;        /* An+1 */
+    const int* ci;
+    const double* val;
+    double diagScale;           /* diagonal entries of the rows below shiftEnd outside [shiftExLo, shiftExHi) are multiplied by it */
+    long long shiftExLo, shiftExHi, shiftEnd;
+} das_bilu_debug_t;
+/* k_bilu_scatter, k_bilu_pad_diag, k_bilu_factor, k_bilu_pack: Lptr / Uptr (nNodes+1; U rows by q = nNodes-1-p), Lcol / Ucol, the
+ * packed Lval / Uval (64 per block, per pass of nb <= 8 blocks [qq][g][k][2]; float if fp32 else double), invD (nNodes*64) and the
+ * number of shifted pivots */
+int das_debug_bilu_factor(const das_bilu_debug_t* in, long long* Lptr, long long* Uptr, int* Lcol, int* Ucol, void* Lval, void* Uval, double* invD,
+                          int* nshift);
+/* the same setup, then k_bilu_reset + k_bilu_sweep (nrhs = 1) or bilu_apply_multi (nrhs = 2..8: groups of 4, 2, 1), twice if `twice`;
+ * b, out column-major nrhs x ld, ld >= n; out is uploaded before every application, so entries nothing writes keep the caller's
+ * values.  y, z (nNodes*8*4 doubles each): the work vectors of the LAST group launched, [(node*8+slot)*S + r] with S = 4, 2 or 1 its
+ * width.  info = {launchGrid, launchSleep, launchPerXcd, xcdProbe} */
+int das_debug_bilu_apply(const das_bilu_debug_t* in, int nrhs, long long ld, const double* b, double* out, int twice, double* y, double* z,
+                         int* abortFlag, int* info);
 long long das_timer_count(das_solver_t* s, const char* name);
 void das_timer_reset(das_solver_t* s);
 void das_timer_enable(das_solver_t* s, int on);

@@ -6,4 +6,4 @@ import __graft_entry__ as g
 
 def test_headers_hold_every_hpp_of_csrc():
     assert g.HEADERS == sorted(f for f in os.listdir(g.CSRC) if f.endswith(".hpp"))
-    assert {"das_simple.hpp", "das_krylov.hpp", "das_krylov_debug.hpp"} <= set(g.HEADERS)
+    assert {"das_simple.hpp", "das_krylov.hpp", "das_krylov_debug.hpp", "das_bilu_debug.hpp"} <= set(g.HEADERS)
