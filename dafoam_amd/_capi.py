@@ -303,6 +303,8 @@ _SIGS = {
     "das_debug_gmres_dr_host": (C.c_int, [C.c_longlong, _VP, _VP, _VP, c_double_p, c_double_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_longlong, c_double_p, C.c_int,
                                           c_double_p, c_double_p]),
     "das_debug_gmres_dr_restart": (C.c_int, [C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "das_debug_block_chol": (C.c_int, [C.c_int, c_double_p, c_double_p, c_double_p]),
+    "das_debug_block_lsq": (C.c_int, [C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "das_ksp_get_status": (C.c_int, [_VP, c_int_p, c_int_p, c_int_p, c_int_p]),
     "das_ksp_get_pc_stability": (C.c_int, [_VP, C.POINTER(C.c_double), c_int_p]),
     "das_ksp_get_pc_subdomains": (C.c_int, [_VP, c_int_p, c_double_p]),

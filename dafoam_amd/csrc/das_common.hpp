@@ -19,14 +19,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/dafoam_amd.h"
+#include "das_error.hpp"
 
 namespace das {
-
-struct Error : std::runtime_error {
-    int code;
-    Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
 
 #define DAS_HIP(expr)                                                                              \
     do {                                                                                           \
@@ -34,11 +29,6 @@ struct Error : std::runtime_error {
         if (_e != hipSuccess)                                                                      \
             throw das::Error(DAS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e) + " @" \
                                               + __FILE__ + ":" + std::to_string(__LINE__));        \
-    } while (0)
-
-#define DAS_CHECK(cond, code, msg)                    \
-    do {                                              \
-        if (!(cond)) throw das::Error((code), (msg)); \
     } while (0)
 
 // workgroups of b items that cover n items

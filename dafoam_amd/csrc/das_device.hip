@@ -1,7 +1,7 @@
 // MI355X device driver of the adjoint hot path: kernel launches, coloured Jacobian assembly (dual numbers / FD),
 // transposed-CSR SpMV (dRdW^T psi), restricted-additive-Schwarz + ILU(k) preconditioner (one workgroup per block, block
 // vector in LDS), the on-device restarted GMRES, objective/boundary-input derivatives, exported through the C-ABI of
-// include/dafoam_amd.h.  gfx950 only.
+// include/dafoam_amd.h.  gfx950 only.  The dense host algebra of the GMRES solvers (no device code) is in das_gmres_host.hpp.
 //
 // Reference orchestration being replaced (file:line):
 //   DASolver::calcdRdWT                         src/adjoint/DASolver/DASolver.C:948-1089
@@ -21,6 +21,7 @@
 #include "das_bilu.hpp"
 #include "das_comm.hpp"
 #include "das_krylov.hpp"
+#include "das_gmres_host.hpp"
 #include "das_block.hpp"
 #include "das_krylov_debug.hpp"
 #include "das_bilu_debug.hpp"
@@ -2605,10 +2606,6 @@ struct GmresRun {
     double betaStart = 0;         // true residual norm at the start of the open cycle
 };
 static bool gmres_trace() { static const bool on = [] { const char* e = getenv("DAS_GMRES_TRACE"); return e && *e && *e != '0'; }(); return on; }
-// a new basis vector whose norm is below this fraction of the norm of the operator image it was projected from is
-// rounding noise (the rounding errors of the projection itself are ~1e-16 of that norm, at any problem size: they are
-// componentwise): the Krylov space is exhausted - happy breakdown
-static constexpr double GMRES_BREAKDOWN_TOL = 1e-13;
 
 static void gmres_true_residual(das_solver* s, das_ksp* k, GmresRun& G, bool haveGuess) {
     const long long n = s->n;
@@ -2624,33 +2621,50 @@ static void gmres_true_residual(das_solver* s, das_ksp* k, GmresRun& G, bool hav
     G.beta = std::sqrt(G.hh[0]);
 }
 
-static void gmres_begin(das_solver* s, das_ksp* k, const double* d_rhs, double* d_x, bool fixed) {
+// what every solve starts with: workspace, a fresh GmresRun with the options read, the true residual of the start vector, the target.
+// `deflated`: run_gmres_dr - fp64 basis, no Hessenberg arrays (gmres_dr_loop keeps its own), the cycle lengths are left alone
+static GmresRun& gmres_begin(das_solver* s, das_ksp* k, const double* d_rhs, double* d_x, bool fixed, bool deflated = false) {
     need_init(s);
     DAS_CHECK(s->op || s->fwd.on, DAS_ERR_STATE, "initializedRdWTMatrixFree() must be called before solveLinearEqn()");
+    if (deflated) DAS_CHECK(!s->halo.active && !s->halo_cb, DAS_ERR_ARG, "amd.gmresDeflation is single-rank (the restart's small dense algebra is not replicated across ranks yet)");
     gmres_ws(s, k);
+    if (deflated) { k->vf32 = false; k->split = false; }  // the deflated solver keeps its (short) basis in fp64
     if (k->useBilu) bilu_clear_abort(k->bilu, s->stream);
     if (!k->run) k->run.reset(new GmresRun);
     GmresRun& G = *k->run;
     const int m = k->restart;
     G = GmresRun();
+    if (deflated) DAS_CHECK(m >= 4, DAS_ERR_ARG, "amd.gmresDeflation needs gmresRestart >= 4");
     G.m = m; G.fixed = fixed; G.d_rhs = d_rhs; G.d_x = d_x;
     G.maxIts = s->opt.geti("adjEqnOption.gmresMaxIters");
     G.rtol = s->opt.getd("adjEqnOption.gmresRelTol"); G.atol = s->opt.getd("adjEqnOption.gmresAbsTol");
-    G.H.assign((size_t)(m + 1) * m, 0.0); G.cs.assign(m, 0.0); G.sn.assign(m, 0.0); G.g.assign(m + 1, 0.0);
-    G.hh.assign(2 * (m + 2), 0.0); G.h2.assign(2 * (m + 2), 0.0); G.y.assign(m, 0.0);
-    const std::string& orth = s->opt.gets("amd.gmresOrthogonalization");
-    DAS_CHECK(orth == "dcgs2" || orth == "cgs", DAS_ERR_ARG, "amd.gmresOrthogonalization \"" + orth + "\" is not one of dcgs2 | cgs");
-    G.dcgs2 = orth == "dcgs2" && s->opt.geti("adjEqnOption.useMGSO") == 0;
-    if (G.dcgs2) { G.Hraw.assign((size_t)(m + 1) * m, 0.0); G.h1.assign(m + 2, 0.0); }
-    k->nrefine = 0;
-    k->hist.clear();
-    k->cycleLens.clear();
+    G.hh.assign(2 * (m + 2), 0.0); G.h2.assign(2 * (m + 2), 0.0);
+    if (!deflated) {
+        G.H.assign((size_t)(m + 1) * m, 0.0); G.cs.assign(m, 0.0); G.sn.assign(m, 0.0); G.g.assign(m + 1, 0.0); G.y.assign(m, 0.0);
+        const std::string& orth = s->opt.gets("amd.gmresOrthogonalization");
+        DAS_CHECK(orth == "dcgs2" || orth == "cgs", DAS_ERR_ARG, "amd.gmresOrthogonalization \"" + orth + "\" is not one of dcgs2 | cgs");
+        G.dcgs2 = orth == "dcgs2" && s->opt.geti("adjEqnOption.useMGSO") == 0;
+        if (G.dcgs2) { G.Hraw.assign((size_t)(m + 1) * m, 0.0); G.h1.assign(m + 2, 0.0); }
+        k->cycleLens.clear();
+    }
+    k->nrefine = 0; k->hist.clear();
     G.t0 = wall_seconds();
     gmres_true_residual(s, k, G, s->opt.geti("adjEqnOption.useNonZeroInitGuess") != 0);
     k->res0 = G.beta;
     k->hist.push_back(G.beta);
     G.target = std::max(G.rtol * G.beta, G.atol);
-    G.recTarget = k->split ? 0.98 * G.target : (k->vf32 ? 0.5 * G.target : G.target);
+    if (!deflated) G.recTarget = k->split ? 0.98 * G.target : (k->vf32 ? 0.5 * G.target : G.target);
+    return G;
+}
+// reference failure rule (DALinearEqn.C:422-434): 1 = failed, the residual misses BOTH tolerances by more than the factor `diff` (gmresTolDiff)
+static int gmres_failed(double res, double res0, double rtol, double atol, double diff) {
+    const double absRatio = res / atol, relRatio = res0 > 0 ? res / res0 / rtol : 0.0;
+    return (relRatio > diff && absRatio > diff) ? 1 : 0;
+}
+// what every solve ends with: wait for the stream, then the abort flag of the preconditioner sweeps
+static void gmres_finish_check(das_solver* s, das_ksp* k) {
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    if (k->useBilu) DAS_CHECK(!bilu_aborted(k->bilu, s->stream), DAS_ERR_INTERNAL, "preconditioner sweep timed out (bounded spin)");
 }
 static void gmres_cycle_start(das_solver* s, das_ksp* k) {
     GmresRun& G = *k->run;
@@ -2730,19 +2744,7 @@ static double gmres_iter_t(das_solver* s, das_ksp* k) {
     for (int i = 0; i <= j; i++) H[(size_t)i * m + j] = hh[i] + h2[i];
     H[(size_t)(j + 1) * m + j] = hn;
     if (hn > 0.0) launch_scale_to(st, n, 1.0 / hn, (const double*)k->w.p, Vb + (long long)(j + 1) * ld, (const float*)nullptr, basis_lo(s, k, j + 1));
-    for (int i = 0; i < j; i++) {
-        double a = H[(size_t)i * m + j], b2 = H[(size_t)(i + 1) * m + j];
-        H[(size_t)i * m + j] = cs[i] * a + sn[i] * b2;
-        H[(size_t)(i + 1) * m + j] = -sn[i] * a + cs[i] * b2;
-    }
-    double a = H[(size_t)j * m + j], b2 = H[(size_t)(j + 1) * m + j];
-    double d = std::hypot(a, b2);
-    cs[j] = d > 0 ? a / d : 1.0;
-    sn[j] = d > 0 ? b2 / d : 0.0;
-    H[(size_t)j * m + j] = d;
-    H[(size_t)(j + 1) * m + j] = 0.0;
-    g[j + 1] = -sn[j] * g[j];
-    g[j] = cs[j] * g[j];
+    gmres_rotate_column(H, cs, sn, g, m, j);
     G.its++;
     G.j++;
     const double res = std::fabs(g[G.j]);
@@ -2751,25 +2753,6 @@ static double gmres_iter_t(das_solver* s, das_ksp* k) {
     return res;
 }
 static double gmres_iter(das_solver* s, das_ksp* k) { return k->vf32 ? gmres_iter_t<float>(s, k) : gmres_iter_t<double>(s, k); }
-// Givens update of Hessenberg column `col` (entries H[0..col+1][col] already set); returns the recurrence residual norm
-static double gmres_rotate_column(GmresRun& G, int col) {
-    const int m = G.m;
-    std::vector<double>&H = G.H, &cs = G.cs, &sn = G.sn, &g = G.g;
-    for (int i = 0; i < col; i++) {
-        const double a = H[(size_t)i * m + col], b2 = H[(size_t)(i + 1) * m + col];
-        H[(size_t)i * m + col] = cs[i] * a + sn[i] * b2;
-        H[(size_t)(i + 1) * m + col] = -sn[i] * a + cs[i] * b2;
-    }
-    const double a = H[(size_t)col * m + col], b2 = H[(size_t)(col + 1) * m + col];
-    const double d = std::hypot(a, b2);
-    cs[col] = d > 0 ? a / d : 1.0;
-    sn[col] = d > 0 ? b2 / d : 0.0;
-    H[(size_t)col * m + col] = d;
-    H[(size_t)(col + 1) * m + col] = 0.0;
-    g[col + 1] = -sn[col] * g[col];
-    g[col] = cs[col] * g[col];
-    return std::fabs(g[col + 1]);
-}
 // One step of GMRES with classical Gram-Schmidt and DELAYED re-orthogonalisation (DCGS2; Bielich, Langou, Thomas,
 // Swirydowicz, Yamazaki, Boman, "Low-synch Gram-Schmidt with delayed reorthogonalization for Krylov solvers", 2022).
 // The reference's CGS with refinement (DALinearEqn.C:160) reads the basis four times per iteration here (it refines at
@@ -2851,7 +2834,7 @@ static double gmres_iter_dcgs2(das_solver* s, das_ksp* k) {
         const int col = j - 1;
         for (int i = 0; i < j; i++) G.Hraw[(size_t)i * m + col] = G.H[(size_t)i * m + col] = G.h1[i] + (breakdown ? 0.0 : sv[i]);
         G.Hraw[(size_t)j * m + col] = G.H[(size_t)j * m + col] = al;
-        res = gmres_rotate_column(G, col);
+        res = gmres_rotate_column(G.H, G.cs, G.sn, G.g, m, col);
         G.its++;
         G.j = j;
         k->hist.push_back(res);
@@ -2890,11 +2873,7 @@ static void gmres_cycle_end_t(das_solver* s, das_ksp* k) {
     const long long n = s->n;
     const int B = 256, m = G.m, j = std::abs(G.j);
     hipStream_t st = s->stream;
-    for (int i = j - 1; i >= 0; i--) {
-        double sacc = G.g[i];
-        for (int q = i + 1; q < j; q++) sacc -= G.H[(size_t)i * m + q] * G.y[q];
-        G.y[i] = sacc / G.H[(size_t)i * m + i];
-    }
+    back_substitute(j, G.H.data(), m, 1, 1, G.g.data(), G.y.data());
     DAS_HIP(hipMemcpyAsync(k->hdev.p, G.y.data(), j * sizeof(double), hipMemcpyHostToDevice, st));
     launch_lincomb(st, n, j, (const VT*)basis_slot<VT>(s, k, 0), basis_ld(s, k), (const double*)k->hdev.p, (double*)k->w.p, (const float*)basis_lo(s, k, 0));
     pc_apply_full(s, k, k->w.p, k->z.p);
@@ -2958,242 +2937,17 @@ static bool gmres_advance(das_solver* s, das_ksp* k, long long nsteps) {
 static int gmres_end(das_solver* s, das_ksp* k) {
     GmresRun& G = *k->run;
     if (G.open) gmres_cycle_end(s, k);
-    DAS_HIP(hipStreamSynchronize(s->stream));
-    if (k->useBilu) DAS_CHECK(!bilu_aborted(k->bilu, s->stream), DAS_ERR_INTERNAL, "preconditioner sweep timed out (bounded spin)");
+    gmres_finish_check(s, k);
     k->iters = (int)G.its;
     k->nBreakdown = G.nBreakdown;
     k->res = k->hist.back();
     k->reason = G.beta <= G.target ? 0 : (G.stalled ? 2 : 1);
     k->seconds = wall_seconds() - G.t0;
-    // reference failure rule (DALinearEqn.C:422-434)
-    double absRatio = k->res / G.atol;
-    double relRatio = k->res0 > 0 ? k->res / k->res0 / G.rtol : 0.0;
-    double diff = s->opt.getd("adjEqnOption.gmresTolDiff");
-    return (relRatio > diff && absRatio > diff) ? 1 : 0;
+    return gmres_failed(k->res, k->res0, G.rtol, G.atol, s->opt.getd("adjEqnOption.gmresTolDiff"));
 }
 
-// ---- GMRES with deflated restarting (opt-in: amd.gmresDeflation = k > 0; Morgan, SIAM J. Sci. Comput. 24 (2002) "GMRES-DR") ------------
-// A restart of length m (adjEqnOption.gmresRestart) keeps the k harmonic Ritz vectors of smallest magnitude: the next cycle starts from
-// the (k+1)-dimensional subspace span{harmonic Ritz vectors, residual}, for which an Arnoldi-like relation A M^-1 V_k = V_{k+1} Hbar_k
-// holds with a DENSE leading block, and continues Arnoldi from there.  Why (round 4, CPU prototype tools/gmres_dr_study.py): the residual
-// history of the airfoil adjoint is a plateau of hundreds of iterations followed by a fast drop - plain restarting inside the plateau
-// stalls (GMRES(100): 0.81 after 1500 iterations where full GMRES needs 302), deflated restarting needs 354-379 with 101-151 basis
-// vectors.  The basis is what limits the mesh size on one GPU (1000 vectors = 125 GB at 2 M cells).  Reference role: PETSc offers the
-// same idea as KSPDGMRES; the reference's default stays the undeflated solver, and so does this library's.
-// Orthogonalisation: classical Gram-Schmidt, always two passes.  The dense eigenproblem of the m x m harmonic matrix is solved through a
-// callback (das_set_dense_eig_callback; the Python mirror installs numpy.linalg.eig) - the library carries no LAPACK.
-typedef int (*das_dense_eig_fn)(int m, const double* A_rowmajor, double* wr, double* wi, double* vr_colmajor, double* vi_colmajor);
+// ---- GMRES with deflated restarting (amd.gmresDeflation): gmres_dr_loop of das_gmres_host.hpp over the device's vector operations; dense-eigen callback
 static das_dense_eig_fn g_dense_eig = nullptr;
-
-namespace {
-// least-squares bookkeeping of min |c - Hbar y|: Qt (accumulated rotations), R = Qt Hbar, gt = Qt c
-struct DrLsq {
-    int m = 0;
-    std::vector<double> Qt, R, gt;
-    void reset(int m_, const std::vector<double>& c) {
-        m = m_;
-        Qt.assign((size_t)(m + 1) * (m + 1), 0.0);
-        for (int i = 0; i <= m; i++) Qt[(size_t)i * (m + 1) + i] = 1.0;
-        R.assign((size_t)(m + 1) * m, 0.0);
-        gt = c;
-    }
-    // append column `col` of Hbar whose entries 0..nr-1 may be non-zero; eliminates everything below the diagonal
-    double add_column(int col, int nr, const double* h) {
-        const int ld = m + 1;
-        std::vector<double> t(nr, 0.0);
-        for (int i = 0; i < nr; i++) { double a = 0.0; for (int q = 0; q < nr; q++) a += Qt[(size_t)i * ld + q] * h[q]; t[i] = a; }
-        for (int r = nr - 1; r > col; r--) {  // rotate rows (r-1, r) so that t[r] = 0
-            const double a = t[r - 1], b = t[r];
-            const double d = std::hypot(a, b);
-            if (d == 0.0) continue;
-            const double cc = a / d, ss = b / d;
-            t[r - 1] = d; t[r] = 0.0;
-            for (int q = 0; q < nr; q++) {
-                const double x = Qt[(size_t)(r - 1) * ld + q], y = Qt[(size_t)r * ld + q];
-                Qt[(size_t)(r - 1) * ld + q] = cc * x + ss * y; Qt[(size_t)r * ld + q] = -ss * x + cc * y;
-            }
-            // (earlier columns of R are zero in rows >= col: nothing to rotate there; later columns do not exist yet)
-            const double gx = gt[r - 1], gy = gt[r];
-            gt[r - 1] = cc * gx + ss * gy; gt[r] = -ss * gx + cc * gy;
-        }
-        for (int i = 0; i < nr; i++) R[(size_t)i * m + col] = t[i];
-        return std::fabs(gt[col + 1]);
-    }
-    void solve(int j, std::vector<double>& y) const {
-        y.assign(j, 0.0);
-        for (int i = j - 1; i >= 0; i--) {
-            double a = gt[i];
-            for (int q = i + 1; q < j; q++) a -= R[(size_t)i * m + q] * y[q];
-            y[i] = a / R[(size_t)i * m + i];
-        }
-    }
-};
-// dense LU solve (partial pivoting) of A^T f = e_last, A row-major n x n (destroyed)
-static bool dr_solve_transposed_last(int n, std::vector<double> A, std::vector<double>& f) {
-    // work on T = A^T
-    std::vector<double> T((size_t)n * n);
-    for (int i = 0; i < n; i++) for (int j = 0; j < n; j++) T[(size_t)i * n + j] = A[(size_t)j * n + i];
-    f.assign(n, 0.0); f[n - 1] = 1.0;
-    for (int c = 0; c < n; c++) {
-        int p = c; double best = std::fabs(T[(size_t)c * n + c]);
-        for (int r = c + 1; r < n; r++) if (std::fabs(T[(size_t)r * n + c]) > best) { best = std::fabs(T[(size_t)r * n + c]); p = r; }
-        if (best == 0.0) return false;
-        if (p != c) { for (int q = 0; q < n; q++) std::swap(T[(size_t)c * n + q], T[(size_t)p * n + q]); std::swap(f[c], f[p]); }
-        for (int r = c + 1; r < n; r++) {
-            const double l = T[(size_t)r * n + c] / T[(size_t)c * n + c];
-            if (l == 0.0) continue;
-            for (int q = c; q < n; q++) T[(size_t)r * n + q] -= l * T[(size_t)c * n + q];
-            f[r] -= l * f[c];
-        }
-    }
-    for (int i = n - 1; i >= 0; i--) {
-        double a = f[i];
-        for (int q = i + 1; q < n; q++) a -= T[(size_t)i * n + q] * f[q];
-        f[i] = a / T[(size_t)i * n + i];
-    }
-    return true;
-}
-}  // namespace
-
-// host part of a deflated restart (also exported for the CPU tier: das_debug_gmres_dr_restart).  In: Hbar ((m+1) x m row-major), the
-// residual vector rvec = c - Hbar y in the basis V_{m+1}, the wanted k.  Out: kk (k or k +- 1: a complex pair is never split), P1
-// ((m+1) x (kk+1) row-major, orthonormal columns: the new basis is V P1), Hnew ((kk+1) x kk row-major), cnew (kk+1).
-static int gmres_dr_restart_host(int m, int k, const std::vector<double>& Hb, const std::vector<double>& rvec, int& kk, std::vector<double>& P1,
-                                 std::vector<double>& Hnew, std::vector<double>& cnew) {
-    DAS_CHECK(g_dense_eig, DAS_ERR_STATE, "amd.gmresDeflation needs a dense eigen-solver callback (das_set_dense_eig_callback; the Python mirror installs numpy's)");
-    std::vector<double> Hm((size_t)m * m), f;
-    for (int i = 0; i < m; i++) for (int j = 0; j < m; j++) Hm[(size_t)i * m + j] = Hb[(size_t)i * m + j];
-    if (!dr_solve_transposed_last(m, Hm, f)) return -1;
-    const double h2 = Hb[(size_t)m * m + (m - 1)] * Hb[(size_t)m * m + (m - 1)];
-    std::vector<double> Gm = Hm;
-    for (int i = 0; i < m; i++) Gm[(size_t)i * m + (m - 1)] += h2 * f[i];
-    std::vector<double> wr(m), wi(m), vr((size_t)m * m), vi((size_t)m * m);
-    if (g_dense_eig(m, Gm.data(), wr.data(), wi.data(), vr.data(), vi.data()) != 0) return -1;
-    std::vector<int> idx(m);
-    for (int i = 0; i < m; i++) idx[i] = i;
-    std::sort(idx.begin(), idx.end(), [&](int a, int b) { const double ma = std::hypot(wr[a], wi[a]), mb = std::hypot(wr[b], wi[b]); return ma < mb || (ma == mb && a < b); });
-    // real basis of the invariant subspace of the k smallest harmonic Ritz values; a conjugate pair contributes (Re v, Im v) once
-    std::vector<std::vector<double>> cols;
-    std::vector<char> used(m, 0);
-    for (int q = 0; q < m && (int)cols.size() < k; q++) {
-        const int e = idx[q];
-        if (used[e]) continue;
-        used[e] = 1;
-        std::vector<double> re(m), im(m);
-        double imax = 0.0;
-        for (int i = 0; i < m; i++) { re[i] = vr[(size_t)e * m + i]; im[i] = vi[(size_t)e * m + i]; imax = std::max(imax, std::fabs(im[i])); }
-        cols.push_back(re);
-        if (std::fabs(wi[e]) > 0.0 && imax > 0.0) {
-            cols.push_back(im);
-            for (int q2 = q + 1; q2 < m; q2++) {  // its conjugate is the same two vectors
-                const int e2 = idx[q2];
-                if (!used[e2] && wr[e2] == wr[e] && wi[e2] == -wi[e]) { used[e2] = 1; break; }
-            }
-        }
-    }
-    kk = (int)cols.size();
-    if (kk > m - 1) { cols.resize(m - 1); kk = m - 1; }
-    // orthonormalise (modified Gram-Schmidt, twice) -> Pk (m x kk); drop numerically dependent columns
-    std::vector<std::vector<double>> Q;
-    for (auto& v : cols) {
-        for (int pass = 0; pass < 2; pass++)
-            for (auto& q : Q) { double d = 0.0; for (int i = 0; i < m; i++) d += q[i] * v[i]; for (int i = 0; i < m; i++) v[i] -= d * q[i]; }
-        double nv = 0.0; for (int i = 0; i < m; i++) nv += v[i] * v[i];
-        nv = std::sqrt(nv);
-        if (!(nv > 1e-10)) continue;
-        for (int i = 0; i < m; i++) v[i] /= nv;
-        Q.push_back(v);
-    }
-    kk = (int)Q.size();
-    if (kk == 0) return -1;
-    // P1 = [ [Pk; 0], rvec orthogonalised against it and normalised ]
-    P1.assign((size_t)(m + 1) * (kk + 1), 0.0);
-    for (int c = 0; c < kk; c++) for (int i = 0; i < m; i++) P1[(size_t)i * (kk + 1) + c] = Q[c][i];
-    std::vector<double> rv = rvec;
-    for (int pass = 0; pass < 2; pass++)
-        for (int c = 0; c < kk; c++) { double d = 0.0; for (int i = 0; i < m; i++) d += Q[c][i] * rv[i]; for (int i = 0; i < m; i++) rv[i] -= d * Q[c][i]; }
-    double nr = 0.0; for (int i = 0; i <= m; i++) nr += rv[i] * rv[i];
-    nr = std::sqrt(nr);
-    if (!(nr > 0.0)) return -1;
-    for (int i = 0; i <= m; i++) P1[(size_t)i * (kk + 1) + kk] = rv[i] / nr;
-    // Hnew = P1^T Hbar Pk, cnew = P1^T rvec
-    std::vector<double> HP((size_t)(m + 1) * kk, 0.0);
-    for (int i = 0; i <= m; i++) for (int c = 0; c < kk; c++) { double a = 0.0; for (int q = 0; q < m; q++) a += Hb[(size_t)i * m + q] * Q[c][q]; HP[(size_t)i * kk + c] = a; }
-    Hnew.assign((size_t)(kk + 1) * kk, 0.0);
-    for (int r = 0; r <= kk; r++) for (int c = 0; c < kk; c++) { double a = 0.0; for (int i = 0; i <= m; i++) a += P1[(size_t)i * (kk + 1) + r] * HP[(size_t)i * kk + c]; Hnew[(size_t)r * kk + c] = a; }
-    cnew.assign(kk + 1, 0.0);
-    for (int r = 0; r <= kk; r++) { double a = 0.0; for (int i = 0; i <= m; i++) a += P1[(size_t)i * (kk + 1) + r] * rvec[i]; cnew[r] = a; }
-    return 0;
-}
-
-// The iteration itself, written once over a small set of vector operations (Ops): the device solver below and the host twin of the CPU
-// tier (das_debug_gmres_dr_host) run THIS loop - what the CPU tests check is what the GPU executes, up to the kernels behind Ops, all of
-// which the undeflated solver already uses.  Ops: n; start(beta) [v_0 = r / beta]; arnoldi(j, h, ww, hn) [w = A M^-1 v_j orthogonalised
-// against v_0..v_j by two classical Gram-Schmidt passes: h[0..j] the summed coefficients, ww = |A M^-1 v_j|^2, hn = |w| afterwards,
-// v_{j+1} = w / hn if hn > 0]; update(j, y) [x += M^-1 (V_j y)]; true_residual() [r = b - A x, returns |r|]; compress(m, kk, P1)
-// [V[:, 0..kk] = V[:, 0..m] P1].
-struct DrResult { long long its = 0; double res0 = 0, res = 0; int nBreakdown = 0, nRestarts = 0, nDeflated = 0; };
-template <class Ops>
-static DrResult gmres_dr_loop(Ops& ops, int m, int kdef, double beta0, double target, long long maxIts, std::vector<double>& hist) {
-    DrResult out;
-    out.res0 = beta0;
-    kdef = std::max(1, std::min(kdef, m - 2));
-    std::vector<double> Hb((size_t)(m + 1) * m, 0.0), c(m + 1, 0.0), y, rvec(m + 1), hcol(m + 2), h(m + 2), P1, Hnew, cnew;
-    DrLsq L;
-    int j0 = 0;  // vectors 0..j0 of the basis and the leading (j0+1) x j0 block of Hbar are in place
-    bool first = true;
-    double beta = beta0;
-    while (beta > target && out.its < maxIts) {
-        if (first) {
-            ops.start(beta);
-            std::fill(Hb.begin(), Hb.end(), 0.0);
-            std::fill(c.begin(), c.end(), 0.0);
-            c[0] = beta;
-            j0 = 0;
-            first = false;
-        }
-        L.reset(m, c);
-        for (int col = 0; col < j0; col++) {  // the dense block carried over the restart
-            for (int i = 0; i <= j0; i++) hcol[i] = Hb[(size_t)i * m + col];
-            L.add_column(col, j0 + 1, hcol.data());
-        }
-        int j = j0;
-        double res = beta;
-        for (; j < m && out.its < maxIts;) {
-            double ww = 0.0, hn = 0.0;
-            ops.arnoldi(j, h.data(), ww, hn);
-            if (!(hn > GMRES_BREAKDOWN_TOL * std::sqrt(std::max(ww, 0.0)))) { hn = 0.0; out.nBreakdown++; }
-            for (int i = 0; i <= j; i++) { hcol[i] = h[i]; Hb[(size_t)i * m + j] = h[i]; }
-            hcol[j + 1] = hn; Hb[(size_t)(j + 1) * m + j] = hn;
-            res = L.add_column(j, j + 2, hcol.data());
-            out.its++;
-            hist.push_back(res);
-            j++;
-            if (res <= target || hn == 0.0) break;
-        }
-        L.solve(j, y);
-        ops.update(j, y.data());
-        beta = ops.true_residual();  // one operator product per cycle: the recurrence is checked against it
-        hist.back() = beta;
-        if (beta <= target || out.its >= maxIts) break;
-        const bool recurrenceOk = std::fabs(res - beta) <= 1e-6 * beta0 + 1e-3 * beta;
-        if (j < m || !recurrenceOk) { first = true; out.nRestarts++; continue; }  // breakdown / early exit / drifted recurrence: plain restart
-        // ---- deflated restart: rvec = c - Hbar y, harmonic Ritz vectors, compression of the basis
-        for (int i = 0; i <= m; i++) { double a = c[i]; for (int q = 0; q < m; q++) a -= Hb[(size_t)i * m + q] * y[q]; rvec[i] = a; }
-        int kk = 0;
-        if (gmres_dr_restart_host(m, kdef, Hb, rvec, kk, P1, Hnew, cnew) != 0) { first = true; out.nRestarts++; continue; }
-        ops.compress(m, kk, P1.data());
-        std::fill(Hb.begin(), Hb.end(), 0.0);
-        for (int r = 0; r <= kk; r++) for (int q = 0; q < kk; q++) Hb[(size_t)r * m + q] = Hnew[(size_t)r * kk + q];
-        std::fill(c.begin(), c.end(), 0.0);
-        for (int r = 0; r <= kk; r++) c[r] = cnew[r];
-        j0 = kk;
-        out.nDeflated++;
-    }
-    out.res = beta;
-    return out;
-}
-
 namespace {
 struct DrDeviceOps {
     das_solver* s; das_ksp* k; GmresRun* G; int kdefMax;
@@ -3246,78 +3000,15 @@ struct DrDeviceOps {
         DAS_HIP(hipMemcpyAsync(k->V.p, scratch.p, (size_t)(kk + 1) * n * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
 };
-// host twin of the vector operations (CPU tier): operator and preconditioner through callbacks, plain loops
-typedef void (*das_host_apply_fn)(const double* x, double* y, void* user);
-struct DrHostOps {
-    long long n; das_host_apply_fn A, M; void* user;
-    const double* b; double* x;
-    std::vector<double> V, w, z, r;
-    int m;
-    void start(double beta) { for (long long i = 0; i < n; i++) V[i] = r[i] / beta; }
-    void arnoldi(int j, double* h, double& ww, double& hn) {
-        M(V.data() + (size_t)j * n, z.data(), user);
-        A(z.data(), w.data(), user);
-        ww = 0.0; for (long long i = 0; i < n; i++) ww += w[i] * w[i];
-        std::vector<double> h1(j + 1), h2(j + 1);
-        for (int pass = 0; pass < 2; pass++) {
-            std::vector<double>& hp = pass ? h2 : h1;
-            for (int q = 0; q <= j; q++) { double a = 0.0; const double* v = V.data() + (size_t)q * n; for (long long i = 0; i < n; i++) a += v[i] * w[i]; hp[q] = a; }
-            for (int q = 0; q <= j; q++) { const double* v = V.data() + (size_t)q * n; for (long long i = 0; i < n; i++) w[i] -= hp[q] * v[i]; }
-        }
-        for (int q = 0; q <= j; q++) h[q] = h1[q] + h2[q];
-        double a = 0.0; for (long long i = 0; i < n; i++) a += w[i] * w[i];
-        hn = std::sqrt(a);
-        if (hn > GMRES_BREAKDOWN_TOL * std::sqrt(ww)) for (long long i = 0; i < n; i++) V[(size_t)(j + 1) * n + i] = w[i] / hn;
-    }
-    void update(int j, const double* y) {
-        std::fill(w.begin(), w.end(), 0.0);
-        for (int q = 0; q < j; q++) { const double* v = V.data() + (size_t)q * n; for (long long i = 0; i < n; i++) w[i] += y[q] * v[i]; }
-        M(w.data(), z.data(), user);
-        for (long long i = 0; i < n; i++) x[i] += z[i];
-    }
-    double true_residual() {
-        A(x, r.data(), user);
-        double a = 0.0;
-        for (long long i = 0; i < n; i++) { r[i] = b[i] - r[i]; a += r[i] * r[i]; }
-        return std::sqrt(a);
-    }
-    void compress(int mm, int kk, const double* P1) {
-        std::vector<double> Vn((size_t)(kk + 1) * n, 0.0);
-        for (int c = 0; c <= kk; c++)
-            for (int q = 0; q <= mm; q++) { const double p = P1[(size_t)q * (kk + 1) + c]; if (p == 0.0) continue; const double* v = V.data() + (size_t)q * n; double* o = Vn.data() + (size_t)c * n; for (long long i = 0; i < n; i++) o[i] += p * v[i]; }
-        std::copy(Vn.begin(), Vn.end(), V.begin());
-    }
-};
 }  // namespace
 
 static int run_gmres_dr(das_solver* s, das_ksp* k, const double* d_rhs, double* d_x, int kdef) {
-    need_init(s);
-    DAS_CHECK(s->op || s->fwd.on, DAS_ERR_STATE, "initializedRdWTMatrixFree() must be called before solveLinearEqn()");
-    DAS_CHECK(!s->halo.active && !s->halo_cb, DAS_ERR_ARG, "amd.gmresDeflation is single-rank (the restart's small dense algebra is not replicated across ranks yet)");
-    gmres_ws(s, k);
-    k->vf32 = false; k->split = false;  // the deflated solver keeps its (short) basis in fp64
-    if (k->useBilu) bilu_clear_abort(k->bilu, s->stream);
-    if (!k->run) k->run.reset(new GmresRun);
-    GmresRun& G = *k->run;
-    G = GmresRun();
-    const int m = k->restart;
-    DAS_CHECK(m >= 4, DAS_ERR_ARG, "amd.gmresDeflation needs gmresRestart >= 4");
-    G.m = m; G.d_rhs = d_rhs; G.d_x = d_x;
-    G.maxIts = s->opt.geti("adjEqnOption.gmresMaxIters");
-    G.rtol = s->opt.getd("adjEqnOption.gmresRelTol"); G.atol = s->opt.getd("adjEqnOption.gmresAbsTol");
-    G.hh.assign(2 * (m + 2), 0.0); G.h2.assign(2 * (m + 2), 0.0);
-    k->nrefine = 0; k->hist.clear();
-    G.t0 = wall_seconds();
-    gmres_true_residual(s, k, G, s->opt.geti("adjEqnOption.useNonZeroInitGuess") != 0);
-    k->res0 = G.beta;
-    k->hist.push_back(G.beta);
-    G.target = std::max(G.rtol * G.beta, G.atol);
+    GmresRun& G = gmres_begin(s, k, d_rhs, d_x, /* fixed */ false, /* deflated */ true);
+    const int m = G.m;
     DAS_CHECK(gmres_map_basis(s, k, m + 2), DAS_ERR_INTERNAL, "GMRES-DR: no device memory for the basis (" + k->V.workerError + ")");
     DrDeviceOps ops{s, k, &G, std::max(1, std::min(kdef, m - 2))};
-    const DrResult R = gmres_dr_loop(ops, m, kdef, G.beta, G.target, G.maxIts, k->hist);
-    hipStream_t st = s->stream;
-    DAS_HIP(hipStreamSynchronize(st));
-    if (k->useBilu) DAS_CHECK(!bilu_aborted(k->bilu, st), DAS_ERR_INTERNAL, "preconditioner sweep timed out (bounded spin)");
+    const DrResult R = gmres_dr_loop(ops, g_dense_eig, m, kdef, G.beta, G.target, G.maxIts, k->hist);
+    gmres_finish_check(s, k);
     G.its = R.its;
     k->iters = (int)R.its;
     k->nBreakdown = R.nBreakdown;
@@ -3325,8 +3016,7 @@ static int run_gmres_dr(das_solver* s, das_ksp* k, const double* d_rhs, double* 
     k->reason = R.res <= G.target ? 0 : 1;
     k->seconds = wall_seconds() - G.t0;
     if (s->opt.geti("debug")) fprintf(stderr, "[dafoam_amd] GMRES-DR(%d, %d): %lld iterations, %d deflated restarts, %d plain restarts, |r| %.3e -> %.3e\n", m, kdef, R.its, R.nDeflated, R.nRestarts, R.res0, R.res);
-    const double absRatio = k->res / G.atol, relRatio = k->res0 > 0 ? k->res / k->res0 / G.rtol : 0.0, diff = s->opt.getd("adjEqnOption.gmresTolDiff");
-    return (relRatio > diff && absRatio > diff) ? 1 : 0;
+    return gmres_failed(k->res, k->res0, G.rtol, G.atol, s->opt.getd("adjEqnOption.gmresTolDiff"));
 }
 
 static int run_gmres(das_solver* s, das_ksp* k, const double* d_rhs, double* d_x, int fixed_iters) {
@@ -3378,30 +3068,7 @@ static void block_cholqr2(das_solver* s, BlockWork& bw, double* W, int sv, std::
     if (bw.Tdev.n < 64) bw.Tdev.alloc(64);
     for (int pass = 0; pass < 2; pass++) {
         block_tn(s, bw, W, sv, W, sv, G.data());
-        // Cholesky G = L L^T (a non-positive pivot = a column that lost all its new content: replaced by a tiny one)
-        std::fill(L.begin(), L.end(), 0.0);
-        double gmax = 0.0;
-        for (int i = 0; i < sv; i++) gmax = std::max(gmax, G[(size_t)i * sv + i]);
-        for (int j = 0; j < sv; j++) {
-            double d = G[(size_t)j * sv + j];
-            for (int q = 0; q < j; q++) d -= L[(size_t)j * sv + q] * L[(size_t)j * sv + q];
-            if (!(d > 1e-28 * gmax)) d = std::max(1e-28 * gmax, 1e-300);
-            L[(size_t)j * sv + j] = std::sqrt(d);
-            for (int i = j + 1; i < sv; i++) {
-                double a = G[(size_t)i * sv + j];
-                for (int q = 0; q < j; q++) a -= L[(size_t)i * sv + q] * L[(size_t)j * sv + q];
-                L[(size_t)i * sv + j] = a / L[(size_t)j * sv + j];
-            }
-        }
-        // T = L^-T (upper triangular): Q = W T
-        std::fill(T.begin(), T.end(), 0.0);
-        for (int c = 0; c < sv; c++) {  // solve L^T t_c = e_c  (upper triangular system, backward)
-            for (int i = sv - 1; i >= 0; i--) {
-                double a = (i == c) ? 1.0 : 0.0;
-                for (int q = i + 1; q < sv; q++) a -= L[(size_t)q * sv + i] * T[(size_t)q * sv + c];
-                T[(size_t)i * sv + c] = a / L[(size_t)i * sv + i];
-            }
-        }
+        chol_upper_inverse(sv, G.data(), L.data(), T.data());
         DAS_HIP(hipMemcpyAsync(bw.Tdev.p, T.data(), (size_t)sv * sv * sizeof(double), hipMemcpyHostToDevice, s->stream));
         launch_block_right_mult(s->stream, s->n, sv, W, s->n, bw.Tdev.p);
         std::vector<double>& Sp = pass == 0 ? S1 : S2;
@@ -3444,10 +3111,8 @@ static int run_block_gmres(das_solver* s, das_ksp* k, int sv, const double* d_B,
     const double t0 = wall_seconds();
     const int B = 256;
     const int ms = (int)m * sv;
-    std::vector<double> H((size_t)(ms + sv) * ms, 0.0);   // row-major, (m+1)s x ms
-    std::vector<double> G((size_t)(ms + sv) * sv, 0.0);   // rotated right-hand sides
-    std::vector<double> rc((size_t)ms * sv), rs((size_t)ms * sv);  // rotation (col q, step u)
-    std::vector<double> S, Hc, Hc2, Y((size_t)ms * sv), res0(sv), res(sv), target(sv), hcol;
+    BlockLsq lsq;
+    std::vector<double> S, Hc, Hc2, Y((size_t)ms * sv), res0(sv), res(sv), target(sv);
     auto col_norms = [&](const double* Rblk, std::vector<double>& out) {
         std::vector<double> Gm((size_t)sv * sv);
         block_tn(s, bw, Rblk, sv, Rblk, sv, Gm.data());
@@ -3465,9 +3130,7 @@ static int run_block_gmres(das_solver* s, das_ksp* k, int sv, const double* d_B,
         // ---- new cycle: R = V_0 S0
         DAS_HIP(hipMemcpyAsync(bw.V.p, bw.R.p, (size_t)sv * n * sizeof(double), hipMemcpyDeviceToDevice, st));
         block_cholqr2(s, bw, bw.V.p, sv, S);
-        std::fill(H.begin(), H.end(), 0.0);
-        std::fill(G.begin(), G.end(), 0.0);
-        for (int i = 0; i < sv; i++) for (int r = 0; r < sv; r++) G[(size_t)i * sv + r] = S[(size_t)i * sv + r];
+        lsq.reset((int)m, sv, S.data());
         int j = 0;
         for (; j < m && its < maxIts; j++) {
             double* Vj = bw.V.p + (size_t)j * sv * n;
@@ -3482,51 +3145,15 @@ static int run_block_gmres(das_solver* s, das_ksp* k, int sv, const double* d_B,
             double* Vn = bw.V.p + (size_t)(j + 1) * sv * n;
             DAS_HIP(hipMemcpyAsync(Vn, bw.W.p, (size_t)sv * n * sizeof(double), hipMemcpyDeviceToDevice, st));
             block_cholqr2(s, bw, Vn, sv, S);
-            // ---- block Hessenberg column j: rows 0..K-1 from the projections, rows K..K+s-1 = S (upper triangular)
-            for (int c = 0; c < sv; c++) {
-                const int q = j * sv + c;
-                hcol.assign((size_t)K + sv, 0.0);
-                for (int i = 0; i < K; i++) hcol[i] = Hc[(size_t)i * sv + c] + Hc2[(size_t)i * sv + c];
-                for (int i = 0; i <= c; i++) hcol[K + i] = S[(size_t)i * sv + c];
-                for (int qq = 0; qq < q; qq++)          // earlier rotations, in the order they were generated
-                    for (int u = sv - 1; u >= 0; u--) {
-                        const int a = qq + u, b2 = qq + u + 1;
-                        if (b2 >= K + sv) continue;
-                        const double cc = rc[(size_t)qq * sv + u], ss = rs[(size_t)qq * sv + u];
-                        const double x = hcol[a], y = hcol[b2];
-                        hcol[a] = cc * x + ss * y; hcol[b2] = -ss * x + cc * y;
-                    }
-                for (int u = sv - 1; u >= 0; u--) {     // eliminate the s sub-diagonal entries of this column
-                    const int a = q + u, b2 = q + u + 1;
-                    const double x = hcol[a], y = hcol[b2];
-                    const double d = std::hypot(x, y);
-                    const double cc = d > 0 ? x / d : 1.0, ss = d > 0 ? y / d : 0.0;
-                    rc[(size_t)q * sv + u] = cc; rs[(size_t)q * sv + u] = ss;
-                    hcol[a] = d; hcol[b2] = 0.0;
-                    for (int r = 0; r < sv; r++) {
-                        const double gx = G[(size_t)a * sv + r], gy = G[(size_t)b2 * sv + r];
-                        G[(size_t)a * sv + r] = cc * gx + ss * gy; G[(size_t)b2 * sv + r] = -ss * gx + cc * gy;
-                    }
-                }
-                for (int i = 0; i <= q; i++) H[(size_t)i * ms + q] = hcol[i];
-            }
+            lsq.add_column(j, Hc.data(), Hc2.data(), S.data());
             its++;
-            for (int r = 0; r < sv; r++) {
-                double a = 0.0;
-                for (int i = K; i < K + sv; i++) a += G[(size_t)i * sv + r] * G[(size_t)i * sv + r];
-                res[r] = std::sqrt(a);
-            }
+            lsq.residuals(j, res.data());
             k->hist.push_back(*std::max_element(res.begin(), res.end()));
             if (all_done()) { j++; break; }
         }
         // ---- x += M^-1 (V Y),  R Y = G  (upper triangular, K x K)
         const int K = j * sv;
-        for (int r = 0; r < sv; r++)
-            for (int i = K - 1; i >= 0; i--) {
-                double a = G[(size_t)i * sv + r];
-                for (int q = i + 1; q < K; q++) a -= H[(size_t)i * ms + q] * Y[(size_t)q * sv + r];
-                Y[(size_t)i * sv + r] = a / H[(size_t)i * ms + i];
-            }
+        lsq.solve(j, Y.data());
         if (bw.Cdev.n < (size_t)K * sv) bw.Cdev.alloc((size_t)K * sv + 1024);
         DAS_HIP(hipMemcpyAsync(bw.Cdev.p, Y.data(), (size_t)K * sv * sizeof(double), hipMemcpyHostToDevice, st));
         launch_block_lincomb(st, n, K, sv, bw.V.p, n, bw.Cdev.p, bw.W.p, n);
@@ -3538,8 +3165,7 @@ static int run_block_gmres(das_solver* s, das_ksp* k, int sv, const double* d_B,
         col_norms(bw.R.p, res);
         k->hist.back() = *std::max_element(res.begin(), res.end());
     }
-    DAS_HIP(hipStreamSynchronize(st));
-    if (k->useBilu) DAS_CHECK(!bilu_aborted(k->bilu, st), DAS_ERR_INTERNAL, "preconditioner sweep timed out (bounded spin)");
+    gmres_finish_check(s, k);
     k->iters = (int)its;
     k->seconds = wall_seconds() - t0;
     k->block_res0 = res0; k->block_res = res;
@@ -3547,10 +3173,7 @@ static int run_block_gmres(das_solver* s, das_ksp* k, int sv, const double* d_B,
     k->res = *std::max_element(res.begin(), res.end());
     const double diff = s->opt.getd("adjEqnOption.gmresTolDiff");
     int failed = 0;
-    for (int r = 0; r < sv; r++) {
-        const double relRatio = res0[r] > 0 ? res[r] / res0[r] / rtol : 0.0;
-        if (relRatio > diff && res[r] / atol > diff) failed = 1;  // reference failure rule per system (DALinearEqn.C:422-434)
-    }
+    for (int r = 0; r < sv; r++) if (gmres_failed(res[r], res0[r], rtol, atol, diff)) failed = 1;  // per system
     return failed;
 }
 
@@ -5675,9 +5298,30 @@ int das_debug_gmres_dr_restart(int m, int kwant, const double* Hbar, const doubl
     DAS_CHECK(m >= 2 && kwant >= 1 && Hbar && rvec && P1 && Hnew && cnew, DAS_ERR_ARG, "bad argument");
     std::vector<double> Hb(Hbar, Hbar + (size_t)(m + 1) * m), rv(rvec, rvec + m + 1), p, h, c;
     int kk = 0;
-    if (gmres_dr_restart_host(m, kwant, Hb, rv, kk, p, h, c) != 0) return -1;
+    if (gmres_dr_restart_host(g_dense_eig, m, kwant, Hb, rv, kk, p, h, c) != 0) return -1;
     std::copy(p.begin(), p.end(), P1); std::copy(h.begin(), h.end(), Hnew); std::copy(c.begin(), c.end(), cnew);
     return kk;
+    DAS_CATCH
+}
+// Cholesky step of CholQR on the host (CPU tier): G sv x sv row-major -> L (lower triangular), T = L^-T
+int das_debug_block_chol(int sv, const double* G, double* L, double* T) {
+    DAS_TRY
+    DAS_CHECK(sv >= 1 && G && L && T, DAS_ERR_ARG, "bad argument");
+    chol_upper_inverse(sv, G, L, T);
+    return DAS_OK;
+    DAS_CATCH
+}
+// the block-Hessenberg least squares fed as run_block_gmres feeds it (CPU tier; layout: include/dafoam_amd.h)
+int das_debug_block_lsq(int sv, int m, int ncols, const double* S0, const double* Hc, const double* Hc2, const double* S, double* Y, double* res) {
+    DAS_TRY
+    DAS_CHECK(sv >= 1 && m >= 1 && ncols >= 1 && ncols <= m && S0 && Hc && Hc2 && S && Y && res, DAS_ERR_ARG, "bad argument");
+    BlockLsq lsq;
+    lsq.reset(m, sv, S0);
+    const size_t blk = (size_t)m * sv * sv;
+    for (int j = 0; j < ncols; j++) lsq.add_column(j, Hc + j * blk, Hc2 + j * blk, S + (size_t)j * sv * sv);
+    lsq.residuals(ncols - 1, res);
+    lsq.solve(ncols, Y);
+    return DAS_OK;
     DAS_CATCH
 }
 // the deflated-restart iteration (gmres_dr_loop, the loop the device solver runs) on host vectors with callback operator / preconditioner:
@@ -5691,12 +5335,11 @@ int das_debug_gmres_dr_host(long long n, void* A, void* M, void* user, const dou
     const double beta0 = ops.true_residual();
     std::vector<double> h{beta0};
     const double target = std::max(rtol * beta0, atol);
-    const DrResult R = gmres_dr_loop(ops, m, kdef, beta0, target, maxIts, h);
+    const DrResult R = gmres_dr_loop(ops, g_dense_eig, m, kdef, beta0, target, maxIts, h);
     if (hist) for (int i = 0; i < histCap && i < (int)h.size(); i++) hist[i] = h[i];
     if (info4) { info4[0] = (double)R.its; info4[1] = R.nDeflated; info4[2] = R.nRestarts; info4[3] = R.nBreakdown; }
     if (res2) { res2[0] = R.res0; res2[1] = R.res; }
-    const double absRatio = R.res / atol, relRatio = beta0 > 0 ? R.res / beta0 / rtol : 0.0;
-    return (relRatio > 1e2 && absRatio > 1e2) ? 1 : 0;
+    return gmres_failed(R.res, beta0, rtol, atol, 1e2);
     DAS_CATCH
 }
 int das_ksp_get_n_refine(das_ksp_t* k) { return k ? k->nrefine : -1; }

@@ -413,6 +413,14 @@ int das_ksp_get_n_refine(das_ksp_t* ksp);
  * algebra of one restart to the CPU tier (returns the number of kept vectors, which never splits a complex pair). */
 int das_set_dense_eig_callback(void* fn);
 int das_debug_gmres_dr_restart(int m, int kwant, const double* Hbar, const double* rvec, double* P1, double* Hnew, double* cnew);
+/* host algebra of the block solve for the CPU tier, all matrices row-major.  das_debug_block_chol: the Cholesky step of CholQR, G (sv x sv
+ * Gram matrix) -> L (lower triangular, G = L L^T; a non-positive pivot is replaced by a tiny one) and T = L^-T (upper triangular).
+ * das_debug_block_lsq: the block-Hessenberg least squares min |[S0; 0] - Hbar Y| of a cycle of at most m block columns, fed ncols <= m
+ * columns as the solver feeds them.  S0: sv x sv.  Hc, Hc2 (the two Gram-Schmidt passes, summed inside): ncols slabs of m sv x sv, slab j
+ * holds the (j+1) sv rows of block column j in its first rows.  S: ncols slabs of sv x sv (upper triangular sub-diagonal blocks).  Out:
+ * Y (ncols sv x sv) and res (sv: the recurrence residual norm of every right-hand side after the last column). */
+int das_debug_block_chol(int sv, const double* G, double* L, double* T);
+int das_debug_block_lsq(int sv, int m, int ncols, const double* S0, const double* Hc, const double* Hc2, const double* S, double* Y, double* res);
 /* the deflated-restart iteration itself on HOST vectors (operator A and preconditioner M as callbacks fn(x, y, user)): the very loop the
  * device solver runs, for the CPU tier; info4 = {iterations, deflated restarts, plain restarts, breakdowns}, res2 = {|r0|, |r|} */
 int das_debug_gmres_dr_host(long long n, void* A, void* M, void* user, const double* b, double* x, int m, int kdef, double rtol, double atol,

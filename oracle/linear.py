@@ -355,7 +355,7 @@ def gmres(matvec, rhs, pc_solve=None, x0=None, restart=1000, max_iters=1000, rel
     return x, dict(iters=its, res0=res0, res=res, hist=np.array(hist), fail=fail)
 
 
-BREAKDOWN_TOL = 1e-13  # csrc/das_device.hip GMRES_BREAKDOWN_TOL
+BREAKDOWN_TOL = 1e-13  # csrc/das_gmres_host.hpp GMRES_BREAKDOWN_TOL
 
 
 def gmres_dcgs2(matvec, rhs, pc_solve=None, restart=1000, max_iters=1000, rel_tol=1e-6, abs_tol=1e-14, tol_diff=1e2, noise=0.0, rng=None):

@@ -1474,7 +1474,7 @@ def test_naca_grid_sequencing_helpers():
 
 
 def test_gmres_dr_loop_host_twin():
-    """amd.gmresDeflation (round 4, opt-in): GMRES with deflated restarting.  The iteration (gmres_dr_loop in csrc/das_device.hip) is
+    """amd.gmresDeflation (round 4, opt-in): GMRES with deflated restarting.  The iteration (gmres_dr_loop in csrc/das_gmres_host.hpp) is
     written once over a handful of vector operations; das_debug_gmres_dr_host runs THAT loop on host vectors - so the least-squares
     bookkeeping with the dense carried-over block, the harmonic-Ritz restart (through the dense-eigen callback the mirror installs)
     and the restart logic are tested here, and the device solver adds only kernels the undeflated solver already uses.  Checked on
