@@ -352,6 +352,16 @@ _SIGS = {
     # test-only entries (tests/test_gpu_bilu_kernels.py): the node-block ILU(0) on a caller-made structure, never called by the bindings
     "das_debug_bilu_factor": (C.c_int, [C.POINTER(das_bilu_debug_t), c_ll_p, c_ll_p, c_int_p, c_int_p, _VP, _VP, c_double_p, c_int_p]),
     "das_debug_bilu_apply": (C.c_int, [C.POINTER(das_bilu_debug_t), C.c_int, C.c_longlong, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p, c_int_p, c_int_p]),
+    # test-only entries (tests/test_gpu_graph_kernels.py, tests/test_gpu_opmat_kernels.py): graph set-up, filter, packed operator and
+    # ghost-row product on caller-made structures, never called by the bindings
+    "das_debug_graph_scan": (C.c_int, [C.c_longlong, c_int_p, c_ll_p, c_ll_p]),
+    "das_debug_graph_transpose": (C.c_int, [C.c_longlong, c_ll_p, c_int_p, c_ll_p, c_int_p]),
+    "das_debug_graph_nets": (C.c_int, [C.c_longlong, c_ll_p, c_int_p, C.c_longlong, c_ll_p, c_ll_p, c_int_p, c_int_p, C.POINTER(C.c_ubyte), c_ll_p]),
+    "das_debug_graph_rows_gather": (C.c_int, [C.c_longlong, c_ll_p, C.c_longlong, c_ll_p, c_int_p, c_ll_p, c_int_p, C.c_longlong]),
+    "das_debug_compact": (C.c_int, [C.c_longlong, c_ll_p, c_int_p, c_double_p, C.c_double, C.c_int, C.POINTER(C.c_ubyte), c_ll_p, c_int_p, c_double_p, c_ll_p]),
+    "das_debug_vecpack": (C.c_int, [C.c_longlong, c_ll_p, c_int_p, c_double_p, C.c_longlong, C.c_longlong, c_int_p, c_ll_p, C.POINTER(C.c_ubyte), C.c_longlong, c_ll_p,
+                                    c_double_p, c_double_p, C.c_longlong]),
+    "das_debug_spmv_rows": (C.c_int, [C.c_longlong, c_int_p, C.c_longlong, c_ll_p, c_int_p, c_double_p, c_double_p, c_double_p, C.c_longlong]),
     "das_timer_count": (C.c_longlong, [_VP, C.c_char_p]),
     "das_timer_reset": (None, [_VP]),
     "das_timer_enable": (None, [_VP, C.c_int]),

@@ -25,6 +25,7 @@
 #include "das_block.hpp"
 #include "das_krylov_debug.hpp"
 #include "das_bilu_debug.hpp"
+#include "das_graph_debug.hpp"
 #include "das_color.hpp"
 #include "das_opmat.hpp"
 #include "das_graph.hpp"
@@ -372,98 +373,10 @@ __global__ __launch_bounds__(256) void k_scatter_fd(long long cnt, const double*
         vals[k] = (R[i] - R0[i]) * rdelta;
     }
 }
-// jacLowerBound filter (reference DAPartDeriv.C:192): keep |v| > bound or diagonal
-// (multi-GPU: columns = residuals not owned by this rank are dropped; `owned` may be null)
-__device__ __forceinline__ bool keep_entry(long long i, int c, double v, double bound, bool useBound, const unsigned char* owned) {
-    if (owned && !owned[c]) return false;
-    return !useBound || fabs(v) > bound || c == i;
-}
-__global__ void k_count_keep(long long n, const long long* __restrict__ rp, const int* __restrict__ ci, const double* __restrict__ v, double bound,
-                             bool useBound, const unsigned char* __restrict__ owned, int* cnt) {
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int c = 0;
-    for (long long k = rp[i]; k < rp[i + 1]; k++) c += keep_entry(i, ci[k], v[k], bound, useBound, owned) ? 1 : 0;
-    cnt[i] = c;
-}
-__global__ void k_compact(long long n, const long long* __restrict__ rp, const int* __restrict__ ci, const double* __restrict__ v, double bound,
-                          bool useBound, const unsigned char* __restrict__ owned, const long long* __restrict__ nrp, int* nci, double* nv) {
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    long long o = nrp[i];
-    for (long long k = rp[i]; k < rp[i + 1]; k++)
-        if (keep_entry(i, ci[k], v[k], bound, useBound, owned)) { nci[o] = ci[k]; nv[o] = v[k]; o++; }
-}
 
 // =====================================================================================================
-// linear algebra kernels
+// linear algebra kernels (the operator product y = A x and the jacLowerBounds filter: das_opmat.hpp)
 // =====================================================================================================
-// y = A x, transposed-CSR dRdW^T (rows hold ~50-280 entries): SPMV_LANES lanes cooperate on one row, 256-thread
-// workgroups.  The matrix is streamed exactly once (non-temporal loads, so that it does not evict the gathered x
-// entries from the per-XCD L2); x is gathered through L2.
-#ifndef SPMV_LANES
-#define SPMV_LANES 16
-#endif
-#ifndef SPMV_NT
-#define SPMV_NT 0
-#endif
-#ifndef SPMV_UNROLL
-#define SPMV_UNROLL 4
-#endif
-__global__ __launch_bounds__(256) void k_spmv_wave(long long n, const long long* __restrict__ rp, const int* __restrict__ ci,
-                                                   const double* __restrict__ v, const double* __restrict__ x, double* __restrict__ y) {
-    constexpr int RPB = 256 / SPMV_LANES;
-    // (measured: giving every XCD one contiguous range of rows - x gathered into one L2 instead of eight - is SLOWER, 7.98 vs
-    // 5.19 ms at 2 M cells: the matrix stream of each XCD then hammers its own few HBM channels; the round-robin deal is kept)
-    long long row = (long long)blockIdx.x * RPB + (threadIdx.x / SPMV_LANES);
-    const int lane = threadIdx.x % SPMV_LANES;
-    if (row >= n) return;
-    const long long b = rp[row], e = rp[row + 1];
-    double acc[SPMV_UNROLL];
-#pragma unroll
-    for (int u = 0; u < SPMV_UNROLL; u++) acc[u] = 0.0;
-    long long k = b + lane;
-    // main loop: SPMV_UNROLL independent (value, column, x) gathers in flight per lane
-    for (; k + (SPMV_UNROLL - 1) * SPMV_LANES < e; k += SPMV_UNROLL * SPMV_LANES) {
-        double vv[SPMV_UNROLL];
-        int cc[SPMV_UNROLL];
-#pragma unroll
-        for (int u = 0; u < SPMV_UNROLL; u++) {
-#if SPMV_NT
-            vv[u] = __builtin_nontemporal_load(v + k + u * SPMV_LANES);
-            cc[u] = __builtin_nontemporal_load(ci + k + u * SPMV_LANES);
-#else
-            vv[u] = v[k + u * SPMV_LANES];
-            cc[u] = ci[k + u * SPMV_LANES];
-#endif
-        }
-#pragma unroll
-        for (int u = 0; u < SPMV_UNROLL; u++) acc[u] += vv[u] * x[cc[u]];
-    }
-    // tail (and the whole of a short row - the phi rows hold ~31 entries): the same SPMV_UNROLL loads in flight, clamped to the
-    // last entry of the row and masked, instead of a serial loop with one load per round trip
-    if (k - lane < e) {
-        double vv[SPMV_UNROLL];
-        int cc[SPMV_UNROLL];
-#pragma unroll
-        for (int u = 0; u < SPMV_UNROLL; u++) {
-            const long long kk = k + u * SPMV_LANES;
-            const long long kc = kk < e ? kk : e - 1;
-            vv[u] = kk < e ? v[kc] : 0.0;
-            cc[u] = ci[kc];
-        }
-#pragma unroll
-        for (int u = 0; u < SPMV_UNROLL; u++) acc[u] += vv[u] * x[cc[u]];
-    }
-    double sacc = acc[0];
-#pragma unroll
-    for (int u = 1; u < SPMV_UNROLL; u++) sacc += acc[u];
-#pragma unroll
-    for (int o = SPMV_LANES / 2; o > 0; o >>= 1) sacc += __shfl_down(sacc, o, SPMV_LANES);
-    if (lane == 0) y[row] = sacc;
-}
-#define SPMV_GRID(n) dim3(nblk((n), 256 / SPMV_LANES))
-
 __global__ void k_axpby(long long n, double a, const double* __restrict__ x, double b, double* __restrict__ y) {
     long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (k < n) y[k] = a * x[k] + b * y[k];
@@ -1237,17 +1150,11 @@ static void ensure_coloring(das_solver* s, const int* preset = nullptr) {
                         const long long nKeep = (long long)keep.size();
                         std::vector<int> netOfRow((size_t)nn, -1);
                         for (long long q = 0; q < nKeep; q++) netOfRow[keep[q]] = (int)q;
-                        DevBuf<int> d_net, d_cnt((size_t)nn);
+                        DevBuf<int> d_net, d_crow, d_cpos;
                         d_net.upload(netOfRow);
-                        hipLaunchKernelGGL(k_net_count, dim3((unsigned)((nn + 15) / 16)), dim3(256), 0, st, nn, c.t_rowptr.p, c.t_col.p, d_net.p, d_cnt.p);
-                        DevBuf<long long> d_cptr((size_t)nn + 1);
-                        const long long tot = device_exclusive_scan(nn, d_cnt.p, d_cptr.p, st);
-                        DevBuf<int> d_crow((size_t)std::max<long long>(1, tot)), d_cpos((size_t)std::max<long long>(1, tot));
-                        hipLaunchKernelGGL(k_net_fill, dim3((unsigned)((nn + 15) / 16)), dim3(256), 0, st, nn, c.t_rowptr.p, c.t_col.p, d_net.p, fullRowMajor.rowptr.p,
-                                           fullRowMajor.col.p, d_cptr.p, d_crow.p, d_cpos.p);
-                        DevBuf<unsigned char> d_start((size_t)nn);
-                        hipLaunchKernelGGL(k_group_flags, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, nn, d_cptr.p, d_crow.p, d_start.p);
-                        DAS_HIP(hipGetLastError());
+                        DevBuf<long long> d_cptr;
+                        DevBuf<unsigned char> d_start;
+                        device_build_nets(nn, c.t_rowptr.p, c.t_col.p, d_net.p, fullRowMajor.rowptr.p, fullRowMajor.col.p, d_cptr, d_crow, d_cpos, d_start, st);
                         std::vector<unsigned char> isStart = d_start.to_host();
                         const std::vector<long long> gstart = color_groups_from_flags(nn, isStart);
                         lap("nets, positions, groups");
@@ -1332,17 +1239,7 @@ static void spmv(das_solver* s, const Mat& A, const double* x, double* y) {
     // sharded: ghost rows first (their contributions travel to the owner ranks while the owned rows are computed)
     if (s->halo.active) s->halo.begin(A, x, s->stream);
     s->timer.begin("spmv", s->stream, ev);
-    if (A.vp.ready) {
-        // vector rows as group rows (one column list, three value planes), the scalar rows from the CSR arrays
-        const long long r1 = A.vp.row0 + 3 * A.vp.nGroups;
-        hipLaunchKernelGGL(k_spmv_vec3, dim3((unsigned)((A.vp.nGroups + 15) / 16)), dim3(256), 0, s->stream, A.vp.nGroups, A.vp.row0, A.vp.cptr.p,
-                           A.vp.data.p, x, y);
-        if (A.vp.row0 > 0) hipLaunchKernelGGL(k_spmv_wave, SPMV_GRID(A.vp.row0), dim3(256), 0, s->stream, A.vp.row0, A.rowptr.p, A.col.p, A.val.p, x, y);
-        if (A.n > r1)
-            hipLaunchKernelGGL(k_spmv_wave, SPMV_GRID(A.n - r1), dim3(256), 0, s->stream, A.n - r1, A.rowptr.p + r1, A.col.p, A.val.p, x, y + r1);
-    } else {
-        hipLaunchKernelGGL(k_spmv_wave, SPMV_GRID(A.n), dim3(256), 0, s->stream, A.n, A.rowptr.p, A.col.p, A.val.p, x, y);
-    }
+    launch_spmv(s->stream, A.n, A.rowptr.p, A.col.p, A.val.p, A.vp, x, y);
     s->timer.end("spmv", s->stream, ev);
     if (s->halo.active) {
         hipEvent_t eh = nullptr;
@@ -1426,17 +1323,7 @@ static das_mat* assemble(das_solver* s, int isPC, int mode) {
         }
         M.val = std::move(vals);
     } else {
-        DevBuf<int> cnt(n);
-        hipLaunchKernelGGL(k_count_keep, dim3(nblk(n, B)), dim3(B), 0, st, n, c.t_rowptr.p, c.t_col.p, vals.p, bound, useBound, colMask, cnt.p);
-        DAS_HIP(hipStreamSynchronize(st));
-        std::vector<int> hc = cnt.to_host();
-        std::vector<long long> nrp(n + 1, 0);
-        for (long long i = 0; i < n; i++) nrp[i + 1] = nrp[i] + hc[i];
-        M.nnz = nrp[n];
-        M.rowptr.upload(nrp);
-        M.col.alloc(M.nnz);
-        M.val.alloc(M.nnz);
-        hipLaunchKernelGGL(k_compact, dim3(nblk(n, B)), dim3(B), 0, st, n, c.t_rowptr.p, c.t_col.p, vals.p, bound, useBound, colMask, M.rowptr.p, M.col.p, M.val.p);
+        M.nnz = filter_compact(n, c.t_rowptr.p, c.t_col.p, vals.p, bound, useBound, colMask, M.rowptr, M.col, M.val, st);
     }
     DAS_HIP(hipStreamSynchronize(st));
     // the per-colour scatter lists and the transposed structure are only needed during assembly: at 2 M cells they hold
@@ -3898,7 +3785,7 @@ int das_mat_mult(das_mat_t* m, const double* x, double* y) {
     DAS_CHECK(m && x && y, DAS_ERR_ARG, "null argument");
     DevBuf<double> dx(m->m.n), dy(m->m.n);
     dx.upload(x, m->m.n);
-    hipLaunchKernelGGL(k_spmv_wave, SPMV_GRID(m->m.n), dim3(256), 0, 0, m->m.n, m->m.rowptr.p, m->m.col.p, m->m.val.p, dx.p, dy.p);
+    launch_spmv(0, m->m.n, m->m.rowptr.p, m->m.col.p, m->m.val.p, VecPack(), dx.p, dy.p);  // the plain CSR product, whatever pack the matrix carries
     DAS_HIP(hipDeviceSynchronize());
     dy.download(y, m->m.n);
     return DAS_OK;
@@ -5832,6 +5719,123 @@ int das_debug_bilu_apply(const das_bilu_debug_t* in, int nrhs, long long ld, con
     return DAS_OK;
     DAS_CATCH
 }
+
+// Test-only entries (tests/test_gpu_graph_kernels.py, tests/test_gpu_opmat_kernels.py): the graph set-up, the jacLowerBounds filter, the
+// packed operator and the ghost-row product on caller-made structures through the helpers the solver uses (das_graph_debug.hpp).
+// Everything a kernel would index with is checked on the host before anything is launched.
+#define DAS_GRAPH_DEVICE(who) DAS_CHECK(das_device_count() > 0, DAS_ERR_NO_DEVICE, std::string(who) + ": no HIP device visible")
+int das_debug_graph_scan(long long n, const int* cnt, long long* out, long long* total) {
+    DAS_TRY
+    const std::string who = "das_debug_graph_scan";
+    graph_check_sizes(who, n);
+    DAS_CHECK(cnt && out && total, DAS_ERR_ARG, who + ": null pointer");
+    for (long long i = 0; i < n; i++) DAS_CHECK(cnt[i] >= 0, DAS_ERR_ARG, who + ": negative count");
+    DAS_GRAPH_DEVICE(who);
+    debug_graph_scan(n, cnt, out, total);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_graph_transpose(long long n, const long long* rowptr, const int* col, long long* trp, int* tcol) {
+    DAS_TRY
+    const std::string who = "das_debug_graph_transpose";
+    graph_check_sizes(who, n);
+    DAS_CHECK(rowptr && col && trp && tcol, DAS_ERR_ARG, who + ": null pointer");
+    graph_check_csr(who, n, rowptr, col, n, true);
+    DAS_CHECK(rowptr[n] > 0, DAS_ERR_ARG, who + ": a pattern without entries");
+    DAS_GRAPH_DEVICE(who);
+    debug_graph_transpose(n, rowptr, col, trp, tcol);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_graph_nets(long long n, const long long* rowptr, const int* col, long long nKeep, const long long* keep, long long* cptr, int* crow, int* cpos,
+                         unsigned char* isStart, long long* total) {
+    DAS_TRY
+    const std::string who = "das_debug_graph_nets";
+    graph_check_sizes(who, n);
+    DAS_CHECK(rowptr && col && cptr && crow && cpos && isStart && total && (keep || nKeep == 0), DAS_ERR_ARG, who + ": null pointer");
+    graph_check_csr(who, n, rowptr, col, n, true);
+    DAS_CHECK(rowptr[n] > 0, DAS_ERR_ARG, who + ": a pattern without entries");
+    DAS_CHECK(nKeep >= 0 && nKeep <= n, DAS_ERR_ARG, who + ": nKeep outside [0, n]");
+    {
+        std::vector<unsigned char> seen((size_t)n, 0);
+        for (long long q = 0; q < nKeep; q++) {
+            DAS_CHECK(keep[q] >= 0 && keep[q] < n, DAS_ERR_ARG, who + ": kept row out of range");
+            DAS_CHECK(!seen[keep[q]], DAS_ERR_ARG, who + ": kept row repeated");
+            seen[keep[q]] = 1;
+        }
+    }
+    DAS_GRAPH_DEVICE(who);
+    debug_graph_nets(n, rowptr, col, nKeep, keep, cptr, crow, cpos, isStart, total);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_graph_rows_gather(long long nSel, const long long* rows, long long n, const long long* rowptr, const int* col, const long long* dst, int* out,
+                                long long outLen) {
+    DAS_TRY
+    const std::string who = "das_debug_graph_rows_gather";
+    graph_check_sizes(who, n);
+    DAS_CHECK(nSel > 0 && outLen > 0, DAS_ERR_ARG, who + ": sizes must be positive");
+    DAS_CHECK(rows && rowptr && dst && out, DAS_ERR_ARG, who + ": null pointer");
+    graph_check_csr(who, n, rowptr, col, n, false);
+    for (long long q = 0; q < nSel; q++) {
+        DAS_CHECK(rows[q] >= 0 && rows[q] < n, DAS_ERR_ARG, who + ": row index out of range");
+        DAS_CHECK(dst[q] >= 0 && dst[q] <= outLen - (rowptr[rows[q] + 1] - rowptr[rows[q]]), DAS_ERR_ARG, who + ": a gathered row does not fit into out");
+    }
+    DAS_GRAPH_DEVICE(who);
+    debug_graph_rows_gather(nSel, rows, n, rowptr, col, dst, out, outLen);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_compact(long long n, const long long* rowptr, const int* col, const double* vals, double bound, int useBound, const unsigned char* owned,
+                      long long* nrp, int* nci, double* nv, long long* nnzOut) {
+    DAS_TRY
+    const std::string who = "das_debug_compact";
+    graph_check_sizes(who, n);
+    DAS_CHECK(rowptr && nrp && nci && nv && nnzOut, DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(useBound == 0 || useBound == 1, DAS_ERR_ARG, who + ": useBound is 0 or 1");
+    graph_check_csr(who, n, rowptr, col, n, false);
+    DAS_CHECK(rowptr[n] == 0 || vals, DAS_ERR_ARG, who + ": null pointer");
+    DAS_GRAPH_DEVICE(who);
+    debug_compact(n, rowptr, col, vals, bound, useBound != 0, owned, nrp, nci, nv, nnzOut);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_vecpack(long long n, const long long* rowptr, const int* col, const double* vals, long long row0, long long nG, int* built, long long* cptr,
+                      unsigned char* data, long long dataCap, long long* nChunks, const double* x, double* y, long long ylen) {
+    DAS_TRY
+    const std::string who = "das_debug_vecpack";
+    graph_check_sizes(who, n);
+    DAS_CHECK(nG > 0, DAS_ERR_ARG, who + ": sizes must be positive");
+    DAS_CHECK(rowptr && built && cptr && data && nChunks && (!x || y), DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(row0 >= 0 && nG <= n && row0 <= n - 3 * nG, DAS_ERR_ARG, who + ": the group rows [row0, row0 + 3 nG) do not lie in [0, n)");
+    DAS_CHECK(!x || ylen >= n, DAS_ERR_ARG, who + ": y shorter than n");
+    graph_check_csr(who, n, rowptr, col, n, false);
+    DAS_CHECK(rowptr[n] == 0 || vals, DAS_ERR_ARG, who + ": null pointer");
+    long long need = 0;
+    for (long long g = 0; g < nG; g++) need += (rowptr[row0 + 3 * g + 1] - rowptr[row0 + 3 * g] + VP_CHUNK - 1) / VP_CHUNK;
+    DAS_CHECK(dataCap >= need * VP_CHUNK_BYTES, DAS_ERR_ARG, who + ": data holds fewer bytes than the chunks of the group rows");
+    DAS_GRAPH_DEVICE(who);
+    debug_vecpack(n, rowptr, col, vals, row0, nG, built, cptr, data, nChunks, x, y, ylen);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_spmv_rows(long long nrows, const int* rows, long long n, const long long* rowptr, const int* col, const double* vals, const double* x, double* buf,
+                        long long buflen) {
+    DAS_TRY
+    const std::string who = "das_debug_spmv_rows";
+    graph_check_sizes(who, n);
+    DAS_CHECK(nrows > 0, DAS_ERR_ARG, who + ": sizes must be positive");
+    DAS_CHECK(rows && rowptr && x && buf, DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(buflen >= nrows, DAS_ERR_ARG, who + ": buf shorter than nrows");
+    graph_check_csr(who, n, rowptr, col, n, false);
+    DAS_CHECK(rowptr[n] == 0 || vals, DAS_ERR_ARG, who + ": null pointer");
+    for (long long k = 0; k < nrows; k++) DAS_CHECK(rows[k] >= 0 && rows[k] < n, DAS_ERR_ARG, who + ": row index out of range");
+    DAS_GRAPH_DEVICE(who);
+    debug_spmv_rows(nrows, rows, n, rowptr, col, vals, x, buf, buflen);
+    return DAS_OK;
+    DAS_CATCH
+}
+#undef DAS_GRAPH_DEVICE
 
 double das_get_elapsed_clock_time(das_solver_t* s) { return s ? wall_seconds() - s->t0_wall : -1.0; }
 double das_get_elapsed_cpu_time(das_solver_t* s) { return s ? (double)(std::clock() - s->t0_cpu) / CLOCKS_PER_SEC : -1.0; }

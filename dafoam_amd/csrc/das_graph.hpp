@@ -200,6 +200,22 @@ __global__ __launch_bounds__(256) void k_group_flags(long long n, const long lon
     for (long long q = 0; same && q < len; q++) same = crow[a + q] == crow[b + q];
     isStart[j] = same ? 0 : 1;
 }
+// the nets of every column of a transposed structure (trp, tcol) restricted to the kept rows (netOfRow), with the positions in the
+// ascending row-major rows (rp, col), and the group flags; returns the number of (column, net) pairs
+inline long long device_build_nets(long long nn, const long long* trp, const int* tcol, const int* netOfRow, const long long* rp, const int* col,
+                                   DevBuf<long long>& d_cptr, DevBuf<int>& d_crow, DevBuf<int>& d_cpos, DevBuf<unsigned char>& d_start, hipStream_t st) {
+    DevBuf<int> d_cnt((size_t)nn);
+    hipLaunchKernelGGL(k_net_count, dim3((unsigned)((nn + 15) / 16)), dim3(256), 0, st, nn, trp, tcol, netOfRow, d_cnt.p);
+    d_cptr.alloc((size_t)nn + 1);
+    const long long tot = device_exclusive_scan(nn, d_cnt.p, d_cptr.p, st);
+    d_crow.alloc((size_t)std::max<long long>(1, tot));
+    d_cpos.alloc((size_t)std::max<long long>(1, tot));
+    hipLaunchKernelGGL(k_net_fill, dim3((unsigned)((nn + 15) / 16)), dim3(256), 0, st, nn, trp, tcol, netOfRow, rp, col, d_cptr.p, d_crow.p, d_cpos.p);
+    d_start.alloc((size_t)nn);
+    hipLaunchKernelGGL(k_group_flags, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, nn, d_cptr.p, d_crow.p, d_start.p);
+    DAS_HIP(hipGetLastError());
+    return tot;
+}
 
 // out[dst[q] ..] = the columns of row rows[q] of a CSR pattern (one wavefront per selected row)
 __global__ __launch_bounds__(256) void k_rows_gather(long long nSel, const long long* __restrict__ rows, const long long* __restrict__ rowptr,

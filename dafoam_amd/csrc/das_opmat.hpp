@@ -12,7 +12,12 @@
 // The scalar rows (p, nuTilda, phi, ...) keep the CSR arrays of the assembled matrix (no copy).  Algorithmic bytes at 2 M cells:
 // 25.4 GB (12 B/entry CSR) -> 22.0 GB.  Built once per operator from the assembled CSR (one pass, ~10 ms); falls back to the
 // scalar kernel when the three rows of a cell do not share their list (jacLowerBounds compaction).
+// Also here, so that the test-only entries of das_graph_debug.hpp can run them without a solver handle: the scalar-row kernel
+// k_spmv_wave, launch_spmv (the launches of one operator product) and the jacLowerBounds filter that makes the assembled CSR
+// (k_count_keep, k_compact, filter_compact).
 #pragma once
+#include <vector>
+
 #include "das_common.hpp"
 
 namespace das {
@@ -152,6 +157,125 @@ inline bool vecpack_build(VecPack& P, long long nG, long long row0, const long l
     DAS_HIP(hipStreamSynchronize(st));
     P.ready = true;
     return true;
+}
+
+// y = A x, transposed-CSR dRdW^T (rows hold ~50-280 entries): SPMV_LANES lanes cooperate on one row, 256-thread
+// workgroups.  The matrix is streamed exactly once (non-temporal loads, so that it does not evict the gathered x
+// entries from the per-XCD L2); x is gathered through L2.
+#ifndef SPMV_LANES
+#define SPMV_LANES 16
+#endif
+#ifndef SPMV_NT
+#define SPMV_NT 0
+#endif
+#ifndef SPMV_UNROLL
+#define SPMV_UNROLL 4
+#endif
+__global__ __launch_bounds__(256) void k_spmv_wave(long long n, const long long* __restrict__ rp, const int* __restrict__ ci,
+                                                   const double* __restrict__ v, const double* __restrict__ x, double* __restrict__ y) {
+    constexpr int RPB = 256 / SPMV_LANES;
+    // (measured: giving every XCD one contiguous range of rows - x gathered into one L2 instead of eight - is SLOWER, 7.98 vs
+    // 5.19 ms at 2 M cells: the matrix stream of each XCD then hammers its own few HBM channels; the round-robin deal is kept)
+    long long row = (long long)blockIdx.x * RPB + (threadIdx.x / SPMV_LANES);
+    const int lane = threadIdx.x % SPMV_LANES;
+    if (row >= n) return;
+    const long long b = rp[row], e = rp[row + 1];
+    double acc[SPMV_UNROLL];
+#pragma unroll
+    for (int u = 0; u < SPMV_UNROLL; u++) acc[u] = 0.0;
+    long long k = b + lane;
+    // main loop: SPMV_UNROLL independent (value, column, x) gathers in flight per lane
+    for (; k + (SPMV_UNROLL - 1) * SPMV_LANES < e; k += SPMV_UNROLL * SPMV_LANES) {
+        double vv[SPMV_UNROLL];
+        int cc[SPMV_UNROLL];
+#pragma unroll
+        for (int u = 0; u < SPMV_UNROLL; u++) {
+#if SPMV_NT
+            vv[u] = __builtin_nontemporal_load(v + k + u * SPMV_LANES);
+            cc[u] = __builtin_nontemporal_load(ci + k + u * SPMV_LANES);
+#else
+            vv[u] = v[k + u * SPMV_LANES];
+            cc[u] = ci[k + u * SPMV_LANES];
+#endif
+        }
+#pragma unroll
+        for (int u = 0; u < SPMV_UNROLL; u++) acc[u] += vv[u] * x[cc[u]];
+    }
+    // tail (and the whole of a short row - the phi rows hold ~31 entries): the same SPMV_UNROLL loads in flight, clamped to the
+    // last entry of the row and masked, instead of a serial loop with one load per round trip
+    if (k - lane < e) {
+        double vv[SPMV_UNROLL];
+        int cc[SPMV_UNROLL];
+#pragma unroll
+        for (int u = 0; u < SPMV_UNROLL; u++) {
+            const long long kk = k + u * SPMV_LANES;
+            const long long kc = kk < e ? kk : e - 1;
+            vv[u] = kk < e ? v[kc] : 0.0;
+            cc[u] = ci[kc];
+        }
+#pragma unroll
+        for (int u = 0; u < SPMV_UNROLL; u++) acc[u] += vv[u] * x[cc[u]];
+    }
+    double sacc = acc[0];
+#pragma unroll
+    for (int u = 1; u < SPMV_UNROLL; u++) sacc += acc[u];
+#pragma unroll
+    for (int o = SPMV_LANES / 2; o > 0; o >>= 1) sacc += __shfl_down(sacc, o, SPMV_LANES);
+    if (lane == 0) y[row] = sacc;
+}
+#define SPMV_GRID(n) dim3(nblk((n), 256 / SPMV_LANES))
+
+// y = A x for the CSR (rp, ci, v) of n rows: with a pack, its vector rows as group rows (one column list, three value planes) and the
+// scalar rows before and after them from the CSR arrays
+inline void launch_spmv(hipStream_t st, long long n, const long long* rp, const int* ci, const double* v, const VecPack& vp, const double* x, double* y) {
+    if (vp.ready) {
+        const long long r1 = vp.row0 + 3 * vp.nGroups;
+        hipLaunchKernelGGL(k_spmv_vec3, dim3((unsigned)((vp.nGroups + 15) / 16)), dim3(256), 0, st, vp.nGroups, vp.row0, vp.cptr.p, vp.data.p, x, y);
+        if (vp.row0 > 0) hipLaunchKernelGGL(k_spmv_wave, SPMV_GRID(vp.row0), dim3(256), 0, st, vp.row0, rp, ci, v, x, y);
+        if (n > r1) hipLaunchKernelGGL(k_spmv_wave, SPMV_GRID(n - r1), dim3(256), 0, st, n - r1, rp + r1, ci, v, x, y + r1);
+    } else {
+        hipLaunchKernelGGL(k_spmv_wave, SPMV_GRID(n), dim3(256), 0, st, n, rp, ci, v, x, y);
+    }
+}
+
+// jacLowerBound filter (reference DAPartDeriv.C:192): keep |v| > bound or diagonal
+// (multi-GPU: columns = residuals not owned by this rank are dropped; `owned` may be null)
+__device__ __forceinline__ bool keep_entry(long long i, int c, double v, double bound, bool useBound, const unsigned char* owned) {
+    if (owned && !owned[c]) return false;
+    return !useBound || fabs(v) > bound || c == i;
+}
+__global__ void k_count_keep(long long n, const long long* __restrict__ rp, const int* __restrict__ ci, const double* __restrict__ v, double bound,
+                             bool useBound, const unsigned char* __restrict__ owned, int* cnt) {
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    int c = 0;
+    for (long long k = rp[i]; k < rp[i + 1]; k++) c += keep_entry(i, ci[k], v[k], bound, useBound, owned) ? 1 : 0;
+    cnt[i] = c;
+}
+__global__ void k_compact(long long n, const long long* __restrict__ rp, const int* __restrict__ ci, const double* __restrict__ v, double bound,
+                          bool useBound, const unsigned char* __restrict__ owned, const long long* __restrict__ nrp, int* nci, double* nv) {
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    long long o = nrp[i];
+    for (long long k = rp[i]; k < rp[i + 1]; k++)
+        if (keep_entry(i, ci[k], v[k], bound, useBound, owned)) { nci[o] = ci[k]; nv[o] = v[k]; o++; }
+}
+
+// the filtered copy (nrp, nci, nv) of a CSR on the device: count, row offsets, compaction; returns the number of kept entries
+inline long long filter_compact(long long n, const long long* rp, const int* ci, const double* v, double bound, bool useBound, const unsigned char* owned,
+                                DevBuf<long long>& nrp, DevBuf<int>& nci, DevBuf<double>& nv, hipStream_t st) {
+    const int B = 256;
+    DevBuf<int> cnt(n);
+    hipLaunchKernelGGL(k_count_keep, dim3(nblk(n, B)), dim3(B), 0, st, n, rp, ci, v, bound, useBound, owned, cnt.p);
+    DAS_HIP(hipStreamSynchronize(st));
+    std::vector<int> hc = cnt.to_host();
+    std::vector<long long> h(n + 1, 0);
+    for (long long i = 0; i < n; i++) h[i + 1] = h[i] + hc[i];
+    nrp.upload(h);
+    nci.alloc(h[n]);
+    nv.alloc(h[n]);
+    hipLaunchKernelGGL(k_compact, dim3(nblk(n, B)), dim3(B), 0, st, n, rp, ci, v, bound, useBound, owned, nrp.p, nci.p, nv.p);
+    return h[n];
 }
 
 }  // namespace das

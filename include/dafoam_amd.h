@@ -597,6 +597,39 @@ int das_debug_bilu_factor(const das_bilu_debug_t* in, long long* Lptr, long long
  * width.  info = {launchGrid, launchSleep, launchPerXcd, xcdProbe} */
 int das_debug_bilu_apply(const das_bilu_debug_t* in, int nrhs, long long ld, const double* b, double* out, int twice, double* y, double* z,
                          int* abortFlag, int* info);
+/* ---- TEST-ONLY entries (tests/test_gpu_graph_kernels.py, tests/test_gpu_opmat_kernels.py): the graph set-up kernels of the colouring
+ * input, the jacLowerBounds filter, the packed operator and the ghost-row product on caller-made CSR structures, kernel by kernel.  No
+ * mesh, no solver handle; the launch sequences THE SOLVER USES run on the null stream.  These kernels index with what they are given,
+ * so everything is checked on the host before anything is launched, and DAS_ERR_ARG is returned for a null pointer, a size <= 0,
+ * rowptr[0] != 0, a decreasing rowptr, a column or row index outside [0, n), columns of a row that do not ascend strictly (transpose
+ * and nets), a pattern without entries (transpose and nets), kept rows out of range or repeated, row0 + 3 nG > n, and an output array
+ * too short for what is written.  All matrices are n x n.  Arrays that a kernel writes into at caller-given places (out, y, buf) are
+ * uploaded and downloaded whole, so that the caller can put a sentinel around the written range and find it untouched. */
+/* device_exclusive_scan (k_scan_block_sums, k_scan_apply): out[0..n] = exclusive prefix of the counts (>= 0), *total = out[n] */
+int das_debug_graph_scan(long long n, const int* cnt, long long* out, long long* total);
+/* device_transpose (k_tr_count, scan, k_tr_fill, k_sort_rows): trp (n+1), tcol (nnz) = the transposed pattern, rows ascending */
+int das_debug_graph_transpose(long long n, const long long* rowptr, const int* col, long long* trp, int* tcol);
+/* device_transpose, then device_build_nets (k_net_count, scan, k_net_fill, k_group_flags) for the kept rows keep[0..nKeep) (net q = row
+ * keep[q]; nKeep = 0 is allowed): cptr (n+1), crow / cpos (*total <= nnz entries: the nets of a column in ascending row order and the
+ * position of the column in each of those rows), isStart (n) */
+int das_debug_graph_nets(long long n, const long long* rowptr, const int* col, long long nKeep, const long long* keep, long long* cptr, int* crow, int* cpos,
+                         unsigned char* isStart, long long* total);
+/* k_rows_gather: out[dst[q] ..] = the columns of row rows[q], q < nSel; out holds outLen entries */
+int das_debug_graph_rows_gather(long long nSel, const long long* rows, long long n, const long long* rowptr, const int* col, const long long* dst, int* out,
+                                long long outLen);
+/* filter_compact (k_count_keep, k_compact): the entries with |v| > bound (if useBound) or on the diagonal, of the columns with
+ * owned[col] != 0 (owned may be null: all); nrp (n+1), nci / nv (*nnzOut <= nnz entries) */
+int das_debug_compact(long long n, const long long* rowptr, const int* col, const double* vals, double bound, int useBound, const unsigned char* owned,
+                      long long* nrp, int* nci, double* nv, long long* nnzOut);
+/* vecpack_build (k_vecpack_count, k_vecpack_fill) of the group rows [row0, row0 + 3 nG): *built = 0 when the three rows of a group do
+ * not share their column list (nothing else is written), else cptr (nG+1), data (*nChunks chunks of 448 bytes; dataCap bytes must hold
+ * them) and, unless x is null, launch_spmv over the whole matrix (k_spmv_vec3 + k_spmv_wave on the rows before and after the pack) into
+ * y[0..n), y holding ylen >= n entries */
+int das_debug_vecpack(long long n, const long long* rowptr, const int* col, const double* vals, long long row0, long long nG, int* built, long long* cptr,
+                      unsigned char* data, long long dataCap, long long* nChunks, const double* x, double* y, long long ylen);
+/* k_spmv_rows_to_buf: buf[k] = A[rows[k], :] . x, k < nrows; buf holds buflen >= nrows entries */
+int das_debug_spmv_rows(long long nrows, const int* rows, long long n, const long long* rowptr, const int* col, const double* vals, const double* x, double* buf,
+                        long long buflen);
 long long das_timer_count(das_solver_t* s, const char* name);
 void das_timer_reset(das_solver_t* s);
 void das_timer_enable(das_solver_t* s, int on);
