@@ -219,6 +219,7 @@ _SIGS = {
     "das_set_option_int": (C.c_int, [_VP, C.c_char_p, C.c_longlong]),
     "das_set_option_str": (C.c_int, [_VP, C.c_char_p, C.c_char_p]),
     "das_get_option_double": (C.c_int, [_VP, C.c_char_p, c_double_p]),
+    "das_get_option_string": (C.c_int, [_VP, C.c_char_p, C.c_char_p, C.c_int]),
     "das_init_solver": (C.c_int, [_VP, C.c_int]),
     "das_get_n_local_adjoint_states": (C.c_longlong, [_VP]),
     "das_get_n_local_cells": (C.c_longlong, [_VP]),
@@ -302,6 +303,18 @@ _SIGS = {
     "das_set_dense_eig_callback": (C.c_int, [_VP]),
     "das_debug_gmres_dr_host": (C.c_int, [C.c_longlong, _VP, _VP, _VP, c_double_p, c_double_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_longlong, c_double_p, C.c_int,
                                           c_double_p, c_double_p]),
+    "das_ksp_get_idr_info": (C.c_int, [_VP, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p]),
+    "das_debug_idrs_host": (C.c_int, [C.c_longlong, _VP, _VP, _VP, c_double_p, c_double_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_longlong, c_double_p, C.c_int,
+                                      c_double_p, c_double_p]),
+    "das_debug_idr_cycle_host": (C.c_int, [C.c_longlong, _VP, _VP, _VP, c_double_p, c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),
+    # test-only entries (tests/test_gpu_idr_kernels.py): the IDR(s) kernels on caller data, never called by the bindings
+    "das_debug_idr_shadow": (C.c_int, [C.c_longlong, C.c_int, C.c_longlong, C.c_int, C.c_int, c_double_p]),
+    "das_debug_idr_combine": (C.c_int, [C.c_longlong, C.c_int, C.c_double, c_double_p, c_double_p, C.c_longlong, C.c_longlong, c_double_p, C.c_longlong, c_double_p,
+                                        C.c_longlong]),
+    "das_debug_idr_biortho_step": (C.c_int, [C.c_longlong, C.c_int, c_double_p, c_double_p, C.c_longlong, C.c_longlong, c_double_p, c_double_p, c_double_p, C.c_longlong,
+                                             c_double_p]),
+    "das_debug_idr_smooth_step": (C.c_int, [C.c_longlong, C.c_int, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, C.c_longlong, c_double_p, C.c_longlong,
+                                            C.c_longlong, c_double_p]),
     "das_debug_gmres_dr_restart": (C.c_int, [C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "das_debug_block_chol": (C.c_int, [C.c_int, c_double_p, c_double_p, c_double_p]),
     "das_debug_block_lsq": (C.c_int, [C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),

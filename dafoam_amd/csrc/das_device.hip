@@ -24,6 +24,8 @@
 #include "das_gmres_host.hpp"
 #include "das_block.hpp"
 #include "das_krylov_debug.hpp"
+#include "das_idr.hpp"
+#include "das_idr_debug.hpp"
 #include "das_bilu_debug.hpp"
 #include "das_graph_debug.hpp"
 #include "das_color.hpp"
@@ -870,6 +872,7 @@ struct das_ksp {
     DevBuf<double> pcin;      // ... its input: a copy of the vector with the overlap entries gathered from their owners
     std::unique_ptr<struct GmresRun> run;
     std::unique_ptr<struct BlockWork> block;
+    std::unique_ptr<struct IdrWork> idr;  // amd.krylovMethod "idrs": the 3 s + O(1) work vectors, allocated once per KSP (idr_ws)
     std::vector<double> block_res0, block_res;
     int iters = 0, nrefine = 0, reason = 0, nBreakdown = 0;
     double res0 = 0, res = 0, seconds = 0;
@@ -2906,7 +2909,10 @@ static int run_gmres_dr(das_solver* s, das_ksp* k, const double* d_rhs, double* 
     return gmres_failed(k->res, k->res0, G.rtol, G.atol, s->opt.getd("adjEqnOption.gmresTolDiff"));
 }
 
+static bool idr_selected(das_solver* s, bool fixed);
+static int run_idrs(das_solver* s, das_ksp* k, const double* d_rhs, double* d_x);
 static int run_gmres(das_solver* s, das_ksp* k, const double* d_rhs, double* d_x, int fixed_iters) {
+    if (idr_selected(s, fixed_iters > 0)) return run_idrs(s, k, d_rhs, d_x);  // opt-in: amd.krylovMethod "idrs"
     {   // opt-in: deflated restarting (never for the fixed-iteration bench windows, the Newton primal's inner solves or several ranks)
         auto it = s->opt.i.find("amd.gmresDeflation");
         const long long kdef = it != s->opt.i.end() ? it->second : 0;
@@ -2964,6 +2970,167 @@ static void block_cholqr2(das_solver* s, BlockWork& bw, double* W, int sv, std::
     S.assign((size_t)sv * sv, 0.0);  // W = Q2 S2 S1
     for (int i = 0; i < sv; i++) for (int j = i; j < sv; j++) { double a = 0.0; for (int q = i; q <= j; q++) a += S2[(size_t)i * sv + q] * S1[(size_t)q * sv + j]; S[(size_t)i * sv + j] = a; }
 }
+// ---- IDR(s) (amd.krylovMethod "idrs"): idrs_loop of das_idr_host.hpp over the device's vector operations (das_idr.hpp) ---------------
+// No Krylov basis: the path never calls gmres_ws, never reserves or maps k->V.  Its vectors - P, G, U (n x s each), r, z, t and the
+// device copies of the right-hand side and the solution - are allocated once per KSP and reused by later solves.
+struct IdrWork {
+    int s = 0;
+    long long n = 0;
+    DevBuf<double> P, G, U, partial, coef, sums;
+    BlockWork bw;  // scratch of block_cholqr2 (the orthonormalisation of P)
+    // last solve (das_ksp_get_idr_info)
+    int cycles = 0, restarts = 0, breakdowns = 0;
+    // a solve opened by das_ksp_begin_device and not run yet
+    bool pending = false;
+    const double* d_rhs = nullptr;
+    double* d_x = nullptr;
+    int rc = 0;
+    int work_vectors() const { return 3 * s + 5; }  // P, G, U; r, z, t; rhs and solution on the device
+};
+// amd.krylovMethod, validated at every solve: true when this solve runs IDR(s).  Fixed-iteration bench windows and the Newton primal's
+// inner solves keep GMRES silently; several ranks, or deflated restarting on top, are errors
+static bool idr_selected(das_solver* s, bool fixed) {
+    const std::string& meth = s->opt.gets("amd.krylovMethod");
+    DAS_CHECK(meth == "gmres" || meth == "idrs", DAS_ERR_ARG, "amd.krylovMethod \"" + meth + "\" is not one of gmres | idrs");
+    if (meth != "idrs") return false;
+    const long long sv = s->opt.geti("amd.idrShadowVectors");
+    DAS_CHECK(sv >= 1 && sv <= IDR_MAX_S, DAS_ERR_ARG, "amd.idrShadowVectors " + std::to_string(sv) + " is outside 1 .. 8");
+    if (fixed || s->fwd.on) return false;
+    DAS_CHECK(!s->halo.active && !s->halo_cb, DAS_ERR_ARG, "amd.krylovMethod \"idrs\" is single-rank (run the sharded solve with \"gmres\")");
+    { auto it = s->opt.i.find("amd.gmresDeflation"); DAS_CHECK(it == s->opt.i.end() || it->second <= 0, DAS_ERR_ARG, "amd.gmresDeflation > 0 belongs to GMRES: not with amd.krylovMethod \"idrs\""); }
+    return true;
+}
+// the work vectors of the IDR(s) path (the ones it shares with the GMRES path are re-allocated by gmres_ws when that runs next: restart = 0)
+static IdrWork& idr_ws(das_solver* s, das_ksp* k) {
+    const long long n = s->n;
+    const int sv = (int)std::min<long long>(s->opt.geti("amd.idrShadowVectors"), n);
+    if (!k->idr) k->idr.reset(new IdrWork);
+    IdrWork& I = *k->idr;
+    if (I.s != sv || I.n != n) {
+        I.s = sv; I.n = n;
+        I.P.alloc((size_t)sv * n); I.G.alloc((size_t)sv * n); I.U.alloc((size_t)sv * n);
+        I.partial.alloc(idr_partial_size(n, sv)); I.coef.alloc(4 * IDR_MAX_S); I.sums.alloc(IDR_MAX_S + 2);
+    }
+    if (k->w.n != (size_t)n || k->z.n != (size_t)n || k->r.n != (size_t)n || k->xdev.n != (size_t)n || k->bdev.n != (size_t)n) {
+        k->restart = 0;
+        k->w.alloc(n); k->z.alloc(n); k->r.alloc(n); k->xdev.alloc(n); k->bdev.alloc(n);
+        k->z.zero();  // the preconditioner's output stays a vector of its own, zero-initialised (as in gmres_ws)
+    }
+    return I;
+}
+namespace {
+struct IdrDeviceOps {
+    das_solver* s; das_ksp* k; IdrWork* I;
+    const double* d_rhs; double* d_x;
+    double hc[4 * IDR_MAX_S], hs[IDR_MAX_S + 2];  // host side of coef / sums: rewritten only after the synchronisation that follows their use
+    void get_sums(int cnt) {
+        DAS_HIP(hipMemcpyAsync(hs, I->sums.p, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        DAS_HIP(hipStreamSynchronize(s->stream));
+    }
+    void shadow(int sv, unsigned seed) {
+        launch_idr_shadow(s->stream, s->n, sv, seed, I->P.p, s->n);
+        std::vector<double> S;
+        block_cholqr2(s, I->bw, I->P.p, sv, S);
+    }
+    void reset_spaces() {
+        DAS_HIP(hipMemsetAsync(I->G.p, 0, (size_t)I->s * s->n * sizeof(double), s->stream));
+        DAS_HIP(hipMemsetAsync(I->U.p, 0, (size_t)I->s * s->n * sizeof(double), s->stream));
+    }
+    void project_r(double* f) {
+        launch_multidot<double>(s->stream, s->n, I->s, I->P.p, s->n, k->r.p, I->partial.p, I->sums.p);
+        get_sums(I->s);
+        std::copy(hs, hs + I->s, f);
+    }
+    void inner_vec(int kk, const double* c, double omega) {
+        const long long n = s->n;
+        hipStream_t st = s->stream;
+        const int m = I->s - kk;
+        for (int i = 0; i < m; i++) { hc[i] = -c[i]; hc[IDR_MAX_S + i] = c[i]; }
+        DAS_HIP(hipMemcpyAsync(I->coef.p, hc, 2 * IDR_MAX_S * sizeof(double), hipMemcpyHostToDevice, st));
+        double* uk = I->U.p + (long long)kk * n;
+        double* gk = I->G.p + (long long)kk * n;
+        launch_idr_combine(st, n, m, 1.0, k->r.p, gk, n, I->coef.p, k->w.p);                // v = r - G[:, k:] c
+        pc_apply_full(s, k, k->w.p, k->z.p);
+        launch_idr_combine(st, n, m, omega, k->z.p, uk, n, I->coef.p + IDR_MAX_S, uk);      // u_k = omega z + U[:, k:] c, in place
+        apply_operator(s, uk, gk);
+    }
+    void dots_g(int kk, double* d, double& gg) {
+        launch_multidot<double>(s->stream, s->n, I->s, I->P.p, s->n, I->G.p + (long long)kk * s->n, I->partial.p, I->sums.p);
+        get_sums(I->s + 1);
+        std::copy(hs, hs + I->s, d);
+        gg = hs[I->s];
+    }
+    double biortho_step(int kk, const double* alpha, double beta) {
+        double* h = hc + 2 * IDR_MAX_S;
+        for (int j = 0; j < kk; j++) h[j] = alpha[j];
+        h[kk] = beta;
+        DAS_HIP(hipMemcpyAsync(I->coef.p + 2 * IDR_MAX_S, h, (size_t)(kk + 1) * sizeof(double), hipMemcpyHostToDevice, s->stream));
+        launch_idr_biortho_step(s->stream, s->n, kk, I->G.p, I->U.p, s->n, I->coef.p + 2 * IDR_MAX_S, k->r.p, d_x, I->partial.p, I->sums.p);
+        get_sums(1);
+        return hs[0];
+    }
+    void smooth_vec() {
+        pc_apply_full(s, k, k->r.p, k->z.p);
+        apply_operator(s, k->z.p, k->w.p);
+    }
+    void dots_t(double& tr, double& tt) {
+        launch_multidot<double>(s->stream, s->n, 1, k->r.p, s->n, k->w.p, I->partial.p, I->sums.p);
+        get_sums(2);
+        tr = hs[0]; tt = hs[1];
+    }
+    double smooth_step(double omega, double* f) {
+        launch_idr_smooth_step(s->stream, s->n, I->s, omega, k->r.p, k->w.p, d_x, k->z.p, I->P.p, s->n, I->partial.p, I->sums.p);
+        get_sums(I->s + 1);
+        std::copy(hs, hs + I->s, f);
+        return hs[I->s];
+    }
+    double norm_r() {
+        launch_multidot<double>(s->stream, s->n, 0, k->r.p, s->n, k->r.p, I->partial.p, I->sums.p);
+        get_sums(1);
+        return std::sqrt(std::max(hs[0], 0.0));
+    }
+    double true_residual() {
+        apply_operator(s, d_x, k->r.p);
+        hipLaunchKernelGGL(k_axpby, dim3(nblk(s->n, 256)), dim3(256), 0, s->stream, s->n, 1.0, d_rhs, -1.0, k->r.p);
+        return norm_r();
+    }
+};
+}  // namespace
+
+static int run_idrs(das_solver* s, das_ksp* k, const double* d_rhs, double* d_x) {
+    need_init(s);
+    DAS_CHECK(s->op, DAS_ERR_STATE, "initializedRdWTMatrixFree() must be called before solveLinearEqn()");
+    IdrWork& I = idr_ws(s, k);
+    if (k->useBilu) bilu_clear_abort(k->bilu, s->stream);
+    const long long n = s->n;
+    const double t0 = wall_seconds();
+    const double rtol = s->opt.getd("adjEqnOption.gmresRelTol"), atol = s->opt.getd("adjEqnOption.gmresAbsTol");
+    const long long maxIts = s->opt.geti("adjEqnOption.gmresMaxIters");
+    IdrDeviceOps ops{s, k, &I, d_rhs, d_x};
+    double beta0;
+    if (s->opt.geti("adjEqnOption.useNonZeroInitGuess") != 0) beta0 = ops.true_residual();
+    else {
+        DAS_HIP(hipMemsetAsync(d_x, 0, n * sizeof(double), s->stream));
+        DAS_HIP(hipMemcpyAsync(k->r.p, d_rhs, n * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+        beta0 = ops.norm_r();
+    }
+    k->nrefine = 0; k->hist.clear(); k->cycleLens.clear();
+    k->hist.push_back(beta0);
+    const double target = std::max(rtol * beta0, atol);
+    const IdrResult R = idrs_loop(ops, I.s, (unsigned)s->opt.geti("amd.idrSeed"), beta0, target, maxIts, k->hist);
+    gmres_finish_check(s, k);
+    I.cycles = R.cycles; I.restarts = R.nRestarts; I.breakdowns = R.nBreakdown;
+    k->iters = (int)R.its;
+    k->nBreakdown = R.nBreakdown;
+    k->res0 = R.res0;
+    k->res = R.res;
+    k->reason = R.reason;
+    k->seconds = wall_seconds() - t0;
+    if (s->opt.geti("debug")) fprintf(stderr, "[dafoam_amd] IDR(%d): %lld products, %d cycles, %d restarts, %d breakdowns, |r| %.3e -> %.3e (reason %d)\n", I.s, R.its, R.cycles, R.nRestarts, R.nBreakdown, R.res0, R.res, R.reason);
+    if (R.reason == 3) return 1;  // a non-finite residual never passes the tolerance rule
+    return gmres_failed(k->res, k->res0, rtol, atol, s->opt.getd("adjEqnOption.gmresTolDiff"));
+}
+
 static void block_spmm(das_solver* s, BlockWork& bw, const Mat& A, const double* X, double* Y, int sv) {
     launch_block_to_rows(s->stream, s->n, sv, X, s->n, bw.Xr.p);
     hipEvent_t ev = nullptr;
@@ -3293,6 +3460,17 @@ int das_get_option_double(das_solver_t* s, const char* key, double* v) {
     DAS_CHECK(s && key && v, DAS_ERR_ARG, "null argument");
     *v = s->opt.getd(key);
     return DAS_OK;
+    DAS_CATCH
+}
+// a string option into buf (cap bytes, always terminated); returns the length of the value
+int das_get_option_string(das_solver_t* s, const char* key, char* buf, int cap) {
+    DAS_TRY
+    DAS_CHECK(s && key && buf && cap > 0, DAS_ERR_ARG, "null argument");
+    const std::string& v = s->opt.gets(key);
+    const size_t m = std::min(v.size(), (size_t)cap - 1);
+    std::copy(v.begin(), v.begin() + m, buf);
+    buf[m] = 0;
+    return (int)v.size();
     DAS_CATCH
 }
 
@@ -5050,7 +5228,8 @@ int das_solve_linear_eqn(das_solver_t* s, das_ksp_t* ksp, const double* rhs, dou
     DAS_TRY
     need_init(s);
     DAS_CHECK(ksp && rhs && sol, DAS_ERR_ARG, "null argument");
-    gmres_ws(s, ksp);
+    if (idr_selected(s, false)) idr_ws(s, ksp);  // (never the Krylov basis)
+    else gmres_ws(s, ksp);
     ksp->bdev.upload(rhs, s->n);
     ksp->xdev.upload(sol, s->n);
     int rc = run_gmres(s, ksp, ksp->bdev.p, ksp->xdev.p, 0);
@@ -5229,6 +5408,97 @@ int das_debug_gmres_dr_host(long long n, void* A, void* M, void* user, const dou
     return gmres_failed(R.res, beta0, rtol, atol, 1e2);
     DAS_CATCH
 }
+// IDR(s) of the last solve of this KSP (amd.krylovMethod "idrs"): s as used (clamped to n), completed cycles, restarts from the true
+// residual, breakdowns; the work vectors the path holds (3 s + 5: P, G, U, r, z, t, right-hand side, solution) and their bytes (8 n each).
+// cycles = 0 and workVectors = 0: this KSP has not run IDR(s)
+int das_ksp_get_idr_info(das_ksp_t* k, int* sv, int* cycles, int* restarts, int* breakdowns, int* workVectors, double* workBytes) {
+    DAS_TRY
+    DAS_CHECK(k, DAS_ERR_ARG, "null ksp handle");
+    const IdrWork* I = k->idr.get();
+    if (sv) *sv = I ? I->s : 0;
+    if (cycles) *cycles = I ? I->cycles : 0;
+    if (restarts) *restarts = I ? I->restarts : 0;
+    if (breakdowns) *breakdowns = I ? I->breakdowns : 0;
+    if (workVectors) *workVectors = I ? I->work_vectors() : 0;
+    if (workBytes) *workBytes = I ? (double)I->work_vectors() * 8.0 * (double)I->n : 0.0;
+    return DAS_OK;
+    DAS_CATCH
+}
+static IdrHostOps idr_host_ops(long long n, void* A, void* M, void* user, const double* b, double* x) {
+    return IdrHostOps{n, (das_host_apply_fn)A, (das_host_apply_fn)M, user, b, x, 0, {}, {}, {}, std::vector<double>(n), std::vector<double>(n), std::vector<double>(n), {}};
+}
+// the IDR(s) iteration (idrs_loop, the loop the device solver runs) on host vectors with callback operator / preconditioner, from x = 0:
+// CPU tier.  info4 = {products, stop reason (0 tolerance, 1 budget, 2 stagnation, 3 non-finite residual), restarts, breakdowns}, res2 = {|r0|, |r|}
+// (true residuals); returns the fail flag
+int das_debug_idrs_host(long long n, void* A, void* M, void* user, const double* b, double* x, int sv, int seed, double rtol, double atol, long long maxIts,
+                        double* hist, int histCap, double* info4, double* res2) {
+    DAS_TRY
+    DAS_CHECK(n > 0 && A && M && b && x && sv >= 1 && sv <= IDR_MAX_S, DAS_ERR_ARG, "bad argument (1 to 8 shadow vectors)");
+    IdrHostOps ops = idr_host_ops(n, A, M, user, b, x);
+    std::fill(x, x + n, 0.0);
+    const double beta0 = ops.true_residual();
+    std::vector<double> h{beta0};
+    const IdrResult R = idrs_loop(ops, (int)std::min<long long>(sv, n), (unsigned)seed, beta0, std::max(rtol * beta0, atol), maxIts, h);
+    if (hist) for (int i = 0; i < histCap && i < (int)h.size(); i++) hist[i] = h[i];
+    if (info4) { info4[0] = (double)R.its; info4[1] = R.reason; info4[2] = R.nRestarts; info4[3] = R.nBreakdown; }
+    if (res2) { res2[0] = R.res0; res2[1] = R.res; }
+    return R.reason == 3 ? 1 : gmres_failed(R.res, beta0, rtol, atol, 1e2);
+    DAS_CATCH
+}
+// exactly one cycle (s + 1 products) of the same loop from x = 0, and the state it leaves: x, the recurrence residual r, the orthonormal
+// shadow space P and the spaces G, U (n x s each, column-major) - what the CPU tier compares with the published sequential form
+int das_debug_idr_cycle_host(long long n, void* A, void* M, void* user, const double* b, double* x, int sv, int seed, double* r, double* P, double* G, double* U) {
+    DAS_TRY
+    DAS_CHECK(n > 0 && A && M && b && x && r && P && G && U && sv >= 1 && sv <= IDR_MAX_S && sv <= n, DAS_ERR_ARG, "bad argument (1 to min(8, n) shadow vectors)");
+    IdrHostOps ops = idr_host_ops(n, A, M, user, b, x);
+    std::fill(x, x + n, 0.0);
+    const double beta0 = ops.true_residual();
+    std::vector<double> h{beta0};
+    const IdrResult R = idrs_loop(ops, sv, (unsigned)seed, beta0, 0.0, (long long)sv + 2, h);  // budget: one cycle and the closing true residual
+    DAS_CHECK(R.its == sv + 2 && R.cycles == 1, DAS_ERR_INTERNAL, "the cycle did not complete (breakdown)");
+    std::copy(ops.rrec.begin(), ops.rrec.end(), r);
+    std::copy(ops.P.begin(), ops.P.end(), P); std::copy(ops.G.begin(), ops.G.end(), G); std::copy(ops.U.begin(), ops.U.end(), U);
+    return DAS_OK;
+    DAS_CATCH
+}
+// test-only entries of the IDR(s) kernels (bodies: das_idr_debug.hpp; layouts: include/dafoam_amd.h)
+int das_debug_idr_shadow(long long n, int sv, long long ld, int seed, int device, double* P) {
+    DAS_TRY
+    DAS_CHECK(P, DAS_ERR_ARG, "null argument");
+    idr_check_shape("das_debug_idr_shadow", n, sv, ld);
+    debug_idr_shadow(n, sv, ld, (unsigned)seed, device != 0, P);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_idr_combine(long long n, int m, double a, const double* x, double* V, long long ld, long long vlen, const double* c, long long yoff, double* y,
+                          long long ylen) {
+    DAS_TRY
+    DAS_CHECK(x && V && c && (yoff >= 0 || y), DAS_ERR_ARG, "null argument");
+    DAS_CHECK(n > 0 && m >= 0 && m <= IDR_MAX_S && ld >= n && vlen >= (long long)std::max(m - 1, 0) * ld + n, DAS_ERR_ARG, "das_debug_idr_combine: bad shape");
+    DAS_CHECK(yoff >= 0 ? yoff + n <= vlen : ylen >= n, DAS_ERR_ARG, "das_debug_idr_combine: the output does not fit");
+    debug_idr_combine(n, m, a, x, V, ld, vlen, c, yoff, y, ylen);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_idr_biortho_step(long long n, int kk, double* G, double* U, long long ld, long long glen, const double* coef, double* r, double* x, long long vlen,
+                               double* rr) {
+    DAS_TRY
+    DAS_CHECK(G && U && coef && r && x && rr, DAS_ERR_ARG, "null argument");
+    DAS_CHECK(n > 0 && kk >= 0 && kk < IDR_MAX_S && ld >= n && glen >= (long long)kk * ld + n && vlen >= n, DAS_ERR_ARG, "das_debug_idr_biortho_step: bad shape");
+    debug_idr_biortho_step(n, kk, G, U, ld, glen, coef, r, x, vlen, rr);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_idr_smooth_step(long long n, int sv, double omega, double* r, const double* t, double* x, const double* z, long long vlen, double* P, long long ld,
+                              long long plen, double* out) {
+    DAS_TRY
+    DAS_CHECK(r && t && x && z && P && out, DAS_ERR_ARG, "null argument");
+    idr_check_shape("das_debug_idr_smooth_step", n, sv, ld);
+    DAS_CHECK(vlen >= n && plen >= (long long)(sv - 1) * ld + n, DAS_ERR_ARG, "das_debug_idr_smooth_step: bad shape");
+    debug_idr_smooth_step(n, sv, omega, r, t, x, z, vlen, P, ld, plen, out);
+    return DAS_OK;
+    DAS_CATCH
+}
 int das_ksp_get_n_refine(das_ksp_t* k) { return k ? k->nrefine : -1; }
 int das_ksp_get_status(das_ksp_t* k, int* reason, int* nBreakdown, int* nSweepGrid, int* sweepPerXcd) {
     DAS_TRY
@@ -5329,19 +5599,40 @@ int das_ksp_run_fixed_device(das_solver_t* s, das_ksp_t* ksp, const double* d_rh
 int das_ksp_begin_device(das_solver_t* s, das_ksp_t* ksp, const double* d_rhs, double* d_sol, int fixed) {
     DAS_TRY
     DAS_CHECK(ksp && d_rhs && d_sol, DAS_ERR_ARG, "bad argument");
+    if (ksp->idr) ksp->idr->pending = false;
+    if (idr_selected(s, fixed != 0)) {  // IDR(s) is not resumable step by step: the first das_ksp_advance runs the whole solve
+        need_init(s);
+        IdrWork& I = idr_ws(s, ksp);
+        I.pending = true; I.d_rhs = d_rhs; I.d_x = d_sol; I.rc = 0;
+        ksp->run.reset();
+        return DAS_OK;
+    }
     gmres_begin(s, ksp, d_rhs, d_sol, fixed != 0);
     return DAS_OK;
     DAS_CATCH
 }
 int das_ksp_advance(das_solver_t* s, das_ksp_t* ksp, int iters) {
     DAS_TRY
-    DAS_CHECK(ksp && ksp->run && iters > 0, DAS_ERR_STATE, "das_ksp_begin_device has not been called");
+    DAS_CHECK(ksp && iters > 0, DAS_ERR_STATE, "das_ksp_begin_device has not been called");
+    if (ksp->idr && !ksp->run && ksp->idr->d_x) {
+        IdrWork& I = *ksp->idr;
+        if (I.pending) { I.pending = false; I.rc = run_idrs(s, ksp, I.d_rhs, I.d_x); }
+        return 1;
+    }
+    DAS_CHECK(ksp->run, DAS_ERR_STATE, "das_ksp_begin_device has not been called");
     return gmres_advance(s, ksp, iters) ? 1 : 0;
     DAS_CATCH
 }
 int das_ksp_end(das_solver_t* s, das_ksp_t* ksp) {
     DAS_TRY
-    DAS_CHECK(ksp && ksp->run, DAS_ERR_STATE, "das_ksp_begin_device has not been called");
+    DAS_CHECK(ksp, DAS_ERR_STATE, "das_ksp_begin_device has not been called");
+    if (ksp->idr && !ksp->run && ksp->idr->d_x) {
+        IdrWork& I = *ksp->idr;
+        if (I.pending) { I.pending = false; I.rc = run_idrs(s, ksp, I.d_rhs, I.d_x); }
+        I.d_rhs = nullptr; I.d_x = nullptr;
+        return I.rc;
+    }
+    DAS_CHECK(ksp->run, DAS_ERR_STATE, "das_ksp_begin_device has not been called");
     return gmres_end(s, ksp);
     DAS_CATCH
 }

@@ -134,6 +134,13 @@ Options::Options() {
     // only the hi array - 12 instead of 16 bytes per basis entry and iteration - every vector-building pass reads hi + lo: Arnoldi relation to
     // 2^-48) | "fp32" (compressed basis, short well-conditioned solves only) | "auto" (default): split for bases >= 1 GB with dcgs2, else fp64
     s["amd.krylovBasisPrecision"] = "auto";
+    // Krylov method of the adjoint solve: "gmres" (default; the reference's KSPGMRES) | "idrs": IDR(s) with biorthogonalisation (das_idr_host.hpp) -
+    // 3 s + O(1) work vectors whatever the iteration count, no Krylov basis.  Opt-in: converges like GMRES on the channels, did not converge on the
+    // 2 M-cell wing in 1000 products (profiles/README.md).
+    // Fixed-iteration bench windows and the Newton primal's inner solves keep GMRES; a sharded solve, or amd.gmresDeflation > 0, with "idrs" is an error.
+    s["amd.krylovMethod"] = "gmres";
+    i["amd.idrShadowVectors"] = 4;  // s, 1 .. 8 (clamped to the number of unknowns)
+    i["amd.idrSeed"] = 1;           // seed of the shadow space (a restart takes the next one)
     // DASimpleFoam cell pass as per-face coefficient passes + a per-cell gather pass (k_fcoef, k_bcoef, k_cell2: every internal face evaluated once
     // instead of twice).  Measured at 2 M cells (profiles/r07n_*): dual numbers 489 + 21 + 938 us against 1100 us for the monolithic k_cell, fp64
     // 317 + 30 + 484 against ~700: the gather pass alone costs what the monolith costs - the time is in the per-cell gathers, not in the face

@@ -179,7 +179,7 @@ class KSP:
         return dict(iters=it.value, res0=r0.value, res=r.value, seconds=sec.value)
 
     def status(self):
-        """How the last solve ended: dict(reason 0 tolerance | 1 gmresMaxIters | 2 breakdown / stagnation, nBreakdown, nRefine,
+        """How the last solve ended: dict(reason 0 tolerance | 1 gmresMaxIters | 2 breakdown / stagnation | 3 non-finite residual (IDR(s)), nBreakdown, nRefine,
         sweepGrid, sweepPerXcd)."""
         a = [C.c_int(0) for _ in range(4)]
         check(lib().das_ksp_get_status(self.handle, *[C.byref(x) for x in a]))
@@ -234,6 +234,14 @@ class KSP:
         f, mb, bv = C.c_int(0), C.c_double(0), C.c_double(0)
         check(lib().das_ksp_get_basis_info(self.handle, C.byref(f), C.byref(mb), C.byref(bv)))
         return dict(fp32=bool(f.value & 1), split=bool(f.value & 2), mappedGB=mb.value / 2**30, bytesPerVector=bv.value)
+
+    def idrInfo(self):
+        """IDR(s) of the last solve (amd.krylovMethod "idrs"): dict(s (as used), cycles, restarts, breakdowns, workVectors (3 s + 5: P, G, U,
+        r, z, t, right-hand side, solution), workBytes (8 n each)); all 0 for a KSP that never ran it."""
+        a = [C.c_int(0) for _ in range(5)]
+        wb = C.c_double(0)
+        check(lib().das_ksp_get_idr_info(self.handle, *[C.byref(x) for x in a], C.byref(wb)))
+        return dict(s=a[0].value, cycles=a[1].value, restarts=a[2].value, breakdowns=a[3].value, workVectors=a[4].value, workBytes=wb.value)
 
     def cycleLengths(self):
         """Columns of every closed Arnoldi cycle of the last solve (all but the last equal gmresRestart, DALinearEqn.C:155)."""

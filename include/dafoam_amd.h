@@ -136,6 +136,8 @@ int das_set_option_double(das_solver_t* s, const char* key, double v);
 int das_set_option_int(das_solver_t* s, const char* key, long long v);
 int das_set_option_str(das_solver_t* s, const char* key, const char* v);
 int das_get_option_double(das_solver_t* s, const char* key, double* v);
+/* a string option into buf (cap bytes, always terminated); returns the length of the value */
+int das_get_option_string(das_solver_t* s, const char* key, char* buf, int cap);
 int das_init_solver(das_solver_t* s, int device);
 
 /* ---- sizes: getNLocalAdjointStates/getNLocalCells/getNGlobalCells/getNLocalPoints  pyDASolvers.pyx:305-317 */
@@ -425,6 +427,40 @@ int das_debug_block_lsq(int sv, int m, int ncols, const double* S0, const double
  * device solver runs, for the CPU tier; info4 = {iterations, deflated restarts, plain restarts, breakdowns}, res2 = {|r0|, |r|} */
 int das_debug_gmres_dr_host(long long n, void* A, void* M, void* user, const double* b, double* x, int m, int kdef, double rtol, double atol,
                             long long maxIts, double* hist, int histCap, double* info4, double* res2);
+/* amd.krylovMethod "idrs" (opt-in): IDR(s) with biorthogonalisation (van Gijzen and Sonneveld, ACM TOMS 38, 2011) instead of GMRES in
+ * das_solve_linear_eqn and das_ksp_begin_device / advance / end - 3 s + O(1) work vectors whatever the iteration count, no Krylov basis
+ * (amd.idrShadowVectors s = 1 .. 8, amd.idrSeed).  adjEqnOption.gmresMaxIters bounds the operator products (the true-residual ones
+ * included), das_ksp_get_info's iters is their number and the history holds one residual norm per product; the reported residual is
+ * always the true one.  The solve is not resumable step by step: the first das_ksp_advance after das_ksp_begin_device runs all of it and
+ * returns 1.  Fixed-iteration windows and the Newton primal's inner solves keep GMRES; a sharded solve, or amd.gmresDeflation > 0, is an
+ * error.  das_ksp_get_status: reason 2 = a restarted run did not halve the true residual, 3 = non-finite residual (fail flag set).
+ * das_ksp_get_idr_info: s as used (clamped to n), completed cycles, restarts from the true residual and breakdowns of the last IDR(s)
+ * solve; the work vectors the path holds (3 s + 5: P, G, U, r, z, t, right-hand side, solution) and their bytes (8 n each); all 0 for a KSP
+ * that never ran it */
+int das_ksp_get_idr_info(das_ksp_t* ksp, int* s, int* cycles, int* restarts, int* breakdowns, int* workVectors, double* workBytes);
+/* the IDR(s) iteration itself on HOST vectors from x = 0 (operator A and preconditioner M as callbacks fn(x, y, user)): the very loop the
+ * device solver runs, for the CPU tier; info4 = {products, stop reason, restarts, breakdowns}, res2 = {|r0|, |r|} (true residuals) */
+int das_debug_idrs_host(long long n, void* A, void* M, void* user, const double* b, double* x, int s, int seed, double rtol, double atol, long long maxIts,
+                        double* hist, int histCap, double* info4, double* res2);
+/* exactly one cycle (s + 1 products) of that loop from x = 0 and the state it leaves: x, the recurrence residual r (n), the orthonormal
+ * shadow space P and the spaces G, U (column-major n x s) */
+int das_debug_idr_cycle_host(long long n, void* A, void* M, void* user, const double* b, double* x, int s, int seed, double* r, double* P, double* G,
+                             double* U);
+/* test-only entries of the IDR(s) kernels (tests/test_gpu_idr_kernels.py): caller data up, the solver's launch helpers, data down.
+ * shadow: P (s columns, ld apart) = the raw hash of (seed, row, column); device = 0 fills it on the host (no GPU needed) */
+int das_debug_idr_shadow(long long n, int s, long long ld, int seed, int device, double* P);
+/* k_idr_combine: y[0..n) = a x + sum_{i < m} c_i V_i, V = m columns ld apart in an array of vlen entries; yoff >= 0: y = V + yoff (in
+ * place; y, ylen unused), else y is an array of ylen >= n entries.  V is copied back in both cases */
+int das_debug_idr_combine(long long n, int m, double a, const double* x, double* V, long long ld, long long vlen, const double* c, long long yoff, double* y,
+                          long long ylen);
+/* k_idr_biortho_step + k_reduce: step k on G, U (glen entries each, columns ld apart), r, x (vlen >= n entries each), coef = [alpha (k);
+ * beta]; *rr = r.r afterwards.  All four arrays are copied back */
+int das_debug_idr_biortho_step(long long n, int k, double* G, double* U, long long ld, long long glen, const double* coef, double* r, double* x,
+                               long long vlen, double* rr);
+/* k_idr_smooth_step + k_reduce: r -= omega t, x += omega z on r, x (vlen >= n entries each), P = s columns ld apart in plen entries;
+ * out[0..s) = P^T r, out[s] = r.r afterwards.  r, x and P are copied back */
+int das_debug_idr_smooth_step(long long n, int s, double omega, double* r, const double* t, double* x, const double* z, long long vlen, double* P,
+                              long long ld, long long plen, double* out);
 /* how the last solve ended: reason 0 = tolerance met (KSP_CONVERGED_RTOL/ATOL), 1 = gmresMaxIters reached (KSP_DIVERGED_ITS),
  * 2 = stopped on stagnation after a Krylov breakdown / at the attainable accuracy (PETSc: KSP_CONVERGED_HAPPY_BREAKDOWN /
  * KSP_DIVERGED_BREAKDOWN; the reference's failure flag is still the tolerance rule of DALinearEqn.C:422-434);
