@@ -304,6 +304,14 @@ _SIGS = {
     "das_debug_gmres_dr_host": (C.c_int, [C.c_longlong, _VP, _VP, _VP, c_double_p, c_double_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_longlong, c_double_p, C.c_int,
                                           c_double_p, c_double_p]),
     "das_ksp_get_idr_info": (C.c_int, [_VP, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p]),
+    "das_ksp_get_poly_info": (C.c_int, [_VP, c_int_p, c_int_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), c_int_p, c_int_p, c_int_p, c_double_p,
+                                        c_int_p, c_double_p, c_double_p]),
+    # test-only entries of amd.polyDegree (tests/test_poly_host_cpu.py, tests/test_gpu_poly_kernels.py, tests/test_gpu_poly_gmres.py)
+    "das_debug_poly_roots": (C.c_int, [C.c_int, c_double_p, c_double_p, c_double_p]),
+    "das_debug_poly_apply_host": (C.c_int, [C.c_longlong, _VP, _VP, _VP, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "das_debug_poly_step": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_longlong, C.c_longlong, c_double_p, c_double_p, c_double_p,
+                                      c_double_p, c_double_p]),
+    "das_debug_ksp_poly_apply": (C.c_int, [_VP, _VP, c_double_p, c_double_p]),
     "das_debug_idrs_host": (C.c_int, [C.c_longlong, _VP, _VP, _VP, c_double_p, c_double_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_longlong, c_double_p, C.c_int,
                                       c_double_p, c_double_p]),
     "das_debug_idr_cycle_host": (C.c_int, [C.c_longlong, _VP, _VP, _VP, c_double_p, c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),

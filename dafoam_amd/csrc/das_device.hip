@@ -26,6 +26,8 @@
 #include "das_krylov_debug.hpp"
 #include "das_idr.hpp"
 #include "das_idr_debug.hpp"
+#include "das_poly.hpp"
+#include "das_poly_debug.hpp"
 #include "das_bilu_debug.hpp"
 #include "das_graph_debug.hpp"
 #include "das_color.hpp"
@@ -872,6 +874,8 @@ struct das_ksp {
     DevBuf<double> pcin;      // ... its input: a copy of the vector with the overlap entries gathered from their owners
     std::unique_ptr<struct GmresRun> run;
     std::unique_ptr<struct BlockWork> block;
+    int polyD = 0;  // amd.polyDegree as the current solve runs it (gmres_ws)
+    std::unique_ptr<struct PolyWork> poly;  // amd.polyDegree > 0: the roots of the GMRES polynomial and its three work vectors (first use)
     std::unique_ptr<struct IdrWork> idr;  // amd.krylovMethod "idrs": the 3 s + O(1) work vectors, allocated once per KSP (idr_ws)
     std::vector<double> block_res0, block_res;
     int iters = 0, nrefine = 0, reason = 0, nBreakdown = 0;
@@ -2230,9 +2234,13 @@ static void pc_apply(das_solver* s, das_ksp* k, const double* b, double* x) {
 // adjEqnOption.useMGSO is set (DALinearEqn.C:162-167).  Givens rotations on the host.  The solve is a small state
 // machine (begin / step / end) so that a caller can advance it a given number of iterations (bench.py times a window of
 // iterations deep inside a cycle).
-static void gmres_ws(das_solver* s, das_ksp* k) {
+// polyD > 0 (amd.polyDegree applies to this solve): gmresMaxIters bounds operator products, a column holds polyD of them - never more
+// basis than min(gmresRestart, ceil(maxIters / polyD) + polyD) columns, and no address range beyond it
+static void gmres_ws(das_solver* s, das_ksp* k, int polyD = 0) {
     const long long n = s->n;
     long long restart = std::min<long long>(s->opt.geti("adjEqnOption.gmresRestart"), s->opt.geti("adjEqnOption.gmresMaxIters"));
+    k->polyD = polyD;
+    if (polyD > 0) restart = std::min<long long>(s->opt.geti("adjEqnOption.gmresRestart"), (std::max<long long>(s->opt.geti("adjEqnOption.gmresMaxIters"), 1) + polyD - 1) / polyD + polyD);
     long long budget = (long long)(32.0 * 1024 * 1024 * 1024);
     auto it = s->opt.i.find("amd.maxKrylovBytes");
     if (it != s->opt.i.end()) budget = it->second;
@@ -2245,7 +2253,7 @@ static void gmres_ws(das_solver* s, das_ksp* k) {
     long long wantVec = std::max<long long>(restart + 2, std::min<long long>(maxVec, 1002));
     // the over-reservation is free only on the virtual-memory path (>= 4 GB, VmBuf::reserve); below that the range is one hipMalloc of
     // real memory: then exactly what this restart needs (~2.8 GB per KSP on small cases otherwise)
-    if ((size_t)wantVec * (size_t)nr * sizeof(double) < ((size_t)4 << 30) || getenv("DAS_NO_VMM")) wantVec = restart + 2;
+    if ((size_t)wantVec * (size_t)nr * sizeof(double) < ((size_t)4 << 30) || getenv("DAS_NO_VMM") || polyD > 0) wantVec = restart + 2;
     if (k->V.n < (size_t)((restart + 2) * nr) || k->Vn != n) {
         k->V.reserve((size_t)(wantVec * nr));  // (sized for fp64 vectors whatever the storage type of this solve: switching needs no new range)
         k->Vn = n;
@@ -2301,7 +2309,9 @@ static inline long long basis_ld(das_solver* s, das_ksp* k) { return k->split ? 
 // false: the device cannot hold that many vectors (gmres_advance then closes the cycle: the mapped part is the restart length)
 static inline bool gmres_map_basis(das_solver* s, das_ksp* k, long long nvec) {
     const long long per = basis_ld(s, k) / (k->vf32 ? 2 : 1);  // fp64 elements of the range one basis vector occupies
-    k->V.request((size_t)((nvec + 64) * per));
+    // (amd.polyDegree: nothing is mapped beyond the column bound of gmres_ws, also in a range an earlier solve reserved)
+    const long long ahead = k->polyD > 0 ? std::min<long long>(nvec + 64, (long long)k->restart + 2) : nvec + 64;
+    k->V.request((size_t)(ahead * per));
     return k->V.try_ensure((size_t)(nvec * per));
 }
 // slot j of the basis in its storage type
@@ -2494,7 +2504,36 @@ struct GmresRun {
     bool stalled = false;
     int nonImproving = 0, nBreakdown = 0;
     double betaStart = 0;         // true residual norm at the start of the open cycle
+    // polynomial preconditioning (amd.polyDegree = polyD > 0, das_poly_host.hpp): the first cycle is closed after polyD columns (cap) and
+    // gives the polynomial; from then on a column is w = B p(B) v (polyOn).  prods counts operator products - what gmresMaxIters bounds
+    // and das_ksp_get_info reports in this mode; its stays the number of Arnoldi columns
+    int cap = 0;                  // columns at which the open cycle is closed: m, or polyD for the generating cycle
+    int polyD = 0;
+    bool polyGen = false, polyTried = false, polyOn = false, budgetOut = false, nonFinite = false;
+    long long prods = 0;
 };
+// the GMRES polynomial of a KSP (amd.polyDegree): ordered roots (a pair once, im > 0), the work vectors of the root walk, and the figures
+// of the last solve (das_ksp_get_poly_info)
+struct PolyWork {
+    long long n = 0;
+    DevBuf<double> prod, poly, tmp;  // allocated when the first polynomial is built, never without one
+    int nroots = 0;
+    double re[POLY_MAX_DEGREE] = {0}, im[POLY_MAX_DEGREE] = {0};
+    int degree = 0, nPairs = 0, generated = 0, fallback = 0;
+    long long products = 0, columns = 0, genColumns = 0;  // columns: Arnoldi columns after the generating cycle's genColumns
+    int work_vectors() const { return prod.n ? 3 : 0; }
+};
+// amd.polyDegree, validated at every solve: the degree this solve runs with.  Fixed-iteration bench windows and the Newton primal's
+// inner solves keep plain GMRES silently; IDR(s), deflated restarting or several ranks on top are errors
+static int poly_degree(das_solver* s, bool fixed) {
+    const long long d = s->opt.geti("amd.polyDegree");
+    DAS_CHECK(d >= 0 && d <= POLY_MAX_DEGREE, DAS_ERR_ARG, "amd.polyDegree " + std::to_string(d) + " is outside 0 .. 16");
+    if (d == 0 || fixed || s->fwd.on) return 0;
+    DAS_CHECK(s->opt.gets("amd.krylovMethod") != "idrs", DAS_ERR_ARG, "amd.polyDegree > 0 belongs to GMRES: not with amd.krylovMethod \"idrs\"");
+    DAS_CHECK(!s->halo.active && !s->halo_cb, DAS_ERR_ARG, "amd.polyDegree > 0 is single-rank (run the sharded solve without it)");
+    { auto it = s->opt.i.find("amd.gmresDeflation"); DAS_CHECK(it == s->opt.i.end() || it->second <= 0, DAS_ERR_ARG, "amd.gmresDeflation > 0 cannot be combined with amd.polyDegree > 0"); }
+    return (int)d;
+}
 static bool gmres_trace() { static const bool on = [] { const char* e = getenv("DAS_GMRES_TRACE"); return e && *e && *e != '0'; }(); return on; }
 
 static void gmres_true_residual(das_solver* s, das_ksp* k, GmresRun& G, bool haveGuess) {
@@ -2502,6 +2541,7 @@ static void gmres_true_residual(das_solver* s, das_ksp* k, GmresRun& G, bool hav
     hipStream_t st = s->stream;
     if (haveGuess) {
         apply_operator(s, G.d_x, k->r.p);
+        G.prods++;
         hipLaunchKernelGGL(k_axpby, dim3(nblk(n, 256)), dim3(256), 0, st, n, 1.0, G.d_rhs, -1.0, k->r.p);
     } else {
         DAS_HIP(hipMemsetAsync(G.d_x, 0, n * sizeof(double), st));
@@ -2513,11 +2553,11 @@ static void gmres_true_residual(das_solver* s, das_ksp* k, GmresRun& G, bool hav
 
 // what every solve starts with: workspace, a fresh GmresRun with the options read, the true residual of the start vector, the target.
 // `deflated`: run_gmres_dr - fp64 basis, no Hessenberg arrays (gmres_dr_loop keeps its own), the cycle lengths are left alone
-static GmresRun& gmres_begin(das_solver* s, das_ksp* k, const double* d_rhs, double* d_x, bool fixed, bool deflated = false) {
+static GmresRun& gmres_begin(das_solver* s, das_ksp* k, const double* d_rhs, double* d_x, bool fixed, bool deflated = false, int polyD = 0) {
     need_init(s);
     DAS_CHECK(s->op || s->fwd.on, DAS_ERR_STATE, "initializedRdWTMatrixFree() must be called before solveLinearEqn()");
     if (deflated) DAS_CHECK(!s->halo.active && !s->halo_cb, DAS_ERR_ARG, "amd.gmresDeflation is single-rank (the restart's small dense algebra is not replicated across ranks yet)");
-    gmres_ws(s, k);
+    gmres_ws(s, k, polyD);
     if (deflated) { k->vf32 = false; k->split = false; }  // the deflated solver keeps its (short) basis in fp64
     if (k->useBilu) bilu_clear_abort(k->bilu, s->stream);
     if (!k->run) k->run.reset(new GmresRun);
@@ -2526,6 +2566,14 @@ static GmresRun& gmres_begin(das_solver* s, das_ksp* k, const double* d_rhs, dou
     G = GmresRun();
     if (deflated) DAS_CHECK(m >= 4, DAS_ERR_ARG, "amd.gmresDeflation needs gmresRestart >= 4");
     G.m = m; G.fixed = fixed; G.d_rhs = d_rhs; G.d_x = d_x;
+    G.cap = m; G.polyD = std::min(polyD, m);  // (a restart shorter than the degree gives a polynomial of the restart's degree)
+    if (polyD > 0) {
+        if (!k->poly) k->poly.reset(new PolyWork);
+        PolyWork& P = *k->poly;
+        P.nroots = 0; P.degree = 0; P.nPairs = 0; P.generated = 0; P.fallback = 0; P.products = 0; P.columns = 0; P.genColumns = 0;
+    } else if (k->poly && !fixed && !deflated) {
+        k->poly.reset();  // a solve without the option: what a KSP that never ran it reports (a bench window leaves the figures alone)
+    }
     G.maxIts = s->opt.geti("adjEqnOption.gmresMaxIters");
     G.rtol = s->opt.getd("adjEqnOption.gmresRelTol"); G.atol = s->opt.getd("adjEqnOption.gmresAbsTol");
     G.hh.assign(2 * (m + 2), 0.0); G.h2.assign(2 * (m + 2), 0.0);
@@ -2535,6 +2583,7 @@ static GmresRun& gmres_begin(das_solver* s, das_ksp* k, const double* d_rhs, dou
         DAS_CHECK(orth == "dcgs2" || orth == "cgs", DAS_ERR_ARG, "amd.gmresOrthogonalization \"" + orth + "\" is not one of dcgs2 | cgs");
         G.dcgs2 = orth == "dcgs2" && s->opt.geti("adjEqnOption.useMGSO") == 0;
         if (G.dcgs2) { G.Hraw.assign((size_t)(m + 1) * m, 0.0); G.h1.assign(m + 2, 0.0); }
+        else if (G.polyD > 0) G.Hraw.assign((size_t)(m + 1) * m, 0.0);  // the generating cycle keeps its unrotated Hessenberg matrix
         k->cycleLens.clear();
     }
     k->nrefine = 0; k->hist.clear();
@@ -2569,6 +2618,9 @@ static void gmres_cycle_start(das_solver* s, das_ksp* k) {
     G.open = true;
     G.earlyClose = false;
     G.betaStart = G.beta;
+    G.polyGen = G.polyD > 0 && !G.polyTried;  // the first cycle of the solve gives the polynomial
+    G.polyTried = true;
+    G.cap = G.polyGen ? G.polyD : G.m;
 }
 // the basis vector in slot j as the fp64 input of the preconditioner (fp32 basis: converted into the staging vector)
 template <class VT>
@@ -2576,6 +2628,54 @@ static const double* basis_as_double(das_solver* s, das_ksp* k, long long j) {
     if (sizeof(VT) == sizeof(double)) return reinterpret_cast<const double*>(basis_slot<VT>(s, k, j));
     launch_scale_to(s->stream, s->n, 1.0, (const VT*)basis_slot<VT>(s, k, j), (double*)k->ustage.p, (const float*)basis_lo(s, k, j), (float*)nullptr);
     return k->ustage.p;
+}
+static das_dense_eig_fn g_dense_eig = nullptr;  // das_set_dense_eig_callback: the restart of GMRES-DR and the roots of the GMRES polynomial
+// ---- the polynomial apply t = p(B) v on the device: poly_walk of das_poly_host.hpp over the kernels of das_poly.hpp ----------------
+// v must be none of k->z, k->w (the scratch of the products) and is not written; the result is P.poly
+namespace {
+struct PolyDeviceOps {
+    das_solver* s; das_ksp* k; PolyWork* P; const double* v;
+    void product(bool fromTmp, bool first) {
+        pc_apply_full(s, k, fromTmp ? P->tmp.p : (first ? v : P->prod.p), k->z.p);
+        apply_operator(s, k->z.p, k->w.p);
+    }
+    void real_step(bool first, bool last, double th) { launch_poly_real(s->stream, s->n, first, last, th, v, k->w.p, P->poly.p, P->prod.p); }
+    void pair_first(bool first, double twoa, double m2) { launch_poly_pair_first(s->stream, s->n, first, twoa, m2, v, P->prod.p, k->w.p, P->poly.p, P->tmp.p); }
+    void pair_second(bool first, double m2) { launch_poly_pair_second(s->stream, s->n, first, m2, v, k->w.p, P->prod.p); }
+};
+}  // namespace
+static void poly_apply_device(das_solver* s, das_ksp* k, const double* v) {
+    PolyWork& P = *k->poly;
+    PolyDeviceOps ops{s, k, &P, v};
+    poly_walk(ops, P.nroots, P.re, P.im);
+}
+// the roots of the generating cycle (j = polyD columns, unrotated Hessenberg matrix in G.Hraw) and the work vectors; no usable roots:
+// the solve goes on without a polynomial and reports the fallback
+static void poly_generate(das_solver* s, das_ksp* k, int j) {
+    GmresRun& G = *k->run;
+    PolyWork& P = *k->poly;
+    P.nroots = poly_roots_host(g_dense_eig, j, G.Hraw.data(), G.m, P.re, P.im, &P.nPairs);
+    if (P.nroots == 0) {
+        P.fallback = 1; P.nPairs = 0;
+        if (s->opt.geti("debug")) fprintf(stderr, "[dafoam_amd] amd.polyDegree %d: no usable harmonic Ritz values (or no dense eigen-solver callback) - this solve runs without the polynomial\n", j);
+        return;
+    }
+    if (P.n != s->n || !P.prod.n) { P.n = s->n; P.prod.alloc(s->n); P.poly.alloc(s->n); P.tmp.alloc(s->n); }
+    P.degree = j; P.generated = 1;
+    G.polyOn = true;
+}
+// the ONE place where the Krylov operator meets the preconditioner: z = M^-1 p(B) v (p = 1 without a polynomial) in k->z, then
+// w = A z unless w is null (the closing step of a cycle).  v is none of k->z, k->w.  Counts the operator products
+static void gmres_precond_product(das_solver* s, das_ksp* k, const double* v, double* w) {
+    GmresRun& G = *k->run;
+    const double* t = v;
+    if (G.polyOn) {
+        poly_apply_device(s, k, v);
+        t = k->poly->poly.p;
+        G.prods += k->poly->degree - 1;
+    }
+    pc_apply_full(s, k, t, k->z.p);
+    if (w) { apply_operator(s, k->z.p, w); G.prods++; }
 }
 // one Arnoldi step; returns the recurrence residual norm
 template <class VT>
@@ -2592,8 +2692,7 @@ static double gmres_iter_t(das_solver* s, das_ksp* k) {
     std::vector<double>&H = G.H, &hh = G.hh, &h2 = G.h2, &cs = G.cs, &sn = G.sn, &g = G.g;
     VT* const Vb = basis_slot<VT>(s, k, 0);
     const long long ld = basis_ld(s, k);
-    pc_apply_full(s, k, basis_as_double<VT>(s, k, j), k->z.p);
-    apply_operator(s, k->z.p, k->w.p);
+    gmres_precond_product(s, k, basis_as_double<VT>(s, k, j), k->w.p);
     double hn;
     std::fill(h2.begin(), h2.end(), 0.0);
     if (mgs) {
@@ -2633,6 +2732,7 @@ static double gmres_iter_t(das_solver* s, das_ksp* k) {
     if (!mgs && !(hn > GMRES_BREAKDOWN_TOL * std::sqrt(std::max(hh[j + 1], 0.0)))) { hn = 0.0; G.nBreakdown++; }  // happy breakdown (hh[j+1] = |A M^-1 v_j|^2)
     for (int i = 0; i <= j; i++) H[(size_t)i * m + j] = hh[i] + h2[i];
     H[(size_t)(j + 1) * m + j] = hn;
+    if (G.polyGen) for (int i = 0; i <= j + 1; i++) G.Hraw[(size_t)i * m + j] = H[(size_t)i * m + j];
     if (hn > 0.0) launch_scale_to(st, n, 1.0 / hn, (const double*)k->w.p, Vb + (long long)(j + 1) * ld, (const float*)nullptr, basis_lo(s, k, j + 1));
     gmres_rotate_column(H, cs, sn, g, m, j);
     G.its++;
@@ -2670,8 +2770,7 @@ static double gmres_iter_dcgs2(das_solver* s, das_ksp* k) {
     VT* const Vb = basis_slot<VT>(s, k, 0);
     const long long ld = basis_ld(s, k);
     VT* u = Vb + (long long)j * ld;
-    pc_apply_full(s, k, basis_as_double<VT>(s, k, j), k->z.p);
-    apply_operator(s, k->z.p, k->w.p);
+    gmres_precond_product(s, k, basis_as_double<VT>(s, k, j), k->w.p);
     const int K = j + 1;
     launch_multidot2<VT>(st, n, K, (const VT*)Vb, ld, (const VT*)u, (const double*)k->w.p, k->partial.p, k->hdev.p);
     rank_allreduce(s, k->hdev.p, 2 * K, st);
@@ -2714,6 +2813,7 @@ static double gmres_iter_dcgs2(das_solver* s, das_ksp* k) {
     // happy breakdown: what is left of B q_{j-1} after the projections is rounding noise (GMRES_BREAKDOWN_TOL).  The column
     // is completed with a ZERO sub-diagonal - the recurrence residual drops to zero - and the cycle is closed; whether the
     // solve is over is decided on the recomputed true residual (gmres_advance)
+    if (G.polyD > 0 && !std::isfinite(al2)) { G.nonFinite = true; return al2; }  // (gmres_advance ends the solve: reason 3)
     const bool breakdown = !(al2 > GMRES_BREAKDOWN_TOL * GMRES_BREAKDOWN_TOL * normBq2);
     const double al = breakdown ? 0.0 : std::sqrt(al2);
     double res = k->hist.back();
@@ -2737,7 +2837,7 @@ static double gmres_iter_dcgs2(das_solver* s, das_ksp* k) {
             return res;
         }
         const bool stop = !G.fixed && (res <= G.recTarget || G.its >= G.maxIts);
-        if (stop || G.j >= m) return res;            // the cycle is closed by the caller: no further basis vector needed
+        if (stop || G.j >= G.cap) return res;        // the cycle is closed by the caller: no further basis vector needed
     }
     const double gam = num / al2;
     // coefficients of the fused update: s, then c = t - gamma s
@@ -2765,11 +2865,17 @@ static void gmres_cycle_end_t(das_solver* s, das_ksp* k) {
     hipStream_t st = s->stream;
     back_substitute(j, G.H.data(), m, 1, 1, G.g.data(), G.y.data());
     DAS_HIP(hipMemcpyAsync(k->hdev.p, G.y.data(), j * sizeof(double), hipMemcpyHostToDevice, st));
-    launch_lincomb(st, n, j, (const VT*)basis_slot<VT>(s, k, 0), basis_ld(s, k), (const double*)k->hdev.p, (double*)k->w.p, (const float*)basis_lo(s, k, 0));
-    pc_apply_full(s, k, k->w.p, k->z.p);
+    // V y: into k->w, or - the polynomial's products use k->w - into k->r, which the true residual below rewrites anyway
+    double* const vy = G.polyOn ? k->r.p : k->w.p;
+    launch_lincomb(st, n, j, (const VT*)basis_slot<VT>(s, k, 0), basis_ld(s, k), (const double*)k->hdev.p, vy, (const float*)basis_lo(s, k, 0));
+    gmres_precond_product(s, k, vy, nullptr);
     hipLaunchKernelGGL(k_axpby, dim3(nblk(n, B)), dim3(B), 0, st, n, 1.0, k->z.p, 1.0, G.d_x);
     const double recRes = k->hist.back();
     gmres_true_residual(s, k, G, true);
+    if (G.polyGen) {  // the generating cycle: a polynomial only from a cycle that ran its polyD columns without a breakdown
+        if (j == G.polyD && !G.earlyClose) poly_generate(s, k, j);
+        G.polyGen = false;
+    }
     k->hist.back() = G.beta;
     k->cycleLens.push_back(j);
     G.open = false;
@@ -2784,19 +2890,31 @@ static void gmres_cycle_end(das_solver* s, das_ksp* k) {
     if (k->vf32) gmres_cycle_end_t<float>(s, k); else gmres_cycle_end_t<double>(s, k);
 }
 // advance by up to `nsteps` iterations (cycles are opened / closed as needed); returns true when the solve is over
-static bool gmres_over(const GmresRun& G) { return !G.fixed && !G.open && (G.beta <= G.target || G.its >= G.maxIts || G.stalled); }
+static bool gmres_over(const GmresRun& G) { return !G.fixed && !G.open && (G.beta <= G.target || G.its >= G.maxIts || G.stalled || G.budgetOut || G.nonFinite); }
 static bool gmres_advance(das_solver* s, das_ksp* k, long long nsteps) {
     GmresRun& G = *k->run;
     for (long long t = 0; t < nsteps; t++) {
         if (gmres_over(G)) return true;
         if (G.beta == 0.0) return true;
+        if (G.polyD > 0) {
+            // gmresMaxIters bounds operator products: a column (polyD of them once the polynomial is there) is started only if the budget
+            // also covers closing its cycle (the polynomial in x += M^-1 p(B) V y, and the true residual); the delayed scheme completes the
+            // first column of a cycle with its second product
+            const long long per = G.polyOn ? k->poly->degree : 1, closing = per;
+            const bool lagged = G.dcgs2 && !G.safeOrth;
+            if (G.prods + (!G.open && lagged ? 2 : 1) * per + closing > G.maxIts) {
+                if (G.open) gmres_cycle_end(s, k);
+                G.budgetOut = true;
+                return true;
+            }
+        }
         if (!G.open) gmres_cycle_start(s, k);
         // the step writes basis slots up to (pending vector) + 2: map them; if the device has no memory left for them the cycle
         // ends here - the mapped part of the basis is the restart length from now on
         // (a cycle of m columns holds m + 1 basis vectors - with the delayed scheme the pending vector of the last step sits in slot
         // m and nothing is written behind it - so the request never exceeds the restart + 2 slots gmres_ws reserved: round 4 asked
         // for pend + 3 = restart + 3 at the last step of a cycle and closed every malloc-path cycle one column early)
-        const long long wantSlots = std::min<long long>(((G.dcgs2 && !G.safeOrth) ? G.pend : G.j) + 3, (long long)G.m + 2);
+        const long long wantSlots = std::min<long long>(((G.dcgs2 && !G.safeOrth) ? G.pend : G.j) + 3, (long long)G.cap + 2);
         if (!gmres_map_basis(s, k, wantSlots)) {
             if (k->V.workerError.empty())
                 k->V.workerError = "request for " + std::to_string(wantSlots) + " basis vectors beyond the reserved range of " + std::to_string(k->V.n / (size_t)std::max<long long>(1, s->n)) + " (internal)";
@@ -2808,8 +2926,14 @@ static bool gmres_advance(das_solver* s, das_ksp* k, long long nsteps) {
             continue;
         }
         const double res = gmres_iter(s, k);
+        if (G.polyD > 0 && (G.nonFinite || !std::isfinite(res))) {
+            // a non-finite value out of the operator, the preconditioner or the polynomial: x keeps the last closed cycle's update
+            if (G.nonFinite) k->hist.push_back(res);  // (the step returned before it recorded anything)
+            G.nonFinite = true; G.open = false;
+            return true;
+        }
         const bool stop = !G.fixed && (res <= G.recTarget || G.its >= G.maxIts);
-        if (G.j < 0 || G.j >= G.m || stop) {
+        if (G.j < 0 || G.j >= G.cap || stop) {
             // a cycle that ends on a breakdown / lost orthogonality, or on a recurrence residual below the target, should
             // leave a TRUE residual below the target.  If it does not, the next cycle works on the rounding level of this
             // system; it may still gain (iterative refinement), but two such cycles in a row that do not halve the true
@@ -2828,16 +2952,22 @@ static int gmres_end(das_solver* s, das_ksp* k) {
     GmresRun& G = *k->run;
     if (G.open) gmres_cycle_end(s, k);
     gmres_finish_check(s, k);
-    k->iters = (int)G.its;
+    k->iters = (int)(G.polyD > 0 ? G.prods : G.its);
     k->nBreakdown = G.nBreakdown;
     k->res = k->hist.back();
-    k->reason = G.beta <= G.target ? 0 : (G.stalled ? 2 : 1);
+    k->reason = G.nonFinite ? 3 : (G.beta <= G.target ? 0 : (G.stalled ? 2 : 1));
     k->seconds = wall_seconds() - G.t0;
+    if (G.polyD > 0) {
+        k->poly->products = G.prods;
+        k->poly->genColumns = k->cycleLens.empty() ? G.its : std::min<long long>(G.its, k->cycleLens[0]);
+        k->poly->columns = G.its - k->poly->genColumns;
+        if (s->opt.geti("debug")) fprintf(stderr, "[dafoam_amd] polynomial GMRES (degree %d%s): %lld products, %lld columns, |r| %.3e -> %.3e (reason %d)\n", k->poly->degree, k->poly->fallback ? ", fallback" : "", G.prods, G.its, k->res0, k->res, k->reason);
+        if (G.nonFinite) return 1;  // a non-finite residual never passes the tolerance rule
+    }
     return gmres_failed(k->res, k->res0, G.rtol, G.atol, s->opt.getd("adjEqnOption.gmresTolDiff"));
 }
 
 // ---- GMRES with deflated restarting (amd.gmresDeflation): gmres_dr_loop of das_gmres_host.hpp over the device's vector operations; dense-eigen callback
-static das_dense_eig_fn g_dense_eig = nullptr;
 namespace {
 struct DrDeviceOps {
     das_solver* s; das_ksp* k; GmresRun* G; int kdefMax;
@@ -2912,6 +3042,7 @@ static int run_gmres_dr(das_solver* s, das_ksp* k, const double* d_rhs, double* 
 static bool idr_selected(das_solver* s, bool fixed);
 static int run_idrs(das_solver* s, das_ksp* k, const double* d_rhs, double* d_x);
 static int run_gmres(das_solver* s, das_ksp* k, const double* d_rhs, double* d_x, int fixed_iters) {
+    const int polyD = poly_degree(s, fixed_iters > 0);  // opt-in: amd.polyDegree
     if (idr_selected(s, fixed_iters > 0)) return run_idrs(s, k, d_rhs, d_x);  // opt-in: amd.krylovMethod "idrs"
     {   // opt-in: deflated restarting (never for the fixed-iteration bench windows, the Newton primal's inner solves or several ranks)
         auto it = s->opt.i.find("amd.gmresDeflation");
@@ -2923,7 +3054,7 @@ static int run_gmres(das_solver* s, das_ksp* k, const double* d_rhs, double* d_x
             told = true;
         }
     }
-    gmres_begin(s, k, d_rhs, d_x, fixed_iters > 0);
+    gmres_begin(s, k, d_rhs, d_x, fixed_iters > 0, /* deflated */ false, polyD);
     if (fixed_iters > 0) gmres_advance(s, k, fixed_iters);
     else while (!gmres_advance(s, k, 1 << 20)) {}
     return gmres_end(s, k);
@@ -5228,8 +5359,9 @@ int das_solve_linear_eqn(das_solver_t* s, das_ksp_t* ksp, const double* rhs, dou
     DAS_TRY
     need_init(s);
     DAS_CHECK(ksp && rhs && sol, DAS_ERR_ARG, "null argument");
+    const int polyD = poly_degree(s, false);
     if (idr_selected(s, false)) idr_ws(s, ksp);  // (never the Krylov basis)
-    else gmres_ws(s, ksp);
+    else gmres_ws(s, ksp, polyD);
     ksp->bdev.upload(rhs, s->n);
     ksp->xdev.upload(sol, s->n);
     int rc = run_gmres(s, ksp, ksp->bdev.p, ksp->xdev.p, 0);
@@ -5245,6 +5377,7 @@ int das_solve_linear_eqn_block(das_solver_t* s, das_ksp_t* ksp, int nrhs, const 
     DAS_TRY
     need_init(s);
     DAS_CHECK(ksp && rhs && sol && nrhs >= 1, DAS_ERR_ARG, "bad argument");
+    DAS_CHECK(poly_degree(s, false) == 0, DAS_ERR_ARG, "amd.polyDegree > 0 is not available for a block (multi-right-hand-side) solve");
     DevBuf<double> dB((size_t)nrhs * s->n), dX((size_t)nrhs * s->n);
     dB.upload(rhs, (size_t)nrhs * s->n);
     int rc = run_block_gmres(s, ksp, nrhs, dB.p, dX.p);
@@ -5499,6 +5632,71 @@ int das_debug_idr_smooth_step(long long n, int sv, double omega, double* r, cons
     return DAS_OK;
     DAS_CATCH
 }
+// ---- amd.polyDegree: the figures of the last solve, and the test-only entries (bodies: das_poly_host.hpp, das_poly_debug.hpp) --------
+int das_ksp_get_poly_info(das_ksp_t* k, int* degree, int* nComplexPairs, long long* products, long long* columns, long long* generatingColumns, int* generated,
+                          int* fallback, int* workVectors, double* workBytes, int* nRoots, double* re, double* im) {
+    DAS_TRY
+    DAS_CHECK(k, DAS_ERR_ARG, "null ksp handle");
+    const PolyWork* P = k->poly.get();
+    if (degree) *degree = P ? P->degree : 0;
+    if (nComplexPairs) *nComplexPairs = P ? P->nPairs : 0;
+    if (products) *products = P ? P->products : 0;
+    if (columns) *columns = P ? P->columns : 0;
+    if (generatingColumns) *generatingColumns = P ? P->genColumns : 0;
+    if (generated) *generated = P ? P->generated : 0;
+    if (fallback) *fallback = P ? P->fallback : 0;
+    if (workVectors) *workVectors = P ? P->work_vectors() : 0;
+    if (workBytes) *workBytes = P ? (double)P->work_vectors() * 8.0 * (double)P->n : 0.0;
+    if (nRoots) *nRoots = P ? P->nroots : 0;
+    for (int i = 0; P && i < P->nroots; i++) { if (re) re[i] = P->re[i]; if (im) im[i] = P->im[i]; }
+    return DAS_OK;
+    DAS_CATCH
+}
+// the ordered roots of a (d + 1) x d Hessenberg matrix (row-major): the number of entries written (real roots and pairs), 0 = fallback
+int das_debug_poly_roots(int d, const double* Hbar, double* re, double* im) {
+    DAS_TRY
+    DAS_CHECK(d >= 1 && d <= POLY_MAX_DEGREE && Hbar && re && im, DAS_ERR_ARG, "bad argument (degree 1 to 16)");
+    return poly_roots_host(g_dense_eig, d, Hbar, d, re, im, nullptr);
+    DAS_CATCH
+}
+// out = p(B) v, B = A M^-1 as callbacks, by the root walk the device solver runs (poly_walk) on host vectors
+int das_debug_poly_apply_host(long long n, void* A, void* M, void* user, int nroots, const double* re, const double* im, const double* v, double* out) {
+    DAS_TRY
+    DAS_CHECK(n > 0 && A && M && re && im && v && out && nroots >= 1 && nroots <= POLY_MAX_DEGREE, DAS_ERR_ARG, "bad argument (1 to 16 roots)");
+    DAS_CHECK(poly_degree_of(nroots, im) <= POLY_MAX_DEGREE, DAS_ERR_ARG, "the degree (real roots + 2 x pairs) is above 16");
+    for (int i = 0; i < nroots; i++) DAS_CHECK(im[i] >= 0.0 && (re[i] != 0.0 || im[i] != 0.0), DAS_ERR_ARG, "a root is zero, or a pair is not given by its member with im > 0");
+    PolyHostOps ops(n, (das_host_apply_fn)A, (das_host_apply_fn)M, user, v);
+    poly_walk(ops, nroots, re, im);
+    std::copy(ops.poly.begin(), ops.poly.end(), out);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_poly_step(long long n, int kind, int first, int last, double re, double im, long long off, long long len, double* v, double* w, double* prod, double* poly,
+                        double* tmp) {
+    DAS_TRY
+    DAS_CHECK(v && w && prod && poly && tmp, DAS_ERR_ARG, "null argument");
+    DAS_CHECK(n > 0 && off >= 0 && len >= off + n && kind >= POLY_STEP_REAL && kind <= POLY_STEP_PAIR_SECOND, DAS_ERR_ARG, "das_debug_poly_step: bad shape or kind");
+    debug_poly_step(n, kind, first != 0, last != 0, re, im, off, len, v, w, prod, poly, tmp);
+    return DAS_OK;
+    DAS_CATCH
+}
+// out = p(B) v on the device with the roots of this KSP's last solve (operator and preconditioner as that solve had them)
+int das_debug_ksp_poly_apply(das_solver_t* s, das_ksp_t* k, const double* v, double* out) {
+    DAS_TRY
+    need_init(s);
+    DAS_CHECK(k && v && out, DAS_ERR_ARG, "null argument");
+    DAS_CHECK(s->op, DAS_ERR_STATE, "initializedRdWTMatrixFree() must be called first");
+    DAS_CHECK(k->poly && k->poly->nroots > 0 && k->poly->n == s->n && k->w.n == (size_t)s->n && k->z.n == (size_t)s->n, DAS_ERR_STATE, "this KSP's last solve built no polynomial (amd.polyDegree)");
+    DevBuf<double> dv(s->n);
+    dv.upload(v, s->n);
+    DAS_HIP(hipDeviceSynchronize());
+    if (k->useBilu) bilu_clear_abort(k->bilu, s->stream);
+    poly_apply_device(s, k, dv.p);
+    gmres_finish_check(s, k);
+    k->poly->poly.download(out, s->n);
+    return DAS_OK;
+    DAS_CATCH
+}
 int das_ksp_get_n_refine(das_ksp_t* k) { return k ? k->nrefine : -1; }
 int das_ksp_get_status(das_ksp_t* k, int* reason, int* nBreakdown, int* nSweepGrid, int* sweepPerXcd) {
     DAS_TRY
@@ -5599,6 +5797,7 @@ int das_ksp_run_fixed_device(das_solver_t* s, das_ksp_t* ksp, const double* d_rh
 int das_ksp_begin_device(das_solver_t* s, das_ksp_t* ksp, const double* d_rhs, double* d_sol, int fixed) {
     DAS_TRY
     DAS_CHECK(ksp && d_rhs && d_sol, DAS_ERR_ARG, "bad argument");
+    const int polyD = poly_degree(s, fixed != 0);
     if (ksp->idr) ksp->idr->pending = false;
     if (idr_selected(s, fixed != 0)) {  // IDR(s) is not resumable step by step: the first das_ksp_advance runs the whole solve
         need_init(s);
@@ -5607,7 +5806,7 @@ int das_ksp_begin_device(das_solver_t* s, das_ksp_t* ksp, const double* d_rhs, d
         ksp->run.reset();
         return DAS_OK;
     }
-    gmres_begin(s, ksp, d_rhs, d_sol, fixed != 0);
+    gmres_begin(s, ksp, d_rhs, d_sol, fixed != 0, /* deflated */ false, polyD);
     return DAS_OK;
     DAS_CATCH
 }

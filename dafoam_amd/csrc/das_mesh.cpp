@@ -141,6 +141,12 @@ Options::Options() {
     s["amd.krylovMethod"] = "gmres";
     i["amd.idrShadowVectors"] = 4;  // s, 1 .. 8 (clamped to the number of unknowns)
     i["amd.idrSeed"] = 1;           // seed of the shadow space (a restart takes the next one)
+    // polynomial preconditioning of the GMRES solve (das_poly_host.hpp): d = 0 (default) off | 1 .. 16: the first cycle is closed after d columns, its
+    // GMRES polynomial p (roots: the harmonic Ritz values) becomes part of the operator, A M^-1 p(A M^-1) - a column then holds d operator products and
+    // nothing but element-wise updates between them.  gmresMaxIters bounds operator products, gmresRestart basis columns.  Opt-in: follows
+    // GMRES on the channels (fewer columns, 1.5 - 2.6 x the products), did not converge on the 2 M-cell wing in 1000 products (profiles/README.md).  Fixed-iteration bench windows and the Newton primal's inner solves ignore it; "idrs", amd.gmresDeflation > 0, a block or a
+    // sharded solve with it is an error.
+    i["amd.polyDegree"] = 0;
     // DASimpleFoam cell pass as per-face coefficient passes + a per-cell gather pass (k_fcoef, k_bcoef, k_cell2: every internal face evaluated once
     // instead of twice).  Measured at 2 M cells (profiles/r07n_*): dual numbers 489 + 21 + 938 us against 1100 us for the monolithic k_cell, fp64
     // 317 + 30 + 484 against ~700: the gather pass alone costs what the monolith costs - the time is in the per-cell gathers, not in the face

@@ -134,7 +134,7 @@ class DAOPTION(object):
         self.unsteadyCompOutput = {}  # :661
         # MI355X-specific additions (not in the reference)
         self.amd = {"pcType": "bilu", "pcCoarseAggregates": -1, "pcCoarseField": "p", "pcCoarseMode": "deflated", "pcUpwindBlend": 0.5, "pcBlockCells": 1024, "jacMode": 1, "pcJacMode": 0, "pcFactorFP32": 0, "cgsAlwaysRefine": 0, "gmresOrthogonalization": "dcgs2", "setupThreads": 32,
-                    "krylovMethod": "gmres", "idrShadowVectors": 4, "idrSeed": 1}
+                    "krylovMethod": "gmres", "idrShadowVectors": 4, "idrSeed": 1, "polyDegree": 0}
         self.amdDevice = 0
         ## directory of the dRdWColoring_<nProcs>.bin cache (the reference keeps it in the case directory,
         ## DAJacCon.C:1886-2019); "" = do not cache

@@ -243,6 +243,20 @@ class KSP:
         check(lib().das_ksp_get_idr_info(self.handle, *[C.byref(x) for x in a], C.byref(wb)))
         return dict(s=a[0].value, cycles=a[1].value, restarts=a[2].value, breakdowns=a[3].value, workVectors=a[4].value, workBytes=wb.value)
 
+    def polyInfo(self):
+        """Polynomial preconditioning of the last solve (amd.polyDegree): dict(degree (as used; 0 = none), nComplexPairs, products (operator
+        products: what info()["iters"] reports in this mode), columns (Arnoldi columns built after the generating cycle: the basis the option is
+        about), generatingColumns (the columns of the generating cycle; the history holds one entry per column of both), generated, fallback (1: no usable roots, the solve ran
+        without a polynomial), workVectors (3 once a polynomial was built), workBytes (8 n each), roots (the ordered roots as (re, im); a pair
+        once, im > 0)); all 0 / empty for a KSP whose last solve ran without the option."""
+        a = [C.c_int(0) for _ in range(6)]
+        pr, co, gc, wb = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0), C.c_double(0)
+        re, im = np.zeros(16), np.zeros(16)
+        check(lib().das_ksp_get_poly_info(self.handle, C.byref(a[0]), C.byref(a[1]), C.byref(pr), C.byref(co), C.byref(gc), C.byref(a[2]), C.byref(a[3]), C.byref(a[4]), C.byref(wb),
+                                          C.byref(a[5]), dptr(re), dptr(im)))
+        return dict(degree=a[0].value, nComplexPairs=a[1].value, products=pr.value, columns=co.value, generatingColumns=gc.value, generated=a[2].value, fallback=a[3].value, workVectors=a[4].value,
+                    workBytes=wb.value, roots=[(float(re[i]), float(im[i])) for i in range(a[5].value)])
+
     def cycleLengths(self):
         """Columns of every closed Arnoldi cycle of the last solve (all but the last equal gmresRestart, DALinearEqn.C:155)."""
         buf = np.zeros(max(1, self.getIterationNumber() + 2), np.int32)

@@ -461,6 +461,35 @@ int das_debug_idr_biortho_step(long long n, int k, double* G, double* U, long lo
  * out[0..s) = P^T r, out[s] = r.r afterwards.  r, x and P are copied back */
 int das_debug_idr_smooth_step(long long n, int s, double omega, double* r, const double* t, double* x, const double* z, long long vlen, double* P,
                               long long ld, long long plen, double* out);
+/* amd.polyDegree = d (opt-in, 0 = off, 1 .. 16): polynomial-preconditioned GMRES.  With B = A M^-1 (M^-1: the whole preconditioner) the
+ * first Arnoldi cycle of a solve is closed after d columns; the roots of its GMRES residual polynomial - the harmonic Ritz values, in
+ * modified Leja order, a complex pair once - define p of degree d - 1, and every later column is w = B p(B) v: d operator products with
+ * nothing but element-wise updates between them; a cycle closes with x += M^-1 p(B) (V y).  A generating cycle that ends early, or roots
+ * that are unusable (zero, not finite, no dense eigen-solver callback: das_set_dense_eig_callback), leave the solve without a polynomial
+ * (degree 0, fallback 1).  adjEqnOption.gmresMaxIters bounds the operator products (polynomial, closing steps and true residuals included;
+ * a column the budget does not cover is not started), gmresRestart the basis columns; das_ksp_get_info's iters is the number of
+ * products, the history keeps one entry per column.  das_ksp_get_status: reason 3 = non-finite residual (fail flag set).  Fixed-iteration
+ * windows and the Newton primal's inner solves ignore the option; amd.krylovMethod "idrs", amd.gmresDeflation > 0, a block solve, a
+ * sharded solve or a degree outside 0 .. 16 is an error.
+ * das_ksp_get_poly_info: the last solve's degree as used, complex pairs, operator products, Arnoldi columns built AFTER the generating
+ * cycle (the basis the option is about; with a polynomial they are columns of B p(B)), the columns of the generating cycle itself (the
+ * history holds one entry per column of both), whether a polynomial was generated, the fallback flag, the work vectors (3 once a polynomial was built) and their bytes (8 n each), and the ordered roots (re, im: room for 16
+ * entries each; nRoots of them are written); all 0 for a KSP whose last solve ran without the option */
+int das_ksp_get_poly_info(das_ksp_t* ksp, int* degree, int* nComplexPairs, long long* products, long long* columns, long long* generatingColumns, int* generated,
+                          int* fallback, int* workVectors, double* workBytes, int* nRoots, double* re, double* im);
+/* test-only entries of amd.polyDegree.  roots: the ordered roots of a (d + 1) x d unrotated Hessenberg matrix (row-major); returns the
+ * number of entries written to re / im (real roots and pairs, a pair by its member with im > 0), 0 = fallback (no usable polynomial) */
+int das_debug_poly_roots(int d, const double* Hbar, double* re, double* im);
+/* out = p(B) v on HOST vectors, B = A M^-1 with A and M^-1 as callbacks fn(x, y, user): the root walk the device solver runs */
+int das_debug_poly_apply_host(long long n, void* A, void* M, void* user, int nroots, const double* re, const double* im, const double* v, double* out);
+/* one root step through the solver's launch helper on caller data: kind 0 = real root (poly (+)= prod / re; unless last: prod -= w / re),
+ * 1 = first step of a pair (tmp = 2 re prod - w; poly (+)= tmp / (re^2 + im^2)), 2 = second step of a pair (prod -= w / (re^2 + im^2);
+ * nothing is launched when last).  first: prod is read from v, poly is not read.  Every array has len entries with its vector in
+ * [off, off + n); the device copies keep the offset (odd off: element-wise path).  All five arrays are copied back */
+int das_debug_poly_step(long long n, int kind, int first, int last, double re, double im, long long off, long long len, double* v, double* w, double* prod, double* poly,
+                        double* tmp);
+/* out = p(B) v on the device with the roots of this KSP's last solve (after initializedRdWTMatrixFree) */
+int das_debug_ksp_poly_apply(das_solver_t* s, das_ksp_t* ksp, const double* v, double* out);
 /* how the last solve ended: reason 0 = tolerance met (KSP_CONVERGED_RTOL/ATOL), 1 = gmresMaxIters reached (KSP_DIVERGED_ITS),
  * 2 = stopped on stagnation after a Krylov breakdown / at the attainable accuracy (PETSc: KSP_CONVERGED_HAPPY_BREAKDOWN /
  * KSP_DIVERGED_BREAKDOWN; the reference's failure flag is still the tolerance rule of DALinearEqn.C:422-434);

@@ -10,12 +10,17 @@ ap.add_argument("--dz", type=float, default=0.1)
 ap.add_argument("--section", type=int, nargs=2, default=None, help="converge this section (n_around n_normal) by grid sequencing instead of loading the 200 x 63 data file")
 ap.add_argument("--first-cell", type=float, default=2e-5)
 ap.add_argument("--combos", nargs="+", default=["-1:additive:rcb:1", "512:additive:rcb:1", "2048:additive:rcb:1", "-1:deflated:rcb:1", "2048:deflated:rcb:1", "-1:additive:strength:1",
-                                                "2048:additive:strength:1", "-1:additive:rcb:2", "0:additive:rcb:1"], help="coarseAgg:coarseMode:aggregation:localPCIters (coarseAgg 'a' = automatic)")
+                                                "2048:additive:strength:1", "-1:additive:rcb:2", "0:additive:rcb:1"],
+                help="coarseAgg:coarseMode:aggregation:localPCIters (coarseAgg 'a' = automatic); 'none' = no sweep (with --poly / --deflation: those runs alone)")
 ap.add_argument("--maxit", type=int, default=1500)
 ap.add_argument("--blend", type=float, nargs="+", default=[0.0], help="amd.pcUpwindBlend values (the PC matrix is re-assembled per value)")
 ap.add_argument("--polish", type=int, default=2)
 ap.add_argument("--deflation", nargs="*", default=[], help="GMRES-DR runs after the sweep: pairs m:k (gmresRestart : amd.gmresDeflation), e.g. 300:100 200:70")
+ap.add_argument("--poly", type=int, nargs="*", default=[], help="polynomial-preconditioned GMRES runs after the sweep: amd.polyDegree values, e.g. 0 4 8 (0 = the default solver in "
+                "the same session); library defaults otherwise, gmresRestart = gmresMaxIters = --maxit, --rtol")
+ap.add_argument("--rtol", type=float, default=1e-6)
 a = ap.parse_args()
+a.combos = [c for c in a.combos if c != "none"]
 import __graft_entry__ as ge
 ge.build()
 from dafoam_amd.meshgen import naca0012_case
@@ -38,7 +43,7 @@ else:
     case2 = naca0012_case(nx, ny, 1, first_cell=fc, perturb=0.0)
     case2.states = d["states"].copy()
 opts = {"solverName": "DASimpleFoam", "debug": False, "normalizeStates": {"U": 10.0, "p": 50.0, "nuTilda": 1e-3, "phi": 1.0},
-        "adjEqnOption": {"gmresRestart": a.maxit, "gmresMaxIters": a.maxit, "gmresRelTol": 1e-6, "printInfo": 0}, "amd": {"maxKrylovBytes": int(140 * 2**30)}}
+        "adjEqnOption": {"gmresRestart": a.maxit, "gmresMaxIters": a.maxit, "gmresRelTol": a.rtol, "printInfo": 0}, "amd": {"maxKrylovBytes": int(140 * 2**30)}}
 for nz in a.nz:
     if nz > 1:
         case, ex = naca_extruded_case(case2, (nx, ny), nz, dz=a.dz, first_cell=fc, options=opts, polish_steps=a.polish)
@@ -81,5 +86,20 @@ for nz in a.nz:
         print(f"SWEEP {nx}x{ny}x{nz} GMRES-DR(m={mm}, k={kk}) blend {a.blend[-1]}: iters {info['iters']} fail {fail} rel {info['res'] / info['res0']:.2e} solve {ts:.2f}s "
               f"({info['iters'] / ts:.1f} it/s, basis {mm + 2} vectors)", flush=True)
         D.solver.updateDAOption({"amd": {"gmresDeflation": 0}, "adjEqnOption": {"gmresRestart": a.maxit}})
+        ksp.destroy(); pc.destroy()
+    for d in a.poly:
+        D.solver.updateDAOption({"amd": {"polyDegree": int(d)}, "adjEqnOption": {"gmresRestart": a.maxit, "gmresMaxIters": a.maxit}})
+        pc = Mat(); D.solver.calcdRdWT(1, pc)
+        ksp = KSP(); D.solverAD.createMLRKSPMatrixFree(pc, ksp)
+        x = Vec(n); r = Vec(n); r.array[:] = rhs
+        t = time.time(); fail = D.solverAD.solveLinearEqn(ksp, r, x); ts = time.time() - t
+        info, pi, basis = ksp.info(), ksp.polyInfo(), ksp.basisInfo()
+        cols = pi["generatingColumns"] + pi["columns"] if d > 0 else info["iters"]
+        print(f"SWEEP {nx}x{ny}x{nz} polyDegree {d} (as used {pi['degree']}, fallback {pi['fallback']}): operator products {info['iters']} columns {cols} "
+              f"(largest cycle {int(max(ksp.cycleLengths(), default=0))}) fail {fail} reason {ksp.status()['reason']} rel {info['res'] / info['res0']:.2e} solve {ts:.2f}s "
+              f"(library {info['seconds']:.2f}s) basis mapped {basis['mappedGB'] * 2**30 / 1e9:.1f} GB work vectors {pi['workBytes'] / 1e9:.2f} GB", flush=True)
+        h = ksp.history()
+        print(f"SWEEP polyDegree {d} residual history / |r0| at columns " + ", ".join(f"{i}: {h[i] / h[0]:.3g}" for i in sorted(set(list(range(0, len(h), max(1, len(h) // 12))) + [len(h) - 1]))), flush=True)
+        D.solver.updateDAOption({"amd": {"polyDegree": 0}})
         ksp.destroy(); pc.destroy()
     del D
