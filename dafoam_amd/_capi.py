@@ -383,6 +383,15 @@ _SIGS = {
     "das_debug_vecpack": (C.c_int, [C.c_longlong, c_ll_p, c_int_p, c_double_p, C.c_longlong, C.c_longlong, c_int_p, c_ll_p, C.POINTER(C.c_ubyte), C.c_longlong, c_ll_p,
                                     c_double_p, c_double_p, C.c_longlong]),
     "das_debug_spmv_rows": (C.c_int, [C.c_longlong, c_int_p, C.c_longlong, c_ll_p, c_int_p, c_double_p, c_double_p, c_double_p, C.c_longlong]),
+    # test-only entries (tests/test_gpu_coarse_kernels.py): the coarse space of the two-level preconditioner on caller-made structures,
+    # never called by the bindings
+    "das_debug_coarse_assemble": (C.c_int, [C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, c_ll_p, c_int_p, c_double_p, c_int_p, c_int_p, C.c_int, C.c_double,
+                                            c_double_p]),
+    "das_debug_coarse_invert": (C.c_int, [C.c_int, c_double_p, c_double_p, c_int_p]),
+    "das_debug_coarse_correct": (C.c_int, [C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, c_int_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                           C.c_longlong, C.c_int]),
+    "das_debug_coarse_az": (C.c_int, [C.c_int, C.c_longlong, c_ll_p, c_int_p, c_double_p, C.c_longlong, C.c_longlong, c_int_p, c_int_p, c_ll_p, c_int_p, c_double_p,
+                                      C.c_longlong, c_ll_p, c_int_p, c_double_p, c_double_p, c_double_p, C.c_longlong]),
     "das_timer_count": (C.c_longlong, [_VP, C.c_char_p]),
     "das_timer_reset": (None, [_VP]),
     "das_timer_enable": (None, [_VP, C.c_int]),

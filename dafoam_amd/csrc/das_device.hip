@@ -30,6 +30,8 @@
 #include "das_poly_debug.hpp"
 #include "das_bilu_debug.hpp"
 #include "das_graph_debug.hpp"
+#include "das_coarse.hpp"
+#include "das_coarse_debug.hpp"
 #include "das_color.hpp"
 #include "das_opmat.hpp"
 #include "das_graph.hpp"
@@ -412,149 +414,6 @@ __global__ void k_newton_update(long long n, long long n0, long long n1, double 
     double w = W[i] + omega * scale[i] * dw[i];
     if (i >= n0 && i < n1 && w < 1e-14) w = 1e-14;
     Wn[i] = w;
-}
-
-// ---- two-level correction: piecewise-constant coarse space on one scalar cell field (the pressure) ---------------------
-// The incomplete factorisation alone leaves the smooth pressure modes to the Krylov method: the iteration count of the
-// adjoint solve grows linearly with the number of cells along the domain (measured ~4.2 x nx for the bench channels).  A
-// Nicolaides-type coarse space - one unknown per aggregate of cells, acting on the p / pRes entries only - removes that
-// growth: M^-1 = ILU^-1 + Z E^-1 Z^T (additive) or ILU^-1 (I - A Z E^-1 Z^T) + Z E^-1 Z^T (deflated, A-DEF1), with
-// E = Z^T P Z assembled from jacPCMat on the device and inverted on the host (nAgg <= 2048).
-// E[I][J] = sum of the field-block entries a_ij with i in aggregate I, j in aggregate J - DETERMINISTIC (the
-// atomicAdd version summed in arrival order, so E - and with it every iterate - differed in the last bits from run to run):
-// one workgroup per row aggregate I walks the rows of its cells in list order; thread t owns the target columns J = t (mod 256)
-// and is the only one that ever adds to them (LDS row of nagg doubles), so every E[I][J] is summed in the same order every time.
-// aggRow: aggregate of a ROW cell (owned and - multi-GPU, global coarse space - ghost cells), aggCol: aggregate of a COLUMN
-// cell (owned residuals only: the matrix holds no other columns); cellsAll / aptrAll: the row cells sorted by aggregate.
-__global__ __launch_bounds__(256) void k_coarse_assemble(int nagg, const long long* __restrict__ aptrAll, const int* __restrict__ cellsAll, long long N,
-                                                         long long off, const long long* __restrict__ rp, const int* __restrict__ ci,
-                                                         const double* __restrict__ v, const int* __restrict__ aggCol, double* __restrict__ E,
-                                                         int transpose, double diagScale) {
-    __shared__ double accs[2048];
-    const int I = blockIdx.x, t = threadIdx.x;
-    const long long q0 = aptrAll[I], q1 = aptrAll[I + 1];
-    if (q0 == q1) return;  // no row cell of this aggregate on this rank: the row of E stays zero here
-    for (int J = t; J < nagg; J += 256) accs[J] = 0.0;
-    for (long long q = q0; q < q1; q++) {
-        const long long c = cellsAll[q];
-        const long long row = off + c;
-        for (long long k = rp[row]; k < rp[row + 1]; k++) {
-            const long long j = (long long)ci[k] - off;
-            if (j < 0 || j >= N) continue;
-            const int J = aggCol[j];
-            if (J >= 0 && (J & 255) == t) accs[J] += (j == c) ? v[k] * diagScale : v[k];
-        }
-    }
-    for (int J = t; J < nagg; J += 256) E[transpose ? (long long)J * nagg + I : (long long)I * nagg + J] = accs[J];
-}
-// dense inverse of the coarse operator by Gauss-Jordan with partial pivoting on the device (n <= 2048): per pivot column
-// one single-workgroup kernel (pivot search, row swap, row scaling) and one elimination kernel (one workgroup per row)
-__global__ __launch_bounds__(256) void k_gj_pivot(int n, int k, double* __restrict__ E, double* __restrict__ Inv, int* __restrict__ singular) {
-    __shared__ double bv[256];
-    __shared__ int bi[256];
-    double best = -1.0;
-    int br = k;
-    for (int r = k + threadIdx.x; r < n; r += 256) { const double a = fabs(E[(long long)r * n + k]); if (a > best) { best = a; br = r; } }
-    bv[threadIdx.x] = best; bi[threadIdx.x] = br;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o && (bv[threadIdx.x + o] > bv[threadIdx.x] || (bv[threadIdx.x + o] == bv[threadIdx.x] && bi[threadIdx.x + o] < bi[threadIdx.x]))) {
-            bv[threadIdx.x] = bv[threadIdx.x + o]; bi[threadIdx.x] = bi[threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-    const int pr = bi[0];
-    if (!(bv[0] > 0.0)) { if (threadIdx.x == 0) *singular = 1; return; }
-    const double ip = 1.0 / E[(long long)pr * n + k];
-    __syncthreads();
-    for (int q = threadIdx.x; q < n; q += 256) {
-        const double ek = E[(long long)k * n + q], ep = E[(long long)pr * n + q];
-        const double ik = Inv[(long long)k * n + q], ipr = Inv[(long long)pr * n + q];
-        if (pr != k) { E[(long long)pr * n + q] = ek; Inv[(long long)pr * n + q] = ik; }
-        E[(long long)k * n + q] = ep * ip;
-        Inv[(long long)k * n + q] = ipr * ip;
-    }
-}
-__global__ __launch_bounds__(256) void k_gj_elim(int n, int k, double* __restrict__ E, double* __restrict__ Inv) {
-    const int r = blockIdx.x;
-    if (r == k) return;
-    __shared__ double fs;
-    if (threadIdx.x == 0) fs = E[(long long)r * n + k];
-    __syncthreads();
-    const double f = fs;
-    if (f == 0.0) return;
-    for (int q = threadIdx.x; q < n; q += 256) {
-        E[(long long)r * n + q] -= f * E[(long long)k * n + q];
-        Inv[(long long)r * n + q] -= f * Inv[(long long)k * n + q];
-    }
-}
-// t[I] = sum of r over the field entries of aggregate I (cells sorted by aggregate: deterministic, one workgroup each)
-__global__ __launch_bounds__(256) void k_coarse_restrict(const long long* __restrict__ aptr, const int* __restrict__ cells, long long off,
-                                                         const double* __restrict__ r, double* __restrict__ t) {  // t: first OWN aggregate
-    __shared__ double red[4];
-    const int I = blockIdx.x;
-    double acc = 0.0;
-    for (long long q = aptr[I] + threadIdx.x; q < aptr[I + 1]; q += 256) acc += r[off + cells[q]];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) t[I] = red[0] + red[1] + red[2] + red[3];
-}
-__global__ void k_coarse_solve(int nagg, const double* __restrict__ Einv, const double* __restrict__ t, double* __restrict__ u) {
-    const int I = blockIdx.x * blockDim.x + threadIdx.x;
-    if (I >= nagg) return;
-    double acc = 0.0;
-    for (int J = 0; J < nagg; J++) acc += Einv[(long long)I * nagg + J] * t[J];
-    u[I] = acc;
-}
-// y[field entry of cell c] (+)= u[agg(c)]; `set`: y is zero elsewhere (the deflation vector), else accumulate
-__global__ void k_coarse_prolong(long long N, long long n, long long off, const int* __restrict__ agg, const double* __restrict__ u,
-                                 double* __restrict__ y, int set) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const long long c = i - off;
-    const double add = (c >= 0 && c < N && agg[c] >= 0) ? u[agg[c]] : 0.0;
-    y[i] = set ? add : y[i] + add;
-}
-
-// A Z for the deflated coarse mode: row i of the operator summed over the field-block columns of every aggregate.  One thread per
-// row, entries in storage order (deterministic); a row whose field columns touch more than AZ_CAP aggregates sets `overflow` (the
-// caller then keeps the full operator product).  pass 0: counts -> cnt[i]; pass 1: fills (ptr from the prefix sum of the counts)
-constexpr int AZ_CAP = 64;  // (round 5: 12 overflowed on the wing - RCB boxes next to the wall are 4 cells thick spanwise, a 7-cell stencil meets 3 x 3 x 2 of them)
-__global__ __launch_bounds__(256) void k_az_build(long long n, const long long* __restrict__ rp, const int* __restrict__ ci, const double* __restrict__ v,
-                                                  long long N, long long off, const int* __restrict__ agg, int pass, int* __restrict__ cnt,
-                                                  const long long* __restrict__ ptr, int* __restrict__ oa, double* __restrict__ ov, int* __restrict__ overflow) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    int la[AZ_CAP];
-    double ls[AZ_CAP];
-    int m = 0;
-    for (long long k = rp[i]; k < rp[i + 1]; k++) {
-        const long long j = (long long)ci[k] - off;
-        if (j < 0 || j >= N) continue;
-        const int a = agg[j];
-        if (a < 0) continue;
-        int q = 0;
-        while (q < m && la[q] != a) q++;
-        if (q == m) {
-            if (m == AZ_CAP) { *overflow = 1; continue; }
-            la[m] = a; ls[m] = 0.0; m++;
-        }
-        ls[q] += v[k];
-    }
-    if (pass == 0) { cnt[i] = m; return; }
-    const long long b = ptr[i];
-    for (int q = 0; q < m; q++) { oa[b + q] = la[q]; ov[b + q] = ls[q]; }
-}
-// out = v - (A Z) u   (v == nullptr: out = (A Z) u - several ranks reduce the ghost rows before the subtraction)
-__global__ __launch_bounds__(256) void k_az_apply(long long n, const long long* __restrict__ ptr, const int* __restrict__ oa, const double* __restrict__ ov,
-                                                  const double* __restrict__ u, const double* __restrict__ v, double* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double acc = 0.0;
-    for (long long k = ptr[i]; k < ptr[i + 1]; k++) acc += ov[k] * u[oa[k]];
-    out[i] = v ? v[i] - acc : acc;
 }
 
 // ---- RAS/ILU(k) apply: one workgroup per (overlapping) additive-Schwarz block -------------------------------------
@@ -2082,43 +1941,26 @@ static void coarse_build_operator(das_solver* s, das_ksp* k, int naggG, int aggO
     const long long N = C.N;
     std::vector<int> aggOwn(N, -1);
     for (long long c = 0; c < N; c++) if (C.h_agg[c] >= 0) aggOwn[c] = aggOff + C.h_agg[c];
-    std::vector<long long> aptrAll(naggG + 1, 0);
-    for (long long c = 0; c < N; c++) if (aggRowG[c] >= 0) aptrAll[aggRowG[c] + 1]++;
-    for (int a = 0; a < naggG; a++) aptrAll[a + 1] += aptrAll[a];
-    std::vector<int> cellsAll(aptrAll[naggG]);
-    {
-        std::vector<long long> pos(aptrAll.begin(), aptrAll.end() - 1);
-        for (long long c = 0; c < N; c++) if (aggRowG[c] >= 0) cellsAll[pos[aggRowG[c]]++] = (int)c;
-    }
+    std::vector<long long> aptrAll;
+    std::vector<int> cellsAll;
+    coarse_sort_cells(N, naggG, aggRowG.data(), aptrAll, cellsAll);
     C.naggG = naggG; C.aggOff = aggOff; C.global = naggG > C.nagg;
     C.azOpId = -1; C.azReady = false;  // the sparse A Z of the deflated mode belongs to the old aggregates
     C.agg.upload(aggOwn); C.aggRow.upload(aggRowG); C.cellsAll.upload(cellsAll); C.aptrAll.upload(aptrAll);
     DevBuf<double> E((size_t)naggG * naggG);
-    E.zero();
     const Mat& P = k->pcmat->m;
     // rows: cells of every aggregate present on this rank (transposed storage: rows = states); columns: owned residual cells
-    hipLaunchKernelGGL(k_coarse_assemble, dim3(naggG), dim3(256), 0, s->stream, naggG, C.aptrAll.p, C.cellsAll.p, N, C.off, P.rowptr.p, P.col.p, P.val.p,
-                       k->pcTranspose ? C.aggRow.p : C.agg.p, E.p, k->pcTranspose ? 1 : 0,
-                       (C.off < k->shiftEnd && !(C.off >= k->shiftExLo && C.off < k->shiftExHi)) ? k->pcDiagScale : 1.0);
+    coarse_assemble(naggG, C.aptrAll.p, C.cellsAll.p, N, C.off, P.rowptr.p, P.col.p, P.val.p, k->pcTranspose ? C.aggRow.p : C.agg.p, E.p, k->pcTranspose ? 1 : 0,
+                    (C.off < k->shiftEnd && !(C.off >= k->shiftExLo && C.off < k->shiftExHi)) ? k->pcDiagScale : 1.0, s->stream);
     if (C.global) {
         DAS_CHECK(!k->pcTranspose, DAS_ERR_ARG, "global coarse space: adjoint preconditioner only");
         rank_allreduce(s, E.p, naggG * naggG, s->stream);
     }
     // E^-1 on the device (Gauss-Jordan, partial pivoting)
     {
-        std::vector<double> I0((size_t)naggG * naggG, 0.0);
-        for (int i = 0; i < naggG; i++) I0[(size_t)i * naggG + i] = 1.0;
-        C.Einv.upload(I0);
+        if (C.Einv.n < (size_t)naggG * naggG) C.Einv.alloc((size_t)naggG * naggG);
         DevBuf<int> sing(1);
-        DAS_HIP(hipMemsetAsync(sing.p, 0, sizeof(int), s->stream));
-        for (int kk = 0; kk < naggG; kk++) {
-            hipLaunchKernelGGL(k_gj_pivot, dim3(1), dim3(256), 0, s->stream, naggG, kk, E.p, C.Einv.p, sing.p);
-            hipLaunchKernelGGL(k_gj_elim, dim3(naggG), dim3(256), 0, s->stream, naggG, kk, E.p, C.Einv.p);
-        }
-        int hs = 0;
-        DAS_HIP(hipMemcpyAsync(&hs, sing.p, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-        DAS_HIP(hipStreamSynchronize(s->stream));
-        if (hs) return;  // singular coarse operator: no coarse correction
+        if (coarse_invert(naggG, E.p, C.Einv.p, sing.p, s->stream)) return;  // singular coarse operator: no coarse correction
     }
     C.t.alloc(naggG); C.u.alloc(naggG);
     C.active = true;
@@ -2176,14 +2018,9 @@ static void setup_coarse(das_solver* s, das_ksp* k) {
             stack.push_back({r.b, mid, r.a0, nl});
         }
     }
-    std::vector<long long> aptr(nagg + 1, 0);
-    for (long long c = 0; c < N; c++) if (agg[c] >= 0) aptr[agg[c] + 1]++;
-    for (int a = 0; a < nagg; a++) aptr[a + 1] += aptr[a];
-    std::vector<int> cells(aptr[nagg]);
-    {
-        std::vector<long long> pos(aptr.begin(), aptr.end() - 1);
-        for (long long c = 0; c < N; c++) if (agg[c] >= 0) cells[pos[agg[c]]++] = (int)c;
-    }
+    std::vector<long long> aptr;
+    std::vector<int> cells;
+    coarse_sort_cells(N, nagg, agg.data(), aptr, cells);
     C.nagg = nagg; C.off = sd->offset; C.N = N; C.h_agg = agg;
     C.cells.upload(cells); C.aptr.upload(aptr);
     C.deflated = s->opt.gets("amd.pcCoarseMode") == "deflated";
@@ -2196,9 +2033,8 @@ static void setup_coarse(das_solver* s, das_ksp* k) {
 static void coarse_solve(das_solver* s, das_ksp* k, const double* r) {
     das_ksp::CoarsePC& C = k->coarse;
     if (C.global) DAS_HIP(hipMemsetAsync(C.t.p, 0, (size_t)C.naggG * sizeof(double), s->stream));
-    if (C.nagg > 0) hipLaunchKernelGGL(k_coarse_restrict, dim3(C.nagg), dim3(256), 0, s->stream, C.aptr.p, C.cells.p, C.off, r, C.t.p + C.aggOff);
-    if (C.global) rank_allreduce(s, C.t.p, C.naggG, s->stream);
-    hipLaunchKernelGGL(k_coarse_solve, dim3(nblk(C.naggG, 64)), dim3(64), 0, s->stream, C.naggG, C.Einv.p, C.t.p, C.u.p);
+    coarse_restrict_solve(C.nagg, C.aptr.p, C.cells.p, C.off, r, C.naggG, C.aggOff, C.Einv.p, C.t.p, C.u.p, s->stream,
+                          [&] { if (C.global) rank_allreduce(s, C.t.p, C.naggG, s->stream); });
 }
 
 static void pc_apply(das_solver* s, das_ksp* k, const double* b, double* x) {
@@ -2351,34 +2187,23 @@ static bool coarse_az_ready(das_solver* s, das_ksp* k) {
     C.azOpId = s->opId; C.azEpoch = s->op_epoch; C.azReady = false; C.azFailed = false;
     const long long n = s->n;
     hipStream_t st = s->stream;
-    DevBuf<int> cnt(n), ovf(1);
-    DAS_HIP(hipMemsetAsync(ovf.p, 0, sizeof(int), st));
-    hipLaunchKernelGGL(k_az_build, dim3(nblk(n, 256)), dim3(256), 0, st, n, A.rowptr.p, A.col.p, A.val.p, C.N, C.off, C.agg.p, 0, cnt.p, (const long long*)nullptr,
-                       (int*)nullptr, (double*)nullptr, ovf.p);
-    DAS_HIP(hipStreamSynchronize(st));
-    int ovfAny = ovf.to_host()[0];
-    if (s->halo.active || s->allreduce_cb) {  // several ranks: all of them take the same path (the fallback is a collective operator product)
-        DevBuf<double> f(1);
-        const double fv = ovfAny ? 1.0 : 0.0;
-        DAS_HIP(hipMemcpyAsync(f.p, &fv, sizeof(double), hipMemcpyHostToDevice, st));
-        rank_allreduce(s, f.p, 1, st);
-        DAS_HIP(hipStreamSynchronize(st));
-        ovfAny = f.to_host()[0] > 0.5 ? 1 : 0;
-    }
-    if (ovfAny) {
+    DevBuf<int> cnt(n);
+    const bool built = coarse_az_build(n, A.rowptr.p, A.col.p, A.val.p, C.N, C.off, C.agg.p, cnt, C.azPtr, C.azAgg, C.azVal, C.azNnz, st, [&](int ovfAny) {
+        if (s->halo.active || s->allreduce_cb) {  // several ranks: all of them take the same path (the fallback is a collective operator product)
+            DevBuf<double> f(1);
+            const double fv = ovfAny ? 1.0 : 0.0;
+            DAS_HIP(hipMemcpyAsync(f.p, &fv, sizeof(double), hipMemcpyHostToDevice, st));
+            rank_allreduce(s, f.p, 1, st);
+            DAS_HIP(hipStreamSynchronize(st));
+            ovfAny = f.to_host()[0] > 0.5 ? 1 : 0;
+        }
+        return ovfAny;
+    });
+    if (!built) {
         C.azFailed = true;
         fprintf(stderr, "[dafoam_amd] deflated coarse mode: a row of the operator touches more than %d aggregates - keeping the full operator product per apply\n", AZ_CAP);
         return false;
     }
-    std::vector<int> h = cnt.to_host();
-    std::vector<long long> ptr(n + 1, 0);
-    for (long long i = 0; i < n; i++) ptr[i + 1] = ptr[i] + h[i];
-    C.azNnz = ptr[n];
-    C.azPtr.upload(ptr);
-    C.azAgg.alloc((size_t)std::max<long long>(1, C.azNnz)); C.azVal.alloc((size_t)std::max<long long>(1, C.azNnz));
-    hipLaunchKernelGGL(k_az_build, dim3(nblk(n, 256)), dim3(256), 0, st, n, A.rowptr.p, A.col.p, A.val.p, C.N, C.off, C.agg.p, 1, cnt.p, C.azPtr.p, C.azAgg.p, C.azVal.p,
-                       ovf.p);
-    DAS_HIP(hipStreamSynchronize(st));
     if (s->opt.geti("debug")) fprintf(stderr, "[dafoam_amd] deflated coarse mode: sparse A Z with %lld entries (%.2f per row)\n", C.azNnz, (double)C.azNnz / (double)n);
     C.azReady = true;
     return true;
@@ -6322,6 +6147,71 @@ int das_debug_spmv_rows(long long nrows, const int* rows, long long n, const lon
     for (long long k = 0; k < nrows; k++) DAS_CHECK(rows[k] >= 0 && rows[k] < n, DAS_ERR_ARG, who + ": row index out of range");
     DAS_GRAPH_DEVICE(who);
     debug_spmv_rows(nrows, rows, n, rowptr, col, vals, x, buf, buflen);
+    return DAS_OK;
+    DAS_CATCH
+}
+// Test-only entries (tests/test_gpu_coarse_kernels.py): the coarse space of the two-level preconditioner on caller-made structures
+// through the helpers the solver uses (das_coarse.hpp, das_coarse_debug.hpp).  Everything a kernel would index with is checked on the
+// host before anything is launched.
+int das_debug_coarse_assemble(int nagg, long long N, long long off, long long n, const long long* rowptr, const int* col, const double* vals, const int* aggRow,
+                              const int* aggCol, int transpose, double diagScale, double* E) {
+    DAS_TRY
+    const std::string who = "das_debug_coarse_assemble";
+    coarse_check_nagg(who, nagg);
+    coarse_check_field(who, N, off, n);
+    DAS_CHECK(rowptr && aggRow && aggCol && E, DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(transpose == 0 || transpose == 1, DAS_ERR_ARG, who + ": transpose is 0 or 1");
+    graph_check_csr(who, n, rowptr, col, n, false);
+    DAS_CHECK(rowptr[n] == 0 || vals, DAS_ERR_ARG, who + ": null pointer");
+    coarse_check_agg(who, N, nagg, aggRow);
+    coarse_check_agg(who, N, nagg, aggCol);
+    DAS_GRAPH_DEVICE(who);
+    debug_coarse_assemble(nagg, N, off, n, rowptr, col, vals, aggRow, aggCol, transpose, diagScale, E);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_coarse_invert(int n, const double* Ein, double* Inv, int* singular) {
+    DAS_TRY
+    const std::string who = "das_debug_coarse_invert";
+    DAS_CHECK(n >= 1 && n <= COARSE_MAX_AGG, DAS_ERR_ARG, who + ": n outside 1 .. 2048");
+    DAS_CHECK(Ein && Inv && singular, DAS_ERR_ARG, who + ": null pointer");
+    DAS_GRAPH_DEVICE(who);
+    debug_coarse_invert(n, Ein, Inv, singular);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_coarse_correct(int nagg, long long N, long long off, long long n, const int* agg, const double* Einv, const double* r, double* t, double* u, double* y,
+                             long long ylen, int set) {
+    DAS_TRY
+    const std::string who = "das_debug_coarse_correct";
+    coarse_check_nagg(who, nagg);
+    coarse_check_field(who, N, off, n);
+    DAS_CHECK(Einv && r && t && u && y, DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(ylen >= n && ylen < (1LL << 31), DAS_ERR_ARG, who + ": y shorter than n");
+    DAS_CHECK(set == 0 || set == 1, DAS_ERR_ARG, who + ": set is 0 or 1");
+    coarse_check_agg(who, N, nagg, agg);
+    DAS_GRAPH_DEVICE(who);
+    debug_coarse_correct(nagg, N, off, n, agg, Einv, r, t, u, y, ylen, set);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_coarse_az(int nagg, long long n, const long long* rowptr, const int* col, const double* vals, long long N, long long off, const int* agg, int* cnt,
+                        long long* ptr, int* oa, double* ov, long long cap, long long* nnz, int* overflow, const double* u, const double* v, double* out,
+                        long long outlen) {
+    DAS_TRY
+    const std::string who = "das_debug_coarse_az";
+    coarse_check_nagg(who, nagg);
+    coarse_check_field(who, N, off, n);
+    DAS_CHECK(rowptr && cnt && ptr && oa && ov && nnz && overflow && u && out, DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(outlen >= n && outlen < (1LL << 31), DAS_ERR_ARG, who + ": out shorter than n");
+    graph_check_csr(who, n, rowptr, col, n, false);
+    DAS_CHECK(rowptr[n] == 0 || vals, DAS_ERR_ARG, who + ": null pointer");
+    coarse_check_agg(who, N, nagg, agg);
+    bool over = false;
+    const long long need = coarse_az_count(n, rowptr, col, N, off, agg, over);
+    DAS_CHECK(cap >= 1 && cap < (1LL << 31) && (over || cap >= need), DAS_ERR_ARG, who + ": oa / ov hold fewer than the entries of the sparse A Z");
+    DAS_GRAPH_DEVICE(who);
+    debug_coarse_az(nagg, n, rowptr, col, vals, N, off, agg, cnt, ptr, oa, ov, cap, nnz, overflow, u, v, out, outlen);
     return DAS_OK;
     DAS_CATCH
 }

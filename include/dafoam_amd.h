@@ -695,6 +695,33 @@ int das_debug_vecpack(long long n, const long long* rowptr, const int* col, cons
 /* k_spmv_rows_to_buf: buf[k] = A[rows[k], :] . x, k < nrows; buf holds buflen >= nrows entries */
 int das_debug_spmv_rows(long long nrows, const int* rows, long long n, const long long* rowptr, const int* col, const double* vals, const double* x, double* buf,
                         long long buflen);
+/* ---- TEST-ONLY entries (tests/test_gpu_coarse_kernels.py): the coarse space of the two-level preconditioner (csrc/das_coarse.hpp) on
+ * caller-made structures, kernel by kernel.  No mesh, no solver handle; the launch sequences THE SOLVER USES run on the null stream.
+ * These kernels index with what they are given, so everything is checked on the host before anything is launched, and DAS_ERR_ARG is
+ * returned for a null pointer, a size <= 0, nagg outside 1 .. 2048, rowptr[0] != 0, a decreasing rowptr, a column outside [0, n), an
+ * aggregate outside [-1, nagg), a field block [off, off + N) that does not lie in [0, n), and an output array too short for what is
+ * written.  All matrices are n x n CSR; the field is the unknowns off .. off + N - 1.  An output array WITHOUT a length argument (E, Inv,
+ * t, u, cnt, ptr) holds 8 entries more than are written; every output is uploaded and downloaded whole, so that the caller can put a
+ * sentinel behind the written range and find it untouched. */
+/* coarse_sort_cells of aggRow, coarse_assemble (E = 0, k_coarse_assemble): E[I][J] (nagg x nagg, J x nagg + I with transpose = 1) = the
+ * sum of the field-block entries a_ij, i in row aggregate I (aggRow, N cells), j in column aggregate J (aggCol), a diagonal entry
+ * (j == i) times diagScale */
+int das_debug_coarse_assemble(int nagg, long long N, long long off, long long n, const long long* rowptr, const int* col, const double* vals, const int* aggRow,
+                              const int* aggCol, int transpose, double diagScale, double* E);
+/* coarse_invert (k_gj_pivot, k_gj_elim per column): Inv = Ein^-1 (n x n, n <= 2048), *singular = 1 when a pivot column holds no
+ * nonzero (Inv is then of no use) */
+int das_debug_coarse_invert(int n, const double* Ein, double* Inv, int* singular);
+/* coarse_sort_cells, coarse_restrict_solve (k_coarse_restrict, k_coarse_solve), k_coarse_prolong: t = Z^T r (nagg), u = Einv t (nagg),
+ * y[off + c] = u[agg(c)] and 0 elsewhere (set = 1) or y[off + c] += u[agg(c)] (set = 0); r holds n entries, y ylen >= n */
+int das_debug_coarse_correct(int nagg, long long N, long long off, long long n, const int* agg, const double* Einv, const double* r, double* t, double* u, double* y,
+                             long long ylen, int set);
+/* coarse_az_build (k_az_build pass 0, prefix sum, pass 1), then k_az_apply: cnt (n), ptr (n + 1), oa / ov (*nnz entries of the cap
+ * that they hold) = the sparse A Z, per row the aggregates in the order of their first appearance; out[0..n) = v - (A Z) u, or (A Z) u
+ * with v null; u holds nagg entries, out outlen >= n.  A row that touches more than 64 aggregates: *overflow = 1 and nothing else is
+ * written (no pass 1, no apply), else *overflow = 0 */
+int das_debug_coarse_az(int nagg, long long n, const long long* rowptr, const int* col, const double* vals, long long N, long long off, const int* agg, int* cnt,
+                        long long* ptr, int* oa, double* ov, long long cap, long long* nnz, int* overflow, const double* u, const double* v, double* out,
+                        long long outlen);
 long long das_timer_count(das_solver_t* s, const char* name);
 void das_timer_reset(das_solver_t* s);
 void das_timer_enable(das_solver_t* s, int on);
