@@ -5,7 +5,8 @@ regression meshes (ConvergentChannel, NACA0012, pitzDaily...) are downloaded at
 test time (reference tests/Allrun:8-18) and are not available here.  These
 generators emit the *same data model* (points / faces / owner / neighbour /
 patch table in OpenFOAM ordering) for hex blocks that are then treated as fully
-unstructured by everything downstream.
+unstructured by everything downstream; mixed_cell_case turns such a block into a
+mesh of pyramids, prisms and polyhedra (triangles and quads, 5 to 16 faces per cell).
 
 Face ordering follows OpenFOAM's polyMesh contract: internal faces first in
 upper-triangular order (by owner, then by neighbour), then boundary faces
@@ -258,28 +259,34 @@ class _InputGeometry:
             return
         F = mesh.n_faces
         nv = np.diff(mesh.face_ptr)
-        assert np.all(nv == nv[0]), "input generator handles uniform polygons"
-        k = int(nv[0])
-        # (component-wise over the k triangles of the fan: np.cross / np.roll on (F, k, 3) temporaries cost 4x as much at 6 M faces)
-        fp = mesh.face_pts.reshape(F, k)
         X = [np.ascontiguousarray(mesh.points[:, d]) for d in range(3)]
-        Pk = [[X[d][fp[:, i]] for d in range(3)] for i in range(k)]  # k x 3 arrays of length F
-        fc = [sum(Pk[i][d] for i in range(k)) / k for d in range(3)]
-        Sf = [np.zeros(F) for _ in range(3)]
-        ac = [np.zeros(F) for _ in range(3)]
-        asum = np.zeros(F)
-        for i in range(k):
-            p, q = Pk[i], Pk[(i + 1) % k]
-            u = [q[d] - p[d] for d in range(3)]
-            v = [fc[d] - p[d] for d in range(3)]
-            n = [u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]]
-            a = np.sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2])
-            asum += a
-            for d in range(3):
-                Sf[d] += n[d]
-                ac[d] += a * (p[d] + q[d] + fc[d])
-        self.Sf = 0.5 * np.stack(Sf, axis=1)
-        self.Cf = np.stack(ac, axis=1) / (3.0 * asum)[:, None]
+        self.Sf, self.Cf = np.zeros((F, 3)), np.zeros((F, 3))
+        # faces of one vertex count at a time (hex blocks: one group of quads; mixed_cell_case: triangles and quads)
+        for k in (int(v) for v in np.unique(nv)):
+            if np.all(nv == k):
+                sel, fp = slice(None), mesh.face_pts.reshape(F, k)
+            else:
+                sel = np.nonzero(nv == k)[0]
+                fp = mesh.face_pts[mesh.face_ptr[sel].astype(np.int64)[:, None] + np.arange(k)[None, :]]
+            Fk = fp.shape[0]
+            # (component-wise over the k triangles of the fan: np.cross / np.roll on (F, k, 3) temporaries cost 4x as much at 6 M faces)
+            Pk = [[X[d][fp[:, i]] for d in range(3)] for i in range(k)]  # k x 3 arrays of length Fk
+            fc = [sum(Pk[i][d] for i in range(k)) / k for d in range(3)]
+            Sf = [np.zeros(Fk) for _ in range(3)]
+            ac = [np.zeros(Fk) for _ in range(3)]
+            asum = np.zeros(Fk)
+            for i in range(k):
+                p, q = Pk[i], Pk[(i + 1) % k]
+                u = [q[d] - p[d] for d in range(3)]
+                v = [fc[d] - p[d] for d in range(3)]
+                n = [u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]]
+                a = np.sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2])
+                asum += a
+                for d in range(3):
+                    Sf[d] += n[d]
+                    ac[d] += a * (p[d] + q[d] + fc[d])
+            self.Sf[sel] = 0.5 * np.stack(Sf, axis=1)
+            self.Cf[sel] = np.stack(ac, axis=1) / (3.0 * asum)[:, None]
         N = mesh.n_cells
         nIF = mesh.n_internal_faces
         own, nei = mesh.owner, mesh.neighbour
@@ -670,7 +677,8 @@ def unroll_periodic_vector(mesh1: PolyMesh, meshC: PolyMesh, vec, copies, dtheta
 
 def renumber_case(case: FoamCase, seed=0) -> FoamCase:
     """Randomly renumber the cells (and therefore re-sort/re-orient the internal faces to keep OpenFOAM's
-    upper-triangular order) - produces a genuinely unstructured numbering of the same mesh and state."""
+    upper-triangular order) - produces a genuinely unstructured numbering of the same mesh and state.  Faces may be
+    ragged (triangles, quads and polygons mixed): a flipped face has its own vertex slice reversed."""
     import copy
 
     m = case.mesh
@@ -682,17 +690,21 @@ def renumber_case(case: FoamCase, seed=0) -> FoamCase:
     flip = o > n
     no, nn = np.where(flip, n, o), np.where(flip, o, n)
     order = np.lexsort((nn, no))
-    nv = np.diff(m.face_ptr)
-    assert np.all(nv == nv[0])
-    k = int(nv[0])
-    fp = m.face_pts.reshape(F, k).copy()
-    fp[:nIF][flip] = fp[:nIF][flip][:, ::-1]
     face_perm = np.concatenate([order, np.arange(nIF, F)])  # new face -> old face
-    mesh = PolyMesh(points=m.points.copy(), face_ptr=m.face_ptr.copy(), face_pts=np.ascontiguousarray(fp[face_perm].ravel()),
+    ptr = m.face_ptr.astype(np.int64)
+    nv = np.diff(ptr)[face_perm]
+    new_ptr = np.concatenate([[0], np.cumsum(nv)])
+    rev = np.zeros(F, dtype=bool)
+    rev[:nIF] = flip[order]
+    j = np.arange(int(new_ptr[-1])) - np.repeat(new_ptr[:-1], nv)  # position inside the own face
+    src = np.repeat(ptr[face_perm], nv) + np.where(np.repeat(rev, nv), np.repeat(nv, nv) - 1 - j, j)
+    mesh = PolyMesh(points=m.points.copy(), face_ptr=new_ptr.astype(np.int32), face_pts=np.ascontiguousarray(m.face_pts[src]),
                     owner=np.concatenate([no[order], new_of_old[m.owner[nIF:]]]).astype(np.int32), neighbour=nn[order].astype(np.int32),
                     patches=copy.deepcopy(m.patches))
     out = copy.copy(case)
     out.mesh = mesh
+    if getattr(out, "_input_geometry", None) is not None:
+        out._input_geometry = None  # (belongs to the old numbering)
     old_of_new = np.argsort(new_of_old)
     if case.y_wall is not None:
         out.y_wall = case.y_wall[old_of_new]
@@ -703,12 +715,209 @@ def renumber_case(case: FoamCase, seed=0) -> FoamCase:
     if case.phi is not None:
         out.phi = case.phi[face_perm] * sign
     W = case.states
-    if case.solver_name == "DASimpleFoam":
-        U = W[: 3 * N].reshape(N, 3)[old_of_new]
-        out.states = np.concatenate([U.ravel(), W[3 * N : 4 * N][old_of_new], W[4 * N : 5 * N][old_of_new], W[5 * N :][face_perm] * sign])
-    else:
+    if case.solver_name == "DAScalarTransportFoam":
         out.states = W[old_of_new]
+    else:  # [U | scalar cell blocks ... | phi]
+        nsc = (W.size - 3 * N - F) // N
+        U = W[: 3 * N].reshape(N, 3)[old_of_new]
+        out.states = np.concatenate([U.ravel()] + [W[(3 + b) * N : (4 + b) * N][old_of_new] for b in range(nsc)] + [W[(3 + nsc) * N :][face_perm] * sign])
     return out
+
+
+def _block_dims(mesh: PolyMesh):
+    """(nx, ny, nz) of a mesh emitted by one hex_block, from the sizes of its x-, y- and z-patches."""
+    a, b, c = mesh.patches[0].size, mesh.patches[2].size, mesh.patches[4].size  # ny nz, nx nz, nx ny
+    nx, ny, nz = int(round(np.sqrt(b * c / a))), int(round(np.sqrt(a * c / b))), int(round(np.sqrt(a * b / c)))
+    assert nx * ny * nz == mesh.n_cells and (ny * nz, nx * nz, nx * ny) == (a, b, c), "not a single hex block"
+    return nx, ny, nz
+
+
+def mixed_cell_case(case: FoamCase, pyramids=(), merges=(), prism_columns=(), dims=None, seed=1, perturb=0.02) -> FoamCase:
+    """The domain, patches and boundary conditions of a case built on ONE hex_block, on a conforming polyMesh with pyramids, prisms and
+    polyhedra (what a user's snappyHexMesh / cfMesh case looks like; the hex blocks alone never leave 6 quads per cell).  Cells are named
+    by their block indices (i, j, k), dims = (nx, ny, nz) of the block (default: from the patch sizes).
+    pyramids: each listed hex becomes six pyramids about a new apex point at the mean of its eight vertices; each keeps one hex face as its
+      base (the neighbours still see a quad), the twelve hex edges give twelve internal triangles (a, b, apex).
+    merges: each listed group of adjacent hexes (a pair, a 2 x 2 x 1 slab) becomes one cell, the faces between members are dropped (10 and
+      16 faces per cell).  Two new cells must not share more than one face: asserted.
+    prism_columns: each listed (i, j) column is cut along the same diagonal for all k into two prisms per hex: the z-faces become two
+      triangles each (internal between stacked prisms, boundary on front / back), one new internal quad per hex lies on the diagonal.
+    Faces: the lower cell id owns, the normal points owner -> neighbour, internal faces in upper-triangular order, boundary faces patch by
+    patch in their old order, ragged face_ptr.  A new cell takes the states (y_wall aside: recomputed) of the hex it came from - the pieces of
+    one hex each with their own seeded perturbation of relative size `perturb`, see below -, a merged cell those of its first member; phi is
+    rebuilt as channel_case builds it (interpolated U . Sf with a seeded perturbation, the boundary rule of the U condition)."""
+    import copy
+
+    m = case.mesh
+    nx, ny, nz = dims if dims is not None else _block_dims(m)
+    N, F, nIF = m.n_cells, m.n_faces, m.n_internal_faces
+    assert N == nx * ny * nz and np.all(np.diff(m.face_ptr) == 4)
+
+    def cid(t):
+        return int(t) if np.ndim(t) == 0 else int(t[0] + nx * (t[1] + ny * t[2]))
+
+    def pid(i, j, k):
+        return i + (nx + 1) * (j + (ny + 1) * k)
+
+    split = [cid(t) for t in pyramids]
+    groups = [[cid(t) for t in grp] for grp in merges]
+    prism = {}  # hex -> its eight vertices, bottom ring then top ring
+    for i, j in prism_columns:
+        for k in range(nz):
+            prism[cid((i, j, k))] = tuple(pid(i + a, j + b, k + c) for c in (0, 1) for a, b in ((0, 0), (1, 0), (1, 1), (0, 1)))
+    touched = split + [c for grp in groups for c in grp] + list(prism)
+    assert len(set(touched)) == len(touched), "a hex takes part in one operation only"
+    fp = m.face_ptr
+    fverts = [tuple(int(v) for v in m.face_pts[fp[f] : fp[f + 1]]) for f in range(F)]
+    cfaces = [[] for _ in range(N)]
+    for f in range(F):
+        cfaces[m.owner[f]].append(f)
+        if f < nIF:
+            cfaces[m.neighbour[f]].append(f)
+    rep = np.arange(N)
+    for grp in groups:
+        rep[grp] = grp[0]
+    # new cell ids in the order of the old ones: (hex, 'A' / 'B') the two prisms, (hex, face) the pyramid on that face, (hex, None) the rest
+    newid, parent = {}, []
+    for c in range(N):
+        keys = [(c, "A"), (c, "B")] if c in prism else [(c, f) for f in cfaces[c]] if c in split else [(c, None)] if rep[c] == c else []
+        for key in keys:
+            newid[key] = len(parent)
+            parent.append(c)
+    parent = np.array(parent)
+
+    def is_zface(c, f):
+        return set(fverts[f]) in (set(prism[c][:4]), set(prism[c][4:]))
+
+    def side(c, f):  # the new cell of old cell c behind old face f (not a z-face of a prism column)
+        c = int(c)
+        if c in prism:  # half A holds the corner (i+1, j), half B the corner (i, j+1)
+            return newid[(c, "A")] if (prism[c][1] in fverts[f] or prism[c][5] in fverts[f]) else newid[(c, "B")]
+        return newid[(c, f)] if c in split else newid[(int(rep[c]), None)]
+
+    pidx = np.full(F, -1)
+    for k, p in enumerate(m.patches):
+        pidx[p.start : p.start + p.size] = k
+    faces = []  # (vertices, cell a, cell b or -1, patch index or -1)
+    for f in range(F):
+        co = int(m.owner[f])
+        if co in prism and is_zface(co, f):
+            ring = prism[co][:4] if set(fverts[f]) == set(prism[co][:4]) else prism[co][4:]
+            for half, tri in (("A", (ring[0], ring[1], ring[2])), ("B", (ring[0], ring[2], ring[3]))):
+                if f < nIF:
+                    cn = int(m.neighbour[f])
+                    faces.append((tri, newid[(co, half)], newid[(cn, half)], -1))
+                else:
+                    faces.append((tri, newid[(co, half)], -1, pidx[f]))
+            continue
+        a = side(co, f)
+        if f < nIF:
+            b = side(m.neighbour[f], f)
+            if a != b:  # (a == b: a face between two members of a merge group)
+                faces.append((fverts[f], a, b, -1))
+        else:
+            faces.append((fverts[f], a, -1, pidx[f]))
+    for c, (p00, p10, p11, p01, q00, q10, q11, q01) in prism.items():
+        faces.append(((p00, p11, q11, q00), newid[(c, "A")], newid[(c, "B")], -1))
+    pts = [tuple(p) for p in m.points]
+    for c in split:
+        apex = len(pts)
+        vs = sorted({v for f in cfaces[c] for v in fverts[f]})
+        pts.append(tuple(np.mean([pts[v] for v in vs], axis=0)))
+        edges = {}
+        for f in cfaces[c]:
+            fv = fverts[f]
+            for i in range(len(fv)):
+                edges.setdefault(tuple(sorted((fv[i], fv[(i + 1) % len(fv)]))), []).append(f)
+        for e, fs in edges.items():
+            assert len(fs) == 2
+            faces.append(((e[0], e[1], apex), newid[(c, fs[0])], newid[(c, fs[1])], -1))
+    P = np.array(pts, dtype=np.float64)
+    nC = len(parent)
+    # orientation: lower id owns, normal away from the owner (the mean of a cell's face centres is inside every cell built here)
+    acc, cnt = np.zeros((nC, 3)), np.zeros(nC)
+    for fv, a, b, _ in faces:
+        cf = P[list(fv)].mean(0)
+        acc[a] += cf
+        cnt[a] += 1
+        if b >= 0:
+            acc[b] += cf
+            cnt[b] += 1
+    cen = acc / cnt[:, None]
+    out = []
+    for fv, a, b, k in faces:
+        fv = list(fv)
+        if 0 <= b < a:
+            a, b = b, a
+        q = P[fv]
+        fc = q.mean(0)
+        nrm = sum(np.cross(q[i] - fc, q[(i + 1) % len(fv)] - fc) for i in range(len(fv)))
+        if np.dot(nrm, fc - cen[a]) < 0:
+            fv = fv[::-1]
+        out.append((fv, a, b, k))
+    internal = sorted([x for x in out if x[2] >= 0], key=lambda x: (x[1], x[2]))
+    pairs = [(x[1], x[2]) for x in internal]
+    assert len(set(pairs)) == len(pairs), "two new cells share more than one face"
+    bnd, patches, start = [], [], len(internal)
+    for k, p in enumerate(m.patches):
+        fk = [x for x in out if x[3] == k]
+        patches.append(Patch(p.name, p.type, start, len(fk), p.neighbour, p.rotation))
+        start += len(fk)
+        bnd += fk
+    allf = internal + bnd
+    mesh = PolyMesh(points=P, face_ptr=np.concatenate([[0], np.cumsum([len(x[0]) for x in allf])]).astype(np.int32),
+                    face_pts=np.concatenate([x[0] for x in allf]).astype(np.int32), owner=np.array([x[1] for x in allf], np.int32),
+                    neighbour=np.array([x[2] for x in internal], np.int32), patches=patches)
+    g = _InputGeometry(mesh)
+    new = copy.copy(case)
+    new.mesh = mesh
+    new._input_geometry = None
+    new.bcs = {k: dict(v) for k, v in case.bcs.items()}
+    if case.y_wall is not None:
+        new.y_wall = wall_distance(mesh, g.C, g.Cf, g.Sf)
+    rng = np.random.default_rng(seed)
+    Fn, nIFn = mesh.n_faces, mesh.n_internal_faces
+    own, nei = mesh.owner, mesh.neighbour
+    W = case.states
+    # the pieces of one hex (six pyramids, two prisms) must not carry IDENTICAL states: U_N - U_P = 0 across their common faces is exactly
+    # the kink of the linearUpwindV limiter (between "no correction" and "scaled correction"), where the residual has no derivative and a
+    # dual number, a complex step and a difference quotient legitimately disagree.  Each piece gets its own seeded perturbation of the
+    # parent's cell values, of the size channel_case uses
+    sibling = np.bincount(parent, minlength=N)[parent] > 1
+    jit = np.where(sibling[:, None], 1.0 + perturb * rng.standard_normal((nC, 5)), 1.0)
+    if case.solver_name == "DAScalarTransportFoam":  # frozen flux of the velocity field of scalar_transport_case at the new centres
+        Lx = float(m.points[:, 0].max())
+        Uc = np.zeros((nC, 3))
+        Uc[:, 0] = 1.0
+        Uc[:, 1] = 0.2 * np.sin(2 * np.pi * g.C[:, 0] / Lx)
+        Uf = np.zeros((Fn, 3))
+        Uf[:nIFn] = g.w[:, None] * Uc[own[:nIFn]] + (1 - g.w[:, None]) * Uc[nei]
+        Uf[nIFn:] = Uc[own[nIFn:]]
+        phi = np.einsum("ij,ij->i", Uf, g.Sf)
+        for pt in patches:
+            if pt.type == "wall":
+                phi[pt.start : pt.start + pt.size] = 0.0
+        new.phi, new.T_old, new.states = phi, case.T_old[parent], W[parent] * jit[:, 0]
+        return new
+    nsc = (W.size - 3 * N - F) // N
+    U = W[: 3 * N].reshape(N, 3)[parent] * jit[:, :1]
+    cellblocks = [W[(3 + b) * N : (4 + b) * N][parent] * jit[:, 1 + b] for b in range(nsc)]
+    phi = np.zeros(Fn)
+    phi[:nIFn] = np.einsum("ij,ij->i", g.w[:, None] * U[own[:nIFn]] + (1 - g.w[:, None]) * U[nei], g.Sf[:nIFn])
+    for pt in patches:
+        sl = slice(pt.start, pt.start + pt.size)
+        code, val = case.bcs[pt.name]["U"]
+        if code == BC_FIXED_VALUE:
+            phi[sl] = g.Sf[sl] @ np.asarray(val, dtype=float)
+        elif code == BC_SYMMETRY:
+            phi[sl] = 0.0
+        else:  # zeroGradient / inletOutlet: the owner cell's velocity
+            phi[sl] = np.einsum("ij,ij->i", U[own[sl]], g.Sf[sl])
+    phi[:nIFn] *= 1.0 + perturb * rng.standard_normal(nIFn)
+    if case.solver_name in ("DARhoSimpleFoam", "DATurboFoam"):  # mass flux with the free-stream density, as rho_channel_case
+        phi *= case.bcs["outlet"]["p"][1] / (8314.47 / case.thermo["molWeight"] * case.bcs["inlet"]["T"][1])
+    new.states = np.concatenate([U.ravel()] + cellblocks + [phi])
+    return new
 
 
 def _logical_centres(nx, ny, nz, i0=0, i1=None, nx_global=None):
