@@ -239,6 +239,7 @@ _SIGS = {
     "das_get_of_mesh_points": (C.c_int, [_VP, c_double_p]),
     "das_set_coloring": (C.c_int, [_VP, c_int_p]),
     "das_debug_factor_block": (C.c_int, [C.c_int, c_ll_p, c_int_p, c_double_p, C.c_int, c_double_p, c_ll_p, c_int_p, c_int_p]),
+    "das_debug_rcb": (C.c_int, [C.c_int, c_double_p, C.c_int, C.c_int, c_int_p]),
     "das_get_n_colors": (C.c_int, [_VP, C.c_int]),
     "das_get_con_nnz": (C.c_longlong, [_VP, C.c_int]),
     "das_get_con": (C.c_int, [_VP, C.c_int, c_ll_p, c_int_p]),

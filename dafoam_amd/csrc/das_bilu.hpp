@@ -784,18 +784,23 @@ struct BiluStructRef {
 inline void bilu_numeric(long long n, const BiluStructRef& S, bool fp32, long long An, const long long* d_rp, const int* d_ci, const double* d_av, hipStream_t st, NodeILU& P,
                          bool debug, bool transpose, double diagScale, long long shiftExLo, long long shiftExHi, long long shiftEnd, double t0);
 
+// the cells of a set of unknowns: a cell is in iff its first cell state is in `mask` (an empty mask: all cells)
+inline std::vector<char> cells_of_mask(const Mesh& m, const std::vector<StateDef>& states, const std::vector<unsigned char>& mask) {
+    std::vector<char> in(m.nC, 1);
+    if (mask.empty()) return in;
+    const StateDef& s0 = states[0];
+    const int stride = s0.kind == KIND_VEC ? 3 : 1;
+    for (int c = 0; c < m.nC; c++) in[c] = mask[s0.offset + (long long)stride * c] ? 1 : 0;
+    return in;
+}
+
 // Numeric setup on the device from the assembled PC matrix (device CSR, rows = states).
 inline void bilu_setup(const Mesh& m, const std::vector<StateDef>& states, long long n, const std::vector<unsigned char>& owned, int reach,
                        bool fp32, long long An, const long long* d_rp, const int* d_ci, const double* d_av, hipStream_t st, NodeILU& P,
                        bool debug, int nthr, int order, bool transpose = false, double diagScale = 1.0, long long shiftExLo = 0,
                        long long shiftExHi = 0, long long shiftEnd = (long long)1 << 62, const double* dir = nullptr) {
     const double t0 = wall_seconds();
-    std::vector<char> cellOwned(m.nC, 1);
-    if (!owned.empty()) {
-        const StateDef& s0 = states[0];
-        const int stride = s0.kind == KIND_VEC ? 3 : 1;
-        for (int c = 0; c < m.nC; c++) cellOwned[c] = owned[s0.offset + (long long)stride * c] ? 1 : 0;
-    }
+    const std::vector<char> cellOwned = cells_of_mask(m, states, owned);
     std::vector<int> unkNode, bcol;
     std::vector<unsigned char> unkSlot;
     std::vector<long long> bptr, bdiag;
@@ -907,10 +912,7 @@ inline void bilu_setup_multi(const Mesh& m, const std::vector<StateDef>& states,
     long long nN = 0, nnzB = 0;
     for (int b = 0; b < K; b++) {
         const std::vector<unsigned char>& mask = *masks[b];
-        std::vector<char> cellOwned(m.nC, 1);
-        const StateDef& s0 = states[0];
-        const int stride = s0.kind == KIND_VEC ? 3 : 1;
-        for (int c = 0; c < m.nC; c++) cellOwned[c] = mask[s0.offset + (long long)stride * c] ? 1 : 0;
+        const std::vector<char> cellOwned = cells_of_mask(m, states, mask);
         bilu_build_structure(m, states, n, mask, cellOwned, reach, B[b].S, B[b].unkNode, B[b].unkSlot, B[b].bptr, B[b].bdiag, B[b].bcol, std::max(1, nthr), orders[b], dir);
         nLv = std::max(nLv, B[b].S.nLevels);
         nN += B[b].S.nNodes;

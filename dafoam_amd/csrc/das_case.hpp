@@ -78,9 +78,9 @@ inline ResParams make_params(const CaseParams& cp, const Options& opt, int isPC)
     p.offN = rho ? 5 : 4;
     p.offPhi = rho ? 6 : 5;
     p.hasT = cp.hasT;
-    { auto it = opt.i.find("amd.gradFaceParallel"); p.gradFaceParallel = it == opt.i.end() ? 1 : (int)it->second; }
+    p.gradFaceParallel = (int)opt.geti_or("amd.gradFaceParallel", 1);
     // the face / cell split of the cell pass (body_fcoef + body_bcoef + body_cell2) serves DASimpleFoam + SA without T field, MRF and cyclic pairs
-    { auto it = opt.i.find("amd.cellFaceSplit"); p.cellFaceSplit = (it == opt.i.end() ? 0 : (int)it->second) && cp.solver == DAS_SOLVER_SIMPLEFOAM && !cp.hasT && !cp.mrf && !cp.hasCyclic; }
+    p.cellFaceSplit = (int)opt.geti_or("amd.cellFaceSplit", 0) && cp.solver == DAS_SOLVER_SIMPLEFOAM && !cp.hasT && !cp.mrf && !cp.hasCyclic;
     p.Cp = cp.Cp;
     p.Rgas = 8314.47 / cp.molWeight;  // Foam::constant::thermodynamic::RR / molWeight
     p.mu = cp.mu;

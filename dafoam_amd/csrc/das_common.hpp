@@ -348,6 +348,10 @@ struct Options {
     long long geti(const std::string& k) const;
     const std::string& gets(const std::string& k) const;
     bool list_has(const std::string& k, const std::string& item) const;
+    // options without a registered default: the value if set (in the map of that type only), else `dflt`
+    double getd_or(const std::string& k, double dflt) const { auto it = d.find(k); return it == d.end() ? dflt : it->second; }
+    long long geti_or(const std::string& k, long long dflt) const { auto it = i.find(k); return it == i.end() ? dflt : it->second; }
+    std::string gets_or(const std::string& k, const std::string& dflt) const { auto it = s.find(k); return it == s.end() ? dflt : it->second; }
 };
 
 // ---- face / cell records as consumed by the kernels (AoS records, fully consumed per access) ----

@@ -19,6 +19,7 @@
 #include "das_case.hpp"
 #include "das_jaccon.hpp"
 #include "das_bilu.hpp"
+#include "das_rcb.hpp"
 #include "das_comm.hpp"
 #include "das_krylov.hpp"
 #include "das_gmres_host.hpp"
@@ -886,14 +887,27 @@ static void need_init(das_solver* s) {
 static void rank_allreduce(das_solver* s, double* p, long long cnt, hipStream_t st) {
     if (!(s->halo.active && s->halo.allreduce(p, (int)cnt, st)) && s->allreduce_cb) s->allreduce_cb(p, (int)cnt, s->comm_user);
 }
+// a flag the ranks must agree on: true everywhere as soon as it is true on one rank (one rank alone: the flag itself)
+static bool rank_any(das_solver* s, bool flag) {
+    if (!(s->halo.active || s->allreduce_cb)) return flag;
+    DevBuf<double> f(1);
+    const double fv = flag ? 1.0 : 0.0;
+    DAS_HIP(hipMemcpyAsync(f.p, &fv, sizeof(double), hipMemcpyHostToDevice, s->stream));
+    rank_allreduce(s, f.p, 1, s->stream);
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    return f.to_host()[0] > 0.5;
+}
+// y = a x + b y on the solver's stream (len: number of entries, s->n if not given)
+static void axpby(das_solver* s, double a, const double* x, double b, double* y, long long len = -1) {
+    const long long n = len < 0 ? s->n : len;
+    hipLaunchKernelGGL(k_axpby, dim3(nblk(n, 256)), dim3(256), 0, s->stream, n, a, x, b, y);
+}
 
 // state scaling s_j (reference DAPartDeriv.C:210-315, DASolver.C:2356-2455)
 static void compute_scales(das_solver* s) {
     s->h_scale.assign(s->n, 1.0);
     for (const StateDef& sd : s->st_full.states) {
-        double v = 1.0;
-        auto it = s->opt.d.find("normalizeStates." + sd.name);
-        if (it != s->opt.d.end()) v = it->second;
+        const double v = s->opt.getd_or("normalizeStates." + sd.name, 1.0);
         for (long long k = 0; k < sd.size; k++)
             s->h_scale[sd.offset + k] = sd.kind == KIND_FACE ? v * s->mesh.fg[k].magSf : v;
     }
@@ -903,8 +917,7 @@ static void compute_scales(das_solver* s) {
 // ---- graph set-up on the device (das_graph.hpp): transposed structures and colouring input from the host's row-major pattern
 static bool graph_on_device(das_solver* s) {
     if (!s->inited) return false;
-    auto it = s->opt.i.find("amd.graphOnDevice");
-    return it == s->opt.i.end() || it->second != 0;
+    return s->opt.geti_or("amd.graphOnDevice", 1) != 0;
 }
 static void upload_pattern(const JacCon& j, DevPattern& P) {
     P.n = j.n; P.nnz = j.nnz;
@@ -990,8 +1003,7 @@ static void ensure_coloring(das_solver* s, const int* preset = nullptr) {
                     // amd.coloringAlgorithm "firstfit" (default): the serial first-fit as a data-flow kernel over net bitmaps (the
                     // host's serial colours, bit for bit); "speculative": rounds of speculate / detect / retry over the same bitmaps
                     // (order-independent, ~20 % more colours; kept for patterns whose index order gives no wavefront parallelism)
-                    auto it = s->opt.s.find("amd.coloringAlgorithm");
-                    const bool spec = it != s->opt.s.end() && it->second == "speculative";
+                    const bool spec = s->opt.gets_or("amd.coloringAlgorithm", "firstfit") == "speculative";
                     const bool ok = spec ? color_speculative_device(nn, keep, cptr, crow, rowptr, col, colors, s->stream, &s->colorRounds)
                                          : color_firstfit_device(nn, keep, cptr, crow, cpos, rowptr, col, colors, s->stream);
                     if (!ok) fprintf(stderr, "[dafoam_amd] device colouring gave up (too many colours or a timeout): host first-fit instead\n");
@@ -1001,8 +1013,7 @@ static void ensure_coloring(das_solver* s, const int* preset = nullptr) {
             // column -> net incidence (with positions) and the groups are derived on the device, then the same first-fit kernel
             ColorGraphFn gfn = nullptr;
             {
-                auto ita = s->opt.s.find("amd.coloringAlgorithm");
-                const bool spec = ita != s->opt.s.end() && ita->second == "speculative";
+                const bool spec = s->opt.gets_or("amd.coloringAlgorithm", "firstfit") == "speculative";
                 if (devGraph && s->opt.geti("amd.coloringOnDevice") && !spec)
                     gfn = [s, &fullRowMajor, &fullTransposed](long long nn, const std::vector<long long>& keep, std::vector<int>& colors) {
                         const bool dbg = getenv("DAS_DEBUG_TIMING") != nullptr;
@@ -1206,206 +1217,11 @@ static das_mat* assemble(das_solver* s, int isPC, int mode) {
 // rings around an RCB sub-domain, restricted variant) and ILU(`pcFillLevel`) sub-solves with a non-zero pivot shift.
 // Unknowns are ordered cell-by-cell inside a block (cf. adjStateOrdering "cell", DAIndex.C:602-651), which the oracle
 // study in DESIGN.md section 6 shows to be the better ILU ordering for this system.
-namespace {
-struct BlockFactor {
-    std::vector<int> gidx, gout;         // extended unknowns (global ids), owned flag
-    std::vector<long long> frp, fdiag;   // local CSR of the factor
-    std::vector<int> fci;
-    std::vector<double> fv;
-    std::vector<int> Lrows, Urows;
-    std::vector<long long> Llev, Ulev;   // local level pointers (into Lrows/Urows)
-    int nshift = 0;
-    long long nnzLU = 0;
-    // level-sorted entry streams (built inside the parallel block loop), [0] = L, [1] = U
-    std::vector<double> sval[2], invd;
-    std::vector<unsigned> src[2];
-    std::vector<long long> slev[2];      // block-relative level pointers, levels split into <= PC_THREADS entries
-};
+#include "das_ilu_host.hpp"  // BlockFactor, ilu_symbolic, factor_local
 
-// symbolic ILU(k) by level of fill on a sorted local CSR pattern (Saad, Alg. 10.5 structure)
-static void ilu_symbolic(int nl, const std::vector<long long>& rp, const std::vector<int>& ci, int lfill, std::vector<long long>& frp,
-                         std::vector<int>& fci, std::vector<long long>& fdiag) {
-    frp.assign(nl + 1, 0);
-    fdiag.assign(nl, -1);
-    fci.clear();
-    if (lfill <= 0) {
-        fci.reserve(ci.size() + nl);
-        for (int i = 0; i < nl; i++) {
-            bool hasd = false;
-            long long b0 = (long long)fci.size();
-            for (long long q = rp[i]; q < rp[i + 1]; q++) {
-                if (!hasd && ci[q] > i) { fdiag[i] = (long long)fci.size(); fci.push_back(i); hasd = true; }
-                if (ci[q] == i) { fdiag[i] = (long long)fci.size(); hasd = true; }
-                fci.push_back(ci[q]);
-            }
-            if (!hasd) { fdiag[i] = (long long)fci.size(); fci.push_back(i); }
-            (void)b0;
-            frp[i + 1] = (long long)fci.size();
-        }
-        return;
-    }
-    if (lfill == 1) {
-        // ILU(1): a fill entry (i,j) needs a pivot k < min(i,j) with a_ik != 0 and a_kj != 0 ORIGINAL entries (level
-        // 0 + 0 + 1), and level-1 entries create no further fill: row i = A(i) united with the upper parts of the rows
-        // k < i of A(i).  No level bookkeeping, no heap (the default fill level; 3-4x cheaper than the general sweep).
-        std::vector<long long> aup(nl);  // first entry of A's row k with column > k
-        for (int k = 0; k < nl; k++) aup[k] = std::upper_bound(ci.begin() + rp[k], ci.begin() + rp[k + 1], k) - ci.begin();
-        std::vector<int> mark(nl, -1), list;
-        fci.reserve(ci.size() * 3);
-        for (int i = 0; i < nl; i++) {
-            list.clear();
-            for (long long q = rp[i]; q < rp[i + 1]; q++) { const int j = ci[q]; if (mark[j] != i) { mark[j] = i; list.push_back(j); } }
-            if (mark[i] != i) { mark[i] = i; list.push_back(i); }
-            for (long long q = rp[i]; q < rp[i + 1] && ci[q] < i; q++) {
-                const int k = ci[q];
-                for (long long r = aup[k]; r < rp[k + 1]; r++) { const int j = ci[r]; if (mark[j] != i) { mark[j] = i; list.push_back(j); } }
-            }
-            std::sort(list.begin(), list.end());
-            for (int j : list) {
-                if (j == i) fdiag[i] = (long long)fci.size();
-                fci.push_back(j);
-            }
-            frp[i + 1] = (long long)fci.size();
-        }
-        return;
-    }
-    std::vector<int> flev;  // level of each stored entry
-    std::vector<int> wlev(nl, -1), list;
-    std::vector<int> heap;  // min-heap of pending pivot columns (< i)
-    fci.reserve(ci.size() * 3);
-    flev.reserve(ci.size() * 3);
-    auto cmp = [](int a, int b) { return a > b; };
-    for (int i = 0; i < nl; i++) {
-        list.clear();
-        heap.clear();
-        bool hasd = false;
-        for (long long q = rp[i]; q < rp[i + 1]; q++) {
-            int j = ci[q];
-            if (wlev[j] < 0) {
-                wlev[j] = 0;
-                list.push_back(j);
-                if (j < i) heap.push_back(j);
-            }
-            if (j == i) hasd = true;
-        }
-        if (!hasd) { wlev[i] = 0; list.push_back(i); }
-        std::make_heap(heap.begin(), heap.end(), cmp);
-        // pivots in increasing column order; fill created by pivot k only has columns > k, so a heap suffices
-        while (!heap.empty()) {
-            std::pop_heap(heap.begin(), heap.end(), cmp);
-            int k = heap.back();
-            heap.pop_back();
-            int lk = wlev[k];
-            for (long long q = fdiag[k] + 1; q < frp[k + 1]; q++) {
-                int j = fci[q];
-                int nlv = lk + flev[q] + 1;
-                if (nlv > lfill) continue;
-                if (wlev[j] < 0) {
-                    wlev[j] = nlv;
-                    list.push_back(j);
-                    if (j < i) { heap.push_back(j); std::push_heap(heap.begin(), heap.end(), cmp); }
-                } else if (nlv < wlev[j]) wlev[j] = nlv;
-            }
-        }
-        std::sort(list.begin(), list.end());
-        for (int j : list) {
-            if (j == i) fdiag[i] = (long long)fci.size();
-            fci.push_back(j);
-            flev.push_back(wlev[j]);
-            wlev[j] = -1;
-        }
-        frp[i + 1] = (long long)fci.size();
-    }
-}
-}  // namespace
-
-// symbolic + numeric ILU(k) of one block-local CSR (sorted columns), level schedules and the level-sorted entry streams
-// the kernel consumes.  `tim` (optional, 4 doubles) accumulates seconds: symbolic, numeric, schedules, streams.
-static void factor_local(int nl, const std::vector<long long>& lrp, const std::vector<int>& lci, const std::vector<double>& lv, int lfill,
-                         BlockFactor& F, std::vector<long long>& where, std::vector<int>& lev, double* tim) {
-    double tq = tim ? wall_seconds() : 0.0;
-    auto lap = [&](int k) { if (tim) { double t2 = wall_seconds(); tim[k] += t2 - tq; tq = t2; } };
-    ilu_symbolic(nl, lrp, lci, lfill, F.frp, F.fci, F.fdiag);
-    lap(0);
-    F.fv.assign(F.fci.size(), 0.0);
-    where.assign(nl, -1);
-    for (int i = 0; i < nl; i++) {
-        for (long long q = F.frp[i]; q < F.frp[i + 1]; q++) where[F.fci[q]] = q;
-        for (long long q = lrp[i]; q < lrp[i + 1]; q++) F.fv[where[lci[q]]] = lv[q];
-        for (long long q = F.frp[i]; q < F.fdiag[i]; q++) {
-            int kk = F.fci[q];
-            double lik = F.fv[q] / F.fv[F.fdiag[kk]];
-            F.fv[q] = lik;
-            if (lik == 0.0) continue;
-            for (long long r = F.fdiag[kk] + 1; r < F.frp[kk + 1]; r++) {
-                long long d = where[F.fci[r]];
-                if (d >= 0) F.fv[d] -= lik * F.fv[r];
-            }
-        }
-        double piv = F.fv[F.fdiag[i]];
-        if (std::fabs(piv) < 1e-300 || piv != piv) { F.fv[F.fdiag[i]] = (piv < 0 ? -1.0 : 1.0) * 1e-12; F.nshift++; }  // MAT_SHIFT_NONZERO analogue
-        for (long long q = F.frp[i]; q < F.frp[i + 1]; q++) where[F.fci[q]] = -1;
-    }
-    lap(1);
-    // level schedules
-    auto schedule = [&](bool lower, std::vector<int>& rows, std::vector<long long>& levp) {
-        lev.assign(nl, 0);
-        int nlv = 0;
-        if (lower) {
-            for (int i = 0; i < nl; i++) {
-                int l = 0;
-                for (long long q = F.frp[i]; q < F.fdiag[i]; q++) l = std::max(l, lev[F.fci[q]] + 1);
-                lev[i] = l;
-                nlv = std::max(nlv, l + 1);
-            }
-        } else {
-            for (int i = nl - 1; i >= 0; i--) {
-                int l = 0;
-                for (long long q = F.fdiag[i] + 1; q < F.frp[i + 1]; q++) l = std::max(l, lev[F.fci[q]] + 1);
-                lev[i] = l;
-                nlv = std::max(nlv, l + 1);
-            }
-        }
-        levp.assign(nlv + 1, 0);
-        for (int i = 0; i < nl; i++) levp[lev[i] + 1]++;
-        for (int l = 0; l < nlv; l++) levp[l + 1] += levp[l];
-        rows.assign(nl, 0);
-        std::vector<long long> fill(levp.begin(), levp.end() - 1);
-        for (int i = 0; i < nl; i++) rows[fill[lev[i]]++] = i;
-    };
-    schedule(true, F.Lrows, F.Llev);
-    schedule(false, F.Urows, F.Ulev);
-    lap(2);
-    // entry streams sorted by (level, row); levels split into pieces of <= PC_THREADS entries (one entry per
-    // thread per level in the kernel); U rows pre-divided by the pivot
-    DAS_CHECK(nl <= 65535, DAS_ERR_ARG, "preconditioner block larger than 65535 unknowns: reduce amd.pcBlockCells");
-    F.invd.resize(nl);
-    for (int i = 0; i < nl; i++) F.invd[i] = 1.0 / F.fv[F.fdiag[i]];
-    for (int t = 0; t < 2; t++) {
-        const std::vector<long long>& lv = t == 0 ? F.Llev : F.Ulev;
-        const std::vector<int>& rows = t == 0 ? F.Lrows : F.Urows;
-        F.sval[t].reserve(F.fci.size() / 2 + 16);
-        F.src[t].reserve(F.fci.size() / 2 + 16);
-        for (size_t l = 0; l + 1 < lv.size(); l++) {
-            F.slev[t].push_back((long long)F.sval[t].size());
-            long long inLevel = 0;
-            for (long long r = lv[l]; r < lv[l + 1]; r++) {
-                const int i = rows[r];
-                const long long q0 = t == 0 ? F.frp[i] : F.fdiag[i] + 1;
-                const long long q1 = t == 0 ? F.fdiag[i] : F.frp[i + 1];
-                const double scale = t == 0 ? 1.0 : F.invd[i];
-                for (long long q = q0; q < q1; q++) {
-                    if (inLevel == PC_THREADS) { F.slev[t].push_back((long long)F.sval[t].size()); inLevel = 0; }
-                    F.sval[t].push_back(F.fv[q] * scale);
-                    F.src[t].push_back((unsigned)i | ((unsigned)F.fci[q] << 16));
-                    inLevel++;
-                }
-            }
-        }
-        F.slev[t].push_back((long long)F.sval[t].size());
-    }
-    lap(3);
-}
+// host threads of a preconditioner set-up: every block touches ~100 MB of fresh host memory; beyond a few dozen threads the kernel's
+// page-fault / mmap paths serialise (measured on the 256-core MI355X host), hence the cap amd.setupThreads
+static int pc_setup_threads(das_solver* s) { return (int)std::max<long long>(1, std::min<long long>(das::host_threads(), s->opt.geti("amd.setupThreads"))); }
 
 static void setup_block_ilu(das_solver* s, das_ksp* k) {
     double t0 = wall_seconds();
@@ -1424,43 +1240,19 @@ static void setup_block_ilu(das_solver* s, das_ksp* k) {
     // scotch, pyDAFoam.py:597-604; RCB gives comparable compact blocks without a graph library)
     // multi-GPU: only cells owned by this rank take part (block-Jacobi across ranks, like the reference's one
     // ASM sub-domain per MPI rank); a cell is owned iff its first cell-state is owned
-    std::vector<char> cellOwned(m.nC, 1);
+    const std::vector<char> cellOwned = cells_of_mask(m, s->st_full.states, s->owned);
     long long nOwnedStates = n;
     if (!s->owned.empty()) {
-        const StateDef& s0 = s->st_full.states[0];
-        const int stride = s0.kind == KIND_VEC ? 3 : 1;
-        for (int c = 0; c < m.nC; c++) cellOwned[c] = s->owned[s0.offset + (long long)stride * c] ? 1 : 0;
         nOwnedStates = 0;
         for (unsigned char o : s->owned) nOwnedStates += o ? 1 : 0;
     }
     std::vector<int> cellOrder;
     cellOrder.reserve(m.nC);
     for (int c = 0; c < m.nC; c++) if (cellOwned[c]) cellOrder.push_back(c);
-    const long long nOwnedCells = (long long)cellOrder.size();
     std::vector<long long> cboff;
-    {
-        struct Range { long long b, e; };
-        std::vector<Range> stack{{0, nOwnedCells}}, leaves;
-        while (!stack.empty()) {
-            Range r = stack.back();
-            stack.pop_back();
-            if (r.e - r.b <= bc) { leaves.push_back(r); continue; }
-            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-            for (long long q = r.b; q < r.e; q++)
-                for (int d = 0; d < 3; d++) { double x = m.cg[cellOrder[q]].C[d]; lo[d] = std::min(lo[d], x); hi[d] = std::max(hi[d], x); }
-            int dim = 0;
-            for (int d = 1; d < 3; d++) if (hi[d] - lo[d] > hi[dim] - lo[dim]) dim = d;
-            long long mid = (r.b + r.e) / 2;
-            std::nth_element(cellOrder.begin() + r.b, cellOrder.begin() + mid, cellOrder.begin() + r.e,
-                             [&](int a, int b2) { double xa = m.cg[a].C[dim], xb = m.cg[b2].C[dim]; return xa < xb || (xa == xb && a < b2); });
-            stack.push_back({mid, r.e});
-            stack.push_back({r.b, mid});
-        }
-        std::sort(leaves.begin(), leaves.end(), [](const Range& a, const Range& b2) { return a.b < b2.b; });
-        for (auto& r : leaves) { std::sort(cellOrder.begin() + r.b, cellOrder.begin() + r.e); cboff.push_back(r.b); }
-        cboff.push_back(nOwnedCells);
-    }
+    rcb_leaves(cellOrder, [&](int c, int d) { return m.cg[c].C[d]; }, bc, cboff);
     const int nB = (int)cboff.size() - 1;
+    for (int b = 0; b < nB; b++) std::sort(cellOrder.begin() + cboff[b], cellOrder.begin() + cboff[b + 1]);
     std::vector<std::vector<int>> owned(m.nC);
     bool hasFace = false;
     for (const StateDef& sd : s->st_full.states) if (sd.kind == KIND_FACE) hasFace = true;
@@ -1469,9 +1261,7 @@ static void setup_block_ilu(das_solver* s, das_ksp* k) {
     std::vector<BlockFactor> BF(nB);
     std::string err;
     const double t_prep = wall_seconds();
-    // every block touches ~100 MB of fresh host memory; beyond a few dozen threads the kernel's page-fault / mmap paths
-    // serialise (measured on the 256-core MI355X host), hence the cap amd.setupThreads
-    const int nthr = (int)std::max<long long>(1, std::min<long long>(das::host_threads(), s->opt.geti("amd.setupThreads")));
+    const int nthr = pc_setup_threads(s);
 #pragma omp parallel num_threads(nthr)
     {
         std::vector<int> cmark(m.nC, -1);
@@ -1678,28 +1468,38 @@ static void pc_flow_direction(das_solver* s, double* dir) {
     }
 }
 
-// global node-block ILU(0) (das_bilu.hpp): one incomplete factorisation of dRdWTPC over this rank's unknowns
-static void setup_node_ilu_into(das_solver* s, das_ksp* k, NodeILU& P, const std::vector<unsigned char>& mask, int order);
-static void setup_node_ilu(das_solver* s, das_ksp* k) {
-    const double t0 = wall_seconds();
-    setup_node_ilu_into(s, k, k->bilu, (s->pcMask.empty() || k->pcTranspose) ? s->owned : s->pcMask, k->pcOrder >= 0 ? k->pcOrder : (pc_ordering_rcm(s) ? 1 : 0));
+// several ranks: the sub-domain of this rank = its owned unknowns, or - asmOverlap > 0 - those plus the overlap rings (das_set_pc_overlap)
+static const std::vector<unsigned char>& pc_mask(das_solver* s, das_ksp* k) { return (s->pcMask.empty() || k->pcTranspose) ? s->owned : s->pcMask; }
+// the elimination order the options ask for (orders: das_bilu.hpp)
+static int pc_configured_order(das_solver* s, das_ksp* k) { return k->pcOrder >= 0 ? k->pcOrder : (pc_ordering_rcm(s) ? 1 : 0); }
+// a DEEP order: levels >> nodes^(1/3) - e.g. reverse Cuthill-McKee of a thin far-field block, 23755 levels for 270 k nodes where ~500 are normal
+static bool pc_order_is_deep(int levels, int nodes) { return (double)levels > 30.0 * std::cbrt((double)std::max(1, nodes)); }
+static const char* rank_label() { return getenv("RANK") ? getenv("RANK") : "0"; }
+
+// what every node-block ILU set-up (das_bilu.hpp) takes from the solver: stencil reach, set-up threads, flow direction, factor precision
+struct BiluInputs {
+    const Mat& A;
+    int reach, nthr;
+    bool fp32, debug;
+    double dir[3];
+    BiluInputs(das_solver* s, das_ksp* k)
+        : A(k->pcmat->m), reach(pc_stencil_reach(s)), nthr(pc_setup_threads(s)), fp32(s->opt.geti("amd.pcFactorFP32") != 0), debug(s->opt.geti("debug") != 0) { pc_flow_direction(s, dir); }
+};
+// global node-block ILU(0): one incomplete factorisation of dRdWTPC over `mask`'s unknowns in elimination order `order`
+static void factorise_node_ilu(das_solver* s, das_ksp* k, NodeILU& P, const std::vector<unsigned char>& mask, int order) {
+    const BiluInputs in(s, k);
+    bilu_setup(s->mesh, s->st_full.states, s->n, mask, in.reach, in.fp32, in.A.n, in.A.rowptr.p, in.A.col.p, in.A.val.p, s->stream,
+               P, in.debug, in.nthr, order, k->pcTranspose, k->pcDiagScale, k->shiftExLo, k->shiftExHi, k->shiftEnd, in.dir);
+}
+// what every node-block ILU set-up ends with: k->bilu holds the factorisation of nBlocks sub-domains, set up since t0
+static void pc_finish_bilu(das_solver* s, das_ksp* k, double t0, int nBlocks, bool rasOverlap) {
     k->useBilu = true;
-    k->rasOverlap = !s->pcMask.empty() && !k->pcTranspose && s->halo.ovActive;
+    k->rasOverlap = rasOverlap;
     if (k->rasOverlap && k->pcin.n != (size_t)s->n) k->pcin.alloc(s->n);
     k->pc.setup_seconds = wall_seconds() - t0;
-    k->pc.nBlocks = 1;
+    k->pc.nBlocks = nBlocks;
     k->pc.fnnz = (k->bilu.nL + k->bilu.nU + k->bilu.nNodes) * (long long)BILU_NB2;
     k->pc.next = (long long)k->bilu.nNodes * BILU_NB;
-}
-static void setup_node_ilu_into(das_solver* s, das_ksp* k, NodeILU& P, const std::vector<unsigned char>& mask, int order) {
-    const Mat& A = k->pcmat->m;
-    const int reach = pc_stencil_reach(s);
-    const int nthr = (int)std::max<long long>(1, std::min<long long>(das::host_threads(), s->opt.geti("amd.setupThreads")));
-    // several ranks: the sub-domain of this rank = its owned unknowns, or - asmOverlap > 0 - those plus the overlap rings (das_set_pc_overlap)
-    double dir[3];
-    pc_flow_direction(s, dir);
-    bilu_setup(s->mesh, s->st_full.states, s->n, mask, reach, s->opt.geti("amd.pcFactorFP32") != 0, A.n, A.rowptr.p, A.col.p, A.val.p, s->stream,
-               P, s->opt.geti("debug") != 0, nthr, order, k->pcTranspose, k->pcDiagScale, k->shiftExLo, k->shiftExHi, k->shiftEnd, dir);
 }
 
 // Stability estimate of the incomplete factorisation: max |(LU)^-1 P e - e| over the sub-domain's unknowns for e = ones and for a +-1
@@ -1741,7 +1541,7 @@ static double pc_stability_estimate(das_solver* s, das_ksp* k, NodeILU& F, const
             if (worst < sd.offset || worst >= sd.offset + sd.size) continue;
             const long long ent = (worst - sd.offset) / (sd.kind == KIND_VEC ? 3 : 1);
             const double* C = sd.kind == KIND_FACE ? s->mesh.fg[ent].Cf : s->mesh.cg[ent].C;
-            fprintf(stderr, "[dafoam_amd] rank %s: worst entry of the stability test: state %s entity %lld at (%.4g %.4g %.4g)%s\n", getenv("RANK") ? getenv("RANK") : "0",
+            fprintf(stderr, "[dafoam_amd] rank %s: worst entry of the stability test: state %s entity %lld at (%.4g %.4g %.4g)%s\n", rank_label(),
                     sd.name.c_str(), ent, C[0], C[1], C[2], (!s->owned.empty() && !s->owned[worst]) ? " (overlap ring)" : "");
         }
     }
@@ -1756,11 +1556,11 @@ static double pc_stability_estimate(das_solver* s, das_ksp* k, NodeILU& F, const
 // orders, > 1000 with reverse Cuthill-McKee everywhere); otherwise the first candidate below the limit.  Local to the rank: no collective.
 static void choose_order_and_factorise(das_solver* s, das_ksp* k, NodeILU& F, const std::vector<unsigned char>& mask, bool pickMin, int& orderUsed, double& estimate,
                                        bool earlyAccept = true) {
-    const int configured = k->pcOrder >= 0 ? k->pcOrder : (pc_ordering_rcm(s) ? 1 : 0);
+    const int configured = pc_configured_order(s, k);
     const double limit = s->opt.getd("amd.pcStabilityLimit");
     if (!(limit > 0.0)) {
         F = NodeILU();
-        setup_node_ilu_into(s, k, F, mask, configured);
+        factorise_node_ilu(s, k, F, mask, configured);
         orderUsed = -1; estimate = -1.0;
         return;
     }
@@ -1784,16 +1584,14 @@ static void choose_order_and_factorise(das_solver* s, das_ksp* k, NodeILU& F, co
     for (size_t attempt = 0; attempt < cand.size(); attempt++) {
         const int o = cand[attempt];
         F = NodeILU();
-        setup_node_ilu_into(s, k, F, mask, o);
+        factorise_node_ilu(s, k, F, mask, o);
         const double est = pc_stability_estimate(s, k, F, mask);
         last = o;
         seen.push_back({o, est, F.nLevels});
         if (s->opt.geti("debug") || getenv("DAS_PC_STAB") || (est > limit && !pickMin))
             fprintf(stderr, "[dafoam_amd] rank %s: preconditioner stability estimate max|(LU)^-1 P e - e| = %.3e with elimination order %d, %d levels (limit %.1e)%s\n",
-                    getenv("RANK") ? getenv("RANK") : "0", est, o, F.nLevels, limit, (est > limit && !pickMin) ? ": unstable, trying another order" : "");
-        // (a DEEP order is never accepted early: levels >> nodes^(1/3) - e.g. reverse Cuthill-McKee of a thin far-field block, 23755 levels
-        //  for 270 k nodes where ~500 are normal)
-        const bool deep = (double)F.nLevels > 30.0 * std::cbrt((double)std::max(1, F.nNodes));
+                    rank_label(), est, o, F.nLevels, limit, (est > limit && !pickMin) ? ": unstable, trying another order" : "");
+        const bool deep = pc_order_is_deep(F.nLevels, F.nNodes);  // (never accepted early)
         // (earlyAccept false - the sub-domains of a multi-rank solve: every candidate is evaluated; 403 k cells on 8 ranks: 722 iterations, with the
         //  early accept 867)
         if (est <= limit && (!pickMin || (earlyAccept && est <= good && !deep))) break;
@@ -1810,11 +1608,25 @@ static void choose_order_and_factorise(das_solver* s, das_ksp* k, NodeILU& F, co
             if ((!anyOk || c.est <= limit) && (double)c.levels <= 1.5 * minLv && c.est < bestEst) { best = c.o; bestEst = c.est; }
     if (last != best) {
         F = NodeILU();
-        setup_node_ilu_into(s, k, F, mask, best);
+        factorise_node_ilu(s, k, F, mask, best);
     }
     if (bestEst > limit)
-        fprintf(stderr, "[dafoam_amd] rank %s: no elimination order passes the stability limit; keeping order %d (estimate %.3e)\n", getenv("RANK") ? getenv("RANK") : "0", best, bestEst);
+        fprintf(stderr, "[dafoam_amd] rank %s: no elimination order passes the stability limit; keeping order %d (estimate %.3e)\n", rank_label(), best, bestEst);
     orderUsed = best; estimate = bestEst;
+}
+
+// ONE node-block ILU over this rank's unknowns.  byEstimate (the adjoint): the elimination order is chosen by the stability estimate - a
+// sub-domain of a multi-rank solve takes the order with the smallest estimate, one rank alone the first stable one; else (the Newton primal,
+// which factorises again and again) the configured order
+static void setup_node_ilu(das_solver* s, das_ksp* k, bool byEstimate) {
+    const double t0 = wall_seconds();
+    if (byEstimate) {
+        choose_order_and_factorise(s, k, k->bilu, pc_mask(s, k), !s->owned.empty(), k->pcOrderUsed, k->pcStability, /*earlyAccept*/ s->owned.empty());
+        if (k->pcOrderUsed >= 0) k->pcOrder = k->pcOrderUsed;
+    } else {
+        factorise_node_ilu(s, k, k->bilu, pc_mask(s, k), pc_configured_order(s, k));
+    }
+    pc_finish_bilu(s, k, t0, 1, !s->pcMask.empty() && !k->pcTranspose && s->halo.ovActive);
 }
 
 // amd.pcSubdomains: K > 1 sub-domain factorisations inside this rank (single-rank adjoint solves only); -1 = automatic: 4 from 1 M cells
@@ -1823,6 +1635,17 @@ static long long pc_subdomain_count(das_solver* s) {
     if (!s->owned.empty()) return 1;
     if (K < 0) K = s->mesh.nC >= 1000000 ? 4 : 1;
     return std::max<long long>(1, std::min<long long>(K, 16));
+}
+
+// fn(unknown, cell) for every unknown with the cell it belongs to: cell states their cell, face states the face's owner cell
+template <class Fn>
+static void for_each_unknown_with_cell(das_solver* s, Fn fn) {
+    const Mesh& m = s->mesh;
+    for (const StateDef& sd : s->st_full.states) {
+        if (sd.kind == KIND_VEC) { for (int c = 0; c < m.nC; c++) for (int q = 0; q < 3; q++) fn(sd.offset + 3LL * c + q, c); }
+        else if (sd.kind == KIND_SCL) { for (int c = 0; c < m.nC; c++) fn(sd.offset + c, c); }
+        else { for (long long f = 0; f < m.nF; f++) fn(sd.offset + f, m.owner[f]); }
+    }
 }
 
 // Restricted additive Schwarz inside one GPU: K blocks of the cells by recursive coordinate bisection of the cell centres (K = 4 on a wing:
@@ -1837,42 +1660,11 @@ static bool setup_subdomain_ilus(das_solver* s, das_ksp* k, int K) {
     const long long N = m.nC, n = s->n;
     // ---- RCB of the cell centres
     std::vector<int> cells(N), blockOf(N, 0);
-    for (long long c = 0; c < N; c++) cells[c] = (int)c;
-    struct Rg { long long b, e; int a0, na; };
-    std::vector<Rg> stack{{0, N, 0, K}};
-    while (!stack.empty()) {
-        Rg r = stack.back();
-        stack.pop_back();
-        if (r.na == 1) { for (long long q = r.b; q < r.e; q++) blockOf[cells[q]] = r.a0; continue; }
-        double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-        for (long long q = r.b; q < r.e; q++)
-            for (int d = 0; d < 3; d++) { const double x = m.cg[cells[q]].C[d]; lo[d] = std::min(lo[d], x); hi[d] = std::max(hi[d], x); }
-        int ax = 0;
-        for (int d = 1; d < 3; d++) if (hi[d] - lo[d] > hi[ax] - lo[ax]) ax = d;
-        const int nl = r.na / 2;
-        const long long mid = r.b + (r.e - r.b) * nl / r.na;
-        std::nth_element(cells.begin() + r.b, cells.begin() + mid, cells.begin() + r.e, [&](int a, int b2) {
-            const double xa = m.cg[a].C[ax], xb = m.cg[b2].C[ax];
-            return xa < xb || (xa == xb && a < b2);
-        });
-        stack.push_back({mid, r.e, r.a0 + nl, r.na - nl});
-        stack.push_back({r.b, mid, r.a0, nl});
-    }
+    std::iota(cells.begin(), cells.end(), 0);
+    rcb_parts(cells, [&](int c, int d) { return m.cg[c].C[d]; }, K, blockOf);
     // ---- unknown -> block (cell states: the cell's block; face states: the owner cell's)
-    auto fill_mask = [&](const std::vector<unsigned char>& cellIn, std::vector<unsigned char>& out) {
-        out.assign(n, 0);
-        for (const StateDef& sd : s->st_full.states) {
-            if (sd.kind == KIND_VEC) { for (long long c = 0; c < N; c++) if (cellIn[c]) { out[sd.offset + 3 * c] = out[sd.offset + 3 * c + 1] = out[sd.offset + 3 * c + 2] = 1; } }
-            else if (sd.kind == KIND_SCL) { for (long long c = 0; c < N; c++) if (cellIn[c]) out[sd.offset + c] = 1; }
-            else { for (long long f = 0; f < m.nF; f++) if (cellIn[m.owner[f]]) out[sd.offset + f] = 1; }
-        }
-    };
     std::vector<unsigned char> subOf(n, 0);
-    for (const StateDef& sd : s->st_full.states) {
-        if (sd.kind == KIND_VEC) { for (long long c = 0; c < N; c++) for (int q = 0; q < 3; q++) subOf[sd.offset + 3 * c + q] = (unsigned char)blockOf[c]; }
-        else if (sd.kind == KIND_SCL) { for (long long c = 0; c < N; c++) subOf[sd.offset + c] = (unsigned char)blockOf[c]; }
-        else { for (long long f = 0; f < m.nF; f++) subOf[sd.offset + f] = (unsigned char)blockOf[m.owner[f]]; }
-    }
+    for_each_unknown_with_cell(s, [&](long long g, int c) { subOf[g] = (unsigned char)blockOf[c]; });
     const int overlap = (int)std::max<long long>(0, s->opt.geti("adjEqnOption.asmOverlap"));
     std::vector<std::vector<unsigned char>> masks(K);
     k->subOrder.assign(K, -1);
@@ -1885,17 +1677,18 @@ static bool setup_subdomain_ilus(das_solver* s, das_ksp* k, int K) {
             for (long long c = 0; c < N; c++) if (cellIn[c]) for (int q = m.cc_ptr[c]; q < m.cc_ptr[c + 1]; q++) grown[m.cc[q]] = 1;
             cellIn.swap(grown);
         }
-        fill_mask(cellIn, masks[b]);
+        masks[b].assign(n, 0);
+        for_each_unknown_with_cell(s, [&](long long g, int c) { masks[b][g] = cellIn[c]; });
         // the block's own factorisation: only to choose its elimination order (smallest stability estimate); released again
         NodeILU F;
         choose_order_and_factorise(s, k, F, masks[b], true, k->subOrder[b], k->subEst[b]);
-        if (k->subOrder[b] < 0) k->subOrder[b] = k->pcOrder >= 0 ? k->pcOrder : (pc_ordering_rcm(s) ? 1 : 0);
+        if (k->subOrder[b] < 0) k->subOrder[b] = pc_configured_order(s, k);
         if (s->opt.geti("debug") || getenv("DAS_PC_STAB"))
             fprintf(stderr, "[dafoam_amd] sub-domain %d of %d: %d nodes, %d levels, elimination order %d, stability estimate %.3e\n", b, K, F.nNodes, F.nLevels, k->subOrder[b], k->subEst[b]);
         // a block whose best order is still DEEP (levels >> nodes^(1/3): coordinate-bisection blocks that cut the grid lines of a swept wing
         // diagonally - round 6: 2489 ... 16618 levels for 540 k nodes, 13.9 ms per apply and more iterations than the single factorisation)
         // makes the merged structure slow: the caller falls back to ONE factorisation
-        if ((double)F.nLevels > 30.0 * std::cbrt((double)std::max(1, F.nNodes)) && s->opt.geti("amd.pcSubdomains") < 0) {
+        if (pc_order_is_deep(F.nLevels, F.nNodes) && s->opt.geti("amd.pcSubdomains") < 0) {
             fprintf(stderr, "[dafoam_amd] sub-domain %d of %d needs %d dependency levels for %d nodes: the blocks do not suit this mesh, one factorisation instead "
                             "(amd.pcSubdomains K > 1 forces the blocks)\n", b, K, F.nLevels, F.nNodes);
             k->subOrder.clear(); k->subEst.clear();
@@ -1904,27 +1697,18 @@ static bool setup_subdomain_ilus(das_solver* s, das_ksp* k, int K) {
     }
     // ---- ONE merged level structure for the K blocks
     {
-        const Mat& A = k->pcmat->m;
-        const int reach = pc_stencil_reach(s);
-        const int nthr = (int)std::max<long long>(1, std::min<long long>(das::host_threads(), s->opt.geti("amd.setupThreads")));
-        double dir[3];
-        pc_flow_direction(s, dir);
+        const BiluInputs in(s, k);
         std::vector<const std::vector<unsigned char>*> mp;
         for (int b = 0; b < K; b++) mp.push_back(&masks[b]);
         k->bilu = NodeILU();
-        bilu_setup_multi(s->mesh, s->st_full.states, n, mp, k->subOrder, subOf, reach, s->opt.geti("amd.pcFactorFP32") != 0, A.n, A.rowptr.p, A.col.p, A.val.p, s->stream, k->bilu,
-                         s->opt.geti("debug") != 0, nthr, dir);
+        bilu_setup_multi(s->mesh, s->st_full.states, n, mp, k->subOrder, subOf, in.reach, in.fp32, in.A.n, in.A.rowptr.p, in.A.col.p, in.A.val.p, s->stream, k->bilu,
+                         in.debug, in.nthr, in.dir);
     }
     k->nSub = K;
-    k->useBilu = true;
-    k->rasOverlap = false;
     k->pcOrderUsed = k->subOrder[0];
     k->pcStability = 0.0;
     for (double e : k->subEst) k->pcStability = std::max(k->pcStability, e);
-    k->pc.setup_seconds = wall_seconds() - t0;
-    k->pc.nBlocks = K;
-    k->pc.fnnz = (k->bilu.nL + k->bilu.nU + k->bilu.nNodes) * (long long)BILU_NB2;
-    k->pc.next = (long long)k->bilu.nNodes * BILU_NB;
+    pc_finish_bilu(s, k, t0, K, false);
     if (s->opt.geti("debug") || getenv("DAS_PC_STAB"))
         fprintf(stderr, "[dafoam_amd] %d sub-domains merged: %d nodes, %d levels (%.0f nodes per level)\n", K, k->bilu.nNodes, k->bilu.nLevels, (double)k->bilu.nNodes / std::max(1, k->bilu.nLevels));
     return true;
@@ -1997,26 +1781,7 @@ static void setup_coarse(das_solver* s, das_ksp* k) {
         if (nagg < 2) return;
     } else {
         // recursive coordinate bisection into nagg parts of (almost) equal size
-        struct Rg { long long b, e; int a0, na; };
-        std::vector<Rg> stack{{0, (long long)owned.size(), 0, nagg}};
-        while (!stack.empty()) {
-            Rg r = stack.back();
-            stack.pop_back();
-            if (r.na == 1) { for (long long q = r.b; q < r.e; q++) agg[owned[q]] = r.a0; continue; }
-            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-            for (long long q = r.b; q < r.e; q++)
-                for (int d = 0; d < 3; d++) { const double x = m.cg[owned[q]].C[d]; lo[d] = std::min(lo[d], x); hi[d] = std::max(hi[d], x); }
-            int ax = 0;
-            for (int d = 1; d < 3; d++) if (hi[d] - lo[d] > hi[ax] - lo[ax]) ax = d;
-            const int nl = r.na / 2;
-            const long long mid = r.b + (r.e - r.b) * nl / r.na;
-            std::nth_element(owned.begin() + r.b, owned.begin() + mid, owned.begin() + r.e, [&](int a, int b2) {
-                const double xa = m.cg[a].C[ax], xb = m.cg[b2].C[ax];
-                return xa < xb || (xa == xb && a < b2);
-            });
-            stack.push_back({mid, r.e, r.a0 + nl, r.na - nl});
-            stack.push_back({r.b, mid, r.a0, nl});
-        }
+        rcb_parts(owned, [&](int c, int d) { return m.cg[c].C[d]; }, nagg, agg);
     }
     std::vector<long long> aptr;
     std::vector<int> cells;
@@ -2077,9 +1842,7 @@ static void gmres_ws(das_solver* s, das_ksp* k, int polyD = 0) {
     long long restart = std::min<long long>(s->opt.geti("adjEqnOption.gmresRestart"), s->opt.geti("adjEqnOption.gmresMaxIters"));
     k->polyD = polyD;
     if (polyD > 0) restart = std::min<long long>(s->opt.geti("adjEqnOption.gmresRestart"), (std::max<long long>(s->opt.geti("adjEqnOption.gmresMaxIters"), 1) + polyD - 1) / polyD + polyD);
-    long long budget = (long long)(32.0 * 1024 * 1024 * 1024);
-    auto it = s->opt.i.find("amd.maxKrylovBytes");
-    if (it != s->opt.i.end()) budget = it->second;
+    const long long budget = s->opt.geti_or("amd.maxKrylovBytes", (long long)(32.0 * 1024 * 1024 * 1024));
     const long long nr = (n + 3) / 4 * 4;  // fp64 elements a basis vector occupies at most (float storage pads its rows to a multiple of 4: basis_ld)
     const long long maxVec = std::max<long long>(3, budget / (8 * nr));  // vectors the budget holds (restart + 2 of them are needed)
     restart = std::max<long long>(1, std::min<long long>(restart, maxVec - 2));
@@ -2097,8 +1860,7 @@ static void gmres_ws(das_solver* s, das_ksp* k, int polyD = 0) {
     {   // storage type of the basis.  "auto" (default): split (hi + lo floats) for the delayed re-orthogonalisation when the basis is >= 1 GB,
         // else fp64; the tolerance does not enter (split storage keeps 48 mantissa bits per entry: the parity tests solve to 1e-10 .. 1e-12
         // with it); always fp64 for modified Gram-Schmidt, deflated restarting and the Newton primal's inner solves
-        std::string prec = "auto";
-        { auto ip = s->opt.s.find("amd.krylovBasisPrecision"); if (ip != s->opt.s.end()) prec = ip->second; }
+        const std::string prec = s->opt.gets_or("amd.krylovBasisPrecision", "auto");
         DAS_CHECK(prec == "auto" || prec == "fp64" || prec == "fp32" || prec == "split", DAS_ERR_ARG, "amd.krylovBasisPrecision: auto | fp64 | split | fp32");
         const bool eligible = s->opt.geti("adjEqnOption.useMGSO") == 0 && !s->fwd.on;
         // "fp32" storage alone (round 5, measured on the 2 M-cell wing, profiles/r06c_*): the recurrence follows the fp64 run to four
@@ -2112,17 +1874,10 @@ static void gmres_ws(das_solver* s, das_ksp* k, int polyD = 0) {
         // "auto" = split for the delayed re-orthogonalisation when the basis is >= 1 GB (the Gram-Schmidt passes then dominate), else fp64.
         const bool dcgs2 = s->opt.gets("amd.gmresOrthogonalization") == "dcgs2" && s->opt.geti("adjEqnOption.useMGSO") == 0;
         bool big = (size_t)(restart + 2) * (size_t)n * 8 >= ((size_t)1 << 30);
-        if (s->halo.active || s->allreduce_cb) {
-            // several ranks: n (owned + ghost rows) differs from rank to rank, but the storage type fixes the recurrence target (recTarget)
-            // every rank compares the SAME all-reduced residual with - the ranks must agree on it or they disagree on closing a cycle
-            // (ADVICE round 5): split everywhere as soon as one rank's basis is that large
-            DevBuf<double> f(1);
-            const double fv = big ? 1.0 : 0.0;
-            DAS_HIP(hipMemcpyAsync(f.p, &fv, sizeof(double), hipMemcpyHostToDevice, s->stream));
-            rank_allreduce(s, f.p, 1, s->stream);
-            DAS_HIP(hipStreamSynchronize(s->stream));
-            big = f.to_host()[0] > 0.5;
-        }
+        // several ranks: n (owned + ghost rows) differs from rank to rank, but the storage type fixes the recurrence target (recTarget)
+        // every rank compares the SAME all-reduced residual with - the ranks must agree on it or they disagree on closing a cycle
+        // (ADVICE round 5): split everywhere as soon as one rank's basis is that large
+        big = rank_any(s, big);
         k->split = eligible && (prec == "split" || (prec == "auto" && dcgs2 && big));
         k->vf32 = k->split || (eligible && prec == "fp32");
         if (k->vf32 && k->ustage.n != (size_t)n) k->ustage.alloc(n);
@@ -2179,7 +1934,7 @@ static void apply_operator(das_solver* s, const double* x, double* y);
 static bool coarse_az_ready(das_solver* s, das_ksp* k) {
     das_ksp::CoarsePC& C = k->coarse;
     if (!s->op || s->fwd.on) return false;
-    { auto it = s->opt.i.find("amd.pcCoarseSparseAZ"); if (it != s->opt.i.end() && it->second == 0) return false; }
+    if (s->opt.geti_or("amd.pcCoarseSparseAZ", 1) == 0) return false;
     const Mat& A = s->op->m;
     // keyed on the operator's id, not its address: solveAdjoint destroys and re-creates the operator per solve and the allocator may hand
     // back the same address
@@ -2188,17 +1943,9 @@ static bool coarse_az_ready(das_solver* s, das_ksp* k) {
     const long long n = s->n;
     hipStream_t st = s->stream;
     DevBuf<int> cnt(n);
-    const bool built = coarse_az_build(n, A.rowptr.p, A.col.p, A.val.p, C.N, C.off, C.agg.p, cnt, C.azPtr, C.azAgg, C.azVal, C.azNnz, st, [&](int ovfAny) {
-        if (s->halo.active || s->allreduce_cb) {  // several ranks: all of them take the same path (the fallback is a collective operator product)
-            DevBuf<double> f(1);
-            const double fv = ovfAny ? 1.0 : 0.0;
-            DAS_HIP(hipMemcpyAsync(f.p, &fv, sizeof(double), hipMemcpyHostToDevice, st));
-            rank_allreduce(s, f.p, 1, st);
-            DAS_HIP(hipStreamSynchronize(st));
-            ovfAny = f.to_host()[0] > 0.5 ? 1 : 0;
-        }
-        return ovfAny;
-    });
+    // (several ranks: all of them take the same path - the fallback is a collective operator product)
+    const bool built = coarse_az_build(n, A.rowptr.p, A.col.p, A.val.p, C.N, C.off, C.agg.p, cnt, C.azPtr, C.azAgg, C.azVal, C.azNnz, st,
+                                       [&](int ovfAny) { return rank_any(s, ovfAny != 0) ? 1 : 0; });
     if (!built) {
         C.azFailed = true;
         fprintf(stderr, "[dafoam_amd] deflated coarse mode: a row of the operator touches more than %d aggregates - keeping the full operator product per apply\n", AZ_CAP);
@@ -2212,8 +1959,9 @@ static bool coarse_az_ready(das_solver* s, das_ksp* k) {
 // z = M^{-1} v: the factorisation, wrapped in globalPCIters x localPCIters Richardson sweeps on jacPCMat when the
 // options ask for more than one (reference DALinearEqn.C:173-205, 237-260: KSPRICHARDSON around ASM and around the
 // sub-domain ILU; with one sub-domain per GPU both iterate the same stationary scheme, so l x g sweeps in total)
+static long long pc_sweeps(das_solver* s) { return std::max<long long>(1, s->opt.geti("adjEqnOption.globalPCIters")) * std::max<long long>(1, s->opt.geti("adjEqnOption.localPCIters")); }
 static void pc_apply_full(das_solver* s, das_ksp* k, const double* v, double* z) {
-    const long long sweeps = std::max<long long>(1, s->opt.geti("adjEqnOption.globalPCIters")) * std::max<long long>(1, s->opt.geti("adjEqnOption.localPCIters"));
+    const long long sweeps = pc_sweeps(s);
     const long long n = s->n;
     das_ksp::CoarsePC& C = k->coarse;
     if (C.active) {
@@ -2230,7 +1978,7 @@ static void pc_apply_full(das_solver* s, das_ksp* k, const double* v, double* z)
                     hipLaunchKernelGGL(k_az_apply, dim3(nblk(n, 256)), dim3(256), 0, s->stream, n, C.azPtr.p, C.azAgg.p, C.azVal.p, C.u.p, (const double*)nullptr, C.rr.p);
                     if (s->halo.active) s->halo.reduce_vector(C.rr.p, s->stream);
                     else s->halo_cb(C.rr.p, s->comm_user);
-                    hipLaunchKernelGGL(k_axpby, dim3(nblk(n, 256)), dim3(256), 0, s->stream, n, 1.0, v, -1.0, C.rr.p);
+                    axpby(s, 1.0, v, -1.0, C.rr.p);
                 } else {
                     hipLaunchKernelGGL(k_az_apply, dim3(nblk(n, 256)), dim3(256), 0, s->stream, n, C.azPtr.p, C.azAgg.p, C.azVal.p, C.u.p, v, C.rr.p);
                 }
@@ -2238,10 +1986,10 @@ static void pc_apply_full(das_solver* s, das_ksp* k, const double* v, double* z)
             } else {
                 s->timer.end("coarse", s->stream, ev);
                 apply_operator(s, C.c.p, C.rr.p);
-                hipLaunchKernelGGL(k_axpby, dim3(nblk(n, 256)), dim3(256), 0, s->stream, n, 1.0, v, -1.0, C.rr.p);
+                axpby(s, 1.0, v, -1.0, C.rr.p);
             }
             pc_apply(s, k, C.rr.p, z);
-            hipLaunchKernelGGL(k_axpby, dim3(nblk(n, 256)), dim3(256), 0, s->stream, n, 1.0, C.c.p, 1.0, z);
+            axpby(s, 1.0, C.c.p, 1.0, z);
         } else {
             s->timer.end("coarse", s->stream, ev);
             pc_apply(s, k, v, z);
@@ -2255,9 +2003,9 @@ static void pc_apply_full(das_solver* s, das_ksp* k, const double* v, double* z)
     const Mat& P = k->pcmat->m;
     for (long long it = 1; it < sweeps; it++) {
         hipLaunchKernelGGL(k_spmv_wave, SPMV_GRID(P.n), dim3(256), 0, s->stream, P.n, P.rowptr.p, P.col.p, P.val.p, z, k->rich_r.p);
-        hipLaunchKernelGGL(k_axpby, dim3(nblk(n, 256)), dim3(256), 0, s->stream, n, 1.0, v, -1.0, k->rich_r.p);  // r = v - P z
+        axpby(s, 1.0, v, -1.0, k->rich_r.p);  // r = v - P z
         pc_apply(s, k, k->rich_r.p, k->rich_d.p);
-        hipLaunchKernelGGL(k_axpby, dim3(nblk(n, 256)), dim3(256), 0, s->stream, n, 1.0, k->rich_d.p, 1.0, z);
+        axpby(s, 1.0, k->rich_d.p, 1.0, z);
     }
 }
 
@@ -2267,7 +2015,7 @@ static void pc_apply_full(das_solver* s, das_ksp* k, const double* v, double* z)
 // round-1 RAS preconditioner fall back to the column loop.
 static void pc_apply_block(das_solver* s, das_ksp* k, const double* V, double* Z, int sv) {
     const long long n = s->n;
-    const long long sweeps = std::max<long long>(1, s->opt.geti("adjEqnOption.globalPCIters")) * std::max<long long>(1, s->opt.geti("adjEqnOption.localPCIters"));
+    const long long sweeps = pc_sweeps(s);
     das_ksp::CoarsePC& C = k->coarse;
     const bool batched = k->useBilu && sweeps <= 1 && !(C.active && C.deflated) && sv > 1 && s->opt.geti("amd.blockBatchedPC") != 0;
     if (!batched) {
@@ -2356,7 +2104,7 @@ static int poly_degree(das_solver* s, bool fixed) {
     if (d == 0 || fixed || s->fwd.on) return 0;
     DAS_CHECK(s->opt.gets("amd.krylovMethod") != "idrs", DAS_ERR_ARG, "amd.polyDegree > 0 belongs to GMRES: not with amd.krylovMethod \"idrs\"");
     DAS_CHECK(!s->halo.active && !s->halo_cb, DAS_ERR_ARG, "amd.polyDegree > 0 is single-rank (run the sharded solve without it)");
-    { auto it = s->opt.i.find("amd.gmresDeflation"); DAS_CHECK(it == s->opt.i.end() || it->second <= 0, DAS_ERR_ARG, "amd.gmresDeflation > 0 cannot be combined with amd.polyDegree > 0"); }
+    DAS_CHECK(s->opt.geti_or("amd.gmresDeflation", 0) <= 0, DAS_ERR_ARG, "amd.gmresDeflation > 0 cannot be combined with amd.polyDegree > 0");
     return (int)d;
 }
 static bool gmres_trace() { static const bool on = [] { const char* e = getenv("DAS_GMRES_TRACE"); return e && *e && *e != '0'; }(); return on; }
@@ -2367,7 +2115,7 @@ static void gmres_true_residual(das_solver* s, das_ksp* k, GmresRun& G, bool hav
     if (haveGuess) {
         apply_operator(s, G.d_x, k->r.p);
         G.prods++;
-        hipLaunchKernelGGL(k_axpby, dim3(nblk(n, 256)), dim3(256), 0, st, n, 1.0, G.d_rhs, -1.0, k->r.p);
+        axpby(s, 1.0, G.d_rhs, -1.0, k->r.p);
     } else {
         DAS_HIP(hipMemsetAsync(G.d_x, 0, n * sizeof(double), st));
         DAS_HIP(hipMemcpyAsync(k->r.p, G.d_rhs, n * sizeof(double), hipMemcpyDeviceToDevice, st));
@@ -2694,7 +2442,7 @@ static void gmres_cycle_end_t(das_solver* s, das_ksp* k) {
     double* const vy = G.polyOn ? k->r.p : k->w.p;
     launch_lincomb(st, n, j, (const VT*)basis_slot<VT>(s, k, 0), basis_ld(s, k), (const double*)k->hdev.p, vy, (const float*)basis_lo(s, k, 0));
     gmres_precond_product(s, k, vy, nullptr);
-    hipLaunchKernelGGL(k_axpby, dim3(nblk(n, B)), dim3(B), 0, st, n, 1.0, k->z.p, 1.0, G.d_x);
+    axpby(s, 1.0, k->z.p, 1.0, G.d_x);
     const double recRes = k->hist.back();
     gmres_true_residual(s, k, G, true);
     if (G.polyGen) {  // the generating cycle: a polynomial only from a cycle that ran its polyD columns without a breakdown
@@ -2825,7 +2573,7 @@ struct DrDeviceOps {
         DAS_HIP(hipStreamSynchronize(st));  // y is the caller's host vector
         launch_lincomb(st, n, j, (const double*)k->V.p, n, (const double*)k->hdev.p, (double*)k->w.p, (const float*)nullptr);
         pc_apply_full(s, k, k->w.p, k->z.p);
-        hipLaunchKernelGGL(k_axpby, dim3(nblk(n, 256)), dim3(256), 0, st, n, 1.0, k->z.p, 1.0, G->d_x);
+        axpby(s, 1.0, k->z.p, 1.0, G->d_x);
     }
     double true_residual() { gmres_true_residual(s, k, *G, true); return G->beta; }
     void compress(int m, int kk, const double* P1) {
@@ -2870,8 +2618,7 @@ static int run_gmres(das_solver* s, das_ksp* k, const double* d_rhs, double* d_x
     const int polyD = poly_degree(s, fixed_iters > 0);  // opt-in: amd.polyDegree
     if (idr_selected(s, fixed_iters > 0)) return run_idrs(s, k, d_rhs, d_x);  // opt-in: amd.krylovMethod "idrs"
     {   // opt-in: deflated restarting (never for the fixed-iteration bench windows, the Newton primal's inner solves or several ranks)
-        auto it = s->opt.i.find("amd.gmresDeflation");
-        const long long kdef = it != s->opt.i.end() ? it->second : 0;
+        const long long kdef = s->opt.geti_or("amd.gmresDeflation", 0);
         if (kdef > 0 && fixed_iters <= 0 && !s->fwd.on && s->opt.geti("adjEqnOption.gmresRestart") < s->opt.geti("adjEqnOption.gmresMaxIters")) {
             if (!s->halo.active && !s->halo_cb) return run_gmres_dr(s, k, d_rhs, d_x, (int)kdef);
             static bool told = false;  // several ranks: the plain restarted solver (the comment promised this, the code threw)
@@ -2953,7 +2700,7 @@ static bool idr_selected(das_solver* s, bool fixed) {
     DAS_CHECK(sv >= 1 && sv <= IDR_MAX_S, DAS_ERR_ARG, "amd.idrShadowVectors " + std::to_string(sv) + " is outside 1 .. 8");
     if (fixed || s->fwd.on) return false;
     DAS_CHECK(!s->halo.active && !s->halo_cb, DAS_ERR_ARG, "amd.krylovMethod \"idrs\" is single-rank (run the sharded solve with \"gmres\")");
-    { auto it = s->opt.i.find("amd.gmresDeflation"); DAS_CHECK(it == s->opt.i.end() || it->second <= 0, DAS_ERR_ARG, "amd.gmresDeflation > 0 belongs to GMRES: not with amd.krylovMethod \"idrs\""); }
+    DAS_CHECK(s->opt.geti_or("amd.gmresDeflation", 0) <= 0, DAS_ERR_ARG, "amd.gmresDeflation > 0 belongs to GMRES: not with amd.krylovMethod \"idrs\"");
     return true;
 }
 // the work vectors of the IDR(s) path (the ones it shares with the GMRES path are re-allocated by gmres_ws when that runs next: restart = 0)
@@ -3047,7 +2794,7 @@ struct IdrDeviceOps {
     }
     double true_residual() {
         apply_operator(s, d_x, k->r.p);
-        hipLaunchKernelGGL(k_axpby, dim3(nblk(s->n, 256)), dim3(256), 0, s->stream, s->n, 1.0, d_rhs, -1.0, k->r.p);
+        axpby(s, 1.0, d_rhs, -1.0, k->r.p);
         return norm_r();
     }
 };
@@ -3103,9 +2850,7 @@ static int run_block_gmres(das_solver* s, das_ksp* k, int sv, const double* d_B,
     const Mat& A = s->op->m;
     const long long n = s->n;
     hipStream_t st = s->stream;
-    long long budget = (long long)(32.0 * 1024 * 1024 * 1024);
-    auto itb = s->opt.i.find("amd.maxKrylovBytes");
-    if (itb != s->opt.i.end()) budget = itb->second;
+    const long long budget = s->opt.geti_or("amd.maxKrylovBytes", (long long)(32.0 * 1024 * 1024 * 1024));
     const long long maxIts = s->opt.geti("adjEqnOption.gmresMaxIters");
     long long m = std::min<long long>(s->opt.geti("adjEqnOption.gmresRestart"), maxIts);
     m = std::max<long long>(1, std::min<long long>(m, std::min<long long>(budget / (8 * n * sv) - 1, 4000 / sv)));
@@ -3168,10 +2913,10 @@ static int run_block_gmres(das_solver* s, das_ksp* k, int sv, const double* d_B,
         DAS_HIP(hipMemcpyAsync(bw.Cdev.p, Y.data(), (size_t)K * sv * sizeof(double), hipMemcpyHostToDevice, st));
         launch_block_lincomb(st, n, K, sv, bw.V.p, n, bw.Cdev.p, bw.W.p, n);
         pc_apply_block(s, k, bw.W.p, bw.Z.p, sv);
-        hipLaunchKernelGGL(k_axpby, dim3(nblk((long long)sv * n, B)), dim3(B), 0, st, (long long)sv * n, 1.0, bw.Z.p, 1.0, d_X);
+        axpby(s, 1.0, bw.Z.p, 1.0, d_X, (long long)sv * n);
         // true residuals
         block_spmm(s, bw, A, d_X, bw.R.p, sv);
-        hipLaunchKernelGGL(k_axpby, dim3(nblk((long long)sv * n, B)), dim3(B), 0, st, (long long)sv * n, 1.0, d_B, -1.0, bw.R.p);
+        axpby(s, 1.0, d_B, -1.0, bw.R.p, (long long)sv * n);
         col_norms(bw.R.p, res);
         k->hist.back() = *std::max_element(res.begin(), res.end());
     }
@@ -3281,7 +3026,7 @@ static int run_newton_primal(das_solver* s, int maxSteps, double relTol, double 
             k->pcDiagScale = 1.0 + 1.0 / tau;
             tauPC = tau;
             if (ptMomentum) { k->shiftExLo = pLo; k->shiftExHi = pHi; k->shiftEnd = phiLo; }
-            setup_node_ilu(s, k.get());
+            setup_node_ilu(s, k.get(), /*byEstimate*/ false);
             setup_coarse(s, k.get());
             if (s->fwd.diag.n != (size_t)n) s->fwd.diag.alloc(n);
             hipLaunchKernelGGL(k_extract_diag, dim3(nblk(n, B)), dim3(B), 0, st, n, P->m.rowptr.p, P->m.col.p, P->m.val.p, s->fwd.diag.p, k->shiftExLo,
@@ -3857,6 +3602,26 @@ int das_debug_factor_block(int nl, const long long* rp, const int* ci, const dou
     return DAS_OK;
     DAS_CATCH
 }
+// host-only test aid: the recursive coordinate bisection (das_rcb.hpp) of n points, centres[3 * i + axis].  mode 0: param parts,
+// out[i] = part of point i; mode 1: leaves of at most param points, out[i] = leaf of point i
+int das_debug_rcb(int n, const double* centres, int mode, int param, int* out) {
+    DAS_TRY
+    DAS_CHECK(n >= 0 && (centres || n == 0) && (out || n == 0) && (mode == 0 || mode == 1) && param >= 1, DAS_ERR_ARG, "bad argument");
+    std::vector<int> idx(n);
+    std::iota(idx.begin(), idx.end(), 0);
+    auto centre = [&](int i, int d) { return centres[3LL * i + d]; };
+    if (mode == 0) {
+        std::vector<int> partOf(n, -1);
+        rcb_parts(idx, centre, param, partOf);
+        std::copy(partOf.begin(), partOf.end(), out);
+    } else {
+        std::vector<long long> leafOff;
+        rcb_leaves(idx, centre, param, leafOff);
+        for (size_t l = 0; l + 1 < leafOff.size(); l++) for (long long q = leafOff[l]; q < leafOff[l + 1]; q++) out[idx[q]] = (int)l;
+    }
+    return DAS_OK;
+    DAS_CATCH
+}
 int das_set_coloring(das_solver_t* s, const int* colors) {
     DAS_TRY
     DAS_CHECK(s && colors, DAS_ERR_ARG, "null argument");
@@ -3950,9 +3715,8 @@ int das_initialize_drdwt_matrix_free(das_solver_t* s) {
     s->opId++;
     // the Krylov operator: vector-state rows repacked as group rows (das_opmat.hpp); amd.opPackVector 0 keeps the plain CSR
     {
-        auto it = s->opt.i.find("amd.opPackVector");
         const StateDef& s0 = s->st_full.states[0];
-        if ((it == s->opt.i.end() || it->second != 0) && s0.kind == KIND_VEC) {
+        if (s->opt.geti_or("amd.opPackVector", 1) != 0 && s0.kind == KIND_VEC) {
             Mat& M = s->op->m;
             const bool ok = vecpack_build(M.vp, s0.size / 3, s0.offset, M.rowptr.p, M.col.p, M.val.p, s->stream);
             if (s->opt.geti("debug"))
@@ -4969,8 +4733,7 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
     }
     ensure_point_influence(s);
     {
-        auto itm = s->opt.s.find("amd.volCoordMode");
-        const std::string mode = itm == s->opt.s.end() ? std::string("dual") : itm->second;
+        const std::string mode = s->opt.gets_or("amd.volCoordMode", "dual");
         DAS_CHECK(mode == "dual" || mode == "fd", DAS_ERR_ARG, "amd.volCoordMode: dual | fd");
         if (mode == "dual") {
             volcoord_product_dual(s, fn, areaAvg, cN, cA, seeds, product, info4);
@@ -5161,19 +4924,7 @@ int das_create_ml_rksp_matrix_free(das_solver_t* s, das_mat_t* pc, das_ksp_t** k
     if (pcType == "bilu") {
         if (getenv("DAS_BILU_ORDER")) k->pcOrder = atoi(getenv("DAS_BILU_ORDER"));
         const long long K = pc_subdomain_count(s);
-        if (!(K > 1 && setup_subdomain_ilus(s, k.get(), (int)K))) {
-            const double t0 = wall_seconds();
-            // a sub-domain of a multi-rank solve takes the elimination order with the smallest estimate, one rank alone the first stable one
-            choose_order_and_factorise(s, k.get(), k->bilu, (s->pcMask.empty() || k->pcTranspose) ? s->owned : s->pcMask, !s->owned.empty(), k->pcOrderUsed, k->pcStability, /*earlyAccept*/ s->owned.empty());
-            if (k->pcOrderUsed >= 0) k->pcOrder = k->pcOrderUsed;
-            k->useBilu = true;
-            k->rasOverlap = !s->pcMask.empty() && !k->pcTranspose && s->halo.ovActive;
-            if (k->rasOverlap && k->pcin.n != (size_t)s->n) k->pcin.alloc(s->n);
-            k->pc.setup_seconds = wall_seconds() - t0;
-            k->pc.nBlocks = 1;
-            k->pc.fnnz = (k->bilu.nL + k->bilu.nU + k->bilu.nNodes) * (long long)BILU_NB2;
-            k->pc.next = (long long)k->bilu.nNodes * BILU_NB;
-        }
+        if (!(K > 1 && setup_subdomain_ilus(s, k.get(), (int)K))) setup_node_ilu(s, k.get(), /*byEstimate*/ true);
     } else setup_block_ilu(s, k.get());
     setup_coarse(s, k.get());
     *ksp = k.release();
@@ -5222,8 +4973,7 @@ int das_ksp_apply_pc(das_solver_t* s, das_ksp_t* ksp, const double* x, double* y
     DAS_HIP(hipDeviceSynchronize());
     dy.zero();
     pc_apply_full(s, ksp, dx.p, dy.p);
-    DAS_HIP(hipStreamSynchronize(s->stream));
-    if (ksp->useBilu) DAS_CHECK(!bilu_aborted(ksp->bilu, s->stream), DAS_ERR_INTERNAL, "preconditioner sweep timed out (bounded spin)");
+    gmres_finish_check(s, ksp);
     dy.download(y, s->n);
     return DAS_OK;
     DAS_CATCH
@@ -5240,17 +4990,11 @@ int das_pc_structure_build(das_solver_t* s, int* nNodes, long long* nBlocks, int
     DAS_TRY
     DAS_CHECK(s, DAS_ERR_ARG, "null solver handle");
     const int rch = pc_stencil_reach(s);
-    std::vector<char> cellOwned(s->mesh.nC, 1);
-    if (!s->owned.empty()) {
-        const StateDef& s0 = s->st_full.states[0];
-        const int stride = s0.kind == KIND_VEC ? 3 : 1;
-        for (int c = 0; c < s->mesh.nC; c++) cellOwned[c] = s->owned[s0.offset + (long long)stride * c] ? 1 : 0;
-    }
+    const std::vector<char> cellOwned = cells_of_mask(s->mesh, s->st_full.states, s->owned);
     std::vector<int> unkNode, bcol;
     std::vector<unsigned char> unkSlot;
     std::vector<long long> bptr, bdiag;
-    const int nthr = (int)std::max<long long>(1, std::min<long long>(das::host_threads(), s->opt.geti("amd.setupThreads")));
-    bilu_build_structure(s->mesh, s->st_full.states, s->n, s->owned, cellOwned, rch, s->pcStruct, unkNode, unkSlot, bptr, bdiag, bcol, nthr, pc_ordering_rcm(s));
+    bilu_build_structure(s->mesh, s->st_full.states, s->n, s->owned, cellOwned, rch, s->pcStruct, unkNode, unkSlot, bptr, bdiag, bcol, pc_setup_threads(s), pc_ordering_rcm(s));
     if (nNodes) *nNodes = s->pcStruct.nNodes;
     if (nBlocks) *nBlocks = s->pcStruct.nnzB;
     if (nLevels) *nLevels = s->pcStruct.nLevels;

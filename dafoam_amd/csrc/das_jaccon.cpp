@@ -12,6 +12,7 @@
 // The pattern is built on the whole (per-GPU) mesh, so the reference's inter-processor bookkeeping
 // (stateBoundaryCon, DAJacCon.C:800-1205) has no counterpart.
 #include "das_jaccon.hpp"
+#include "das_rcb.hpp"
 
 #include <omp.h>
 #include <cstdlib>
@@ -458,29 +459,10 @@ int d2_coloring(const JacCon& con, std::vector<int>& colors, const double* centr
         {
             std::vector<int> idx(nAnch);
             std::iota(idx.begin(), idx.end(), 0);
-            struct Rg { long long b, e; };
-            std::vector<Rg> stack{{0, nAnch}};
-            while (!stack.empty()) {
-                Rg r = stack.back();
-                stack.pop_back();
-                if (r.e - r.b <= tileCells) {
-                    for (long long q = r.b; q < r.e; q++) tileOf[idx[q]] = nT;
-                    nT++;
-                    continue;
-                }
-                double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-                for (long long q = r.b; q < r.e; q++)
-                    for (int d = 0; d < 3; d++) { double x = centres[3LL * idx[q] + d]; lo[d] = std::min(lo[d], x); hi[d] = std::max(hi[d], x); }
-                int ax = 0;
-                for (int d = 1; d < 3; d++) if (hi[d] - lo[d] > hi[ax] - lo[ax]) ax = d;
-                const long long mid = (r.b + r.e) / 2;
-                std::nth_element(idx.begin() + r.b, idx.begin() + mid, idx.begin() + r.e, [&](int a, int b2) {
-                    const double xa = centres[3LL * a + ax], xb = centres[3LL * b2 + ax];
-                    return xa < xb || (xa == xb && a < b2);
-                });
-                stack.push_back({mid, r.e});
-                stack.push_back({r.b, mid});
-            }
+            std::vector<long long> tileOff;
+            rcb_leaves(idx, [&](int a, int d) { return centres[3LL * a + d]; }, tileCells, tileOff);
+            nT = (int)tileOff.size() - 1;
+            for (int t = 0; t < nT; t++) for (long long q = tileOff[t]; q < tileOff[t + 1]; q++) tileOf[idx[q]] = t;
         }
         // tile adjacency from the kept rows (bit matrix, OR-merged over threads)
         const size_t words = ((size_t)nT * nT + 63) / 64;

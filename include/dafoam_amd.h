@@ -220,6 +220,10 @@ int das_set_coloring(das_solver_t* s, const int* colors);
  * block - symbolic ILU(lfill), numeric, level schedules, entry streams - and returns the four phase times [s] */
 int das_debug_factor_block(int nl, const long long* rowptr, const int* col, const double* val, int lfill, double* tim4, long long* nnzLU,
                            int* nLevelsL, int* nLevelsU);
+/* host-only test aid (no GPU, no solver handle): the recursive coordinate bisection that cuts the "ras" blocks, the sub-domains,
+ * the "rcb" aggregates and the colouring tiles, on n points centres[3 * i + axis].  mode 0: param parts of almost equal size,
+ * out[i] = part of point i; mode 1: halving until a leaf holds at most param points, out[i] = leaf of point i */
+int das_debug_rcb(int n, const double* centres, int mode, int param, int* out);
 int das_get_n_colors(das_solver_t* s, int isPC);
 long long das_get_con_nnz(das_solver_t* s, int isPC);
 int das_get_con(das_solver_t* s, int isPC, long long* rowptr /*n+1*/, int* colidx /*nnz*/);
