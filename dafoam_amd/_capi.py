@@ -277,6 +277,8 @@ _SIGS = {
     "das_define_patch_field_function": (C.c_int, [_VP, C.c_char_p, C.c_char_p, c_int_p, C.c_int, C.c_char_p, c_int_p, C.c_int, c_double_p, C.c_int, C.c_double, C.c_double]),
     "das_define_cell_function": (C.c_int, [_VP, C.c_char_p, C.c_char_p, c_int_p, C.c_int, C.c_char_p, c_int_p, C.c_int, c_double_p, C.c_int, C.c_double, C.c_double]),
     "das_calc_function": (C.c_int, [_VP, C.c_char_p, c_double_p]),
+    "das_define_force_coupling": (C.c_int, [_VP, C.c_char_p, c_int_p, C.c_int, C.c_double]),
+    "das_calc_force_coupling": (C.c_int, [_VP, C.c_char_p, c_double_p, C.c_int]),
     "das_get_input_size": (C.c_int, [_VP, C.c_char_p, C.c_char_p]),
     "das_get_output_size": (C.c_int, [_VP, C.c_char_p, C.c_char_p]),
     "das_calc_jac_t_vec_product": (

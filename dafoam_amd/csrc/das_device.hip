@@ -39,6 +39,7 @@
 #include "das_volcoord.hpp"
 #include "das_cellfn.hpp"
 #include "das_facefn.hpp"
+#include "das_forcecoupling.hpp"
 #include "das_simple.hpp"
 
 #include <omp.h>
@@ -164,7 +165,7 @@ __global__ __launch_bounds__(256) void k_fn_value(DevMesh m, ResParams prm, cons
     if (k >= fn.nf) return;
     double dir[3] = {0.0, 0.0, 0.0};
     if (fn.dir) { dir[0] = fn.dir[3 * k]; dir[1] = fn.dir[3 * k + 1]; dir[2] = fn.dir[3 * k + 2]; }
-    fv[k] = fn.w[k] * body_facefn<double, RHO>(fn.faces[k], m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc);
+    fv[k] = fn.w[k] * body_facefn<double, RHO>(fn.faces[k], m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc, fn.pRef);
 }
 // out2[g] = sum of fv[k] over the entries of group g (group == nullptr: everything is group 0); one workgroup, fixed order
 __global__ __launch_bounds__(256) void k_group_sum(long long cnt, const unsigned char* __restrict__ group, const double* __restrict__ fv, double* __restrict__ out2) {
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(256) void k_fn_tangent(DevMesh m, ResParams prm, co
     if (k >= fn.nf) return;
     double dir[3] = {0.0, 0.0, 0.0};
     if (fn.dir) { dir[0] = fn.dir[3 * k]; dir[1] = fn.dir[3 * k + 1]; dir[2] = fn.dir[3 * k + 2]; }
-    Dual<1> v = body_facefn<Dual<1>, RHO>(fn.faces[k], m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc);
+    Dual<1> v = body_facefn<Dual<1>, RHO>(fn.faces[k], m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc, fn.pRef);
     fv[k] = seed * fn.w[k] * v.d[0];
 }
 // part[b] = sum over the block's rows of psi_i * dR_i  (dR = tangent part of a dual residual); k_group_sum adds the parts
@@ -216,7 +217,7 @@ __global__ __launch_bounds__(256) void k_fn_grad(DevMesh m, ResParams prm, const
     double dir[3] = {0.0, 0.0, 0.0};
     if (fn.dir) { dir[0] = fn.dir[3 * k]; dir[1] = fn.dir[3 * k + 1]; dir[2] = fn.dir[3 * k + 2]; }
     const int f = fn.faces[k];
-    Dual<1> v = body_facefn<Dual<1>, RHO>(f, m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc);
+    Dual<1> v = body_facefn<Dual<1>, RHO>(f, m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc, fn.pRef);
     if (v.d[0] == 0.0) return;
     const double g = seed * fn.w[k] * v.d[0];
     const long long N = m.nC;
@@ -798,12 +799,28 @@ struct das_solver {
         bool byUnitArea = true, ks = false;
         double coeffKS = 1.0, loc[6] = {1, 0, 0, 0, 0, 0};
         DevBuf<double> d_ks, d_kpart;
+        double pRef = 0.0;  // the reference pressure of the forces (the internal function of a ForceCoupling; 0 for the objectives)
         FaceFnView view(const double* w) const {
             return FaceFnView{d_faces.p, d_group.p, w, dir.empty() ? nullptr : d_dir.p, (int)faces.size(), kind, gammaFn, RFn,
-                              {loc[0], loc[1], loc[2], loc[3], loc[4], loc[5]}};
+                              {loc[0], loc[1], loc[2], loc[3], loc[4], loc[5]}, pRef};
         }
     };
     std::map<std::string, FaceFn> functions;
+    // a forceCouplingOutput (das_forcecoupling.hpp): nodal forces on the points of the patches.  The topology (which points, which
+    // faces feed them) depends on the connectivity only: das_update_of_mesh leaves it alone.  `fn` is the force functional
+    // seeds . output = sum_f d_f . F_f of the derivative passes: kind force, unit weights, the directions d_f written on the device
+    // by k_fc_seed_dir (never rebuilt from the geometry: it is no moment and has no fixed direction).
+    struct ForceCoupling {
+        std::vector<int> patches;  // in output order (the caller sorts them by name)
+        int nOut = 0;              // output points (a point shared by two patches counts twice); the output has 3 nOut entries
+        std::vector<int> ptPtr, ptSlot;      // output point -> face slots, ascending
+        std::vector<int> fcPtr, fcPt;        // face slot -> output points (fcPtr[k + 1] - fcPtr[k] = the points of the face)
+        DevBuf<int> d_ptPtr, d_ptSlot, d_fcPtr, d_fcPt;
+        DevBuf<double> d_ff, d_out, d_seeds;
+        FaceFn fn;
+        bool uploaded = false;
+    };
+    std::map<std::string, ForceCoupling> forceCouplings;
     struct CellFn {  // a cell-set objective (see das_cellfn.hpp)
         bool variance = false, square = false, multiplyVol = true, divByTotalVol = false, refVar = false, geoWeight = false, hasData = true;
         bool field = false;  // src = betaFINuTilda instead of the states
@@ -4214,6 +4231,7 @@ int das_calc_function(das_solver_t* s, const char* name, double* value) {
     return DAS_OK;
     DAS_CATCH
 }
+static void face_function_gradient(das_solver* s, das_solver::FaceFn& fn, double seed, double* product);
 // product_j = seed * s_j dF/dW_j : coloured forward-mode gradient of the objective (one k_grad + one k_force per colour)
 static void function_gradient(das_solver* s, const char* name, double seed, double* product) {
     need_init(s);
@@ -4227,6 +4245,10 @@ static void function_gradient(das_solver* s, const char* name, double seed, doub
         std::fill(product, product + s->n, 0.0);
         return;
     }
+    face_function_gradient(s, fn, seed, product);
+}
+// the coloured passes of function_gradient for a face function whose device arrays are in place
+static void face_function_gradient(das_solver* s, das_solver::FaceFn& fn, double seed, double* product) {
     ensure_con_dev(s, 0);
     function_effective_weights(s, fn);
     ResParams prm = s->wk1.bind(s->cp.solver, s->dm.nC, s->dm.nF, make_params(s->cp, s->opt, 0));
@@ -4244,6 +4266,115 @@ static void function_gradient(das_solver* s, const char* name, double seed, doub
     DAS_HIP(hipGetLastError());
     DAS_HIP(hipMemcpyAsync(product, s->d_tmp2.p, n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     DAS_HIP(hipStreamSynchronize(s->stream));
+}
+
+// ---- forceCouplingOutput (reference DAOutputForceCoupling.C; layout and kernels: das_forcecoupling.hpp) --------------------------
+static bool is_force_coupling(const std::string& outputType) { return outputType == "forceCouplingOutput"; }
+static void need_force_coupling_solver(das_solver* s) {
+    DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver), DAS_ERR_ARG,
+              "forceCouplingOutput needs a flow solver with a pressure field (DAScalarTransportFoam has no p)");
+    DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "forceCouplingOutput runs on an undecomposed solver (sharded solvers are not supported)");
+}
+int das_define_force_coupling(das_solver_t* s, const char* name, const int* patch_ids, int npatch, double pRef) {
+    DAS_TRY
+    DAS_CHECK(s && name && patch_ids && npatch > 0, DAS_ERR_ARG, "bad argument");
+    need_force_coupling_solver(s);
+    const Mesh& m = s->mesh;
+    das_solver::ForceCoupling fc;
+    das_solver::FaceFn& fn = fc.fn;
+    fc.fcPtr.push_back(0);
+    for (int k = 0; k < npatch; k++) {
+        const int p = patch_ids[k];
+        DAS_CHECK(p >= 0 && p < m.nPatch, DAS_ERR_ARG,
+                  "forceCouplingOutput " + std::string(name) + ": patch id " + std::to_string(p) + " is not in the mesh (" + std::to_string(m.nPatch) + " patches)");
+        DAS_CHECK(m.patch_type[p] != DAS_PATCH_CYCLIC, DAS_ERR_ARG, "forceCouplingOutput cannot be defined on cyclic patches");
+        const int f0 = m.patch_start[p], f1 = f0 + m.patch_size[p];
+        // the distinct points of the patch's faces, ascending: this patch's share of the output (DAOutputForceCoupling.C:194-201)
+        std::vector<int> pts(m.face_pts.begin() + m.face_ptr[f0], m.face_pts.begin() + m.face_ptr[f1]);
+        std::sort(pts.begin(), pts.end());
+        pts.erase(std::unique(pts.begin(), pts.end()), pts.end());
+        for (int f = f0; f < f1; f++) {
+            fn.faces.push_back(f);
+            for (int q = m.face_ptr[f]; q < m.face_ptr[f + 1]; q++)
+                fc.fcPt.push_back(fc.nOut + (int)(std::lower_bound(pts.begin(), pts.end(), m.face_pts[q]) - pts.begin()));
+            fc.fcPtr.push_back((int)fc.fcPt.size());
+        }
+        fc.nOut += (int)pts.size();
+        fc.patches.push_back(p);
+    }
+    const int nf = (int)fn.faces.size();
+    DAS_CHECK(nf > 0, DAS_ERR_ARG, "the patches of forceCouplingOutput " + std::string(name) + " have no faces");
+    // output point -> face slots: filled slot by slot, so every list is ascending - the order k_fc_nodal adds in
+    fc.ptPtr.assign(fc.nOut + 1, 0);
+    for (int o : fc.fcPt) fc.ptPtr[o + 1]++;
+    for (int o = 0; o < fc.nOut; o++) fc.ptPtr[o + 1] += fc.ptPtr[o];
+    fc.ptSlot.resize(fc.fcPt.size());
+    std::vector<int> pos(fc.ptPtr.begin(), fc.ptPtr.end() - 1);
+    for (int k = 0; k < nf; k++)
+        for (int q = fc.fcPtr[k]; q < fc.fcPtr[k + 1]; q++) fc.ptSlot[pos[fc.fcPt[q]]++] = k;
+    fn.kind = DAS_FN_FORCE;
+    fn.pRef = pRef;
+    fn.group.assign(nf, 0);
+    fn.w0.assign(nf, 1.0);
+    fn.dir.assign(3 * (size_t)nf, 0.0);
+    s->forceCouplings[name] = std::move(fc);
+    return DAS_OK;
+    DAS_CATCH
+}
+static das_solver::ForceCoupling& get_force_coupling(das_solver* s, const char* name, bool device = true) {
+    auto it = s->forceCouplings.find(name ? name : "");
+    DAS_CHECK(it != s->forceCouplings.end(), DAS_ERR_ARG, std::string("forceCouplingOutput not defined: ") + (name ? name : "(null)"));
+    need_force_coupling_solver(s);
+    das_solver::ForceCoupling& fc = it->second;
+    if (device && !fc.uploaded) {
+        das_solver::FaceFn& fn = fc.fn;
+        fn.d_faces.upload(fn.faces);
+        fn.d_group.upload(fn.group);
+        fn.d_w0.upload(fn.w0);
+        fn.d_weff.alloc(fn.w0.size());
+        fn.d_dir.upload(fn.dir);
+        fn.geomVersion = s->geomVersion;
+        fn.uploaded = true;
+        fc.d_ptPtr.upload(fc.ptPtr); fc.d_ptSlot.upload(fc.ptSlot);
+        fc.d_fcPtr.upload(fc.fcPtr); fc.d_fcPt.upload(fc.fcPt);
+        fc.d_ff.alloc(3 * fn.faces.size());
+        fc.d_out.alloc(3 * (size_t)fc.nOut);
+        fc.d_seeds.alloc(3 * (size_t)fc.nOut);
+        fc.uploaded = true;
+    }
+    return fc;
+}
+// seeds (3 nOut, host) -> the per-face directions of the force functional seeds . output = sum_f d_f . F_f; returns that functional
+static das_solver::FaceFn& force_coupling_functional(das_solver* s, const char* name, const double* seeds) {
+    das_solver::ForceCoupling& fc = get_force_coupling(s, name);
+    const int nf = (int)fc.fn.faces.size();
+    DAS_HIP(hipMemcpyAsync(fc.d_seeds.p, seeds, 3 * (size_t)fc.nOut * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    hipLaunchKernelGGL(k_fc_seed_dir, dim3(nblk(nf, 256)), dim3(256), 0, s->stream, nf, (const int*)fc.d_fcPtr.p, (const int*)fc.d_fcPt.p, (const double*)fc.d_seeds.p,
+                       fc.fn.d_dir.p);
+    DAS_HIP(hipGetLastError());
+    return fc.fn;
+}
+int das_calc_force_coupling(das_solver_t* s, const char* name, double* out, int n) {
+    DAS_TRY
+    need_init(s);
+    DAS_CHECK(out, DAS_ERR_ARG, "null output");
+    das_solver::ForceCoupling& fc = get_force_coupling(s, name);
+    DAS_CHECK(n == 3 * fc.nOut, DAS_ERR_ARG,
+              "forceCouplingOutput " + std::string(name) + " has " + std::to_string(3 * fc.nOut) + " entries (3 per point), not " + std::to_string(n));
+    const bool rho = DAS_IS_COMPRESSIBLE(s->cp.solver);
+    const int B = 256, nf = (int)fc.fn.faces.size();
+    const ResParams prm = s->wk.bind(s->cp.solver, s->dm.nC, s->dm.nF, make_params(s->cp, s->opt, 0));
+    launch_grad_and_faces(s->stream, rho, s->dm, prm, (const double*)s->d_W.p, s->wk, true, [&](auto R) {
+        hipLaunchKernelGGL((k_fc_face_force<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, nf,
+                           (const int*)fc.fn.d_faces.p, fc.fn.pRef, fc.d_ff.p);
+    });
+    hipLaunchKernelGGL(k_fc_nodal, dim3(nblk(fc.nOut, B)), dim3(B), 0, s->stream, fc.nOut, (const int*)fc.d_ptPtr.p, (const int*)fc.d_ptSlot.p, (const int*)fc.d_fcPtr.p,
+                       (const double*)fc.d_ff.p, fc.d_out.p);
+    DAS_HIP(hipGetLastError());
+    DAS_HIP(hipMemcpyAsync(out, fc.d_out.p, 3 * (size_t)fc.nOut * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    return DAS_OK;
+    DAS_CATCH
 }
 
 long long das_op_nnz(das_solver_t* s) { return (s && s->op) ? s->op->m.nnz : -1; }
@@ -4324,7 +4455,9 @@ int das_calc_dbc_product(das_solver_t* s, const int* patches, int np, const char
     check_patches(s, patches, np);
     const int fid = bc_field_id(field);
     const std::string ot = outputType;
-    DAS_CHECK(ot == "residual" || ot == "function", DAS_ERR_ARG, "outputType not supported on this path: " + ot);
+    const bool isFC = is_force_coupling(ot);
+    DAS_CHECK(ot == "residual" || ot == "function" || isFC, DAS_ERR_ARG, "outputType not supported on this path: " + ot);
+    if (isFC) (void)get_force_coupling(s, outputName);  // an unknown name fails before the patch table is touched
     std::vector<PatchBC> bc = s->mesh.bc;
     for (int i = 0; i < np; i++) {
         PatchBC& b = bc[patches[i]];
@@ -4354,21 +4487,23 @@ int das_calc_dbc_product(das_solver_t* s, const int* patches, int np, const char
         hipLaunchKernelGGL(k_tangent_dot, dim3(1024), dim3(256), 0, st, n, s->d_Rd.p, s->d_tmp2.p, part.p);
         hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, st, 1024LL, (const unsigned char*)nullptr, (const double*)part.p, s->d_tmp1.p);
         DAS_HIP(hipStreamSynchronize(st));  // part goes out of scope
-    } else if (find_cell_function(s, outputName)) {  // cell-set functions read no boundary value
+    } else if (!isFC && find_cell_function(s, outputName)) {  // cell-set functions read no boundary value
         product[0] = 0.0;
         return DAS_OK;
-    } else if (DAS_FN_BASE(get_function(s, outputName).kind) == DAS_FN_LOCATION) {  // geometry only
+    } else if (!isFC && DAS_FN_BASE(get_function(s, outputName).kind) == DAS_FN_LOCATION) {  // geometry only
         product[0] = 0.0;
         return DAS_OK;
     } else {
-        das_solver::FaceFn& fn = get_function(s, outputName);
+        // forceCouplingOutput: the force functional seeds . output (its directions carry the seeds: the seed of the pass is 1)
+        das_solver::FaceFn& fn = isFC ? force_coupling_functional(s, outputName, seeds) : get_function(s, outputName);
+        const double fnSeed = isFC ? 1.0 : seeds[0];
         function_effective_weights(s, fn);
         DAS_HIP(hipMemsetAsync(s->d_tmp1.p, 0, sizeof(double), st));  // function_sums used the scratch
         prm = s->wk1.bind(s->cp.solver, s->dm.nC, s->dm.nF, prm);
         const int nf = (int)fn.faces.size();
         if (fn.d_fv.n != (size_t)nf) fn.d_fv.alloc(nf);
         launch_grad_and_faces(st, rho, s->dm, prm, (const Dual<1>*)s->d_Wd.p, s->wk1, true, [&](auto R) {
-            hipLaunchKernelGGL((k_fn_tangent<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, fn.view(fn.d_weff.p), seeds[0], fn.d_fv.p);
+            hipLaunchKernelGGL((k_fn_tangent<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, fn.view(fn.d_weff.p), fnSeed, fn.d_fv.p);
         });
         hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, st, (long long)nf, (const unsigned char*)nullptr, (const double*)fn.d_fv.p, s->d_tmp1.p);
     }
@@ -4420,8 +4555,13 @@ int das_calc_dfield_product(das_solver_t* s, const char* fieldName, const char* 
     DAS_CHECK(outputType && seeds && product, DAS_ERR_ARG, "null argument");
     check_field(fieldName);
     const std::string ot = outputType;
-    DAS_CHECK(ot == "residual" || ot == "function", DAS_ERR_ARG, "outputType not supported on this path: " + ot);
+    DAS_CHECK(ot == "residual" || ot == "function" || is_force_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
     const long long N = s->mesh.nC, n = s->n;
+    if (is_force_coupling(ot)) {  // like the patch-integral functions: the forces do not see the production term
+        (void)get_force_coupling(s, outputName, false);
+        std::fill(product, product + N, 0.0);
+        return DAS_OK;
+    }
     if (ot == "function") {
         das_solver::CellFn* cf = find_cell_function(s, outputName);
         if (!cf) (void)get_function(s, outputName);  // the patch-integral functions do not see the production term
@@ -4689,8 +4829,19 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
     need_init(s);
     DAS_CHECK(outputType && seeds && product, DAS_ERR_ARG, "null argument");
     const std::string ot = outputType;
-    DAS_CHECK(ot == "residual" || ot == "function", DAS_ERR_ARG, "outputType not supported on this path: " + ot);
+    DAS_CHECK(ot == "residual" || ot == "function" || is_force_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
     DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "the volCoord product runs on an undecomposed mesh (sharded solvers: use calcVolCoordDirectionalProduct)");
+    if (is_force_coupling(ot)) {
+        // the force functional seeds . output through the dual-point metrics: S_f carries the tangent, so the pRef S_f term is included
+        (void)get_force_coupling(s, outputName, false);
+        DAS_CHECK(s->opt.gets_or("amd.volCoordMode", "dual") == "dual", DAS_ERR_ARG,
+                  "the volCoord product of a forceCouplingOutput needs amd.volCoordMode dual (fd is not implemented for it)");
+        das_solver::FaceFn& fn = force_coupling_functional(s, outputName, seeds);
+        const double one = 1.0, zero2[2] = {0.0, 0.0};
+        ensure_point_influence(s);
+        volcoord_product_dual(s, &fn, false, zero2, zero2, &one, product, info4);
+        return DAS_OK;
+    }
     const Mesh& m = s->mesh;
     const bool isFn = ot == "function";
     if (isFn) {
@@ -4848,6 +4999,7 @@ int das_get_output_size(das_solver_t* s, const char* outputName, const char* out
     DAS_TRY
     DAS_CHECK(s && outputType, DAS_ERR_ARG, "null argument");
     if (std::string(outputType) == "function") return 1;
+    if (is_force_coupling(outputType)) return 3 * get_force_coupling(s, outputName, false).nOut;
     DAS_CHECK(std::string(outputType) == "residual", DAS_ERR_ARG, std::string("outputType not supported on this path: ") + outputType);
     return (int)s->n;
     DAS_CATCH
@@ -4865,8 +5017,16 @@ int das_calc_jac_t_vec_product(das_solver_t* s, const char* inputName, const cha
         function_gradient(s, outputName, seeds[0], product);
         return DAS_OK;
     }
+    if (is_force_coupling(outputType)) {
+        // d(seeds . output)/dW, state-scaled like the function branch: the coloured passes on the force functional
+        (void)get_force_coupling(s, outputName, false);
+        s->h_W.assign(inputs, inputs + s->n);
+        s->d_W.upload(s->h_W);
+        face_function_gradient(s, force_coupling_functional(s, outputName, seeds), 1.0, product);
+        return DAS_OK;
+    }
     DAS_CHECK(std::string(outputType) == "residual", DAS_ERR_ARG,
-              "calcJacTVecProduct: only (stateVar -> residual | function) is implemented on the GPU path");
+              "calcJacTVecProduct: only (stateVar -> residual | function | forceCouplingOutput) is implemented on the GPU path");
     // DAInputStateVar::run assigns the inputs to the states (reference DASolver.C:1690-1839)
     // the operator initializedRdWTMatrixFree built is reused when it was assembled at these very states (the reference
     // replays its tape; re-assembling all colours for one product would cost ~nColors residual passes)

@@ -1077,8 +1077,15 @@ DAS_HD void body_pres(int c, const DevMeshT<G>& m, const ResParams& prm, const T
 // DAFunctionForce::calcFunction (reference src/adjoint/DAFunction/DAFunctionForce.C:79-158) for one boundary face:
 //   F_f = scale * ( S_f p_b + S_f . devRhoReff_b ) . dir,  devRhoReff = (-rho nuEff) dev(twoSymm(grad U))
 //   (reference DATurbulenceModel.C:360-376), boundary field from the boundary values of nuEff, rho and grad(U).
-template <class T, bool RHO, class G, class DV>
-DAS_HD T body_force(int f, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* nut, const T* gradU, const DV* dir, double scale) {
+// The vector S_f (p_b - pRef) + S_f . devRhoReff_b of one boundary face, component by component (force_terms, then force_component for
+// j = 0, 1, 2).  body_force contracts it with a direction; body_force_vec (the nodal forces of forceCouplingOutput, reference
+// DAOutputForceCoupling.C:107-116) keeps the three components.  pRef = 0 leaves every bit of the force objectives as it was: x - 0.0 = x.
+template <class T>
+struct ForceTerms {
+    T gUb[9], muEff_b, tr3, pb;
+};
+template <class T, bool RHO, class G>
+DAS_HD void force_terms(int f, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* nut, const T* gradU, ForceTerms<T>& t) {
     const long long N = m.nC;
     const FaceGeomT<G>& g = m.fg[f];
     const int c = m.owner[f];
@@ -1087,7 +1094,7 @@ DAS_HD T body_force(int f, const DevMeshT<G>& m, const ResParams& prm, const T* 
     T Tc = RHO ? W[prm.offT * N + c] : T(0.0);
     BFace<T, G> b;
     eval_bface<T, RHO>(m.bc[m.bpatch[f - m.nIF]], g, m.cg[c], prm, Uc, pc, Tc, nc, nut[c], val(W[prm.offPhi * N + f]), b);
-    T gUb[9], dsn[3];
+    T dsn[3];
 #pragma unroll
     for (int j = 0; j < 3; j++) {
         T snG = b.U.gic[j] * Uc[j] + b.U.gbc[j];
@@ -1097,22 +1104,38 @@ DAS_HD T body_force(int f, const DevMeshT<G>& m, const ResParams& prm, const T* 
 #pragma unroll
     for (int i = 0; i < 3; i++)
 #pragma unroll
-        for (int j = 0; j < 3; j++) gUb[3 * i + j] = gradU[9LL * c + 3 * i + j] + b.nrm[i] * dsn[j];
-    T muEff_b = b.rho_b * (b.nu_b + b.nut_b);
-    T tr3 = (2.0 / 3.0) * (gUb[0] + gUb[4] + gUb[8]);  // tr(twoSymm)/3
+        for (int j = 0; j < 3; j++) t.gUb[3 * i + j] = gradU[9LL * c + 3 * i + j] + b.nrm[i] * dsn[j];
+    t.muEff_b = b.rho_b * (b.nu_b + b.nut_b);
+    t.tr3 = (2.0 / 3.0) * (t.gUb[0] + t.gUb[4] + t.gUb[8]);  // tr(twoSymm)/3
+    t.pb = b.p.xb;
+}
+template <class T, class G>
+DAS_HD T force_component(const FaceGeomT<G>& g, const ForceTerms<T>& t, int j, double pRef) {
+    T fT(0.0);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        T sij = t.gUb[3 * i + j] + t.gUb[3 * j + i];
+        if (i == j) sij = sij - t.tr3;
+        fT += g.Sf[i] * sij;
+    }
+    return g.Sf[j] * (t.pb - pRef) - t.muEff_b * fT;
+}
+template <class T, bool RHO, class G, class DV>
+DAS_HD T body_force(int f, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* nut, const T* gradU, const DV* dir, double scale,
+                    double pRef = 0.0) {
+    ForceTerms<T> t;
+    force_terms<T, RHO>(f, m, prm, W, nut, gradU, t);
     T acc(0.0);
 #pragma unroll
-    for (int j = 0; j < 3; j++) {
-        T fT(0.0);
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            T sij = gUb[3 * i + j] + gUb[3 * j + i];
-            if (i == j) sij = sij - tr3;
-            fT += g.Sf[i] * sij;
-        }
-        acc += dir[j] * (g.Sf[j] * b.p.xb - muEff_b * fT);
-    }
+    for (int j = 0; j < 3; j++) acc += dir[j] * force_component<T>(m.fg[f], t, j, pRef);
     return scale * acc;
+}
+template <class T, bool RHO, class G>
+DAS_HD void body_force_vec(int f, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* nut, const T* gradU, double pRef, T F[3]) {
+    ForceTerms<T> t;
+    force_terms<T, RHO>(f, m, prm, W, nut, gradU, t);
+#pragma unroll
+    for (int j = 0; j < 3; j++) F[j] = force_component<T>(m.fg[f], t, j, pRef);
 }
 
 // ================================================================================ face-integral objectives
@@ -1167,8 +1190,8 @@ DAS_HD G location_radius(const FaceGeomT<G>& g, const double* loc, bool inverse)
 }
 template <class T, bool RHO, class G, class DV>
 DAS_HD T body_facefn(int f, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* nut, const T* gradU, int kind, const DV* dir,
-                     double gammaFn, double RFn, const double* loc = nullptr) {
-    if (kind == DAS_FN_FORCE) return body_force<T, RHO>(f, m, prm, W, nut, gradU, dir, 1.0);
+                     double gammaFn, double RFn, const double* loc = nullptr, double pRef = 0.0) {
+    if (kind == DAS_FN_FORCE) return body_force<T, RHO>(f, m, prm, W, nut, gradU, dir, 1.0, pRef);
     if (DAS_FN_BASE(kind) == DAS_FN_LOCATION) return T(location_radius<G>(m.fg[f], loc, DAS_FN_ALT(kind)));
     const long long N = m.nC;
     const FaceGeomT<G>& g = m.fg[f];
@@ -1298,6 +1321,7 @@ struct FaceFnView {
     int nf, kind;
     double gammaFn, RFn;
     double loc[6];               // location: axis (unit), center
+    double pRef = 0.0;           // force: the reference pressure (forceCouplingOutput; 0 for the force / moment objectives)
 };
 
 }  // namespace das

@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void k_fn_dual(DevMeshT<VD> m, ResParams prm, 
     } else if (fn.dir) {
         dir[0] = VD(fn.dir[3 * k]); dir[1] = VD(fn.dir[3 * k + 1]); dir[2] = VD(fn.dir[3 * k + 2]);
     }
-    const VD q = body_facefn<VD, RHO>(f, m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc);
+    const VD q = body_facefn<VD, RHO>(f, m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc, fn.pRef);
     VD v;
     if (areaAvg) v = (fn.group[k] ? (cN1 * q + cA1) : (cN0 * q + cA0)) * m.fg[f].magSf;
     else v = fn.w[k] * q;

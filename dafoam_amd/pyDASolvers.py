@@ -325,6 +325,7 @@ class pyDASolvers:
         self._flowdir_fns = {}
         self._wallDistanceMethod = pyOptions.get("wallDistanceMethod", "default") if isinstance(pyOptions, dict) else "default"
         self._define_functions(pyOptions.get("function") if isinstance(pyOptions, dict) else None)
+        self._define_outputs(pyOptions.get("outputInfo") if isinstance(pyOptions, dict) else None)
         if case.states is not None:  # FoamCase.states is always in "state" ordering (input data)
             check(lib().das_update_of_fields(self._h, dptr(np.ascontiguousarray(case.states, dtype=np.float64))))
 
@@ -738,7 +739,7 @@ class pyDASolvers:
         tmp = np.zeros(len(product)) if self._perm is not None else product
         check(lib().das_calc_jac_t_vec_product(
             self._h, inputName.encode(), inputType.encode(), dptr(np.ascontiguousarray(self._to_state(inputs))), outputName.encode(),
-            outputType.encode(), dptr(seeds_s), dptr(tmp)))
+            outputType.encode(), dptr(np.ascontiguousarray(seeds_s, dtype=np.float64)), dptr(tmp)))
         self._from_state(tmp, product)
 
     def calcJacVecProduct(self, v, product):
@@ -941,6 +942,27 @@ class pyDASolvers:
         check(lib().das_define_face_function(self._h, (name or fname).encode(), b"force", ids.ctypes.data_as(_capi.c_int_p), None, ids.size,
                                              dptr(d), None, meta["scale"], 0.0))
 
+    def _define_outputs(self, outputInfo):
+        """"outputInfo" option dict (reference pyDAFoam.py DAOPTION.outputInfo): the entries of type forceCouplingOutput
+        ({"type", "patches", "components": ["forceCoupling"], "pRef"}, DAOutputForceCoupling.C:38-41) are defined on the device.  The
+        reference sorts the patches by name before anything else and reads pRef unconditionally; so does this."""
+        names = [p.name for p in self._case.mesh.patches]
+        for oname, od in (outputInfo or {}).items():
+            otype = od.get("type")
+            if otype != "forceCouplingOutput":
+                raise NotImplementedError(f"outputInfo[{oname}]: output type {otype} is not built (forceCouplingOutput is; thermalCouplingOutput "
+                                          "and its thermalCoupling input are not)")
+            if "pRef" not in od:
+                raise _capi.DASError(f"outputInfo[{oname}]: forceCouplingOutput needs pRef")
+            patches = sorted(od.get("patches") or [])
+            if not patches:
+                raise _capi.DASError(f"outputInfo[{oname}]: forceCouplingOutput needs patches")
+            for p in patches:
+                if p not in names:
+                    raise _capi.DASError(f"outputInfo[{oname}]: patch {p} is not in the mesh (patches: {', '.join(names)})")
+            ids = np.array([names.index(p) for p in patches], dtype=np.int32)
+            check(lib().das_define_force_coupling(self._h, oname.encode(), ids.ctypes.data_as(_capi.c_int_p), ids.size, float(od["pRef"])))
+
     def calcFunction(self, functionName):
         v = C.c_double(0.0)
         check(lib().das_calc_function(self._h, functionName.encode(), C.byref(v)))
@@ -1067,8 +1089,8 @@ class pyDASolvers:
     caseDir = "."  # where the IO methods read / write (the reference runs inside its case directory)
 
     def calcOutput(self, outputName, outputType, output):
-        """pyDASolvers.pyx:204-206 -> DAOutput::run: the function value (1 entry) or the residual vector (state ordering of the
-        caller: adjStateOrdering) at the current states."""
+        """pyDASolvers.pyx:204-206 -> DAOutput::run: the function value (1 entry), the residual vector (state ordering of the
+        caller: adjStateOrdering) or the nodal forces of a forceCouplingOutput at the current states."""
         assert len(output) == self.getOutputSize(outputName, outputType), "invalid array size!"
         if outputType == "function":
             output[0] = self.calcFunction(outputName)
@@ -1076,6 +1098,12 @@ class pyDASolvers:
             R = np.zeros(self.getNLocalAdjointStates())
             self.getResiduals(R)
             output[:] = R
+        elif outputType == "forceCouplingOutput":
+            # DAOutputForceCoupling::run: [fx0, fy0, fz0, fx1, ...] over the points of the (sorted) patches
+            out = output if isinstance(output, np.ndarray) and output.dtype == np.float64 and output.flags["C_CONTIGUOUS"] else np.zeros(len(output))
+            check(lib().das_calc_force_coupling(self._h, outputName.encode(), dptr(out), len(out)))
+            if out is not output:
+                output[:] = out
         else:
             raise _capi.DASError(f"outputType not supported on this path: {outputType}")
 
@@ -1095,8 +1123,11 @@ class pyDASolvers:
         raise _capi.DASError(f"inputType not supported on this path: {inputType}")
 
     def getOutputDistributed(self, outputName, outputType):
-        """DAOutputResidual.H:59 (1), DAOutputFunction.H:76 (0)."""
+        """DAOutputResidual.H:59 (1), DAOutputFunction.H:76 (0), DAOutputForceCoupling.H (1)."""
         if outputType == "residual":
+            return 1
+        if outputType == "forceCouplingOutput":
+            self.getOutputSize(outputName, outputType)  # an unknown name is an error here as well
             return 1
         if outputType == "function":
             return 0

@@ -357,6 +357,18 @@ int das_define_patch_field_function(das_solver_t* s, const char* name, const cha
 int das_define_cell_function(das_solver_t* s, const char* name, const char* type, const int* cells, int ncells, const char* var, const int* comps,
                              int ncomp, const double* data, int flags, double scale, double ref);
 int das_calc_function(das_solver_t* s, const char* name, double* value);
+/* das_define_force_coupling <- the "outputInfo" option entry {type: forceCouplingOutput, patches, pRef} consumed by DAOutputForceCoupling
+ *   (reference src/adjoint/DAOutput/DAOutputForceCoupling.C): the force S_f (p_b - pRef) + S_f . devRhoReff_b of every face of the patches,
+ *   handed in equal shares to the points of the face.  The output lists the points patch by patch in the order of patch_ids (the reference
+ *   sorts the patches by name, :41 - the caller does), inside a patch in ascending mesh-point index, as [fx0, fy0, fz0, fx1, ...]; a point
+ *   that two of the patches share appears once per patch and each copy receives its own patch's faces only.  The size is
+ *   das_get_output_size(name, "forceCouplingOutput") = 3 x points; it depends on the connectivity only (das_update_of_mesh keeps it).
+ * das_calc_force_coupling   <- calcOutput(name, "forceCouplingOutput", output): n = that size.  No atomics: the same bits on every call.
+ * Derivatives: outputType "forceCouplingOutput" with `size` seeds in das_calc_jac_t_vec_product (stateVar, state-scaled like a function),
+ * das_calc_dbc_product, das_calc_dfield_product (zero: the forces do not read the field) and das_calc_dvolcoord_product
+ * (amd.volCoordMode dual only).  DAScalarTransportFoam (no p) and sharded solvers (owned-cell mask) return DAS_ERR_ARG. */
+int das_define_force_coupling(das_solver_t* s, const char* name, const int* patch_ids, int npatch, double pRef);
+int das_calc_force_coupling(das_solver_t* s, const char* name, double* out, int n);
 
 /* das_calc_jac_t_vec_product <- calcJacTVecProduct(inputName,inputType,inputs,outputName,outputType,seeds,product)
  *   pyDASolvers.pyx:208-235 (DASolver.C:1690-1839).  Supported pair on this path: inputType "stateVar",
