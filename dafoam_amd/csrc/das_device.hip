@@ -41,6 +41,7 @@
 #include "das_facefn.hpp"
 #include "das_forcecoupling.hpp"
 #include "das_simple.hpp"
+#include "das_simple_host.hpp"
 
 #include <omp.h>
 
@@ -3375,13 +3376,10 @@ __global__ __launch_bounds__(256) void k_simple_saeqn(DevMesh m, ResParams prm, 
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c < m.nC) body_simple_saeqn(c, m, prm, W, gU, gN, fc, brec, diag, rhs);
 }
-// U = HbyA - rAU grad(p), p <- relaxed pressure, both written into the state vector Wn
 __global__ __launch_bounds__(256) void k_simple_correct(long long N, int offP, const double* __restrict__ HbyA, const double* rAU, const double* gradP, const double* pRel,
                                                         double* Wn) {
     const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= N) return;
-    for (int k = 0; k < 3; k++) Wn[3 * c + k] = HbyA[3 * c + k] - rAU[c] * gradP[3 * c + k];
-    Wn[offP * N + c] = pRel[c];
+    if (c < N) body_sv_correct(c, N, offP, HbyA, rAU, gradP, pRel, Wn);
 }
 // small vector kernels of the inner Krylov solvers (host scalars; the sweeps are the reference's primal, not the fast path)
 __global__ __launch_bounds__(256) void k_sv_dot(long long n, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ part) {
@@ -3393,110 +3391,99 @@ __global__ __launch_bounds__(256) void k_sv_dot(long long n, const double* __res
     for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o]; __syncthreads(); }
     if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
 }
-__global__ __launch_bounds__(256) void k_sv_lin(long long n, double* y, double a, const double* x, double b, const double* z) {  // y = a x + b z
+__global__ __launch_bounds__(256) void k_sv_lin(long long n, double* y, double a, const double* x, double b, const double* z) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) y[i] = a * x[i] + b * z[i];
+    if (i < n) body_sv_lin(i, y, a, x, b, z);
 }
-__global__ __launch_bounds__(256) void k_sv_bicg_p(long long n, double* p, const double* r, double beta, double om, const double* v) {  // p = r + beta (p - om v)
+__global__ __launch_bounds__(256) void k_sv_bicg_p(long long n, double* p, const double* r, double beta, double om, const double* v) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = r[i] + beta * (p[i] - om * v[i]);
+    if (i < n) body_sv_bicg_p(i, p, r, beta, om, v);
 }
 __global__ __launch_bounds__(256) void k_sv_divdiag(long long n, double* out, const double* in, const double* diag, double sign) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = in[i] / (sign * diag[i]);
+    if (i < n) body_sv_divdiag(i, out, in, diag, sign);
 }
 __global__ __launch_bounds__(256) void k_sv_bicg_x(long long n, double* x, double alpha, const double* ph, double om, const double* sh, double* r, const double* s, const double* t) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { x[i] += alpha * ph[i] + om * sh[i]; r[i] = s[i] - om * t[i]; }
+    if (i < n) body_sv_bicg_x(i, x, alpha, ph, om, sh, r, s, t);
 }
 __global__ __launch_bounds__(256) void k_sv_gather3(long long n, const double* W, int k, const double* D, const double* bd, const double* rhs3, double* x, double* dg, double* b) {
     const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < n) { x[c] = W[3 * c + k]; dg[c] = D[c] + bd[3 * c + k]; b[c] = rhs3[3 * c + k]; }
+    if (c < n) body_sv_gather3(c, W, k, D, bd, rhs3, x, dg, b);
 }
 __global__ __launch_bounds__(256) void k_sv_scatter3(long long n, const double* x, int k, double* W) {
     const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < n) W[3 * c + k] = x[c];
+    if (c < n) body_sv_scatter3(c, x, k, W);
 }
-__global__ __launch_bounds__(256) void k_sv_relax(long long n, double* pn, const double* pold, double alpha) {  // pn = pold + alpha (pn - pold)
+__global__ __launch_bounds__(256) void k_sv_relax(long long n, double* pn, const double* pold, double alpha) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) pn[i] = pold[i] + alpha * (pn[i] - pold[i]);
+    if (i < n) body_sv_relax(i, pn, pold, alpha);
 }
 __global__ __launch_bounds__(256) void k_sv_bound(long long n, const double* x, double lo, double* out) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = x[i] > lo ? x[i] : lo;
+    if (i < n) body_sv_bound(i, x, lo, out);
 }
 
+// device storage of one run of sweeps: the vectors of SimpleVecs and the partial sums of the dot product
 struct SimpleWork {
-    DevBuf<double> Wn, D, bd, sb, rhsU, up, lo, rAU, HbyA, phiH, gpf, cp, pbc, dp, rp, x, b, dg, pn, phiN, gPn;
-    DevBuf<double> r, r0, p, v, sv, t, ph, sh, part, red;
+    std::vector<DevBuf<double>> store;
+    DevBuf<double> part{512}, red{2};
+    double* take(long long cnt) { store.emplace_back((size_t)cnt); return store.back().p; }
 };
-struct LduDev { const double* diag; const double* up; const double* lo; };
-
-static double sv_dot(das_solver* s, SimpleWork& w, long long n, const double* a, const double* b) {
+static double sv_dot(hipStream_t st, SimpleWork& w, long long n, const double* a, const double* b) {
     const int nb = (int)std::min<long long>(512, (n + 255) / 256);
-    hipLaunchKernelGGL(k_sv_dot, dim3(nb), dim3(256), 0, s->stream, n, a, b, w.part.p);
-    hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, s->stream, (long long)nb, (const unsigned char*)nullptr, (const double*)w.part.p, w.red.p);
+    hipLaunchKernelGGL(k_sv_dot, dim3(nb), dim3(256), 0, st, n, a, b, w.part.p);
+    hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, st, (long long)nb, (const unsigned char*)nullptr, (const double*)w.part.p, w.red.p);
     double h[2];
-    DAS_HIP(hipMemcpyAsync(h, w.red.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-    DAS_HIP(hipStreamSynchronize(s->stream));
+    DAS_HIP(hipMemcpyAsync(h, w.red.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    DAS_HIP(hipStreamSynchronize(st));
     return h[0];
 }
-// Jacobi-preconditioned BiCGStab (convection-diffusion systems) on the LDU matrix; x holds the start vector; returns the iterations
-static int sv_bicgstab(das_solver* s, SimpleWork& w, const LduDev& A, const double* b, double* x, double tol, int maxit) {
-    const long long n = s->dm.nC;
-    const int G = nblk(n, 256);
-    hipStream_t st = s->stream;
-    hipLaunchKernelGGL(k_ldu_mv, dim3(G), dim3(256), 0, st, s->dm, A.diag, A.up, A.lo, (const double*)x, w.r.p, 1.0);
-    hipLaunchKernelGGL(k_sv_lin, dim3(G), dim3(256), 0, st, n, w.r.p, 1.0, b, -1.0, (const double*)w.r.p);
-    DAS_HIP(hipMemcpyAsync(w.r0.p, w.r.p, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    w.p.zero(); w.v.zero();
-    const double bn = std::sqrt(sv_dot(s, w, n, b, b)) + 1e-300;
-    double rho = 1.0, alpha = 1.0, om = 1.0;
-    for (int it = 1; it <= maxit; it++) {
-        if (std::sqrt(sv_dot(s, w, n, w.r.p, w.r.p)) <= tol * bn) return it - 1;
-        const double rho1 = sv_dot(s, w, n, w.r0.p, w.r.p);
-        if (rho1 == 0.0 || !std::isfinite(rho1)) return it - 1;  // breakdown: keep the iterate (right-hand sides that vanish to rounding end here)
-        const double beta = (rho1 / rho) * (alpha / om);
-        hipLaunchKernelGGL(k_sv_bicg_p, dim3(G), dim3(256), 0, st, n, w.p.p, (const double*)w.r.p, beta, om, (const double*)w.v.p);
-        hipLaunchKernelGGL(k_sv_divdiag, dim3(G), dim3(256), 0, st, n, w.ph.p, (const double*)w.p.p, A.diag, 1.0);
-        hipLaunchKernelGGL(k_ldu_mv, dim3(G), dim3(256), 0, st, s->dm, A.diag, A.up, A.lo, (const double*)w.ph.p, w.v.p, 1.0);
-        alpha = rho1 / sv_dot(s, w, n, w.r0.p, w.v.p);
-        hipLaunchKernelGGL(k_sv_lin, dim3(G), dim3(256), 0, st, n, w.sv.p, 1.0, (const double*)w.r.p, -alpha, (const double*)w.v.p);
-        if (std::sqrt(sv_dot(s, w, n, w.sv.p, w.sv.p)) <= tol * bn) {
-            hipLaunchKernelGGL(k_sv_lin, dim3(G), dim3(256), 0, st, n, x, 1.0, (const double*)x, alpha, (const double*)w.ph.p);
-            return it;
-        }
-        hipLaunchKernelGGL(k_sv_divdiag, dim3(G), dim3(256), 0, st, n, w.sh.p, (const double*)w.sv.p, A.diag, 1.0);
-        hipLaunchKernelGGL(k_ldu_mv, dim3(G), dim3(256), 0, st, s->dm, A.diag, A.up, A.lo, (const double*)w.sh.p, w.t.p, 1.0);
-        om = sv_dot(s, w, n, w.t.p, w.sv.p) / sv_dot(s, w, n, w.t.p, w.t.p);
-        hipLaunchKernelGGL(k_sv_bicg_x, dim3(G), dim3(256), 0, st, n, x, alpha, (const double*)w.ph.p, om, (const double*)w.sh.p, w.r.p, (const double*)w.sv.p, (const double*)w.t.p);
-        rho = rho1;
+// the operations of simple_sweep / simple_bicgstab / simple_pcg (das_simple_host.hpp) as kernel launches on the solver's stream
+extern "C++" struct SimpleDeviceOps {  // (a member template inside the C-ABI block)
+    const DevMesh& dm;
+    ResParams prm;
+    ResWork<double>& wk;
+    hipStream_t st;
+    SimpleWork w;
+    SimpleVecs v{};
+    SimpleDeviceOps(das_solver* s) : dm(s->dm), prm(s->wk.bind(s->cp.solver, s->dm.nC, s->dm.nF, make_params(s->cp, s->opt, 0))), wk(s->wk), st(s->stream) {
+        const long long N = dm.nC, F = dm.nF, nIF = dm.nIF, nBF = F - nIF;
+        if (wk.fc.n != (size_t)DAS_FC_N * nIF) wk.fc.alloc((size_t)DAS_FC_N * nIF);
+        if (wk.brec.n != (size_t)DAS_BREC_N * nBF) wk.brec.alloc((size_t)DAS_BREC_N * nBF);
+        simple_alloc(v, s->n, N, F, nIF, [&](long long cnt) { return w.take(cnt); });
+        v.W = s->d_W.p; v.Wp = v.W + prm.offP * N; v.WnNu = v.Wn + prm.offN * N; v.WnPhi = v.Wn + prm.offPhi * N;
+        v.nut = wk.nut.p; v.gU = wk.gU.p; v.gP = wk.gP.p; v.gN = wk.gN.p; v.fc = wk.fc.p; v.brec = wk.brec.p;
     }
-    return maxit;
-}
-// Jacobi-preconditioned conjugate gradients on sign * A (the pressure equation: A symmetric negative definite, sign = -1)
-static int sv_pcg(das_solver* s, SimpleWork& w, const LduDev& A, double sign, const double* b, double* x, double tol, int maxit) {
-    const long long n = s->dm.nC;
-    const int G = nblk(n, 256);
-    hipStream_t st = s->stream;
-    hipLaunchKernelGGL(k_ldu_mv, dim3(G), dim3(256), 0, st, s->dm, A.diag, A.up, A.lo, (const double*)x, w.r.p, 1.0);
-    hipLaunchKernelGGL(k_sv_lin, dim3(G), dim3(256), 0, st, n, w.r.p, sign, b, -sign, (const double*)w.r.p);
-    const double bn = std::sqrt(sv_dot(s, w, n, b, b)) + 1e-300;
-    double rz = 0.0;
-    for (int it = 1; it <= maxit; it++) {
-        if (std::sqrt(sv_dot(s, w, n, w.r.p, w.r.p)) <= tol * bn) return it - 1;
-        hipLaunchKernelGGL(k_sv_divdiag, dim3(G), dim3(256), 0, st, n, w.ph.p, (const double*)w.r.p, A.diag, sign);  // z
-        const double rz1 = sv_dot(s, w, n, w.r.p, w.ph.p);
-        if (it == 1) DAS_HIP(hipMemcpyAsync(w.p.p, w.ph.p, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        else hipLaunchKernelGGL(k_sv_lin, dim3(G), dim3(256), 0, st, n, w.p.p, 1.0, (const double*)w.ph.p, rz1 / rz, (const double*)w.p.p);
-        rz = rz1;
-        hipLaunchKernelGGL(k_ldu_mv, dim3(G), dim3(256), 0, st, s->dm, A.diag, A.up, A.lo, (const double*)w.p.p, w.v.p, sign);  // q = sign A p
-        const double alpha = rz / sv_dot(s, w, n, w.p.p, w.v.p);
-        hipLaunchKernelGGL(k_sv_lin, dim3(G), dim3(256), 0, st, n, x, 1.0, (const double*)x, alpha, (const double*)w.p.p);
-        hipLaunchKernelGGL(k_sv_lin, dim3(G), dim3(256), 0, st, n, w.r.p, 1.0, (const double*)w.r.p, -alpha, (const double*)w.v.p);
+    template <class K, class... A>
+    void launch(K k, long long cnt, A... a) { hipLaunchKernelGGL(k, dim3(nblk(cnt, 256)), dim3(256), 0, st, a...); }
+    void ldu_mv(const SimpleLdu& A, const double* x, double* y, double sign) { launch(k_ldu_mv, v.N, dm, A.diag, A.up, A.lo, x, y, sign); }
+    void lin(double* y, double a, const double* x, double b, const double* z) { launch(k_sv_lin, v.N, v.N, y, a, x, b, z); }
+    void bicg_p(double* p, const double* r, double beta, double om, const double* vv) { launch(k_sv_bicg_p, v.N, v.N, p, r, beta, om, vv); }
+    void divdiag(double* out, const double* in, const double* diag, double sign) { launch(k_sv_divdiag, v.N, v.N, out, in, diag, sign); }
+    void bicg_x(double* x, double alpha, const double* ph, double om, const double* sh, double* r, const double* s, const double* t) { launch(k_sv_bicg_x, v.N, v.N, x, alpha, ph, om, sh, r, s, t); }
+    double dot(const double* a, const double* b) { return sv_dot(st, w, v.N, a, b); }
+    void copy(double* dst, const double* src, long long cnt) { DAS_HIP(hipMemcpyAsync(dst, src, cnt * sizeof(double), hipMemcpyDeviceToDevice, st)); }
+    void zero(double* x, long long cnt) { if (cnt) DAS_HIP(hipMemset(x, 0, cnt * sizeof(double))); }
+    void grads_and_records(const double* W) {
+        launch_grad_simple<double, double>(dm, prm, W, wk, st);
+        if (v.nIF > 0) launch(k_fcoef<double>, v.nIF, dm, prm, W, v.nut, v.gU, v.gN, v.fc);
+        if (v.F > v.nIF) launch(k_bcoef<double>, v.F - v.nIF, dm, prm, W, v.nut, v.gU, v.brec);
     }
-    return maxit;
-}
+    void ueqn() { launch(k_simple_ueqn, v.N, dm, prm, v.W, v.gP, v.fc, v.brec, v.D, v.bd, v.sb, v.rhsU); }
+    void offdiag(const double* W, int cdIdx) { if (v.nIF > 0) launch(k_simple_offdiag, v.nIF, dm, prm, W, v.fc, cdIdx, v.up, v.lo); }
+    void gather3(int k) { launch(k_sv_gather3, v.N, v.N, v.W, k, v.D, v.bd, v.rhsU, v.x, v.dg, v.b); }
+    void scatter3(int k) { launch(k_sv_scatter3, v.N, v.N, v.x, k, v.Wn); }
+    void hbya() { launch(k_simple_hbya, v.N, dm, v.Wn, v.D, v.bd, v.sb, v.up, v.lo, v.rAU, v.HbyA); }
+    void pface() { launch(k_simple_pface, v.F, dm, prm, v.Wn, v.nut, v.rAU, v.HbyA, v.phiH, v.gpf, v.cp, v.pbc); }
+    void peqn() { launch(k_simple_peqn, v.N, dm, v.phiH, v.gpf, v.cp, v.pbc, v.gPn, v.dp, v.rp); }
+    void gradp() { launch(k_simple_gradp, v.N, dm, v.pn, v.pbc, v.gPn); }
+    void flux() { launch(k_simple_flux, v.F, dm, v.pn, v.gPn, v.phiH, v.gpf, v.cp, v.pbc, v.phiN); }
+    void relax(double alphaP) { launch(k_sv_relax, v.N, v.N, v.pn, v.Wp, alphaP); }
+    void correct() { launch(k_simple_correct, v.N, v.N, prm.offP, v.HbyA, v.rAU, v.gPn, v.pn, v.Wn); }
+    void saeqn() { launch(k_simple_saeqn, v.N, dm, prm, v.Wn, v.gU, v.gN, v.fc, v.brec, v.dg, v.b); }
+    void bound() { launch(k_sv_bound, v.N, v.N, v.x, 1e-16, v.WnNu); }  // DAUtility::boundVar
+};
 
 // nSweeps SIMPLE iterations on the solver's states (DASimpleFoam + SA without T field, MRF, cyclic pairs; single rank).  alphaP: explicit
 // pressure relaxation (fvSolution relaxationFactors.fields.p), linTol / maxLin: relative tolerance and iteration cap of the inner solves
@@ -3507,73 +3494,13 @@ static void run_simple_sweeps(das_solver* s, int nSweeps, double alphaP, double 
     DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM && !s->cp.hasT && !s->cp.mrf && !s->cp.hasCyclic, DAS_ERR_ARG,
               "SIMPLE sweeps serve DASimpleFoam + SA without T field, MRF and cyclic pairs");
     DAS_CHECK(!s->halo.active && !s->halo_cb && s->owned.empty(), DAS_ERR_ARG, "the SIMPLE sweeps are single-rank");
-    const DevMesh& dm = s->dm;
-    const long long N = dm.nC, F = dm.nF, nIF = dm.nIF, nBF = F - nIF, n = s->n;
-    const int B = 256;
-    hipStream_t st = s->stream;
-    ResParams prm = s->wk.bind(s->cp.solver, N, F, make_params(s->cp, s->opt, 0));
-    ResWork<double>& wk = s->wk;
-    if (wk.fc.n != (size_t)DAS_FC_N * nIF) wk.fc.alloc((size_t)DAS_FC_N * nIF);
-    if (wk.brec.n != (size_t)DAS_BREC_N * nBF) wk.brec.alloc((size_t)DAS_BREC_N * nBF);
-    SimpleWork w;
-    w.Wn.alloc(n); w.D.alloc(N); w.bd.alloc(3 * N); w.sb.alloc(3 * N); w.rhsU.alloc(3 * N); w.up.alloc(nIF); w.lo.alloc(nIF); w.rAU.alloc(N); w.HbyA.alloc(3 * N);
-    w.phiH.alloc(F); w.gpf.alloc(F); w.cp.alloc(nIF); w.pbc.alloc(4 * std::max<long long>(1, nBF)); w.dp.alloc(N); w.rp.alloc(N); w.x.alloc(N); w.b.alloc(N); w.dg.alloc(N);
-    w.pn.alloc(N); w.phiN.alloc(F); w.gPn.alloc(3 * N);
-    w.r.alloc(N); w.r0.alloc(N); w.p.alloc(N); w.v.alloc(N); w.sv.alloc(N); w.t.alloc(N); w.ph.alloc(N); w.sh.alloc(N); w.part.alloc(512); w.red.alloc(2);
-    double* W = s->d_W.p;
-    int itU = 0, itP = 0, itN = 0;
-    auto grads_and_records = [&](const double* Wc) {
-        launch_grad_simple<double, double>(dm, prm, Wc, wk, st);
-        if (nIF > 0) hipLaunchKernelGGL((k_fcoef<double>), dim3(nblk(nIF, B)), dim3(B), 0, st, dm, prm, Wc, (const double*)wk.nut.p, (const double*)wk.gU.p, (const double*)wk.gN.p, wk.fc.p);
-        if (nBF > 0) hipLaunchKernelGGL((k_bcoef<double>), dim3(nblk(nBF, B)), dim3(B), 0, st, dm, prm, Wc, (const double*)wk.nut.p, (const double*)wk.gU.p, wk.brec.p);
-    };
-    for (int sw = 0; sw < nSweeps; sw++) {
-        itU = itP = itN = 0;
-        // ---- momentum predictor (UEqnSimple.H)
-        grads_and_records(W);
-        hipLaunchKernelGGL(k_simple_ueqn, dim3(nblk(N, B)), dim3(B), 0, st, dm, prm, (const double*)W, (const double*)wk.gP.p, (const double*)wk.fc.p, (const double*)wk.brec.p, w.D.p,
-                           w.bd.p, w.sb.p, w.rhsU.p);
-        if (nIF > 0) hipLaunchKernelGGL(k_simple_offdiag, dim3(nblk(nIF, B)), dim3(B), 0, st, dm, prm, (const double*)W, (const double*)wk.fc.p, 0, w.up.p, w.lo.p);
-        DAS_HIP(hipMemcpyAsync(w.Wn.p, W, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-        for (int k = 0; k < 3; k++) {
-            hipLaunchKernelGGL(k_sv_gather3, dim3(nblk(N, B)), dim3(B), 0, st, N, (const double*)W, k, (const double*)w.D.p, (const double*)w.bd.p, (const double*)w.rhsU.p, w.x.p, w.dg.p, w.b.p);
-            itU += sv_bicgstab(s, w, LduDev{w.dg.p, w.up.p, w.lo.p}, w.b.p, w.x.p, linTol, maxLin);
-            hipLaunchKernelGGL(k_sv_scatter3, dim3(nblk(N, B)), dim3(B), 0, st, N, (const double*)w.x.p, k, w.Wn.p);
-        }
-        // ---- pressure corrector (pEqnSimple.H)
-        hipLaunchKernelGGL(k_simple_hbya, dim3(nblk(N, B)), dim3(B), 0, st, dm, (const double*)w.Wn.p, (const double*)w.D.p, (const double*)w.bd.p, (const double*)w.sb.p,
-                           (const double*)w.up.p, (const double*)w.lo.p, w.rAU.p, w.HbyA.p);
-        hipLaunchKernelGGL(k_simple_pface, dim3(nblk(F, B)), dim3(B), 0, st, dm, prm, (const double*)w.Wn.p, (const double*)wk.nut.p, (const double*)w.rAU.p, (const double*)w.HbyA.p,
-                           w.phiH.p, w.gpf.p, w.cp.p, w.pbc.p);
-        DAS_HIP(hipMemcpyAsync(w.gPn.p, wk.gP.p, 3 * N * sizeof(double), hipMemcpyDeviceToDevice, st));
-        DAS_HIP(hipMemcpyAsync(w.pn.p, W + prm.offP * N, N * sizeof(double), hipMemcpyDeviceToDevice, st));
-        for (int corr = 0; corr < 2; corr++) {  // nNonOrthogonalCorrectors 1
-            hipLaunchKernelGGL(k_simple_peqn, dim3(nblk(N, B)), dim3(B), 0, st, dm, (const double*)w.phiH.p, (const double*)w.gpf.p, (const double*)w.cp.p, (const double*)w.pbc.p,
-                               (const double*)w.gPn.p, w.dp.p, w.rp.p);
-            itP += sv_pcg(s, w, LduDev{w.dp.p, w.cp.p, w.cp.p}, -1.0, w.rp.p, w.pn.p, linTol, maxLin);
-            hipLaunchKernelGGL(k_simple_gradp, dim3(nblk(N, B)), dim3(B), 0, st, dm, (const double*)w.pn.p, (const double*)w.pbc.p, w.gPn.p);
-        }
-        hipLaunchKernelGGL(k_simple_flux, dim3(nblk(F, B)), dim3(B), 0, st, dm, (const double*)w.pn.p, (const double*)w.gPn.p, (const double*)w.phiH.p, (const double*)w.gpf.p,
-                           (const double*)w.cp.p, (const double*)w.pbc.p, w.phiN.p);
-        hipLaunchKernelGGL(k_sv_relax, dim3(nblk(N, B)), dim3(B), 0, st, N, w.pn.p, (const double*)(W + prm.offP * N), alphaP);
-        hipLaunchKernelGGL(k_simple_gradp, dim3(nblk(N, B)), dim3(B), 0, st, dm, (const double*)w.pn.p, (const double*)w.pbc.p, w.gPn.p);
-        hipLaunchKernelGGL(k_simple_correct, dim3(nblk(N, B)), dim3(B), 0, st, N, prm.offP, (const double*)w.HbyA.p, (const double*)w.rAU.p, (const double*)w.gPn.p,
-                           (const double*)w.pn.p, w.Wn.p);
-        DAS_HIP(hipMemcpyAsync(w.Wn.p + prm.offPhi * N, w.phiN.p, F * sizeof(double), hipMemcpyDeviceToDevice, st));
-        // ---- SA transport at the updated U / phi (DASpalartAllmaras::correct)
-        grads_and_records(w.Wn.p);
-        hipLaunchKernelGGL(k_simple_saeqn, dim3(nblk(N, B)), dim3(B), 0, st, dm, prm, (const double*)w.Wn.p, (const double*)wk.gU.p, (const double*)wk.gN.p, (const double*)wk.fc.p,
-                           (const double*)wk.brec.p, w.dg.p, w.b.p);
-        if (nIF > 0) hipLaunchKernelGGL(k_simple_offdiag, dim3(nblk(nIF, B)), dim3(B), 0, st, dm, prm, (const double*)w.Wn.p, (const double*)wk.fc.p, 1, w.up.p, w.lo.p);
-        DAS_HIP(hipMemcpyAsync(w.x.p, w.Wn.p + prm.offN * N, N * sizeof(double), hipMemcpyDeviceToDevice, st));
-        itN += sv_bicgstab(s, w, LduDev{w.dg.p, w.up.p, w.lo.p}, w.b.p, w.x.p, linTol, maxLin);
-        hipLaunchKernelGGL(k_sv_bound, dim3(nblk(N, B)), dim3(B), 0, st, N, (const double*)w.x.p, 1e-16, w.Wn.p + prm.offN * N);  // DAUtility::boundVar
-        DAS_HIP(hipMemcpyAsync(W, w.Wn.p, n * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
+    SimpleDeviceOps ops(s);
+    SimpleIters its;
+    for (int sw = 0; sw < nSweeps; sw++) its = simple_sweep(ops, alphaP, linTol, maxLin, maxLin);
     DAS_HIP(hipGetLastError());
-    DAS_HIP(hipStreamSynchronize(st));
+    DAS_HIP(hipStreamSynchronize(s->stream));
     s->h_W = s->d_W.to_host();
-    if (info) { info[0] = itU; info[1] = itP; info[2] = itN; }
+    if (info) { info[0] = its.U; info[1] = its.p; info[2] = its.nuTilda; }
 }
 
 int das_simple_iteration(das_solver_t* s, int nSweeps, double alphaP, double linTol, int maxLinIters, double* info3) {

@@ -8,8 +8,9 @@
 // sweeps of the oracle's restatement (oracle/primal.py simple_iteration) to solver tolerance (tests).
 //
 // The per-entity bodies below are plain templates (DAS_HD) like the residual bodies: the HIP kernels of das_device.hip wrap them, and the
-// test harness (tests/hostemu) runs the same bodies in host loops.  They reuse the face records of the cell-pass split (body_fcoef /
-// body_bcoef, das_kernels.hpp): fc = [cd | cdn | F0 F1 F2 | FN] per internal face, brec = 13 scalars per boundary face.
+// test harness (tests/hostemu) loops over them on the host.  The sweep and its inner solvers are written once, in das_simple_host.hpp
+// (simple_sweep<Ops>): the device and the harness run the same loop, each with its own Ops.  The bodies reuse the face records of the
+// cell-pass split (body_fcoef / body_bcoef, das_kernels.hpp): fc = [cd | cdn | F0 F1 F2 | FN] per internal face, brec = 13 scalars per boundary face.
 // DASimpleFoam + SA without T field, MRF and cyclic pairs.
 #pragma once
 #include "das_kernels.hpp"
@@ -238,6 +239,28 @@ DAS_HD void body_simple_saeqn(int c, const DevMeshT<double>& m, const ResParams&
     sN += (Dr - dN) * nc;
     diag[c] = Dr + bdN;
     rhs[c] = sN + bsN;
+}
+
+// ---- element expressions of the inner Krylov solvers and of the sweep's vector steps (das_simple_host.hpp)
+DAS_HD void body_sv_lin(long long i, double* y, double a, const double* x, double b, const double* z) { y[i] = a * x[i] + b * z[i]; }  // y = a x + b z
+DAS_HD void body_sv_bicg_p(long long i, double* p, const double* r, double beta, double om, const double* v) { p[i] = r[i] + beta * (p[i] - om * v[i]); }
+DAS_HD void body_sv_divdiag(long long i, double* out, const double* in, const double* diag, double sign) { out[i] = in[i] / (sign * diag[i]); }
+DAS_HD void body_sv_bicg_x(long long i, double* x, double alpha, const double* ph, double om, const double* sh, double* r, const double* s, const double* t) {
+    x[i] += alpha * ph[i] + om * sh[i];
+    r[i] = s[i] - om * t[i];
+}
+DAS_HD void body_sv_gather3(long long c, const double* W, int k, const double* D, const double* bd, const double* rhs3, double* x, double* dg, double* b) {
+    x[c] = W[3 * c + k];
+    dg[c] = D[c] + bd[3 * c + k];
+    b[c] = rhs3[3 * c + k];
+}
+DAS_HD void body_sv_scatter3(long long c, const double* x, int k, double* W) { W[3 * c + k] = x[c]; }
+DAS_HD void body_sv_relax(long long i, double* pn, const double* pold, double alpha) { pn[i] = pold[i] + alpha * (pn[i] - pold[i]); }  // pn = pold + alpha (pn - pold)
+DAS_HD void body_sv_bound(long long i, const double* x, double lo, double* out) { out[i] = x[i] > lo ? x[i] : lo; }
+// U = HbyA - rAU grad(p), p <- relaxed pressure, both written into the state vector Wn
+DAS_HD void body_sv_correct(long long c, long long N, int offP, const double* HbyA, const double* rAU, const double* gradP, const double* pRel, double* Wn) {
+    for (int k = 0; k < 3; k++) Wn[3 * c + k] = HbyA[3 * c + k] - rAU[c] * gradP[3 * c + k];
+    Wn[offP * N + c] = pRel[c];
 }
 
 }  // namespace das

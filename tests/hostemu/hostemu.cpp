@@ -167,65 +167,57 @@ extern "C" int emu_residual_geom(const das_case_t* c, const double* Win, long lo
     }
 }
 
-// ---- SIMPLE sweeps (csrc/das_simple.hpp) in host loops: the same per-entity bodies as the device driver, serial Krylov solvers --------------
+// ---- SIMPLE sweeps: the loop and the Krylov solvers of the device driver (csrc/das_simple_host.hpp) over host vectors and host loops
+// over the same per-entity bodies (csrc/das_simple.hpp); serial dot products
 #include "../../dafoam_amd/csrc/das_simple.hpp"
+#include "../../dafoam_amd/csrc/das_simple_host.hpp"
 namespace {
-struct Ldu { const DevMeshT<double>* m; const double* diag; const double* up; const double* lo; };
-static void ldu_mv(const Ldu& A, const std::vector<double>& x, std::vector<double>& y) {
-    for (int c = 0; c < A.m->nC; c++) y[c] = body_ldu_row(c, *A.m, A.diag, A.up, A.lo, x.data());
-}
-static double vdot(const std::vector<double>& a, const std::vector<double>& b) { double s = 0; for (size_t i = 0; i < a.size(); i++) s += a[i] * b[i]; return s; }
-// Jacobi-preconditioned BiCGStab; returns iterations
-static int bicgstab(const Ldu& A, const std::vector<double>& b, std::vector<double>& x, double tol, int maxit) {
-    const int n = A.m->nC;
-    std::vector<double> r(n), r0(n), p(n, 0.0), v(n, 0.0), s(n), t(n), ph(n), sh(n);
-    ldu_mv(A, x, r);
-    for (int i = 0; i < n; i++) r[i] = b[i] - r[i];
-    r0 = r;
-    const double bn = std::sqrt(vdot(b, b)) + 1e-300;
-    double rho = 1, alpha = 1, om = 1;
-    for (int it = 1; it <= maxit; it++) {
-        if (std::sqrt(vdot(r, r)) <= tol * bn) return it - 1;
-        const double rho1 = vdot(r0, r);
-        if (rho1 == 0.0 || !std::isfinite(rho1)) { if (getenv("EMU_SIMPLE_DEBUG")) fprintf(stderr, "bicgstab: breakdown rho %g at it %d |b| %.3e |r| %.3e\n", rho1, it, bn, std::sqrt(vdot(r, r))); return -it; }
-        const double beta = (rho1 / rho) * (alpha / om);
-        for (int i = 0; i < n; i++) p[i] = r[i] + beta * (p[i] - om * v[i]);
-        for (int i = 0; i < n; i++) ph[i] = p[i] / A.diag[i];
-        ldu_mv(A, ph, v);
-        alpha = rho1 / vdot(r0, v);
-        for (int i = 0; i < n; i++) s[i] = r[i] - alpha * v[i];
-        if (std::sqrt(vdot(s, s)) <= tol * bn) { for (int i = 0; i < n; i++) x[i] += alpha * ph[i]; return it; }  // converged at the half step
-        for (int i = 0; i < n; i++) sh[i] = s[i] / A.diag[i];
-        ldu_mv(A, sh, t);
-        om = vdot(t, s) / vdot(t, t);
-        for (int i = 0; i < n; i++) { x[i] += alpha * ph[i] + om * sh[i]; r[i] = s[i] - om * t[i]; }
-        rho = rho1;
+struct SimpleHostOps {
+    const DevMeshT<double>& m;
+    ResParams prm;
+    std::vector<std::vector<double>> store;
+    SimpleVecs v{};
+    double* gH = nullptr;
+    // n = 0: the solvers alone
+    explicit SimpleHostOps(const DevMeshT<double>& m_, const ResParams& prm_ = ResParams{}, const double* Win = nullptr, long long n = 0) : m(m_), prm(prm_) {
+        auto take = [&](long long cnt) { store.emplace_back((size_t)cnt, 0.0); return store.back().data(); };
+        const long long N = m.nC, F = m.nF, nIF = m.nIF;
+        simple_alloc(v, n, N, F, nIF, take);
+        if (!n) return;
+        v.W = take(n); v.nut = take(N); v.gU = take(9 * N); v.gP = take(3 * N); v.gN = take(3 * N); gH = take(3 * N);
+        v.fc = take(DAS_FC_N * nIF); v.brec = take(DAS_BREC_N * (F - nIF));
+        v.Wp = v.W + prm.offP * N; v.WnNu = v.Wn + prm.offN * N; v.WnPhi = v.Wn + prm.offPhi * N;
+        std::copy(Win, Win + n, v.W);
     }
-    if (getenv("EMU_SIMPLE_DEBUG")) fprintf(stderr, "bicgstab: %d iterations, relative residual %.3e\n", maxit, std::sqrt(vdot(r, r)) / bn);
-    return maxit;
-}
-// Jacobi-preconditioned conjugate gradients on sign * A (A symmetric, sign * A positive definite: the pressure equation has sign = -1)
-static int pcg(const Ldu& A, double sign, const std::vector<double>& b, std::vector<double>& x, double tol, int maxit) {
-    const int n = A.m->nC;
-    std::vector<double> r(n), z(n), p(n), q(n);
-    ldu_mv(A, x, r);
-    for (int i = 0; i < n; i++) r[i] = sign * (b[i] - r[i]);
-    const double bn = std::sqrt(vdot(b, b)) + 1e-300;
-    double rz = 0;
-    for (int it = 1; it <= maxit; it++) {
-        if (std::sqrt(vdot(r, r)) <= tol * bn) return it - 1;
-        for (int i = 0; i < n; i++) z[i] = r[i] / (sign * A.diag[i]);
-        const double rz1 = vdot(r, z);
-        if (it == 1) p = z; else { const double beta = rz1 / rz; for (int i = 0; i < n; i++) p[i] = z[i] + beta * p[i]; }
-        rz = rz1;
-        ldu_mv(A, p, q);
-        for (int i = 0; i < n; i++) q[i] *= sign;
-        const double alpha = rz / vdot(p, q);
-        for (int i = 0; i < n; i++) { x[i] += alpha * p[i]; r[i] -= alpha * q[i]; }
+    template <class Fn>
+    static void each(long long cnt, Fn fn) { for (long long i = 0; i < cnt; i++) fn(i); }
+    void ldu_mv(const SimpleLdu& A, const double* x, double* y, double sign) { each(v.N, [&](long long c) { y[c] = sign * body_ldu_row((int)c, m, A.diag, A.up, A.lo, x); }); }
+    void lin(double* y, double a, const double* x, double b, const double* z) { each(v.N, [&](long long i) { body_sv_lin(i, y, a, x, b, z); }); }
+    void bicg_p(double* p, const double* r, double beta, double om, const double* vv) { each(v.N, [&](long long i) { body_sv_bicg_p(i, p, r, beta, om, vv); }); }
+    void divdiag(double* out, const double* in, const double* diag, double sign) { each(v.N, [&](long long i) { body_sv_divdiag(i, out, in, diag, sign); }); }
+    void bicg_x(double* x, double alpha, const double* ph, double om, const double* sh, double* r, const double* s, const double* t) { each(v.N, [&](long long i) { body_sv_bicg_x(i, x, alpha, ph, om, sh, r, s, t); }); }
+    double dot(const double* a, const double* b) const { double s = 0; for (long long i = 0; i < v.N; i++) s += a[i] * b[i]; return s; }
+    void copy(double* dst, const double* src, long long cnt) { std::copy(src, src + cnt, dst); }
+    void zero(double* x, long long cnt) { std::fill(x, x + cnt, 0.0); }
+    void grads_and_records(const double* W) {
+        each(v.N, [&](long long c) { body_grad<double, false>((int)c, m, prm, W, v.nut, v.gU, v.gP, v.gN, gH); });
+        each(v.nIF, [&](long long f) { body_fcoef<double>((int)f, m, prm, W, v.nut, v.gU, v.gN, v.fc); });
+        each(v.F - v.nIF, [&](long long b) { body_bcoef<double>((int)b, m, prm, W, v.nut, v.gU, v.brec); });
     }
-    if (getenv("EMU_SIMPLE_DEBUG")) fprintf(stderr, "pcg: %d iterations, relative residual %.3e\n", maxit, std::sqrt(vdot(r, r)) / bn);
-    return maxit;
-}
+    void ueqn() { each(v.N, [&](long long c) { body_simple_ueqn((int)c, m, prm, v.W, v.gP, v.fc, v.brec, v.D, v.bd, v.sb, v.rhsU); }); }
+    void offdiag(const double* W, int cdIdx) { each(v.nIF, [&](long long f) { body_simple_offdiag((int)f, m, prm, W, v.fc, cdIdx, v.up, v.lo); }); }
+    void gather3(int k) { each(v.N, [&](long long c) { body_sv_gather3(c, v.W, k, v.D, v.bd, v.rhsU, v.x, v.dg, v.b); }); }
+    void scatter3(int k) { each(v.N, [&](long long c) { body_sv_scatter3(c, v.x, k, v.Wn); }); }
+    void hbya() { each(v.N, [&](long long c) { body_simple_hbya((int)c, m, v.Wn, v.D, v.bd, v.sb, v.up, v.lo, v.rAU, v.HbyA); }); }
+    void pface() { each(v.F, [&](long long f) { body_simple_pface((int)f, m, prm, v.Wn, v.nut, v.rAU, v.HbyA, v.phiH, v.gpf, v.cp, v.pbc); }); }
+    void peqn() { each(v.N, [&](long long c) { body_simple_peqn((int)c, m, v.phiH, v.gpf, v.cp, v.pbc, v.gPn, v.dp, v.rp); }); }
+    void gradp() { each(v.N, [&](long long c) { body_simple_gradp((int)c, m, v.pn, v.pbc, v.gPn); }); }
+    void flux() { each(v.F, [&](long long f) { body_simple_flux((int)f, m, v.pn, v.gPn, v.phiH, v.gpf, v.cp, v.pbc, v.phiN); }); }
+    void relax(double alphaP) { each(v.N, [&](long long i) { body_sv_relax(i, v.pn, v.Wp, alphaP); }); }
+    void correct() { each(v.N, [&](long long c) { body_sv_correct(c, v.N, prm.offP, v.HbyA, v.rAU, v.gPn, v.pn, v.Wn); }); }
+    void saeqn() { each(v.N, [&](long long c) { body_simple_saeqn((int)c, m, prm, v.Wn, v.gU, v.gN, v.fc, v.brec, v.dg, v.b); }); }
+    void bound() { each(v.N, [&](long long i) { body_sv_bound(i, v.x, 1e-16, v.WnNu); }); }  // DAUtility::boundVar
+};
 }  // namespace
 
 // nSweeps SIMPLE iterations from Win; alphaP = explicit pressure relaxation; linTol = relative tolerance of the inner solves
@@ -237,58 +229,35 @@ extern "C" int emu_simple_iteration(const das_case_t* c, const double* Win, long
         cp.from_case(c);
         DAS_CHECK(cp.solver == DAS_SOLVER_SIMPLEFOAM && !cp.hasT && !cp.mrf && !cp.hasCyclic, DAS_ERR_ARG, "SIMPLE sweeps: DASimpleFoam + SA without T / MRF / cyclic pairs");
         Options opt;
-        ResParams prm = make_params(cp, opt, 0);
         const DevMeshT<double> m = host_view(mesh);
-        const long long N = m.nC, F = m.nF, nIF = m.nIF, nBF = F - nIF;
-        std::vector<double> W(Win, Win + n), nut(N), gU(9 * N), gP(3 * N), gN(3 * N), gH(3 * N), fc(DAS_FC_N * nIF), brec(DAS_BREC_N * nBF);
-        std::vector<double> D(N), bd(3 * N), sb(3 * N), rhsU(3 * N), up(nIF), lo(nIF), rAU(N), HbyA(3 * N), phiH(F), gpf(F), cpv(nIF), pbc(4 * nBF), dp(N), rp(N);
-        std::vector<double> x(N), b(N), dg(N), pn(N), phiN(F), gPn(3 * N);
-        for (int sw = 0; sw < nSweeps; sw++) {
-            // ---- momentum predictor
-            for (int cc = 0; cc < N; cc++) body_grad<double, false>(cc, m, prm, W.data(), nut.data(), gU.data(), gP.data(), gN.data(), gH.data());
-            for (int f = 0; f < nIF; f++) body_fcoef<double>(f, m, prm, W.data(), nut.data(), gU.data(), gN.data(), fc.data());
-            for (int bb = 0; bb < nBF; bb++) body_bcoef<double>(bb, m, prm, W.data(), nut.data(), gU.data(), brec.data());
-            for (int cc = 0; cc < N; cc++) body_simple_ueqn(cc, m, prm, W.data(), gP.data(), fc.data(), brec.data(), D.data(), bd.data(), sb.data(), rhsU.data());
-            for (int f = 0; f < nIF; f++) body_simple_offdiag(f, m, prm, W.data(), fc.data(), 0, up.data(), lo.data());
-            std::vector<double> Wn(W);
-            for (int k = 0; k < 3; k++) {
-                for (int cc = 0; cc < N; cc++) { dg[cc] = D[cc] + bd[3LL * cc + k]; b[cc] = rhsU[3LL * cc + k]; x[cc] = W[3LL * cc + k]; }
-                bicgstab(Ldu{&m, dg.data(), up.data(), lo.data()}, b, x, linTol, 2000);
-                for (int cc = 0; cc < N; cc++) Wn[3LL * cc + k] = x[cc];
-            }
-            // ---- pressure corrector
-            for (int cc = 0; cc < N; cc++) body_simple_hbya(cc, m, Wn.data(), D.data(), bd.data(), sb.data(), up.data(), lo.data(), rAU.data(), HbyA.data());
-            for (int f = 0; f < F; f++) body_simple_pface(f, m, prm, Wn.data(), nut.data(), rAU.data(), HbyA.data(), phiH.data(), gpf.data(), cpv.data(), pbc.data());
-            gPn = gP;
-            for (int cc = 0; cc < N; cc++) pn[cc] = W[prm.offP * N + cc];
-            for (int corr = 0; corr < 2; corr++) {  // nNonOrthogonalCorrectors 1
-                for (int cc = 0; cc < N; cc++) body_simple_peqn(cc, m, phiH.data(), gpf.data(), cpv.data(), pbc.data(), gPn.data(), dp.data(), rp.data());
-                pcg(Ldu{&m, dp.data(), cpv.data(), cpv.data()}, -1.0, rp, pn, linTol, 20000);
-                for (int cc = 0; cc < N; cc++) body_simple_gradp(cc, m, pn.data(), pbc.data(), gPn.data());
-            }
-            for (int f = 0; f < F; f++) body_simple_flux(f, m, pn.data(), gPn.data(), phiH.data(), gpf.data(), cpv.data(), pbc.data(), phiN.data());
-            for (int cc = 0; cc < N; cc++) pn[cc] = W[prm.offP * N + cc] + alphaP * (pn[cc] - W[prm.offP * N + cc]);
-            for (int cc = 0; cc < N; cc++) body_simple_gradp(cc, m, pn.data(), pbc.data(), gPn.data());
-            for (int cc = 0; cc < N; cc++) {
-                for (int k = 0; k < 3; k++) Wn[3LL * cc + k] = HbyA[3LL * cc + k] - rAU[cc] * gPn[3LL * cc + k];
-                Wn[prm.offP * N + cc] = pn[cc];
-            }
-            for (int f = 0; f < F; f++) Wn[prm.offPhi * N + f] = phiN[f];
-            // ---- SA transport at the updated U / phi
-            for (int cc = 0; cc < N; cc++) body_grad<double, false>(cc, m, prm, Wn.data(), nut.data(), gU.data(), gP.data(), gN.data(), gH.data());
-            for (int f = 0; f < nIF; f++) body_fcoef<double>(f, m, prm, Wn.data(), nut.data(), gU.data(), gN.data(), fc.data());
-            for (int bb = 0; bb < nBF; bb++) body_bcoef<double>(bb, m, prm, Wn.data(), nut.data(), gU.data(), brec.data());
-            for (int cc = 0; cc < N; cc++) body_simple_saeqn(cc, m, prm, Wn.data(), gU.data(), gN.data(), fc.data(), brec.data(), dg.data(), b.data());
-            for (int f = 0; f < nIF; f++) body_simple_offdiag(f, m, prm, Wn.data(), fc.data(), 1, up.data(), lo.data());
-            for (int cc = 0; cc < N; cc++) x[cc] = Wn[prm.offN * N + cc];
-            bicgstab(Ldu{&m, dg.data(), up.data(), lo.data()}, b, x, linTol, 2000);
-            for (int cc = 0; cc < N; cc++) Wn[prm.offN * N + cc] = std::max(x[cc], 1e-16);  // DAUtility::boundVar
-            W.swap(Wn);
-        }
-        for (long long i = 0; i < n; i++) Wout[i] = W[i];
+        SimpleHostOps ops(m, make_params(cp, opt, 0), Win, n);
+        for (int sw = 0; sw < nSweeps; sw++) simple_sweep(ops, alphaP, linTol, 2000, 20000);
+        std::copy(ops.v.W, ops.v.W + n, Wout);
         return 0;
     } catch (const std::exception& e) {
         fprintf(stderr, "emu_simple_iteration: %s\n", e.what());
         return -1;
     }
+}
+
+// The shared solvers alone, on the mesh of the case: LDU matrix diag[nCells] / up, lo[nInternalFaces], right-hand side b, start vector and
+// result x; return the iterations done (-1: error)
+template <class Solve>
+static int emu_simple_solve(const char* name, const das_case_t* c, Solve solve) {
+    try {
+        Mesh mesh;
+        mesh.build(c);
+        const DevMeshT<double> m = host_view(mesh);
+        SimpleHostOps ops(m);
+        return solve(ops);
+    } catch (const std::exception& e) {
+        fprintf(stderr, "%s: %s\n", name, e.what());
+        return -1;
+    }
+}
+extern "C" int emu_simple_bicgstab(const das_case_t* c, const double* diag, const double* up, const double* lo, const double* b, double* x, double tol, int maxit) {
+    return emu_simple_solve("emu_simple_bicgstab", c, [&](SimpleHostOps& ops) { return simple_bicgstab(ops, SimpleLdu{diag, up, lo}, b, x, tol, maxit); });
+}
+extern "C" int emu_simple_pcg(const das_case_t* c, const double* diag, const double* up, const double* lo, const double* b, double* x, double sign, double tol, int maxit) {
+    return emu_simple_solve("emu_simple_pcg", c, [&](SimpleHostOps& ops) { return simple_pcg(ops, SimpleLdu{diag, up, lo}, sign, b, x, tol, maxit); });
 }

@@ -1319,6 +1319,29 @@ def test_simple_sweeps_on_the_device_equal_the_oracle_and_reach_the_newton_fixed
     assert relerr(W / sc, conv.states / sc) < 1e-5
 
 
+def test_simple_sweep_on_the_device_equals_the_host_twin_of_the_same_loop():
+    """simple_sweep<Ops> (csrc/das_simple_host.hpp) is one loop with two sets of operations: kernel launches (das_simple_iteration) and the
+    harness's host loops (emu_simple_iteration).  One sweep of each from the same state: the two differ in the summation order of the
+    dot products only, so every state block agrees to the 1e-9 the device meets against the oracle.  (The inner iteration counts may
+    differ by one at the tolerance threshold and are not compared.)"""
+    from dafoam_amd._capi import CaseStruct, c_double_p, das_case_t, dptr
+
+    case = channel_case(7, 6, 5, perturb=0.0)
+    g = Geometry(case.mesh)
+    W0 = case.states.copy()
+    E = C.CDLL(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "hostemu", "libhostemu.so"))
+    E.emu_simple_iteration.argtypes = [C.POINTER(das_case_t), c_double_p, C.c_longlong, C.c_int, C.c_double, C.c_double, c_double_p]
+    Wh = np.zeros_like(W0)
+    cs = CaseStruct(case)
+    assert E.emu_simple_iteration(cs.byref(),dptr(W0), W0.size, 1, 0.3, 1e-13, dptr(Wh)) == 0
+    D = make(case)
+    D.solver.simpleIteration(1, alphaP=0.3, linTol=1e-13)
+    Wd = np.zeros(W0.size)
+    D.solver.getOFFields(Wd)
+    for nm, sl in blocks(case, g):
+        assert relerr(Wd[sl], Wh[sl]) < 1e-9, nm
+
+
 def test_newton_krylov_primal_compressible():
     """The same Newton-Krylov primal on DARhoSimpleFoam + SA: the fixed point of the oracle's compressible SIMPLE loop."""
     from oracle.primal import solve_primal

@@ -254,6 +254,101 @@ def test_simple_sweep_bodies_equal_the_oracle_simple_iteration():
                 assert relerr(out[sl], oracle_states[ns][sl]) < 1e-10, (nm, ns)
 
 
+class _SimpleSolvers:
+    """The inner solvers of the SIMPLE sweep (csrc/das_simple_host.hpp: simple_bicgstab, simple_pcg - the code the device driver runs, here
+    over the harness's host operations) on random LDU matrices on the mesh of channel_case(4, 3, 3) (36 cells), and the same matrices
+    assembled densely as body_ldu_row reads them: the owner's row takes up[f], the neighbour's row lo[f]."""
+
+    def __init__(self):
+        self.case = channel_case(4, 3, 3, perturb=0.0)
+        mesh = self.case.mesh
+        self.N, nIF = mesh.n_cells, mesh.n_internal_faces
+        assert self.N == 36
+        self.own, self.nei = np.asarray(mesh.owner[:nIF]), np.asarray(mesh.neighbour[:nIF])
+        self.cs = CaseStruct(self.case)
+        self.E = _emu()
+        dp = _capi.c_double_p
+        self.E.emu_simple_bicgstab.argtypes = [C.POINTER(das_case_t), dp, dp, dp, dp, dp, C.c_double, C.c_int]
+        self.E.emu_simple_pcg.argtypes = [C.POINTER(das_case_t), dp, dp, dp, dp, dp, C.c_double, C.c_double, C.c_int]
+        rng = np.random.default_rng(20240607)
+        self.b = rng.standard_normal(self.N)
+        # non-symmetric, |diag| > sum |off| per row
+        up, lo = rng.uniform(-1.0, 1.0, nIF), rng.uniform(-1.0, 1.0, nIF)
+        self.nonsym = (self._dominant_diag(up, lo, rng), up, lo)
+        # symmetric with negative diagonal, -A positive definite (diagonally dominant): the shape of the pressure equation
+        off = rng.uniform(-1.0, 1.0, nIF)
+        self.sym = (-self._dominant_diag(off, off, rng), off, off.copy())
+
+    def _dominant_diag(self, up, lo, rng):
+        s = np.zeros(self.N)
+        np.add.at(s, self.own, np.abs(up))
+        np.add.at(s, self.nei, np.abs(lo))
+        return s + rng.uniform(0.1, 1.0, self.N)
+
+    def dense(self, ldu):
+        diag, up, lo = ldu
+        A = np.diag(diag)
+        A[self.own, self.nei] = up
+        A[self.nei, self.own] = lo
+        return A
+
+    def bicgstab(self, ldu, b, x0, tol, maxit):
+        x = x0.copy()
+        its = self.E.emu_simple_bicgstab(self.cs.byref(), dptr(ldu[0]), dptr(ldu[1]), dptr(ldu[2]), dptr(b), dptr(x), tol, maxit)
+        return its, x
+
+    def pcg(self, ldu, b, x0, sign, tol, maxit):
+        x = x0.copy()
+        its = self.E.emu_simple_pcg(self.cs.byref(), dptr(ldu[0]), dptr(ldu[1]), dptr(ldu[2]), dptr(b), dptr(x), sign, tol, maxit)
+        return its, x
+
+
+@pytest.fixture(scope="module")
+def simple_solvers():
+    return _SimpleSolvers()
+
+
+def test_simple_bicgstab_equals_a_direct_solve(simple_solvers):
+    S = simple_solvers
+    A = S.dense(S.nonsym)
+    assert np.all(np.abs(np.diag(A)) > np.abs(A - np.diag(np.diag(A))).sum(axis=1)) and not np.allclose(A, A.T)
+    its, x = S.bicgstab(S.nonsym, S.b, np.zeros(S.N), 1e-13, 500)
+    assert 0 < its < 500
+    assert relerr(x, np.linalg.solve(A, S.b)) < 1e-10
+
+
+def test_simple_pcg_with_sign_minus_one_equals_a_direct_solve(simple_solvers):
+    S = simple_solvers
+    A = S.dense(S.sym)
+    assert np.array_equal(A, A.T) and np.all(np.diag(A) < 0) and np.linalg.eigvalsh(-A).min() > 0
+    its, x = S.pcg(S.sym, S.b, np.zeros(S.N), -1.0, 1e-13, 500)
+    assert 0 < its < 500
+    assert relerr(x, np.linalg.solve(A, S.b)) < 1e-10
+
+
+def test_simple_solvers_return_at_once_on_a_zero_right_hand_side(simple_solvers):
+    S = simple_solvers
+    zero = np.zeros(S.N)
+    its, x = S.bicgstab(S.nonsym, zero, zero, 1e-13, 500)
+    assert its == 0 and np.array_equal(x, zero)
+    its, x = S.pcg(S.sym, zero, zero, -1.0, 1e-13, 500)
+    assert its == 0 and np.array_equal(x, zero)
+
+
+def test_simple_solvers_respect_the_iteration_cap(simple_solvers):
+    S = simple_solvers
+    A = S.dense(S.nonsym)
+    _, xc = S.bicgstab(S.nonsym, S.b, np.zeros(S.N), 1e-13, 500)
+    its, x1 = S.bicgstab(S.nonsym, S.b, np.zeros(S.N), 1e-13, 1)
+    assert its == 1
+    assert np.linalg.norm(S.b - A @ x1) > np.linalg.norm(S.b - A @ xc)
+    A = S.dense(S.sym)
+    _, xc = S.pcg(S.sym, S.b, np.zeros(S.N), -1.0, 1e-13, 500)
+    its, x1 = S.pcg(S.sym, S.b, np.zeros(S.N), -1.0, 1e-13, 1)
+    assert its == 1
+    assert np.linalg.norm(S.b - A @ x1) > np.linalg.norm(S.b - A @ xc)
+
+
 def test_seam_folded_cell_numbering_is_the_same_mesh_and_keeps_the_grid_sequencing_helpers_consistent():
     """Round 6 (naca0012_case(fold_seam=True), bench.py --naca-fold): the O-grid with the ring positions numbered 0, n-1, 1, n-2, ... - the
     same cells, geometry and state as the plain numbering under the permutation naca_ring_position decodes; ring neighbours are at most
