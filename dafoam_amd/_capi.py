@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .meshgen import FoamCase
+from .meshgen import BC_MIXED, FoamCase
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DAFOAM_AMD_LIB") or os.path.join(_HERE, "lib", "libdafoam_amd.so")  # (override: tuning builds)
@@ -75,6 +75,8 @@ class das_case_t(C.Structure):
         ("sutherland_As", C.c_double),
         ("sutherland_Ts", C.c_double),
         ("beta_fi_nuTilda", c_double_p),
+        ("bc_T_mixed_ref", c_double_p),
+        ("bc_T_mixed_frac", c_double_p),
     ]
 
 
@@ -141,6 +143,8 @@ class CaseStruct:
                     code[i] = 1  # zeroGradient
                     continue
                 present = True
+                if ent[0] == BC_MIXED and field != "T":
+                    raise DASError(f"patch {p.name}: the mixed patch field is built for T only, not for {field}")
                 code[i] = ent[0]
                 val[i] = ent[1]
             return (code, np.ascontiguousarray(val)) if present else (None, None)
@@ -150,6 +154,19 @@ class CaseStruct:
         k["bc_nuTilda_code"], k["bc_nuTilda_val"] = table("nuTilda")
         k["bc_nut_code"], _ = table("nut")
         k["bc_T_code"], k["bc_T_val"] = table("T")
+        k["bc_T_mixed_ref"] = k["bc_T_mixed_frac"] = None
+        if k["bc_T_code"] is not None and (k["bc_T_code"] == BC_MIXED).any():
+            # refValue / valueFraction of the mixed patches, one entry per boundary face of the mesh
+            k["bc_T_mixed_ref"], k["bc_T_mixed_frac"] = np.zeros(m.n_faces - m.n_internal_faces), np.zeros(m.n_faces - m.n_internal_faces)
+            for i, p in enumerate(m.patches):
+                if k["bc_T_code"][i] != BC_MIXED:
+                    continue
+                if p.name not in getattr(case, "mixed_T", {}):
+                    raise DASError(f"patch {p.name}: T is mixed but FoamCase.mixed_T has no refValue / valueFraction for it")
+                if any(np.shape(a) != (p.size,) for a in case.mixed_T[p.name]):
+                    raise DASError(f"patch {p.name}: the refValue / valueFraction of the mixed T need one entry per face ({p.size})")
+                sl = slice(p.start - m.n_internal_faces, p.start - m.n_internal_faces + p.size)
+                k["bc_T_mixed_ref"][sl], k["bc_T_mixed_frac"][sl] = case.mixed_T[p.name]
         k["y_wall"] = None if case.y_wall is None else np.ascontiguousarray(case.y_wall, dtype=np.float64)
         k["phi_frozen"] = None if case.phi is None else np.ascontiguousarray(case.phi, dtype=np.float64)
         k["T_old"] = None if case.T_old is None else np.ascontiguousarray(case.T_old, dtype=np.float64)
@@ -164,7 +181,7 @@ class CaseStruct:
             m.n_cells,
             P,
         )
-        for name in ("points", "bc_U_val", "bc_p_val", "bc_nuTilda_val", "bc_T_val", "y_wall", "phi_frozen", "T_old"):
+        for name in ("points", "bc_U_val", "bc_p_val", "bc_nuTilda_val", "bc_T_val", "y_wall", "phi_frozen", "T_old", "bc_T_mixed_ref", "bc_T_mixed_frac"):
             setattr(s, name, _dp(k[name]))
         for name in (
             "face_ptr", "face_pts", "owner", "neighbour", "patch_start", "patch_size", "patch_type",
@@ -279,6 +296,12 @@ _SIGS = {
     "das_calc_function": (C.c_int, [_VP, C.c_char_p, c_double_p]),
     "das_define_force_coupling": (C.c_int, [_VP, C.c_char_p, c_int_p, C.c_int, C.c_double]),
     "das_calc_force_coupling": (C.c_int, [_VP, C.c_char_p, c_double_p, C.c_int]),
+    "das_define_thermal_coupling": (C.c_int, [_VP, C.c_char_p, c_int_p, C.c_int, C.c_int]),
+    "das_calc_thermal_coupling": (C.c_int, [_VP, C.c_char_p, c_double_p, C.c_int]),
+    "das_define_thermal_coupling_input": (C.c_int, [_VP, C.c_char_p, c_int_p, C.c_int, C.c_int]),
+    "das_set_thermal_coupling_input": (C.c_int, [_VP, C.c_char_p, c_double_p, C.c_int]),
+    "das_get_patch_mixed": (C.c_int, [_VP, C.c_int, c_double_p, c_double_p]),
+    "das_calc_dthermal_coupling_product": (C.c_int, [_VP, C.c_char_p, C.c_char_p, C.c_char_p, c_double_p, c_double_p, C.c_int]),
     "das_get_input_size": (C.c_int, [_VP, C.c_char_p, C.c_char_p]),
     "das_get_output_size": (C.c_int, [_VP, C.c_char_p, C.c_char_p]),
     "das_calc_jac_t_vec_product": (

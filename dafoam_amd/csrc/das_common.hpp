@@ -399,6 +399,9 @@ struct Mesh {
     std::vector<CellGeom> cg;
     std::vector<int> bface_patch;  // nBF
     std::vector<int> cyc_face;     // nBF: the paired face of a cyclic boundary face, -1 otherwise
+    // patches with a mixed T (DAS_BC_MIXED): 4 per boundary face - refValue, valueFraction and their tangents (forward-mode seeds, zero
+    // except inside the products of the thermalCoupling input); empty when no patch is mixed
+    std::vector<double> mixed;
     // cell -> faces CSR; entry = face id | (side<<31), side 1 = this cell is the face's neighbour
     std::vector<int> cf_ptr, cf_face, cf_other;
     // cell -> cells CSR (face neighbours, ascending)

@@ -40,6 +40,7 @@
 #include "das_cellfn.hpp"
 #include "das_facefn.hpp"
 #include "das_forcecoupling.hpp"
+#include "das_thermalcoupling.hpp"
 #include "das_simple.hpp"
 #include "das_simple_host.hpp"
 
@@ -763,6 +764,7 @@ struct das_solver {
     DevBuf<CellGeom> d_cg;
     DevBuf<int> d_cf_ptr, d_cf_face, d_cf_other, d_owner, d_neigh, d_bpatch, d_cyc;
     DevBuf<PatchBC> d_bc;
+    DevBuf<double> d_mixed;  // Mesh::mixed (the per-face records of the mixed T patches), when there are any
     DevBuf<double> d_phiF, d_Told;
     DevMesh dm;
     DevBuf<double> d_W, d_R, d_R0, d_Wp, d_scale, d_tmp1, d_tmp2;
@@ -822,6 +824,18 @@ struct das_solver {
         bool uploaded = false;
     };
     std::map<std::string, ForceCoupling> forceCouplings;
+    // a thermalCouplingOutput (das_thermalcoupling.hpp): [T of the owner cells, kappa / d] over the faces of the patches.  `fn` lists the
+    // faces and is the functional seeds . output of the derivative passes: kind thermalCoupling, unit weights, d_f = the two seeds of the
+    // face, written on the device by k_tc_seed_dir.
+    struct ThermalCoupling {
+        std::vector<int> patches;  // in output order (the caller sorts them by name)
+        DevBuf<double> d_out, d_seeds;
+        FaceFn fn;
+        bool uploaded = false;
+        std::vector<double> in;  // a thermalCoupling input: what was set last (empty before the first time); d_out then holds the myK used
+    };
+    // the outputs, and the thermalCoupling inputs (reference DAInputThermalCoupling.C): the same faces and kernels, on mixed T patches
+    std::map<std::string, ThermalCoupling> thermalCouplings, thermalInputs;
     struct CellFn {  // a cell-set objective (see das_cellfn.hpp)
         bool variance = false, square = false, multiplyVol = true, divByTotalVol = false, refVar = false, geoWeight = false, hasData = true;
         bool field = false;  // src = betaFINuTilda instead of the states
@@ -3217,6 +3231,7 @@ int das_init_solver(das_solver_t* s, int device) {
     if (!s->cp.T_old.empty()) s->d_Told.upload(s->cp.T_old);
     s->dm = DevMesh{m.nC, m.nF, m.nIF, s->d_fg.p, s->d_cg.p, s->d_cf_ptr.p, s->d_cf_face.p, s->d_cf_other.p, s->d_owner.p, s->d_neigh.p,
                     s->d_bpatch.p, s->d_bc.p, s->d_cyc.p};
+    if (!m.mixed.empty()) { s->d_mixed.upload(m.mixed); s->dm.mixed = s->d_mixed.p; }
     s->d_W.upload(s->h_W);
     s->d_R.alloc(s->n);
     s->d_tmp1.alloc(s->n);
@@ -4248,6 +4263,16 @@ int das_define_force_coupling(das_solver_t* s, const char* name, const int* patc
     return DAS_OK;
     DAS_CATCH
 }
+// the device arrays of the internal face function of a coupling output (unit weights; the directions are written per product)
+static void upload_coupling_functional(das_solver* s, das_solver::FaceFn& fn) {
+    fn.d_faces.upload(fn.faces);
+    fn.d_group.upload(fn.group);
+    fn.d_w0.upload(fn.w0);
+    fn.d_weff.alloc(fn.w0.size());
+    fn.d_dir.upload(fn.dir);
+    fn.geomVersion = s->geomVersion;
+    fn.uploaded = true;
+}
 static das_solver::ForceCoupling& get_force_coupling(das_solver* s, const char* name, bool device = true) {
     auto it = s->forceCouplings.find(name ? name : "");
     DAS_CHECK(it != s->forceCouplings.end(), DAS_ERR_ARG, std::string("forceCouplingOutput not defined: ") + (name ? name : "(null)"));
@@ -4255,13 +4280,7 @@ static das_solver::ForceCoupling& get_force_coupling(das_solver* s, const char* 
     das_solver::ForceCoupling& fc = it->second;
     if (device && !fc.uploaded) {
         das_solver::FaceFn& fn = fc.fn;
-        fn.d_faces.upload(fn.faces);
-        fn.d_group.upload(fn.group);
-        fn.d_w0.upload(fn.w0);
-        fn.d_weff.alloc(fn.w0.size());
-        fn.d_dir.upload(fn.dir);
-        fn.geomVersion = s->geomVersion;
-        fn.uploaded = true;
+        upload_coupling_functional(s, fn);
         fc.d_ptPtr.upload(fc.ptPtr); fc.d_ptSlot.upload(fc.ptSlot);
         fc.d_fcPtr.upload(fc.fcPtr); fc.d_fcPt.upload(fc.fcPt);
         fc.d_ff.alloc(3 * fn.faces.size());
@@ -4302,6 +4321,143 @@ int das_calc_force_coupling(das_solver_t* s, const char* name, double* out, int 
     DAS_HIP(hipStreamSynchronize(s->stream));
     return DAS_OK;
     DAS_CATCH
+}
+
+// ---- thermalCouplingOutput (reference DAOutputThermalCoupling.C; layout and kernels: das_thermalcoupling.hpp) ---------------------
+static void need_thermal_coupling_solver(das_solver* s) {
+    DAS_CHECK(DAS_IS_COMPRESSIBLE(s->cp.solver) || (s->cp.solver == DAS_SOLVER_SIMPLEFOAM && s->cp.hasT), DAS_ERR_ARG,
+              "thermalCouplingOutput needs a solver that carries a T field (DASimpleFoam with T, DARhoSimpleFoam, DATurboFoam)");
+    DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "thermalCouplingOutput runs on an undecomposed solver (sharded solvers are not supported)");
+}
+// the faces of an output (input: the patches must carry a mixed T, where the reference's refCast aborts);
+// flags & 2: wallDistanceMethod daCustom (the bit das_define_face_function_ex gives wallHeatFlux)
+static int define_thermal_coupling(das_solver_t* s, const char* name, const int* patch_ids, int npatch, int flags, bool input) {
+    DAS_TRY
+    DAS_CHECK(s && name && patch_ids && npatch > 0, DAS_ERR_ARG, "bad argument");
+    need_thermal_coupling_solver(s);
+    const Mesh& m = s->mesh;
+    const std::string what = std::string(input ? "thermalCoupling input " : "thermalCouplingOutput ") + name;
+    das_solver::ThermalCoupling tc;
+    das_solver::FaceFn& fn = tc.fn;
+    for (int k = 0; k < npatch; k++) {
+        const int p = patch_ids[k];
+        DAS_CHECK(p >= 0 && p < m.nPatch, DAS_ERR_ARG, what + ": patch id " + std::to_string(p) + " is not in the mesh (" + std::to_string(m.nPatch) + " patches)");
+        DAS_CHECK(m.patch_type[p] != DAS_PATCH_CYCLIC, DAS_ERR_ARG, what + " cannot be defined on cyclic patches");
+        DAS_CHECK(!input || m.bc[p].T_code == DAS_BC_MIXED, DAS_ERR_ARG, what + ": patch id " + std::to_string(p) + " does not carry a mixed T patch field");
+        for (int q = 0; q < m.patch_size[p]; q++) fn.faces.push_back(m.patch_start[p] + q);
+        tc.patches.push_back(p);
+    }
+    const size_t nf = fn.faces.size();
+    DAS_CHECK(nf > 0, DAS_ERR_ARG, "the patches of " + what + " have no faces");
+    fn.kind = DAS_FN_THERMALCOUPLING | ((flags & 2) ? DAS_FN_ALT_BIT : 0);
+    fn.group.assign(nf, 0);
+    fn.w0.assign(nf, 1.0);
+    fn.dir.assign(3 * nf, 0.0);
+    (input ? s->thermalInputs : s->thermalCouplings)[name] = std::move(tc);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_define_thermal_coupling(das_solver_t* s, const char* name, const int* patch_ids, int npatch, int flags) {
+    return define_thermal_coupling(s, name, patch_ids, npatch, flags, false);
+}
+int das_define_thermal_coupling_input(das_solver_t* s, const char* name, const int* patch_ids, int npatch, int flags) {
+    return define_thermal_coupling(s, name, patch_ids, npatch, flags, true);
+}
+static das_solver::ThermalCoupling& get_thermal_coupling(das_solver* s, const char* name, bool device = true, bool input = false) {
+    auto& table = input ? s->thermalInputs : s->thermalCouplings;
+    auto it = table.find(name ? name : "");
+    DAS_CHECK(it != table.end(), DAS_ERR_ARG, std::string(input ? "thermalCoupling input not defined: " : "thermalCouplingOutput not defined: ") + (name ? name : "(null)"));
+    need_thermal_coupling_solver(s);
+    das_solver::ThermalCoupling& tc = it->second;
+    if (device && !tc.uploaded) {
+        upload_coupling_functional(s, tc.fn);
+        tc.d_out.alloc(2 * tc.fn.faces.size());
+        tc.d_seeds.alloc(2 * tc.fn.faces.size());
+        tc.uploaded = true;
+    }
+    return tc;
+}
+// [T of the owner cells, kappa / d] of the faces of tc at the current states -> tc.d_out
+static void thermal_coupling_values(das_solver* s, das_solver::ThermalCoupling& tc) {
+    const int B = 256, nf = (int)tc.fn.faces.size();
+    const ResParams prm = s->wk.bind(s->cp.solver, s->dm.nC, s->dm.nF, make_params(s->cp, s->opt, 0));
+    // the gradient pass fills nut of the cells, which a symmetry-type nut patch reads
+    launch_grad_and_faces(s->stream, DAS_IS_COMPRESSIBLE(s->cp.solver), s->dm, prm, (const double*)s->d_W.p, s->wk, true, [&](auto R) {
+        hipLaunchKernelGGL((k_tc_values<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_W.p, s->wk.nut.p, nf,
+                           (const int*)tc.fn.d_faces.p, (int)DAS_FN_ALT(tc.fn.kind), tc.d_out.p);
+    });
+    DAS_HIP(hipGetLastError());
+}
+int das_calc_thermal_coupling(das_solver_t* s, const char* name, double* out, int n) {
+    DAS_TRY
+    need_init(s);
+    DAS_CHECK(out, DAS_ERR_ARG, "null output");
+    das_solver::ThermalCoupling& tc = get_thermal_coupling(s, name);
+    const int nf = (int)tc.fn.faces.size();
+    DAS_CHECK(n == 2 * nf, DAS_ERR_ARG,
+              "thermalCouplingOutput " + std::string(name) + " has " + std::to_string(2 * nf) + " entries (2 per face), not " + std::to_string(n));
+    thermal_coupling_values(s, tc);
+    DAS_HIP(hipMemcpyAsync(out, tc.d_out.p, 2 * (size_t)nf * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    return DAS_OK;
+    DAS_CATCH
+}
+// DAInputThermalCoupling::run: in[k] -> refValue, in[nF + k] = the neighbour's kappa / d -> valueFraction = nk / (myK + nk), myK this side's
+// kappa / d at the current states, geometry and boundary values (those from before this call, like the reference's alphaEff field)
+int das_set_thermal_coupling_input(das_solver_t* s, const char* name, const double* in, int n) {
+    DAS_TRY
+    need_init(s);
+    DAS_CHECK(in, DAS_ERR_ARG, "null input");
+    das_solver::ThermalCoupling& tc = get_thermal_coupling(s, name, true, true);
+    const int nf = (int)tc.fn.faces.size();
+    DAS_CHECK(n == 2 * nf, DAS_ERR_ARG,
+              "thermalCoupling input " + std::string(name) + " has " + std::to_string(2 * nf) + " entries (2 per face), not " + std::to_string(n));
+    for (int k = 0; k < nf; k++)
+        DAS_CHECK(in[nf + k] >= 0.0, DAS_ERR_ARG, "thermalCoupling input " + std::string(name) + ": a negative kappa / d of the neighbour (entry " + std::to_string(nf + k) + ")");
+    thermal_coupling_values(s, tc);
+    DAS_HIP(hipMemcpyAsync(tc.d_seeds.p, in, 2 * (size_t)nf * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    hipLaunchKernelGGL(k_tc_set_mixed, dim3(nblk(nf, 256)), dim3(256), 0, s->stream, nf, (const int*)tc.fn.d_faces.p, s->dm.nIF, (const double*)tc.d_seeds.p,
+                       (const double*)(tc.d_out.p + nf), s->d_mixed.p);
+    DAS_HIP(hipGetLastError());
+    DAS_HIP(hipMemcpyAsync(s->mesh.mixed.data(), s->d_mixed.p, s->mesh.mixed.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    tc.in.assign(in, in + n);
+    s->opEpoch++;
+    return DAS_OK;
+    DAS_CATCH
+}
+// refValue and valueFraction of the faces of a patch with a mixed T, as they stand (size: the faces of the patch)
+int das_get_patch_mixed(das_solver_t* s, int patch, double* refValue, double* valueFraction) {
+    DAS_TRY
+    DAS_CHECK(s && refValue && valueFraction, DAS_ERR_ARG, "null argument");
+    const Mesh& m = s->mesh;
+    DAS_CHECK(patch >= 0 && patch < m.nPatch, DAS_ERR_ARG, "patch id out of range");
+    DAS_CHECK(m.bc[patch].T_code == DAS_BC_MIXED, DAS_ERR_ARG, "patch id " + std::to_string(patch) + " does not carry a mixed T patch field");
+    for (int k = 0; k < m.patch_size[patch]; k++) {
+        const size_t bf = (size_t)(m.patch_start[patch] - m.nIF + k);
+        refValue[k] = m.mixed[4 * bf];
+        valueFraction[k] = m.mixed[4 * bf + 1];
+    }
+    return DAS_OK;
+    DAS_CATCH
+}
+
+// ---- both coupling outputs, as the derivative products and das_get_output_size see them ------------------------------------------
+static bool is_coupling(const std::string& outputType) { return outputType == "forceCouplingOutput" || outputType == "thermalCouplingOutput"; }
+// the number of entries; an unknown name or a solver the output does not run on is an error
+static int coupling_size(das_solver* s, const std::string& outputType, const char* name) {
+    if (is_force_coupling(outputType)) return 3 * get_force_coupling(s, name, false).nOut;
+    return 2 * (int)get_thermal_coupling(s, name, false).fn.faces.size();
+}
+// seeds (host, one per entry) -> the face functional seeds . output of the derivative passes, its per-face directions set on the device
+static das_solver::FaceFn& coupling_functional(das_solver* s, const std::string& outputType, const char* name, const double* seeds) {
+    if (is_force_coupling(outputType)) return force_coupling_functional(s, name, seeds);
+    das_solver::ThermalCoupling& tc = get_thermal_coupling(s, name);
+    const int nf = (int)tc.fn.faces.size();
+    DAS_HIP(hipMemcpyAsync(tc.d_seeds.p, seeds, 2 * (size_t)nf * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    hipLaunchKernelGGL(k_tc_seed_dir, dim3(nblk(nf, 256)), dim3(256), 0, s->stream, nf, (const double*)tc.d_seeds.p, tc.fn.d_dir.p);
+    DAS_HIP(hipGetLastError());
+    return tc.fn;
 }
 
 long long das_op_nnz(das_solver_t* s) { return (s && s->op) ? s->op->m.nnz : -1; }
@@ -4382,9 +4538,9 @@ int das_calc_dbc_product(das_solver_t* s, const int* patches, int np, const char
     check_patches(s, patches, np);
     const int fid = bc_field_id(field);
     const std::string ot = outputType;
-    const bool isFC = is_force_coupling(ot);
+    const bool isFC = is_coupling(ot);
     DAS_CHECK(ot == "residual" || ot == "function" || isFC, DAS_ERR_ARG, "outputType not supported on this path: " + ot);
-    if (isFC) (void)get_force_coupling(s, outputName);  // an unknown name fails before the patch table is touched
+    if (isFC) (void)coupling_size(s, ot, outputName);  // an unknown name fails before the patch table is touched
     std::vector<PatchBC> bc = s->mesh.bc;
     for (int i = 0; i < np; i++) {
         PatchBC& b = bc[patches[i]];
@@ -4421,8 +4577,8 @@ int das_calc_dbc_product(das_solver_t* s, const int* patches, int np, const char
         product[0] = 0.0;
         return DAS_OK;
     } else {
-        // forceCouplingOutput: the force functional seeds . output (its directions carry the seeds: the seed of the pass is 1)
-        das_solver::FaceFn& fn = isFC ? force_coupling_functional(s, outputName, seeds) : get_function(s, outputName);
+        // coupling outputs: the functional seeds . output (its directions carry the seeds: the seed of the pass is 1)
+        das_solver::FaceFn& fn = isFC ? coupling_functional(s, ot, outputName, seeds) : get_function(s, outputName);
         const double fnSeed = isFC ? 1.0 : seeds[0];
         function_effective_weights(s, fn);
         DAS_HIP(hipMemsetAsync(s->d_tmp1.p, 0, sizeof(double), st));  // function_sums used the scratch
@@ -4437,6 +4593,108 @@ int das_calc_dbc_product(das_solver_t* s, const int* patches, int np, const char
     DAS_HIP(hipGetLastError());
     DAS_HIP(hipMemcpyAsync(product, s->d_tmp1.p, sizeof(double), hipMemcpyDeviceToHost, st));
     DAS_HIP(hipStreamSynchronize(st));
+    return DAS_OK;
+    DAS_CATCH
+}
+
+// ---- thermalCoupling input -> residual | function | thermalCouplingOutput: product = [d output / d input]^T seeds (2 nF entries) ---------------
+// The input reaches the solver through refValue_f = in[k] and valueFraction_f = nk / (myK + nk), nk = in[nF + k]:
+//   product[k]      = seeds . d output / d refValue_f
+//   product[nF + k] = seeds . d output / d valueFraction_f  x  myK / (myK + nk)^2,   myK as it was when the input was set.
+// Forward-mode passes with the seed in the mixed records (bc_mixed carries it).  A function or a thermalCouplingOutput reads the record of a face
+// in the summand of that face only: one pass per kind of seed with all faces seeded, the per-face tangents are the derivatives.  The
+// residual: a face acts on the rows that read T of its owner cell, so faces whose owner cells' T states have the same
+// colour do not share a row and are seeded together; faces that share an owner cell (corner cells) are told apart by their rank in
+// the cell.  After each pass k_tc_gather adds psi_r dR_r over the rows of the owner's T column, face by face: no atomics.
+int das_calc_dthermal_coupling_product(das_solver_t* s, const char* inputName, const char* outputName, const char* outputType, const double* seeds,
+                                       double* product, int n) {
+    DAS_TRY
+    need_init(s);
+    DAS_CHECK(outputType && seeds && product, DAS_ERR_ARG, "null argument");
+    const std::string ot = outputType;
+    const bool isFC = ot == "thermalCouplingOutput";
+    DAS_CHECK(ot == "residual" || ot == "function" || isFC, DAS_ERR_ARG, "outputType not supported on this path: " + ot);
+    das_solver::ThermalCoupling& tc = get_thermal_coupling(s, inputName, true, true);
+    const int nf = (int)tc.fn.faces.size(), B = 256;
+    DAS_CHECK(n == 2 * nf, DAS_ERR_ARG, "thermalCoupling input " + std::string(inputName ? inputName : "") + " has " + std::to_string(2 * nf) + " entries, not " + std::to_string(n));
+    DAS_CHECK((int)tc.in.size() == 2 * nf, DAS_ERR_ARG, "thermalCoupling input " + std::string(inputName ? inputName : "") + " has not been set");
+    if (isFC) (void)coupling_size(s, ot, outputName);
+    std::fill(product, product + n, 0.0);
+    if (ot == "function") {  // cell-set functions and location read no boundary value of T
+        if (find_cell_function(s, outputName)) return DAS_OK;
+        if (DAS_FN_BASE(get_function(s, outputName).kind) == DAS_FN_LOCATION) return DAS_OK;
+    }
+    hipStream_t st = s->stream;
+    const long long ns = s->n;
+    const int* faces = (const int*)tc.fn.d_faces.p;
+    struct Restore {  // whatever happens, the records carry no tangent afterwards
+        das_solver* s;
+        ~Restore() { (void)hipStreamSynchronize(s->stream); s->d_mixed.upload(s->mesh.mixed); }
+    } restore{s};
+    ResParams prm = make_params(s->cp, s->opt, 0);
+    const bool rho = DAS_IS_COMPRESSIBLE(s->cp.solver);
+    if (s->d_Wd.n != (size_t)ns) { s->d_Wd.alloc(ns); s->d_Rd.alloc(ns); }
+    hipLaunchKernelGGL(k_lift, dim3(nblk(ns, B)), dim3(B), 0, st, ns, s->d_W.p, s->d_Wd.p);  // states carry no tangent
+    std::vector<double> dOut[2] = {std::vector<double>(nf, 0.0), std::vector<double>(nf, 0.0)};  // d / d refValue_f, d / d valueFraction_f
+    if (ot == "residual") {
+        ConDev& c = ensure_con_dev(s, 0);
+        const long long colOff = (long long)prm.offT * s->mesh.nC;
+        // groups: (colour of the owner's T state, rank of the face among the input's faces of that cell)
+        std::map<std::pair<int, int>, std::vector<int>> groups;
+        std::map<int, int> seen;
+        for (int k = 0; k < nf; k++) {
+            const int cell = s->mesh.owner[tc.fn.faces[k]];
+            groups[{s->colors[colOff + cell], seen[cell]++}].push_back(k);
+        }
+        DAS_HIP(hipMemcpyAsync(s->d_tmp2.p, seeds, ns * sizeof(double), hipMemcpyHostToDevice, st));
+        DevBuf<double> d_face((size_t)nf);
+        DevBuf<int> d_sel((size_t)nf);
+        for (int which = 2; which <= 3; which++) {
+            for (const auto& grp : groups) {
+                const int cnt = (int)grp.second.size();
+                DAS_HIP(hipMemcpyAsync(d_sel.p, grp.second.data(), cnt * sizeof(int), hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL(k_tc_seed_mixed, dim3(nblk(cnt, B)), dim3(B), 0, st, cnt, (const int*)d_sel.p, faces, s->dm.nIF, which, 1.0, s->d_mixed.p);
+                eval_residual<Dual<1>>(s->dm, s->cp, prm, s->d_Wd.p, s->d_Rd.p, s->wk1, s->d_phiF.p, s->d_Told.p, st);
+                hipLaunchKernelGGL(k_tc_gather, dim3(nblk(cnt, B)), dim3(B), 0, st, cnt, (const int*)d_sel.p, faces, (const int*)s->d_owner.p, colOff,
+                                   (const long long*)c.t_rowptr.p, (const int*)c.t_col.p, (const double*)s->d_tmp2.p, (const Dual<1>*)s->d_Rd.p, d_face.p);
+                hipLaunchKernelGGL(k_tc_seed_mixed, dim3(nblk(cnt, B)), dim3(B), 0, st, cnt, (const int*)d_sel.p, faces, s->dm.nIF, which, 0.0, s->d_mixed.p);
+                DAS_HIP(hipGetLastError());
+                DAS_HIP(hipStreamSynchronize(st));  // d_sel is written again by the next group
+            }
+            DAS_HIP(hipMemcpy(dOut[which - 2].data(), d_face.p, nf * sizeof(double), hipMemcpyDeviceToHost));
+        }
+    } else {
+        das_solver::FaceFn& fn = isFC ? coupling_functional(s, ot, outputName, seeds) : get_function(s, outputName);
+        const double fnSeed = isFC ? 1.0 : seeds[0];
+        function_effective_weights(s, fn);
+        prm = s->wk1.bind(s->cp.solver, s->dm.nC, s->dm.nF, prm);
+        const int nfn = (int)fn.faces.size();
+        if (fn.d_fv.n != (size_t)nfn) fn.d_fv.alloc(nfn);
+        std::map<int, int> slotOf;  // mesh face -> slot of the input
+        for (int k = 0; k < nf; k++) slotOf[tc.fn.faces[k]] = k;
+        std::vector<double> fv(nfn);
+        for (int which = 2; which <= 3; which++) {
+            hipLaunchKernelGGL(k_tc_seed_mixed, dim3(nblk(nf, B)), dim3(B), 0, st, nf, (const int*)nullptr, faces, s->dm.nIF, which, 1.0, s->d_mixed.p);
+            launch_grad_and_faces(st, rho, s->dm, prm, (const Dual<1>*)s->d_Wd.p, s->wk1, true, [&](auto R) {
+                hipLaunchKernelGGL((k_fn_tangent<decltype(R)::value>), dim3(nblk(nfn, B)), dim3(B), 0, st, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, fn.view(fn.d_weff.p), fnSeed, fn.d_fv.p);
+            });
+            hipLaunchKernelGGL(k_tc_seed_mixed, dim3(nblk(nf, B)), dim3(B), 0, st, nf, (const int*)nullptr, faces, s->dm.nIF, which, 0.0, s->d_mixed.p);
+            DAS_HIP(hipGetLastError());
+            DAS_HIP(hipMemcpyAsync(fv.data(), fn.d_fv.p, nfn * sizeof(double), hipMemcpyDeviceToHost, st));
+            DAS_HIP(hipStreamSynchronize(st));
+            for (int q = 0; q < nfn; q++) {  // in slot order of the function: a fixed order
+                auto it = slotOf.find(fn.faces[q]);
+                if (it != slotOf.end()) dOut[which - 2][it->second] += fv[q];
+            }
+        }
+    }
+    std::vector<double> myK(nf);
+    DAS_HIP(hipMemcpy(myK.data(), tc.d_out.p + nf, nf * sizeof(double), hipMemcpyDeviceToHost));
+    for (int k = 0; k < nf; k++) {
+        const double nk = tc.in[nf + k], sum = myK[k] + nk;
+        product[k] = dOut[0][k];
+        product[nf + k] = dOut[1][k] * (myK[k] / (sum * sum));
+    }
     return DAS_OK;
     DAS_CATCH
 }
@@ -4482,10 +4740,10 @@ int das_calc_dfield_product(das_solver_t* s, const char* fieldName, const char* 
     DAS_CHECK(outputType && seeds && product, DAS_ERR_ARG, "null argument");
     check_field(fieldName);
     const std::string ot = outputType;
-    DAS_CHECK(ot == "residual" || ot == "function" || is_force_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
+    DAS_CHECK(ot == "residual" || ot == "function" || is_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
     const long long N = s->mesh.nC, n = s->n;
-    if (is_force_coupling(ot)) {  // like the patch-integral functions: the forces do not see the production term
-        (void)get_force_coupling(s, outputName, false);
+    if (is_coupling(ot)) {  // like the patch-integral functions: the coupling outputs do not see the production term
+        (void)coupling_size(s, ot, outputName);
         std::fill(product, product + N, 0.0);
         return DAS_OK;
     }
@@ -4690,7 +4948,7 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
     dmD.nC = m.nC; dmD.nF = m.nF; dmD.nIF = m.nIF;
     dmD.fg = d_fgD.p; dmD.cg = d_cgD.p;
     dmD.cf_ptr = s->dm.cf_ptr; dmD.cf_face = s->dm.cf_face; dmD.cf_other = s->dm.cf_other;
-    dmD.owner = s->dm.owner; dmD.neigh = s->dm.neigh; dmD.bpatch = s->dm.bpatch; dmD.bc = s->dm.bc; dmD.cyc = s->dm.cyc;
+    dmD.owner = s->dm.owner; dmD.neigh = s->dm.neigh; dmD.bpatch = s->dm.bpatch; dmD.bc = s->dm.bc; dmD.cyc = s->dm.cyc; dmD.mixed = s->dm.mixed;
     ResParams prm0 = make_params(s->cp, s->opt, 0);
     RowLayout L{};
     int nf = 0;
@@ -4756,14 +5014,15 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
     need_init(s);
     DAS_CHECK(outputType && seeds && product, DAS_ERR_ARG, "null argument");
     const std::string ot = outputType;
-    DAS_CHECK(ot == "residual" || ot == "function" || is_force_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
+    DAS_CHECK(ot == "residual" || ot == "function" || is_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
     DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "the volCoord product runs on an undecomposed mesh (sharded solvers: use calcVolCoordDirectionalProduct)");
-    if (is_force_coupling(ot)) {
-        // the force functional seeds . output through the dual-point metrics: S_f carries the tangent, so the pRef S_f term is included
-        (void)get_force_coupling(s, outputName, false);
+    if (is_coupling(ot)) {
+        // the functional seeds . output through the dual-point metrics (forces: S_f carries the tangent, so the pRef S_f term is included;
+        // thermal coupling: the delta coefficient of either wallDistanceMethod and the wall distance of a wall function do)
+        (void)coupling_size(s, ot, outputName);
         DAS_CHECK(s->opt.gets_or("amd.volCoordMode", "dual") == "dual", DAS_ERR_ARG,
-                  "the volCoord product of a forceCouplingOutput needs amd.volCoordMode dual (fd is not implemented for it)");
-        das_solver::FaceFn& fn = force_coupling_functional(s, outputName, seeds);
+                  "the volCoord product of a " + ot + " needs amd.volCoordMode dual (fd is not implemented for it)");
+        das_solver::FaceFn& fn = coupling_functional(s, ot, outputName, seeds);
         const double one = 1.0, zero2[2] = {0.0, 0.0};
         ensure_point_influence(s);
         volcoord_product_dual(s, &fn, false, zero2, zero2, &one, product, info4);
@@ -4926,7 +5185,7 @@ int das_get_output_size(das_solver_t* s, const char* outputName, const char* out
     DAS_TRY
     DAS_CHECK(s && outputType, DAS_ERR_ARG, "null argument");
     if (std::string(outputType) == "function") return 1;
-    if (is_force_coupling(outputType)) return 3 * get_force_coupling(s, outputName, false).nOut;
+    if (is_coupling(outputType)) return coupling_size(s, outputType, outputName);
     DAS_CHECK(std::string(outputType) == "residual", DAS_ERR_ARG, std::string("outputType not supported on this path: ") + outputType);
     return (int)s->n;
     DAS_CATCH
@@ -4944,16 +5203,17 @@ int das_calc_jac_t_vec_product(das_solver_t* s, const char* inputName, const cha
         function_gradient(s, outputName, seeds[0], product);
         return DAS_OK;
     }
-    if (is_force_coupling(outputType)) {
-        // d(seeds . output)/dW, state-scaled like the function branch: the coloured passes on the force functional
-        (void)get_force_coupling(s, outputName, false);
+    if (is_coupling(outputType)) {
+        // d(seeds . output)/dW, state-scaled like the function branch: the coloured passes on the functional seeds . output
+        const std::string ot = outputType;
+        (void)coupling_size(s, ot, outputName);
         s->h_W.assign(inputs, inputs + s->n);
         s->d_W.upload(s->h_W);
-        face_function_gradient(s, force_coupling_functional(s, outputName, seeds), 1.0, product);
+        face_function_gradient(s, coupling_functional(s, ot, outputName, seeds), 1.0, product);
         return DAS_OK;
     }
     DAS_CHECK(std::string(outputType) == "residual", DAS_ERR_ARG,
-              "calcJacTVecProduct: only (stateVar -> residual | function | forceCouplingOutput) is implemented on the GPU path");
+              "calcJacTVecProduct: only (stateVar -> residual | function | forceCouplingOutput | thermalCouplingOutput) is implemented on the GPU path");
     // DAInputStateVar::run assigns the inputs to the states (reference DASolver.C:1690-1839)
     // the operator initializedRdWTMatrixFree built is reused when it was assembled at these very states (the reference
     // replays its tape; re-assembling all colours for one product would cost ~nColors residual passes)

@@ -40,8 +40,15 @@ struct DevMeshT {  // G: the scalar of the metrics (double; Dual<1> in the mesh-
     const int* bpatch;  // boundary face -> patch
     const PatchBC* bc;
     const int* cyc;     // boundary face -> paired face of a cyclic pair, -1 otherwise
+    // patches with a mixed T (DAS_BC_MIXED): per boundary face refValue, valueFraction and their tangents; null when no patch is mixed
+    const double* mixed = nullptr;
 };
 typedef DevMeshT<double> DevMesh;
+// the mixed-T record of boundary face f (a mesh face index); it is read only where the patch's T_code says mixed
+template <class G>
+DAS_HD const double* mixed_of(const DevMeshT<G>& m, int f) {
+    return m.mixed ? m.mixed + 4LL * (f - m.nIF) : nullptr;
+}
 
 struct ResParams {
     double nu, alphaU, alphaN, DT, deltaT;
@@ -162,6 +169,28 @@ DAS_HD void bc_scalar(int code, double value, double dvalue, const G& delta, dou
     o.gbc = (f * delta) * val;
     o.xb = o.vic * xc + o.vbc;
 }
+// mixedFvPatchField with refGrad = 0 and a fraction f and refValue of the face's own, mx = {refValue, f, d refValue, d f}:
+//   x_b = f ref + (1 - f) x_c,  snGrad = f delta (ref - x_c):  vic = 1 - f, vbc = f ref, gic = -f delta, gbc = f delta ref
+// - bc_scalar with a per-face f and value; fixedValue at f = 1, zeroGradient at f = 0, bit for bit.  vic and gic are metrics-typed and
+// carry no tangent, so the tangent of f (the products of the thermalCoupling input) rides on vbc and gbc: d x_b = (ref - x_c) df + f dref.
+// Every user multiplies vic and gic with the owner-cell value x_c, so the sums vic x_c + vbc and gic x_c + gbc have the right tangent.
+// scale, shift: the energy variable is scale (T - shift) (he = Cp (T - Tref); T itself: 1, 0)
+template <class T, class G>
+DAS_HD void bc_mixed(const double* mx, double scale, double shift, const G& delta, const T& xc, ScalarBC<T, G>& o) {
+    const double f = mx[1];
+    const double ref = scale * (mx[0] - shift);
+    const T rv = MkSeed<T>::make(ref, scale * mx[2]);
+    o.vic = 1.0 - f;
+    o.vbc = f * rv;
+    o.gic = -f * delta;
+    o.gbc = (f * delta) * rv;
+    if (mx[3] != 0.0) {
+        const double dx = (ref - val(xc)) * mx[3];
+        o.vbc = MkSeed<T>::make(o.vbc, dx);
+        o.gbc = o.gbc + delta * MkSeed<T>::make(0.0, dx);
+    }
+    o.xb = o.vic * xc + o.vbc;
+}
 template <class T, class G = double>
 struct VectorBC {
     T xb[3];
@@ -235,7 +264,7 @@ struct BFace {
 // evaluate all patch fields of one boundary face from the owner cell's values
 template <class T, bool RHO, class G>
 DAS_HD void eval_bface(const PatchBC& bc, const FaceGeomT<G>& g, const CellGeomT<G>& cgc, const ResParams& prm, const T* Uc, const T& pc,
-                       const T& Tc, const T& nc, const T& nut_c, double phib, BFace<T, G>& o) {
+                       const T& Tc, const T& nc, const T& nut_c, double phib, BFace<T, G>& o, const double* mx = nullptr) {
 #pragma unroll
     for (int k = 0; k < 3; k++) o.nrm[k] = g.Sf[k] / g.magSf;
     if (prm.mrf && bc.mrf_included && bc.U_code == DAS_BC_FIXED_VALUE) {
@@ -250,9 +279,14 @@ DAS_HD void eval_bface(const PatchBC& bc, const FaceGeomT<G>& g, const CellGeomT
     bc_scalar<T>(bc.p_code, bc.p_val, bc.dp_val, g.nod, phib, pc, o.p);
     bc_scalar<T>(bc.nuTilda_code, bc.nuTilda_val, bc.dnuTilda_val, g.nod, phib, nc, o.n);
     if (RHO) {
-        bc_scalar<T>(bc.T_code, bc.T_val, bc.dT_val, g.nod, phib, Tc, o.Tt);
         T hec = prm.Cp * (Tc - DAS_TREF);
-        bc_scalar<T>(bc.T_code, prm.Cp * (bc.T_val - DAS_TREF), prm.Cp * bc.dT_val, g.nod, phib, hec, o.he);
+        if (bc.T_code == DAS_BC_MIXED) {
+            bc_mixed<T>(mx, 1.0, 0.0, g.nod, Tc, o.Tt);
+            bc_mixed<T>(mx, prm.Cp, DAS_TREF, g.nod, hec, o.he);
+        } else {
+            bc_scalar<T>(bc.T_code, bc.T_val, bc.dT_val, g.nod, phib, Tc, o.Tt);
+            bc_scalar<T>(bc.T_code, prm.Cp * (bc.T_val - DAS_TREF), prm.Cp * bc.dT_val, g.nod, phib, hec, o.he);
+        }
         o.rho_b = o.p.xb / (prm.Rgas * o.Tt.xb);
         o.mu_b = mu_of<T>(prm, o.Tt.xb);
         o.nu_b = o.mu_b / o.rho_b;
@@ -260,7 +294,8 @@ DAS_HD void eval_bface(const PatchBC& bc, const FaceGeomT<G>& g, const CellGeomT
         o.rho_b = T(1.0);
         o.nu_b = T(prm.nu);
         if (prm.hasT) {  // passive T of DASimpleFoam: "he" is T itself
-            bc_scalar<T>(bc.T_code, bc.T_val, bc.dT_val, g.nod, phib, Tc, o.Tt);
+            if (bc.T_code == DAS_BC_MIXED) bc_mixed<T>(mx, 1.0, 0.0, g.nod, Tc, o.Tt);
+            else bc_scalar<T>(bc.T_code, bc.T_val, bc.dT_val, g.nod, phib, Tc, o.Tt);
             o.he = o.Tt;
         }
     }
@@ -339,7 +374,7 @@ DAS_HD void grad_face(int c, int s, const DevMeshT<G>& m, const ResParams& prm, 
         else if (energy) hf = wc * Tc + (1.0 - wc) * W[prm.offT * N + o];
     } else {
         BFace<T, G> b;
-        eval_bface<T, RHO>(m.bc[m.bpatch[f - m.nIF]], g, cgc, prm, Uc, pc, Tc, nc, nut_c, val(W[prm.offPhi * N + f]), b);
+        eval_bface<T, RHO>(m.bc[m.bpatch[f - m.nIF]], g, cgc, prm, Uc, pc, Tc, nc, nut_c, val(W[prm.offPhi * N + f]), b, mixed_of(m, f));
 #pragma unroll
         for (int k = 0; k < 3; k++) Uf[k] = b.U.xb[k];
         pf = b.p.xb;
@@ -585,7 +620,7 @@ DAS_HD void body_cell(int c, const DevMeshT<G>& m, const ResParams& prm, const T
         } else {
             BFace<T, G> b;
             double pv = val(phi);
-            eval_bface<T, RHO>(m.bc[m.bpatch[f - m.nIF]], g, cgc, prm, Uc, pc, Tc, nc, nut_c, pv, b);
+            eval_bface<T, RHO>(m.bc[m.bpatch[f - m.nIF]], g, cgc, prm, Uc, pc, Tc, nc, nut_c, pv, b, mixed_of(m, f));
             sumPhi += phi;
             T muEff_b = b.rho_b * (b.nu_b + b.nut_b);
             T gam_b = muEff_b * g.magSf;
@@ -800,7 +835,7 @@ DAS_HD void body_bcoef(int b, const DevMeshT<double>& m, const ResParams& prm, c
 #pragma unroll
     for (int k = 0; k < 9; k++) gUc[k] = gradU[9LL * c + k];
     BFace<T, double> bf;
-    eval_bface<T, false>(m.bc[m.bpatch[b]], g, cgc, prm, Uc, pc, T(0.0), nc, nut_c, val(phi), bf);
+    eval_bface<T, false>(m.bc[m.bpatch[b]], g, cgc, prm, Uc, pc, T(0.0), nc, nut_c, val(phi), bf, mixed_of(m, f));
     T* r = brec + (long long)DAS_BREC_N * b;
     const T muEff_b = bf.rho_b * (bf.nu_b + bf.nut_b);
     const T gam_b = muEff_b * g.magSf;
@@ -976,7 +1011,7 @@ DAS_HD void body_face(int f, const DevMeshT<G>& m, const ResParams& prm, const T
             T Uc[3] = {W[3LL * c], W[3LL * c + 1], W[3LL * c + 2]};
             T pc = W[prm.offP * N + c], nc = W[prm.offN * N + c], Tc = W[prm.offT * N + c];
             BFace<T, G> b;
-            eval_bface<T, RHO>(bc, g, m.cg[c], prm, Uc, pc, Tc, nc, nut[c], val(W[prm.offPhi * N + f]), b);
+            eval_bface<T, RHO>(bc, g, m.cg[c], prm, Uc, pc, Tc, nc, nut[c], val(W[prm.offPhi * N + f]), b, mixed_of(m, f));
             T Hb[3] = {HbyA[3LL * c], HbyA[3LL * c + 1], HbyA[3LL * c + 2]};
             if (bc.U_code == DAS_BC_SYMMETRY) {
                 T hn = b.nrm[0] * Hb[0] + b.nrm[1] * Hb[1] + b.nrm[2] * Hb[2];
@@ -1035,7 +1070,7 @@ DAS_HD void body_face(int f, const DevMeshT<G>& m, const ResParams& prm, const T
         T pc = W[prm.offP * N + c], nc = W[prm.offN * N + c];
         T Tc = RHO ? W[prm.offT * N + c] : T(0.0);
         BFace<T, G> b;
-        eval_bface<T, RHO>(bc, g, m.cg[c], prm, Uc, pc, Tc, nc, nut[c], val(W[prm.offPhi * N + f]), b);
+        eval_bface<T, RHO>(bc, g, m.cg[c], prm, Uc, pc, Tc, nc, nut[c], val(W[prm.offPhi * N + f]), b, mixed_of(m, f));
         T Hb[3] = {HbyA[3LL * c], HbyA[3LL * c + 1], HbyA[3LL * c + 2]};
         if (bc.U_code == DAS_BC_SYMMETRY) {
             T hn = b.nrm[0] * Hb[0] + b.nrm[1] * Hb[1] + b.nrm[2] * Hb[2];
@@ -1093,7 +1128,7 @@ DAS_HD void force_terms(int f, const DevMeshT<G>& m, const ResParams& prm, const
     T pc = W[prm.offP * N + c], nc = W[prm.offN * N + c];
     T Tc = RHO ? W[prm.offT * N + c] : T(0.0);
     BFace<T, G> b;
-    eval_bface<T, RHO>(m.bc[m.bpatch[f - m.nIF]], g, m.cg[c], prm, Uc, pc, Tc, nc, nut[c], val(W[prm.offPhi * N + f]), b);
+    eval_bface<T, RHO>(m.bc[m.bpatch[f - m.nIF]], g, m.cg[c], prm, Uc, pc, Tc, nc, nut[c], val(W[prm.offPhi * N + f]), b, mixed_of(m, f));
     T dsn[3];
 #pragma unroll
     for (int j = 0; j < 3; j++) {
@@ -1169,8 +1204,11 @@ DAS_HD void body_force_vec(int f, const DevMeshT<G>& m, const ResParams& prm, co
 #define DAS_FN_TOTALPRESSURERATIO 6
 #define DAS_FN_WALLHEATFLUX 7
 #define DAS_FN_LOCATION 8
+//   kind 9  thermalCoupling  d_f[0] T_c + d_f[1] Cp alphaEff_b deltaCoeff: the functional seeds . output of a thermalCouplingOutput, d_f the
+//                            seeds of the two entries of the face (body_thermal_coupling; DAS_FN_ALT_BIT set: the daCustom deltaCoeff)
+#define DAS_FN_THERMALCOUPLING 9
 #define DAS_FN_BASE(kind) ((kind) & 15)
-// the kind word above its base: bit 4 selects the other form of kinds 7 and 8; kinds 4 and 5 keep their variable and component mask there
+// the kind word above its base: bit 4 selects the other form of kinds 7, 8 and 9; kinds 4 and 5 keep their variable and component mask there
 #define DAS_FN_ALT_BIT 16
 #define DAS_FN_ALT(kind) (((kind) >> 4) & 1)
 #define DAS_FN_VAR(kind) (((kind) >> 4) & 15)
@@ -1188,10 +1226,38 @@ DAS_HD G location_radius(const FaceGeomT<G>& g, const double* loc, bool inverse)
     const G r = dsqrt(r2);
     return inverse ? G(1.0 / (r + 1e-12)) : r;
 }
+// thermalCouplingOutput (reference DAOutputThermalCoupling.C:79-211, discipline aero) for one boundary face: the temperature of the
+// owner cell and kappa / d = Cp alphaEff_b deltaCoeff, with alphaEff_b the boundary alphaEff of the energy rows and of wallHeatFlux
+// (alpha_eff: nut_b / Prt of a wall function included) and deltaCoeff the face's delta coefficient (wallDistanceMethod default) or
+// custom: 1 / |C_f - C_c| (daCustom).  Cp for DASimpleFoam (:117, transportProperties) and for the compressible solvers (:181): they
+// solve for the enthalpy here, so the reference's internal-energy branch (Cp - R, :174-177) does not occur and is not built.
+template <class T, bool RHO, class G>
+DAS_HD void body_thermal_coupling(int f, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* nut, bool custom, T& Tnear, T& kd) {
+    const long long N = m.nC;
+    const FaceGeomT<G>& g = m.fg[f];
+    const int c = m.owner[f];
+    T Uc[3] = {W[3LL * c], W[3LL * c + 1], W[3LL * c + 2]};
+    T pc = W[prm.offP * N + c], nc = W[prm.offN * N + c];
+    T Tc = W[prm.offT * N + c];  // a solver with a T field (the caller checks)
+    BFace<T, G> b;
+    eval_bface<T, RHO>(m.bc[m.bpatch[f - m.nIF]], g, m.cg[c], prm, Uc, pc, Tc, nc, nut[c], val(W[prm.offPhi * N + f]), b, mixed_of(m, f));
+    G delta = g.nod;
+    if (custom) {
+        const G d0 = g.Cf[0] - m.cg[c].C[0], d1 = g.Cf[1] - m.cg[c].C[1], d2 = g.Cf[2] - m.cg[c].C[2];
+        delta = 1.0 / dsqrt(d0 * d0 + d1 * d1 + d2 * d2);
+    }
+    Tnear = Tc;
+    kd = (prm.Cp * alpha_eff<T, RHO>(prm, b.mu_b, b.rho_b, b.nut_b)) * delta;
+}
 template <class T, bool RHO, class G, class DV>
 DAS_HD T body_facefn(int f, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* nut, const T* gradU, int kind, const DV* dir,
                      double gammaFn, double RFn, const double* loc = nullptr, double pRef = 0.0) {
     if (kind == DAS_FN_FORCE) return body_force<T, RHO>(f, m, prm, W, nut, gradU, dir, 1.0, pRef);
+    if (DAS_FN_BASE(kind) == DAS_FN_THERMALCOUPLING) {
+        T Tnear, kd;
+        body_thermal_coupling<T, RHO>(f, m, prm, W, nut, DAS_FN_ALT(kind), Tnear, kd);
+        return dir[0] * Tnear + dir[1] * kd;
+    }
     if (DAS_FN_BASE(kind) == DAS_FN_LOCATION) return T(location_radius<G>(m.fg[f], loc, DAS_FN_ALT(kind)));
     const long long N = m.nC;
     const FaceGeomT<G>& g = m.fg[f];
@@ -1200,7 +1266,7 @@ DAS_HD T body_facefn(int f, const DevMeshT<G>& m, const ResParams& prm, const T*
     T pc = W[prm.offP * N + c], nc = W[prm.offN * N + c];
     T Tc = (RHO || prm.hasT) ? W[prm.offT * N + c] : T(0.0);
     BFace<T, G> b;
-    eval_bface<T, RHO>(m.bc[m.bpatch[f - m.nIF]], g, m.cg[c], prm, Uc, pc, Tc, nc, nut[c], val(W[prm.offPhi * N + f]), b);
+    eval_bface<T, RHO>(m.bc[m.bpatch[f - m.nIF]], g, m.cg[c], prm, Uc, pc, Tc, nc, nut[c], val(W[prm.offPhi * N + f]), b, mixed_of(m, f));
     T U2 = b.U.xb[0] * b.U.xb[0] + b.U.xb[1] * b.U.xb[1] + b.U.xb[2] * b.U.xb[2];
     if (kind == DAS_FN_MASSFLOW) return b.rho_b * (b.U.xb[0] * g.Sf[0] + b.U.xb[1] * g.Sf[1] + b.U.xb[2] * g.Sf[2]);
     if (kind == DAS_FN_TOTALPRESSURE) return b.p.xb + 0.5 * b.rho_b * U2;

@@ -230,6 +230,25 @@ void Mesh::build(const das_case_t* c) {
         }
     }
     DAS_CHECK(expect == nF, DAS_ERR_ARG, "patches do not cover all boundary faces");
+    // mixed patch fields: T only, flow solvers only; refValue and valueFraction face by face
+    mixed.clear();
+    for (int p = 0; p < nPatch; p++) {
+        const PatchBC& b = bc[p];
+        DAS_CHECK(b.U_code != DAS_BC_MIXED && b.p_code != DAS_BC_MIXED && b.nuTilda_code != DAS_BC_MIXED, DAS_ERR_ARG,
+                  "patch " + std::to_string(p) + ": the mixed patch field is built for T only, not for " +
+                      (b.U_code == DAS_BC_MIXED ? "U" : b.p_code == DAS_BC_MIXED ? "p" : "nuTilda"));
+        if (b.T_code != DAS_BC_MIXED) continue;
+        DAS_CHECK(c->solver != DAS_SOLVER_SCALARTRANSPORTFOAM, DAS_ERR_ARG, "the mixed T patch field is built for the flow solvers, not for DAScalarTransportFoam");
+        DAS_CHECK(patch_type[p] != DAS_PATCH_CYCLIC, DAS_ERR_ARG, "a cyclic patch cannot carry a mixed T");
+        if (mixed.empty()) mixed.assign(4 * (size_t)(nF - nIF), 0.0);
+        for (int k = 0; k < patch_size[p]; k++) {
+            const size_t bf = (size_t)(patch_start[p] - nIF + k);
+            mixed[4 * bf] = c->bc_T_mixed_ref ? c->bc_T_mixed_ref[bf] : 0.0;
+            mixed[4 * bf + 1] = c->bc_T_mixed_frac ? c->bc_T_mixed_frac[bf] : 0.0;
+            DAS_CHECK(mixed[4 * bf + 1] >= 0.0 && mixed[4 * bf + 1] <= 1.0, DAS_ERR_ARG,
+                      "patch " + std::to_string(p) + ": valueFraction of the mixed T outside [0, 1]");
+        }
+    }
     // cyclic pairs (cyclicPolyPatch: neighbPatch, same size, face k <-> face k)
     cyc_face.assign(nF - nIF, -1);
     for (int p = 0; p < nPatch; p++) {

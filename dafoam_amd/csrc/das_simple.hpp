@@ -116,7 +116,7 @@ DAS_HD void body_simple_pface(int f, const DevMeshT<double>& m, const ResParams&
         const PatchBC& bc = m.bc[m.bpatch[b]];
         const double Uc[3] = {Wn[3LL * c], Wn[3LL * c + 1], Wn[3LL * c + 2]};
         BFace<double, double> bf;
-        eval_bface<double, false>(bc, g, m.cg[c], prm, Uc, Wn[prm.offP * N + c], 0.0, Wn[prm.offN * N + c], nut[c], Wn[prm.offPhi * N + f], bf);
+        eval_bface<double, false>(bc, g, m.cg[c], prm, Uc, Wn[prm.offP * N + c], 0.0, Wn[prm.offN * N + c], nut[c], Wn[prm.offPhi * N + f], bf, mixed_of(m, f));
         double Hb[3] = {HbyA[3LL * c], HbyA[3LL * c + 1], HbyA[3LL * c + 2]};
         if (bc.U_code == DAS_BC_SYMMETRY) {
             const double hn = bf.nrm[0] * Hb[0] + bf.nrm[1] * Hb[1] + bf.nrm[2] * Hb[2];

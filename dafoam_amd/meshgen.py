@@ -28,6 +28,7 @@ BC_ZERO_GRADIENT = 1
 BC_INLET_OUTLET = 2
 BC_SYMMETRY = 3
 BC_CYCLIC = 4  # coupled (cyclic) patch: no patch-field coefficients, the paired cell acts as a neighbour
+BC_MIXED = 5  # T only: mixedFvPatchField with refGrad = 0 and a refValue / valueFraction per face (FoamCase.mixed_T)
 # nut wall treatment codes
 NUT_CALCULATED = 0
 NUT_LOWRE_WALL = 1  # nut_w = 0 (nutLowReWallFunction, reference DAField.C:1155-1218)
@@ -105,6 +106,8 @@ class FoamCase:
     # reference data of the variance functions, 0/<var>Data: {"pData": {"internal": (N,) | (N, 3), "boundary": (nBF,) | (nBF, 3)}}
     # (boundary = the boundary faces in face order; read by foam_io.read_case when the files exist)
     ref_data: Dict[str, dict] = field(default_factory=dict)
+    # the patches whose T is (BC_MIXED, 0.0): {patch: (refValue (size,), valueFraction (size,))}, one entry per face of the patch
+    mixed_T: Dict[str, tuple] = field(default_factory=dict)
 
 
 def hex_block(
@@ -1087,6 +1090,21 @@ def simple_T_channel_case(nx=7, ny=7, nz=7, T0=300.0, **kw) -> FoamCase:
     case.has_T = True
     case.relax = dict(case.relax, T=1.0)
     return case
+
+
+def with_mixed_T(case: FoamCase, patch: str, ref_value, value_fraction) -> FoamCase:
+    """A copy of the case whose T patch field on `patch` is mixed (refGrad = 0) with the given refValue and valueFraction - scalars or one
+    entry per face of the patch.  What a conjugate heat transfer loop starts from; the thermalCoupling input overwrites both."""
+    import copy
+
+    size = {p.name: p.size for p in case.mesh.patches}[patch]
+    c = copy.copy(case)
+    c.bcs = copy.deepcopy(case.bcs)
+    c.bcs[patch]["T"] = (BC_MIXED, 0.0)
+    c.mixed_T = dict(case.mixed_T)
+    c.mixed_T[patch] = (np.broadcast_to(np.asarray(ref_value, dtype=np.float64), (size,)).copy(),
+                        np.broadcast_to(np.asarray(value_fraction, dtype=np.float64), (size,)).copy())
+    return c
 
 
 def turbo_channel_case(nx=7, ny=7, nz=7, omega=(60.0, 0.0, 0.0), origin=(0.0, -0.3, 0.0), transonic=False, mrf=True,

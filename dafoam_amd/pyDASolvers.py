@@ -324,8 +324,10 @@ class pyDASolvers:
         self._patchVelocity = [0.0, 0.0]  # DAGlobalVar::patchVelocity = [UMag, AoA(deg)], set by DAInputPatchVelocity::run
         self._flowdir_fns = {}
         self._wallDistanceMethod = pyOptions.get("wallDistanceMethod", "default") if isinstance(pyOptions, dict) else "default"
+        self._discipline = pyOptions.get("discipline", "aero") if isinstance(pyOptions, dict) else "aero"
         self._define_functions(pyOptions.get("function") if isinstance(pyOptions, dict) else None)
         self._define_outputs(pyOptions.get("outputInfo") if isinstance(pyOptions, dict) else None)
+        self._define_thermal_inputs()
         if case.states is not None:  # FoamCase.states is always in "state" ordering (input data)
             check(lib().das_update_of_fields(self._h, dptr(np.ascontiguousarray(case.states, dtype=np.float64))))
 
@@ -431,6 +433,9 @@ class pyDASolvers:
         if inputType == "field":  # reference DAInputField.H size(): the selected cells (here: all) x 1 for a scalar field
             self._field_entry(inputName)
             return self._case.mesh.n_cells
+        if inputType == "thermalCoupling":  # reference DAInputThermalCoupling.C:52-63: two entries per face of the patches
+            sizes = {p.name: p.size for p in self._case.mesh.patches}
+            return 2 * sum(sizes[p] for p in self._input_entry(inputName, inputType)["patches"])
         if inputType == "volCoord":  # reference DAInputVolCoord.H size() = nLocalPoints * 3
             return self.getNLocalPoints() * 3
         return check(lib().das_get_input_size(self._h, inputName.encode(), inputType.encode()))
@@ -499,6 +504,10 @@ class pyDASolvers:
             # DAInputField::run (reference DAInputField.C:88-151): the input array IS the volScalarField (all cells; scalar fields)
             e = self._field_entry(inputName)
             return check(lib().das_set_field(self._h, e["fieldName"].encode(), dptr(np.ascontiguousarray(inputs, dtype=np.float64))))
+        if inputType == "thermalCoupling":
+            # DAInputThermalCoupling::run: refValue and, from the neighbour's kappa / d, the valueFraction of the mixed T patches
+            self._input_entry(inputName, inputType)
+            return check(lib().das_set_thermal_coupling_input(self._h, inputName.encode(), dptr(np.ascontiguousarray(inputs, dtype=np.float64)), inputSize))
         if inputType not in ("patchVelocity", "patchVar"):
             raise _capi.DASError(f"inputType not supported on this path: {inputType}")
         field, val, _ = self._patch_input_tangents(inputName, inputType, inputs)
@@ -709,6 +718,14 @@ class pyDASolvers:
             check(lib().das_calc_dvolcoord_product(self._h, outputName.encode(), outputType.encode(),
                                                    dptr(np.ascontiguousarray(seeds_s, dtype=np.float64)), dptr(product), dptr(info)))
             self._volCoordInfo = dict(colors=int(info[0]), passes=int(info[1]), seconds=float(info[2]), build_seconds=float(info[3]))
+            return
+        if inputType == "thermalCoupling":
+            # run(input), then forward-mode passes with the seeds in the mixed records and a per-face gather
+            self.setSolverInput(inputName, inputType, inputSize, inputs)
+            out = np.zeros(inputSize)
+            check(lib().das_calc_dthermal_coupling_product(self._h, inputName.encode(), outputName.encode(), outputType.encode(),
+                                                           dptr(np.ascontiguousarray(seeds_s, dtype=np.float64)), dptr(out), inputSize))
+            product[:] = out
             return
         if inputType == "field":
             # run(input), then ONE forward-mode pass with a unit tangent on every cell (das_calc_dfield_product)
@@ -944,24 +961,79 @@ class pyDASolvers:
 
     def _define_outputs(self, outputInfo):
         """"outputInfo" option dict (reference pyDAFoam.py DAOPTION.outputInfo): the entries of type forceCouplingOutput
-        ({"type", "patches", "components": ["forceCoupling"], "pRef"}, DAOutputForceCoupling.C:38-41) are defined on the device.  The
-        reference sorts the patches by name before anything else and reads pRef unconditionally; so does this."""
-        names = [p.name for p in self._case.mesh.patches]
+        ({"type", "patches", "components": ["forceCoupling"], "pRef"}, DAOutputForceCoupling.C:38-41) and thermalCouplingOutput
+        ({"type", "patches", "components": ["thermalCoupling"]}, DAOutputThermalCoupling.C:38-53) are defined on the device.  The
+        reference sorts the patches by name before anything else and reads pRef unconditionally; so does this.  The thermal output
+        reads the options `discipline` and `wallDistanceMethod`; discipline thermal is the solid solver DAHeatTransferFoam, which is
+        not built."""
         for oname, od in (outputInfo or {}).items():
             otype = od.get("type")
-            if otype != "forceCouplingOutput":
-                raise NotImplementedError(f"outputInfo[{oname}]: output type {otype} is not built (forceCouplingOutput is; thermalCouplingOutput "
-                                          "and its thermalCoupling input are not)")
-            if "pRef" not in od:
-                raise _capi.DASError(f"outputInfo[{oname}]: forceCouplingOutput needs pRef")
-            patches = sorted(od.get("patches") or [])
-            if not patches:
-                raise _capi.DASError(f"outputInfo[{oname}]: forceCouplingOutput needs patches")
+            if otype not in ("forceCouplingOutput", "thermalCouplingOutput"):
+                raise NotImplementedError(f"outputInfo[{oname}]: output type {otype} is not built (forceCouplingOutput and "
+                                          "thermalCouplingOutput are)")
+            thermal = otype == "thermalCouplingOutput"
+            what = f"outputInfo[{oname}]"
+            if thermal:
+                flags = self._thermal_coupling_checks(what)
+            elif "pRef" not in od:
+                raise _capi.DASError(f"{what}: forceCouplingOutput needs pRef")
+            patches, ids = self._sorted_patch_ids(f"{what}: {otype}", od)
+            if thermal:
+                check(lib().das_define_thermal_coupling(self._h, oname.encode(), ids.ctypes.data_as(_capi.c_int_p), ids.size, flags))
+            else:
+                check(lib().das_define_force_coupling(self._h, oname.encode(), ids.ctypes.data_as(_capi.c_int_p), ids.size, float(od["pRef"])))
+
+    def _thermal_coupling_checks(self, what):
+        """What the reference's DAOutputThermalCoupling / DAInputThermalCoupling constructors read besides the patches: the options
+        `wallDistanceMethod` and `discipline`; and the solver must carry T.  Returns the flags of the C entries."""
+        sn = self._case.solver_name
+        if not (sn in ("DARhoSimpleFoam", "DATurboFoam") or (sn == "DASimpleFoam" and getattr(self._case, "has_T", False))):
+            raise NotImplementedError(f"{what}: the thermal coupling (thermalCouplingOutput and the thermalCoupling input) is not built for "
+                                      f"solvers without a T field ({sn} here; DASimpleFoam with T, DARhoSimpleFoam and DATurboFoam carry one)")
+        wdm = self._wallDistanceMethod
+        if wdm not in ("default", "daCustom"):
+            raise _capi.DASError(f"wallDistanceMethod: {wdm} not supported! Options are: default and daCustom.")
+        if self._discipline != "aero":
+            raise _capi.DASError(f"{what}: the thermal coupling is built for discipline aero only (discipline {self._discipline}: the "
+                                 "solid solver DAHeatTransferFoam is not)")
+        return 2 if wdm == "daCustom" else 0
+
+    def _sorted_patch_ids(self, what, entry):
+        names = [p.name for p in self._case.mesh.patches]
+        patches = sorted(entry.get("patches") or [])
+        if not patches:
+            raise _capi.DASError(f"{what} needs patches")
+        for p in patches:
+            if p not in names:
+                raise _capi.DASError(f"{what}: patch {p} is not in the mesh (patches: {', '.join(names)})")
+        return patches, np.array([names.index(p) for p in patches], dtype=np.int32)
+
+    def _define_thermal_inputs(self):
+        """The inputInfo entries of type thermalCoupling ({"type", "patches", "components"}, DAInputThermalCoupling.C:35-64): the patches are
+        sorted by name, and each must carry a mixed T (meshgen.BC_MIXED) - the reference's refCast<mixedFvPatchField> aborts otherwise."""
+        from .meshgen import BC_MIXED
+
+        for iname, e in self._inputInfo.items():
+            if not isinstance(e, dict) or e.get("type") != "thermalCoupling":
+                continue
+            what = f"inputInfo[{iname}]"
+            flags = self._thermal_coupling_checks(what)
+            patches, ids = self._sorted_patch_ids(what, e)
             for p in patches:
-                if p not in names:
-                    raise _capi.DASError(f"outputInfo[{oname}]: patch {p} is not in the mesh (patches: {', '.join(names)})")
-            ids = np.array([names.index(p) for p in patches], dtype=np.int32)
-            check(lib().das_define_force_coupling(self._h, oname.encode(), ids.ctypes.data_as(_capi.c_int_p), ids.size, float(od["pRef"])))
+                if self._case.bcs[p].get("T", (None,))[0] != BC_MIXED:
+                    raise _capi.DASError(f"{what}: patch {p} does not carry a mixed T patch field (the thermalCoupling input writes its "
+                                         "refValue and valueFraction)")
+            check(lib().das_define_thermal_coupling_input(self._h, iname.encode(), ids.ctypes.data_as(_capi.c_int_p), ids.size, flags))
+
+    def getPatchMixedT(self, patchName):
+        """(refValue, valueFraction) of the faces of a patch with a mixed T, as they stand on the solver."""
+        names = [p.name for p in self._case.mesh.patches]
+        if patchName not in names:
+            raise _capi.DASError(f"patch {patchName} is not in the mesh (patches: {', '.join(names)})")
+        n = self._case.mesh.patches[names.index(patchName)].size
+        ref, frac = np.zeros(n), np.zeros(n)
+        check(lib().das_get_patch_mixed(self._h, names.index(patchName), dptr(ref), dptr(frac)))
+        return ref, frac
 
     def calcFunction(self, functionName):
         v = C.c_double(0.0)
@@ -1090,7 +1162,8 @@ class pyDASolvers:
 
     def calcOutput(self, outputName, outputType, output):
         """pyDASolvers.pyx:204-206 -> DAOutput::run: the function value (1 entry), the residual vector (state ordering of the
-        caller: adjStateOrdering) or the nodal forces of a forceCouplingOutput at the current states."""
+        caller: adjStateOrdering), the nodal forces of a forceCouplingOutput or the [T, kappa / d] of a thermalCouplingOutput at the
+        current states."""
         assert len(output) == self.getOutputSize(outputName, outputType), "invalid array size!"
         if outputType == "function":
             output[0] = self.calcFunction(outputName)
@@ -1098,10 +1171,12 @@ class pyDASolvers:
             R = np.zeros(self.getNLocalAdjointStates())
             self.getResiduals(R)
             output[:] = R
-        elif outputType == "forceCouplingOutput":
-            # DAOutputForceCoupling::run: [fx0, fy0, fz0, fx1, ...] over the points of the (sorted) patches
+        elif outputType in ("forceCouplingOutput", "thermalCouplingOutput"):
+            # DAOutputForceCoupling::run: [fx0, fy0, fz0, fx1, ...] over the points of the (sorted) patches; DAOutputThermalCoupling::run:
+            # T of the owner cells, then kappa / d, over the faces of the (sorted) patches
             out = output if isinstance(output, np.ndarray) and output.dtype == np.float64 and output.flags["C_CONTIGUOUS"] else np.zeros(len(output))
-            check(lib().das_calc_force_coupling(self._h, outputName.encode(), dptr(out), len(out)))
+            calc = lib().das_calc_force_coupling if outputType == "forceCouplingOutput" else lib().das_calc_thermal_coupling
+            check(calc(self._h, outputName.encode(), dptr(out), len(out)))
             if out is not output:
                 output[:] = out
         else:
@@ -1116,6 +1191,9 @@ class pyDASolvers:
         field input says so itself, DAInputField.H:110-114), 0 for the global ones (patchVelocity, patchVar)."""
         if inputType in ("stateVar", "volCoord"):
             return 1
+        if inputType == "thermalCoupling":  # DAInputThermalCoupling.H
+            self._input_entry(inputName, inputType)
+            return 1
         if inputType == "field":
             return int(self._field_entry(inputName).get("distributed", 1))
         if inputType in ("patchVelocity", "patchVar"):
@@ -1123,10 +1201,10 @@ class pyDASolvers:
         raise _capi.DASError(f"inputType not supported on this path: {inputType}")
 
     def getOutputDistributed(self, outputName, outputType):
-        """DAOutputResidual.H:59 (1), DAOutputFunction.H:76 (0), DAOutputForceCoupling.H (1)."""
+        """DAOutputResidual.H:59 (1), DAOutputFunction.H:76 (0), DAOutputForceCoupling.H (1), DAOutputThermalCoupling.H (1)."""
         if outputType == "residual":
             return 1
-        if outputType == "forceCouplingOutput":
+        if outputType in ("forceCouplingOutput", "thermalCouplingOutput"):
             self.getOutputSize(outputName, outputType)  # an unknown name is an error here as well
             return 1
         if outputType == "function":

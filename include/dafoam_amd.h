@@ -51,6 +51,10 @@ extern "C" {
 #define DAS_BC_INLET_OUTLET 2
 #define DAS_BC_SYMMETRY 3
 #define DAS_BC_CYCLIC 4 /* placeholder code of coupled patches: no patch-field coefficients are evaluated */
+/* T only: OpenFOAM's mixedFvPatchField with refGrad = 0 and a refValue and a valueFraction f of its own on every face,
+ * x_b = f refValue + (1 - f) x_c, snGrad = f deltaCoeff (refValue - x_c) (bc_T_mixed_ref / bc_T_mixed_frac below); what the
+ * thermalCoupling input of a conjugate heat transfer loop writes (reference DAInputThermalCoupling.C) */
+#define DAS_BC_MIXED 5
 /* nut patch treatment (reference DAField.C:1155-1218, DAMisc/nutUSpaldingWallFunctionDF) */
 #define DAS_NUT_CALCULATED 0
 #define DAS_NUT_LOWRE_WALL 1
@@ -118,6 +122,10 @@ typedef struct das_case {
     /* betaFINuTilda (n_cells, may be NULL = 1): the field-inversion multiplier of the Spalart-Allmaras production term
      * (reference DASpalartAllmaras.C betaFINuTilda_), the volScalarField a `field` input assigns (DAInputField.C:88-110) */
     const double* beta_fi_nuTilda;
+    /* refValue and valueFraction of the patches whose bc_T_code is DAS_BC_MIXED: one entry per boundary face of the mesh (n_faces -
+     * n_internal_faces, boundary-face order; the entries of other patches are not read).  NULL with such a patch: refValue 0, fraction 0. */
+    const double* bc_T_mixed_ref;
+    const double* bc_T_mixed_frac;
 } das_case_t;
 
 const char* das_last_error(void);
@@ -369,6 +377,34 @@ int das_calc_function(das_solver_t* s, const char* name, double* value);
  * (amd.volCoordMode dual only).  DAScalarTransportFoam (no p) and sharded solvers (owned-cell mask) return DAS_ERR_ARG. */
 int das_define_force_coupling(das_solver_t* s, const char* name, const int* patch_ids, int npatch, double pRef);
 int das_calc_force_coupling(das_solver_t* s, const char* name, double* out, int n);
+/* das_define_thermal_coupling <- the "outputInfo" option entry {type: thermalCouplingOutput, patches} consumed by DAOutputThermalCoupling
+ *   (reference src/adjoint/DAOutput/DAOutputThermalCoupling.C, discipline aero): with nF the faces of the patches, taken in the order of
+ *   patch_ids (the reference sorts the patches by name, :40 - the caller does) and in face order inside a patch, entries [0, nF) hold T of
+ *   the owner cell of the face and entries [nF, 2 nF) hold kappa / d = Cp alphaEff_b deltaCoeff, alphaEff_b as in wallHeatFlux.  flags & 2:
+ *   wallDistanceMethod daCustom (deltaCoeff = 1 / |C_f - C_c|) instead of the face's delta coefficient.  The size is
+ *   das_get_output_size(name, "thermalCouplingOutput") = 2 nF.
+ * das_calc_thermal_coupling   <- calcOutput(name, "thermalCouplingOutput", output): n = that size.  No atomics: the same bits on every call.
+ * Derivatives: outputType "thermalCouplingOutput", as for forceCouplingOutput above.  Solvers without a T field (DAScalarTransportFoam,
+ * DASimpleFoam without T) and sharded solvers return DAS_ERR_ARG. */
+int das_define_thermal_coupling(das_solver_t* s, const char* name, const int* patch_ids, int npatch, int flags);
+int das_calc_thermal_coupling(das_solver_t* s, const char* name, double* out, int n);
+/* das_define_thermal_coupling_input <- the "inputInfo" option entry {type: thermalCoupling, patches} consumed by DAInputThermalCoupling
+ *   (reference src/adjoint/DAInput/DAInputThermalCoupling.C): the faces as for the output; every patch must carry a mixed T
+ *   (DAS_BC_MIXED), where the reference's refCast aborts.  The size is 2 nF.
+ * das_set_thermal_coupling_input    <- setSolverInput(name, "thermalCoupling", ...): in[k] becomes the refValue of face k and in[nF + k], the
+ *   neighbour's kappa / d (nk), its valueFraction nk / (myK + nk), with myK this side's kappa / d (the second half of the output) at the
+ *   current states, geometry and boundary values.  The fraction then stays as it is - a constant of the residual, of the Jacobians and of
+ *   the volCoord products - until the input is set again.
+ * das_get_patch_mixed                   the refValue and valueFraction of the faces of one mixed patch, as they stand.
+ * das_calc_dthermal_coupling_product <- calcJacTVecProduct(name, "thermalCoupling", inputs, outputName, outputType, seeds, product) after
+ *   the input has been set: product = [d output / d input]^T seeds (n = 2 nF), outputType "residual" (seeds: one per state), "function"
+ *   (one seed), "thermalCouplingOutput" (one per entry).  d valueFraction / d nk = myK / (myK + nk)^2 is part of
+ *   it.  Forward-mode passes and a per-face gather over the transposed structure of dRdW: no atomics, the same bits on every call. */
+int das_define_thermal_coupling_input(das_solver_t* s, const char* name, const int* patch_ids, int npatch, int flags);
+int das_set_thermal_coupling_input(das_solver_t* s, const char* name, const double* in, int n);
+int das_get_patch_mixed(das_solver_t* s, int patch, double* refValue, double* valueFraction);
+int das_calc_dthermal_coupling_product(das_solver_t* s, const char* inputName, const char* outputName, const char* outputType, const double* seeds,
+                                       double* product, int n);
 
 /* das_calc_jac_t_vec_product <- calcJacTVecProduct(inputName,inputType,inputs,outputName,outputType,seeds,product)
  *   pyDASolvers.pyx:208-235 (DASolver.C:1690-1839).  Supported pair on this path: inputType "stateVar",
