@@ -15,7 +15,7 @@ from .meshgen import BC_MIXED, FoamCase
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DAFOAM_AMD_LIB") or os.path.join(_HERE, "lib", "libdafoam_amd.so")  # (override: tuning builds)
 
-SOLVER_IDS = {"DASimpleFoam": 0, "DAScalarTransportFoam": 1, "DARhoSimpleFoam": 2, "DATurboFoam": 3}
+SOLVER_IDS = {"DASimpleFoam": 0, "DAScalarTransportFoam": 1, "DARhoSimpleFoam": 2, "DATurboFoam": 3, "DAHeatTransferFoam": 4}
 PATCH_TYPES = {"patch": 0, "wall": 1, "symmetry": 2, "cyclic": 3}
 
 c_double_p = C.POINTER(C.c_double)
@@ -77,6 +77,8 @@ class das_case_t(C.Structure):
         ("beta_fi_nuTilda", c_double_p),
         ("bc_T_mixed_ref", c_double_p),
         ("bc_T_mixed_frac", c_double_p),
+        ("n_kappa_coeffs", C.c_int),
+        ("kappa_coeffs", C.c_double * 8),
     ]
 
 
@@ -218,6 +220,14 @@ class CaseStruct:
                     [np.asarray(p.rotation, dtype=np.float64).reshape(9) if getattr(p, "rotation", None) is not None else np.eye(3).reshape(9)
                      for p in m.patches], dtype=np.float64)
                 s.patch_rotation = _dp(k["patch_rotation"])
+        if case.solver_name == "DAHeatTransferFoam":
+            # constant/solidProperties: `kappa` is one coefficient, `kappaCoeffs` the polynomial in T
+            coeffs = [float(x) for x in np.atleast_1d(getattr(case, "kappa_coeffs", None) if getattr(case, "kappa_coeffs", None) is not None else [])]
+            if not 1 <= len(coeffs) <= 8:
+                raise DASError(f"DAHeatTransferFoam needs kappa or kappaCoeffs with 1 to 8 coefficients, not {len(coeffs)}")
+            s.n_kappa_coeffs = len(coeffs)
+            for i, x in enumerate(coeffs):
+                s.kappa_coeffs[i] = x
         s.simple_has_T = 1 if (case.solver_name == "DASimpleFoam" and getattr(case, "has_T", False)) else 0
 
     def byref(self):

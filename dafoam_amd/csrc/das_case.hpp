@@ -18,8 +18,18 @@ struct CaseParams {
     std::vector<double> beta_fi;
     const double* betaFI_ptr = nullptr;
     const double* dBetaFI_ptr = nullptr;
+    // DAHeatTransferFoam: kappa(T) = sum_k kappa[k] T^k (constant/solidProperties kappa / kappaCoeffs)
+    int nKappa = 0;
+    double kappa[DAS_MAX_KAPPA_COEFFS] = {0, 0, 0, 0, 0, 0, 0, 0};
     void from_case(const das_case_t* c) {
         solver = c->solver;
+        if (solver == DAS_SOLVER_HEATTRANSFERFOAM) {
+            DAS_CHECK(c->n_kappa_coeffs >= 1 && c->n_kappa_coeffs <= DAS_MAX_KAPPA_COEFFS, DAS_ERR_ARG,
+                      "DAHeatTransferFoam needs kappa or kappaCoeffs with 1 to " + std::to_string(DAS_MAX_KAPPA_COEFFS) + " coefficients, not " +
+                          std::to_string(c->n_kappa_coeffs));
+            nKappa = c->n_kappa_coeffs;
+            for (int k = 0; k < nKappa; k++) kappa[k] = c->kappa_coeffs[k];
+        }
         nu = c->nu;
         relax_U = c->relax_U;
         relax_nuTilda = c->relax_nuTilda;
@@ -100,6 +110,9 @@ inline ResParams make_params(const CaseParams& cp, const Options& opt, int isPC)
     p.wTU = nullptr;
     p.betaFI = cp.betaFI_ptr;
     p.dBetaFI = cp.dBetaFI_ptr;
+    p.solid = cp.solver == DAS_SOLVER_HEATTRANSFERFOAM;
+    p.nKappa = cp.nKappa;
+    for (int k = 0; k < DAS_MAX_KAPPA_COEFFS; k++) p.kappa[k] = cp.kappa[k];
     for (int k = 0; k < 3; k++) { p.om[k] = cp.om[k]; p.org[k] = cp.org[k]; }
     return p;
 }

@@ -160,14 +160,14 @@ __global__ __launch_bounds__(256) void k_pres(DevMeshT<G> m, ResParams prm, cons
 // face-integral objectives: value (atomic sums per group), forward-mode tangent, coloured dual-number gradient scatter
 // (deterministic: per-face / per-block values first, then ONE workgroup sums them in a fixed order - the atomicAdd versions of
 //  round 2 summed in arrival order)
-template <bool RHO>
+template <bool RHO, bool SOLID = false>
 __global__ __launch_bounds__(256) void k_fn_value(DevMesh m, ResParams prm, const double* __restrict__ W, const double* nut, const double* gU,
                                                   FaceFnView fn, double* __restrict__ fv) {
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= fn.nf) return;
     double dir[3] = {0.0, 0.0, 0.0};
     if (fn.dir) { dir[0] = fn.dir[3 * k]; dir[1] = fn.dir[3 * k + 1]; dir[2] = fn.dir[3 * k + 2]; }
-    fv[k] = fn.w[k] * body_facefn<double, RHO>(fn.faces[k], m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc, fn.pRef);
+    fv[k] = fn.w[k] * facefn_of<double, RHO, SOLID>(fn.faces[k], m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc, fn.pRef);
 }
 // out2[g] = sum of fv[k] over the entries of group g (group == nullptr: everything is group 0); one workgroup, fixed order
 __global__ __launch_bounds__(256) void k_group_sum(long long cnt, const unsigned char* __restrict__ group, const double* __restrict__ fv, double* __restrict__ out2) {
@@ -186,14 +186,14 @@ __global__ __launch_bounds__(256) void k_group_sum(long long cnt, const unsigned
     if (threadIdx.x == 0) { out2[0] = sh[0][0]; out2[1] = sh[1][0]; }
 }
 // tangent of the objective for seeded boundary values (dF/d(BC value), one forward pass): per-face summands
-template <bool RHO>
+template <bool RHO, bool SOLID = false>
 __global__ __launch_bounds__(256) void k_fn_tangent(DevMesh m, ResParams prm, const Dual<1>* __restrict__ W, const Dual<1>* nut, const Dual<1>* gU,
                                                     FaceFnView fn, double seed, double* __restrict__ fv) {
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= fn.nf) return;
     double dir[3] = {0.0, 0.0, 0.0};
     if (fn.dir) { dir[0] = fn.dir[3 * k]; dir[1] = fn.dir[3 * k + 1]; dir[2] = fn.dir[3 * k + 2]; }
-    Dual<1> v = body_facefn<Dual<1>, RHO>(fn.faces[k], m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc, fn.pRef);
+    Dual<1> v = facefn_of<Dual<1>, RHO, SOLID>(fn.faces[k], m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc, fn.pRef);
     fv[k] = seed * fn.w[k] * v.d[0];
 }
 // part[b] = sum over the block's rows of psi_i * dR_i  (dR = tangent part of a dual residual); k_group_sum adds the parts
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256) void k_tangent_dot(long long n, const Dual<1>*
 }
 // the derivative of q_f w.r.t. the (unique) state of colour `col` in the stencil of face f (cell c and its face
 // neighbours: U, p, (T), nuTilda) is accumulated into dFdW
-template <bool RHO>
+template <bool RHO, bool SOLID = false>
 __global__ __launch_bounds__(256) void k_fn_grad(DevMesh m, ResParams prm, const Dual<1>* __restrict__ W, const Dual<1>* nut, const Dual<1>* gU,
                                                  FaceFnView fn, double seed, const int* __restrict__ colors, int col, double* dFdW) {
     int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -219,11 +219,15 @@ __global__ __launch_bounds__(256) void k_fn_grad(DevMesh m, ResParams prm, const
     double dir[3] = {0.0, 0.0, 0.0};
     if (fn.dir) { dir[0] = fn.dir[3 * k]; dir[1] = fn.dir[3 * k + 1]; dir[2] = fn.dir[3 * k + 2]; }
     const int f = fn.faces[k];
-    Dual<1> v = body_facefn<Dual<1>, RHO>(f, m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc, fn.pRef);
+    Dual<1> v = facefn_of<Dual<1>, RHO, SOLID>(f, m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc, fn.pRef);
     if (v.d[0] == 0.0) return;
     const double g = seed * fn.w[k] * v.d[0];
     const long long N = m.nC;
     const int c = m.owner[f];
+    if constexpr (SOLID) {  // the one-block layout [T]: the summand of a face reads T of its owner cell alone
+        if (colors[c] == col) atomicAdd(&dFdW[c], g);
+        return;
+    }
     const int nsc = prm.offPhi - 3;  // scalar cell blocks after U (p, [T], nuTilda)
     auto try_cell = [&](int x) -> bool {
         for (int q = 0; q < 3; q++) if (colors[3LL * x + q] == col) { atomicAdd(&dFdW[3LL * x + q], g); return true; }
@@ -247,6 +251,18 @@ __global__ __launch_bounds__(256) void k_T(DevMeshT<G> m, ResParams prm, const T
                                            const T* gT, T* R) {
     int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c < m.nC) body_T<T>(c, m, prm, W, phiF, Told, gT, R);
+}
+
+// DAHeatTransferFoam: Gauss gradient of T, then TRes = laplacian(kappa(T), T) (body_heat_grad / body_heat); one thread per cell
+template <class T, class G = double>
+__global__ __launch_bounds__(256) void k_heat_grad(DevMeshT<G> m, ResParams prm, const T* __restrict__ W, T* gT) {
+    int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < m.nC) body_heat_grad<T>(c, m, prm, W, gT);
+}
+template <class T, class G = double>
+__global__ __launch_bounds__(256) void k_heat(DevMeshT<G> m, ResParams prm, const T* __restrict__ W, const T* gT, T* R) {
+    int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < m.nC) body_heat<T>(c, m, prm, W, gT, R);
 }
 
 template <class T>
@@ -319,6 +335,9 @@ static void eval_residual(const DevMeshT<G>& dm, const CaseParams& cp, const Res
                            (const T*)wk.gH.p, R, wk.rAU.p, wk.HbyA.p);
         hipLaunchKernelGGL((k_face<T, true, G>), dim3(nblk(dm.nF, B)), dim3(B), 0, st, dm, prm, W, wk.nut.p, wk.gP.p, wk.rAU.p, wk.HbyA.p, wk.q.p, R);
         hipLaunchKernelGGL((k_pres<T, true, G>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, wk.q.p, R);
+    } else if (cp.solver == DAS_SOLVER_HEATTRANSFERFOAM) {
+        hipLaunchKernelGGL((k_heat_grad<T, G>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, W, wk.gT.p);
+        hipLaunchKernelGGL((k_heat<T, G>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, W, (const T*)wk.gT.p, R);
     } else {
         hipLaunchKernelGGL((k_gradT<T, G>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, W, d_phiF, wk.gT.p);
         hipLaunchKernelGGL((k_T<T, G>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, W, d_phiF, d_Told, wk.gT.p, R);
@@ -1176,7 +1195,7 @@ static das_mat* assemble(das_solver* s, int isPC, int mode) {
     // in-pattern entries of the same colour - an accepted approximation of the PRECONDITIONER matrix only, the operator
     // dRdW^T always uses the full tables
     // A user table with URes < 2 gets the reference's upwind div(pc) back (weight 0) with a warning instead of an error.
-    if (isPC && prm.convBlend > 0.0 && s->cp.solver != DAS_SOLVER_SCALARTRANSPORTFOAM && s->opt.geti("maxResConLv4JacPCMat.URes") < 2) {
+    if (isPC && prm.convBlend > 0.0 && s->cp.solver != DAS_SOLVER_SCALARTRANSPORTFOAM && s->cp.solver != DAS_SOLVER_HEATTRANSFERFOAM && s->opt.geti("maxResConLv4JacPCMat.URes") < 2) {
         static bool warned = false;
         if (!warned) fprintf(stderr, "[dafoam_amd] warning: amd.pcUpwindBlend %.3g needs maxResConLv4JacPCMat.URes >= 2 (the second-order correction reaches two cell rings); "
                                      "the PC matrix is assembled with the upwind div(pc) (weight 0) instead\n", prm.convBlend);
@@ -2985,7 +3004,17 @@ static double device_norm2(das_solver* s, das_ksp* k, const double* x) {
 
 static int run_newton_primal(das_solver* s, int maxSteps, double relTol, double absTol, NewtonInfo& info) {
     need_init(s);
-    DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver), DAS_ERR_ARG, "the Newton primal needs a flow solver");
+    DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver) || s->cp.solver == DAS_SOLVER_HEATTRANSFERFOAM, DAS_ERR_ARG,
+              "the Newton primal needs a flow solver or DAHeatTransferFoam");
+    if (s->cp.solver == DAS_SOLVER_HEATTRANSFERFOAM) {
+        // pure zeroGradient boundaries leave T undetermined up to a constant: the steady conduction problem is singular
+        bool anchored = false;
+        for (int p = 0; p < (int)s->mesh.bc.size(); p++) {
+            const int code = s->mesh.bc[p].T_code;
+            anchored = anchored || (s->mesh.patch_size[p] > 0 && (code == DAS_BC_FIXED_VALUE || code == DAS_BC_MIXED));
+        }
+        DAS_CHECK(anchored, DAS_ERR_ARG, "DAHeatTransferFoam: no patch carries a fixedValue or mixed T - the steady conduction problem is singular");
+    }
     DAS_CHECK(!s->halo.active && !s->halo_cb, DAS_ERR_ARG, "the Newton primal is single-rank");
     const long long n = s->n;
     const int B = 256;
@@ -3141,7 +3170,7 @@ das_solver_t* das_create(const das_case_t* c) {
         s->t0_cpu = std::clock();
         s->cp.from_case(c);
         s->mesh.build(c);
-        s->opt.s["solverName"] = c->solver == DAS_SOLVER_SIMPLEFOAM ? "DASimpleFoam" : (c->solver == DAS_SOLVER_RHOSIMPLEFOAM ? "DARhoSimpleFoam" : (c->solver == DAS_SOLVER_TURBOFOAM ? "DATurboFoam" : "DAScalarTransportFoam"));
+        s->opt.s["solverName"] = c->solver == DAS_SOLVER_SIMPLEFOAM ? "DASimpleFoam" : (c->solver == DAS_SOLVER_RHOSIMPLEFOAM ? "DARhoSimpleFoam" : (c->solver == DAS_SOLVER_TURBOFOAM ? "DATurboFoam" : (c->solver == DAS_SOLVER_HEATTRANSFERFOAM ? "DAHeatTransferFoam" : "DAScalarTransportFoam")));
         s->st_full = make_stencil(s->cp.solver, s->mesh.nC, s->mesh.nF, s->opt, false, s->cp.hasT != 0);
         s->n = s->st_full.n;
         s->h_W.assign(s->n, 0.0);
@@ -3734,16 +3763,22 @@ int das_set_old_time_fields(das_solver_t* s, const double* phi_frozen, const dou
 
 // ---- shared by the host paths of the objective functions ----------------------------------------------------------------------
 extern "C++" {  // templates: not under the C linkage of the entry points around them
-// f with the compressible switch as a compile-time tag: f(std::true_type{}) or f(std::false_type{})
+// f with the compressible switch as a compile-time tag: f(SolverTag<true, false>{}) or f(SolverTag<false, false>{})
+template <bool RHO, bool SOLID>
+struct SolverTag { static constexpr bool value = RHO, solid = SOLID; };  // value: the compressible switch; solid: DAHeatTransferFoam's layout [T]
 template <class F>
 static void with_rho(bool rho, F&& f) {
-    if (rho) f(std::true_type{});
-    else f(std::false_type{});
+    if (rho) f(SolverTag<true, false>{});
+    else f(SolverTag<false, false>{});
 }
 // the two launches of a function pass: the gradient fields of W into wk (k_grad; not for location, which reads no state: grad = false),
 // then the per-face kernel - `face` launches it and takes the same tag
 template <class T, class G, class F>
 static void launch_grad_and_faces(hipStream_t st, bool rho, const DevMeshT<G>& dm, const ResParams& prm, const T* W, ResWork<T>& wk, bool grad, F&& face) {
+    if (prm.solid) {  // DAHeatTransferFoam: the face functions read T of the owner cell and the patch field - no gradient pass
+        face(SolverTag<false, true>{});
+        return;
+    }
     with_rho(rho, [&](auto R) {
         if (grad) hipLaunchKernelGGL((k_grad<T, decltype(R)::value, G>), dim3(nblk(dm.nC, 256)), dim3(256), 0, st, dm, prm, W, wk.nut.p, wk.gU.p, wk.gP.p, wk.gN.p, wk.gH.p);
         face(R);
@@ -3755,6 +3790,10 @@ static double ref_var_value(bool refVar, double ref, double F0) { return refVar 
 static double ref_var_outer(bool refVar, double ref, double F0) { return refVar ? 2.0 * (F0 - ref) : 1.0; }
 static void need_flow_solver(das_solver* s) {
     DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver), DAS_ERR_ARG, "function needs a flow solver");
+}
+// the derivative passes of a face function that is already defined: the flow solvers, and DAHeatTransferFoam (wallHeatFlux, thermal coupling)
+static void need_face_function_solver(das_solver* s) {
+    if (s->cp.solver != DAS_SOLVER_HEATTRANSFERFOAM) need_flow_solver(s);
 }
 
 // geometry-dependent part of a face function: per-face weights (scale, area fractions) and directions (moment arms)
@@ -3824,6 +3863,19 @@ int das_define_face_function_ex(das_solver_t* s, const char* name, const char* t
     DAS_TRY
     DAS_CHECK(s && name && type && patch_ids && npatch > 0, DAS_ERR_ARG, "bad argument");
     const std::string ty = type;
+    if (s->cp.solver == DAS_SOLVER_HEATTRANSFERFOAM) {  // the solid: kappa(T_b) snGrad(T) on the one-block layout (body_facefn_solid)
+        DAS_CHECK(ty == "wallHeatFlux", DAS_ERR_ARG, "function type " + ty + " (function " + name + ") is not built for DAHeatTransferFoam; wallHeatFlux and variableVolSum of T are");
+        DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "DAHeatTransferFoam functions run on an undecomposed solver (sharded solvers are not supported)");
+        das_solver::FaceFn fn;
+        fn.kind = DAS_FN_WALLHEATFLUX | ((flags & 2) ? DAS_FN_ALT_BIT : 0);
+        fn.byUnitArea = (flags & 1) != 0;
+        collect_patch_faces(s, patch_ids, nullptr, npatch, fn);
+        fn.scale = scale;
+        fn.refVar = (flags & 8) != 0;
+        fn.ref = ref;
+        register_face_function(s, name, std::move(fn), false);
+        return DAS_OK;
+    }
     DAS_CHECK(ty != "wallHeatFlux" || DAS_IS_COMPRESSIBLE(s->cp.solver) || (s->cp.solver == DAS_SOLVER_SIMPLEFOAM && s->cp.hasT), DAS_ERR_ARG,
               std::string("wallHeatFlux function ") + name + " needs a T field (DASimpleFoam with T, DARhoSimpleFoam, DATurboFoam)");
     need_flow_solver(s);
@@ -3905,7 +3957,7 @@ int das_define_force_function(das_solver_t* s, const char* name, const int* patc
 static int field_var_id(das_solver* s, const char* var, bool allowField) {
     const std::string v = var ? var : "";
     const bool flow = s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver);
-    const bool hasT = DAS_IS_COMPRESSIBLE(s->cp.solver) || s->cp.hasT || s->cp.solver == DAS_SOLVER_SCALARTRANSPORTFOAM;
+    const bool hasT = DAS_IS_COMPRESSIBLE(s->cp.solver) || s->cp.hasT || s->cp.solver == DAS_SOLVER_SCALARTRANSPORTFOAM || s->cp.solver == DAS_SOLVER_HEATTRANSFERFOAM;
     const std::string supported = std::string(flow ? "U, p, nuTilda" : "") + (hasT ? (flow ? ", T" : "T") : "") + (allowField && flow ? ", betaFINuTilda" : "");
     int id = -1;
     if (v == "U" && flow) id = 0;
@@ -4090,7 +4142,7 @@ static void function_sums(das_solver* s, das_solver::FaceFn& fn, double S[2]) {
     } else {
         const ResParams prm = s->wk.bind(s->cp.solver, s->dm.nC, s->dm.nF, make_params(s->cp, s->opt, 0));
         launch_grad_and_faces(s->stream, rho, s->dm, prm, (const double*)s->d_W.p, s->wk, true, [&](auto R) {
-            hipLaunchKernelGGL((k_fn_value<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn.view(fn.d_w0.p), fn.d_fv.p);
+            hipLaunchKernelGGL((k_fn_value<decltype(R)::value, decltype(R)::solid>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn.view(fn.d_w0.p), fn.d_fv.p);
         });
     }
     hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, s->stream, (long long)nf, (const unsigned char*)fn.d_group.p, (const double*)fn.d_fv.p, s->d_tmp1.p);
@@ -4202,7 +4254,7 @@ static void face_function_gradient(das_solver* s, das_solver::FaceFn& fn, double
     for (int col = 0; col < s->nColors; col++) {
         hipLaunchKernelGGL(k_seed<1>, dim3(nblk(n, B)), dim3(B), 0, s->stream, n, s->d_W.p, s->d_colors.p, s->d_scale.p, col, s->d_Wd.p);
         launch_grad_and_faces(s->stream, rho, s->dm, prm, (const Dual<1>*)s->d_Wd.p, s->wk1, true, [&](auto R) {
-            hipLaunchKernelGGL((k_fn_grad<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, fn.view(fn.d_weff.p), seed, s->d_colors.p, col, s->d_tmp2.p);
+            hipLaunchKernelGGL((k_fn_grad<decltype(R)::value, decltype(R)::solid>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, fn.view(fn.d_weff.p), seed, s->d_colors.p, col, s->d_tmp2.p);
         });
     }
     DAS_HIP(hipGetLastError());
@@ -4325,7 +4377,7 @@ int das_calc_force_coupling(das_solver_t* s, const char* name, double* out, int 
 
 // ---- thermalCouplingOutput (reference DAOutputThermalCoupling.C; layout and kernels: das_thermalcoupling.hpp) ---------------------
 static void need_thermal_coupling_solver(das_solver* s) {
-    DAS_CHECK(DAS_IS_COMPRESSIBLE(s->cp.solver) || (s->cp.solver == DAS_SOLVER_SIMPLEFOAM && s->cp.hasT), DAS_ERR_ARG,
+    DAS_CHECK(DAS_IS_COMPRESSIBLE(s->cp.solver) || (s->cp.solver == DAS_SOLVER_SIMPLEFOAM && s->cp.hasT) || s->cp.solver == DAS_SOLVER_HEATTRANSFERFOAM, DAS_ERR_ARG,
               "thermalCouplingOutput needs a solver that carries a T field (DASimpleFoam with T, DARhoSimpleFoam, DATurboFoam)");
     DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "thermalCouplingOutput runs on an undecomposed solver (sharded solvers are not supported)");
 }
@@ -4383,7 +4435,7 @@ static void thermal_coupling_values(das_solver* s, das_solver::ThermalCoupling& 
     const ResParams prm = s->wk.bind(s->cp.solver, s->dm.nC, s->dm.nF, make_params(s->cp, s->opt, 0));
     // the gradient pass fills nut of the cells, which a symmetry-type nut patch reads
     launch_grad_and_faces(s->stream, DAS_IS_COMPRESSIBLE(s->cp.solver), s->dm, prm, (const double*)s->d_W.p, s->wk, true, [&](auto R) {
-        hipLaunchKernelGGL((k_tc_values<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_W.p, s->wk.nut.p, nf,
+        hipLaunchKernelGGL((k_tc_values<decltype(R)::value, decltype(R)::solid>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_W.p, s->wk.nut.p, nf,
                            (const int*)tc.fn.d_faces.p, (int)DAS_FN_ALT(tc.fn.kind), tc.d_out.p);
     });
     DAS_HIP(hipGetLastError());
@@ -4586,7 +4638,7 @@ int das_calc_dbc_product(das_solver_t* s, const int* patches, int np, const char
         const int nf = (int)fn.faces.size();
         if (fn.d_fv.n != (size_t)nf) fn.d_fv.alloc(nf);
         launch_grad_and_faces(st, rho, s->dm, prm, (const Dual<1>*)s->d_Wd.p, s->wk1, true, [&](auto R) {
-            hipLaunchKernelGGL((k_fn_tangent<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, fn.view(fn.d_weff.p), fnSeed, fn.d_fv.p);
+            hipLaunchKernelGGL((k_fn_tangent<decltype(R)::value, decltype(R)::solid>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, fn.view(fn.d_weff.p), fnSeed, fn.d_fv.p);
         });
         hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, st, (long long)nf, (const unsigned char*)nullptr, (const double*)fn.d_fv.p, s->d_tmp1.p);
     }
@@ -4676,7 +4728,7 @@ int das_calc_dthermal_coupling_product(das_solver_t* s, const char* inputName, c
         for (int which = 2; which <= 3; which++) {
             hipLaunchKernelGGL(k_tc_seed_mixed, dim3(nblk(nf, B)), dim3(B), 0, st, nf, (const int*)nullptr, faces, s->dm.nIF, which, 1.0, s->d_mixed.p);
             launch_grad_and_faces(st, rho, s->dm, prm, (const Dual<1>*)s->d_Wd.p, s->wk1, true, [&](auto R) {
-                hipLaunchKernelGGL((k_fn_tangent<decltype(R)::value>), dim3(nblk(nfn, B)), dim3(B), 0, st, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, fn.view(fn.d_weff.p), fnSeed, fn.d_fv.p);
+                hipLaunchKernelGGL((k_fn_tangent<decltype(R)::value, decltype(R)::solid>), dim3(nblk(nfn, B)), dim3(B), 0, st, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, fn.view(fn.d_weff.p), fnSeed, fn.d_fv.p);
             });
             hipLaunchKernelGGL(k_tc_seed_mixed, dim3(nblk(nf, B)), dim3(B), 0, st, nf, (const int*)nullptr, faces, s->dm.nIF, which, 0.0, s->d_mixed.p);
             DAS_HIP(hipGetLastError());
@@ -4708,7 +4760,7 @@ int das_set_field(das_solver_t* s, const char* fieldName, const double* values) 
     DAS_TRY
     DAS_CHECK(s && values, DAS_ERR_ARG, "null argument");
     check_field(fieldName);
-    DAS_CHECK(s->cp.solver != DAS_SOLVER_SCALARTRANSPORTFOAM, DAS_ERR_ARG, "betaFINuTilda needs a Spalart-Allmaras solver");
+    DAS_CHECK(s->cp.solver != DAS_SOLVER_SCALARTRANSPORTFOAM && s->cp.solver != DAS_SOLVER_HEATTRANSFERFOAM, DAS_ERR_ARG, "betaFINuTilda needs a Spalart-Allmaras solver");
     s->cp.beta_fi.assign(values, values + s->mesh.nC);
     if (s->inited) {
         DAS_HIP(hipStreamSynchronize(s->stream));
@@ -4742,6 +4794,13 @@ int das_calc_dfield_product(das_solver_t* s, const char* fieldName, const char* 
     const std::string ot = outputType;
     DAS_CHECK(ot == "residual" || ot == "function" || is_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
     const long long N = s->mesh.nC, n = s->n;
+    if (s->cp.solver == DAS_SOLVER_SCALARTRANSPORTFOAM || s->cp.solver == DAS_SOLVER_HEATTRANSFERFOAM) {
+        // no Spalart-Allmaras production term: nothing of these solvers reads the field - exact zeros (an unknown output still fails by name)
+        if (is_coupling(ot)) (void)coupling_size(s, ot, outputName);
+        else if (ot == "function" && !find_cell_function(s, outputName)) (void)get_function(s, outputName);
+        std::fill(product, product + N, 0.0);
+        return DAS_OK;
+    }
     if (is_coupling(ot)) {  // like the patch-integral functions: the coupling outputs do not see the production term
         (void)coupling_size(s, ot, outputName);
         std::fill(product, product + N, 0.0);
@@ -4958,7 +5017,7 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
         d_Rd.alloc((size_t)n);
         d_seeds.upload(seeds, (size_t)n);
     } else {
-        need_flow_solver(s);
+        need_face_function_solver(s);
         nf = (int)fn->faces.size();
         d_fvd.alloc((size_t)nf);
         std::vector<int> cptr, cidx;
@@ -4989,7 +5048,7 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
                 const bool isLoc = DAS_FN_BASE(fn->kind) == DAS_FN_LOCATION;  // the linearised functional sum w_eff a_f; no state is read
                 const FaceFnView fv = fn->view(isLoc ? fn->d_weff.p : fn->d_w0.p);
                 launch_grad_and_faces(st, rho, dmD, prm, (const D*)d_Wd.p, s->wk1, !isLoc, [&](auto R) {
-                    hipLaunchKernelGGL((k_fn_dual<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, st, dmD, prm, (const D*)d_Wd.p, (const D*)s->wk1.nut.p, (const D*)s->wk1.gU.p, fv,
+                    hipLaunchKernelGGL((k_fn_dual<decltype(R)::value, decltype(R)::solid>), dim3(nblk(nf, B)), dim3(B), 0, st, dmD, prm, (const D*)d_Wd.p, (const D*)s->wk1.nut.p, (const D*)s->wk1.gU.p, fv,
                                        (int)fn->isMoment, fn->vecA[0], fn->vecA[1], fn->vecA[2], fn->vecB[0], fn->vecB[1], fn->vecB[2], (int)areaAvg, cN[0], cN[1], cA[0], cA[1], d_fvd.p);
                 });
                 hipLaunchKernelGGL(k_vc_fn_cells_dual, dim3(nblk(m.nC, B)), dim3(B), 0, st, m.nC, (const int*)d_fnPtr.p, (const int*)d_fnIdx.p, seeds[0],
@@ -5116,7 +5175,7 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
         v.d_Rp.alloc(n); v.d_Rm.alloc(n);
         v.d_seeds.upload(seeds, n);
     } else {
-        need_flow_solver(s);
+        need_face_function_solver(s);
         nf = (int)fn->faces.size();
         v.d_fvp.alloc(nf); v.d_fvm.alloc(nf);
         std::vector<int> cptr, cidx;
@@ -5138,8 +5197,8 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
             hipLaunchKernelGGL(k_fn_moment_dir, dim3(nblk(nf, B)), dim3(B), 0, st, nf, (const int*)fn->d_faces.p, (const FaceGeom*)s->d_fg.p, fn->vecA[0], fn->vecA[1],
                                fn->vecA[2], fn->vecB[0], fn->vecB[1], fn->vecB[2], fn->d_dir.p);
         launch_grad_and_faces(st, rho, s->dm, prm, (const double*)s->d_W.p, s->wk, true, [&](auto R) {
-            if (areaAvg) hipLaunchKernelGGL((k_fn_area_avg<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn->view(fn->d_w0.p), cN[0], cN[1], cA[0], cA[1], fvOut);
-            else hipLaunchKernelGGL((k_fn_value<decltype(R)::value>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn->view(fn->d_w0.p), fvOut);
+            if (areaAvg) hipLaunchKernelGGL((k_fn_area_avg<decltype(R)::value, decltype(R)::solid>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn->view(fn->d_w0.p), cN[0], cN[1], cA[0], cA[1], fvOut);
+            else hipLaunchKernelGGL((k_fn_value<decltype(R)::value, decltype(R)::solid>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn->view(fn->d_w0.p), fvOut);
         });
     };
     const double t0 = wall_seconds();

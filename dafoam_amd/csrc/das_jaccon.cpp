@@ -81,7 +81,7 @@ Stencil make_stencil(int solver, int nC, int nF, const Options& opt, bool isPC, 
         st.levels[2] = {bits({"U", "p", "T", "nuTilda", "phi"}), bits({"U", "p", "T", "nuTilda"}), bits({"U", "p", "T"})};                  // TRes
         st.levels[3] = {bits({"U", "T", "p", "nuTilda", "phi"}), bits({"U", "T", "p", "nuTilda"}), bits({"T", "p", "nuTilda"})};            // nuTildaRes
         st.levels[4] = {bits({"U", "p", "T", "nuTilda", "phi"}), bits({"U", "p", "T", "nuTilda"}), bits({"U", "T"})};                       // phiRes
-    } else if (solver == DAS_SOLVER_SCALARTRANSPORTFOAM) {
+    } else if (solver == DAS_SOLVER_SCALARTRANSPORTFOAM || solver == DAS_SOLVER_HEATTRANSFERFOAM) {  // DAStateInfoHeatTransferFoam.C:69-75: the same table
         add_state("T", KIND_SCL);
         st.levels.resize(1);
         st.levels[0] = {bits({"T"}), bits({"T"}), bits({"T"})};

@@ -7,6 +7,7 @@
 //   DATurbulenceModel::divDevRhoReff            src/adjoint/DAModel/DATurbulenceModel/DATurbulenceModel.C:378-408
 //   nutUSpaldingWallFunction calcNut/calcUTau   src/adjoint/DAMisc/nutUSpaldingWallFunctionDF/...DF.C:42-150
 //   DAResidualScalarTransportFoam::calcResiduals src/adjoint/DAResidual/DAResidualScalarTransportFoam.C:57-84
+//   DAResidualHeatTransferFoam::calcResiduals   src/adjoint/DAResidual/DAResidualHeatTransferFoam.C:97-132   (body_heat_grad / body_heat)
 //   residual normalisation macros               src/include/DAMacroFunctions.H:28-51
 //   DAResidualRhoSimpleFoam::calcResiduals      src/adjoint/DAResidual/DAResidualRhoSimpleFoam.C:84-211   (RHO = true)
 //   DAResidualTurboFoam::calcResiduals          src/adjoint/DAResidual/DAResidualTurboFoam.C:66-233       (RHO = true, prm.turbo)
@@ -76,6 +77,9 @@ struct ResParams {
     // `field` input betaFINuTilda (per cell; null = 1) and its tangent (null = 0)
     const double* betaFI;
     const double* dBetaFI;
+    // DAHeatTransferFoam: kappa(T) = sum_k kappa[k] T^k, nKappa terms (kappa_of); solid = 1: the one-block state layout [T] (host-side launch switch)
+    int solid, nKappa;
+    double kappa[DAS_MAX_KAPPA_COEFFS];
 };
 #define DAS_TREF 298.15
 
@@ -1376,6 +1380,134 @@ DAS_HD void body_T(int c, const DevMeshT<G>& m, const ResParams& prm, const T* W
     T res = ((d + bd) * Tc + off - sS - bs) * (1.0 / cgc.V);
     if (!prm.normT) res = res * cgc.V;
     R[c] = res;
+}
+
+// ================================================================================ DAHeatTransferFoam
+// kappa(T) = sum_k kappa[k] T^k by Horner (reference DAResidualHeatTransferFoam.C:105-132 sums kappaCoeffs[k] pow(T, k)); recomputed where
+// it is used - no conductivity array exists
+template <class T>
+DAS_HD T kappa_of(const ResParams& prm, const T& Tk) {
+    T k(prm.kappa[prm.nKappa - 1]);
+    for (int i = prm.nKappa - 2; i >= 0; i--) k = k * Tk + prm.kappa[i];
+    return k;
+}
+// the T patch field of boundary face f of the solid: fixedValue / zeroGradient through bc_scalar, mixed (the thermalCoupling input) through
+// bc_mixed; there is no flux, so inletOutlet degenerates to zeroGradient (phib = 0)
+template <class T, class G>
+DAS_HD void heat_bface(const DevMeshT<G>& m, int f, const T& Tc, ScalarBC<T, G>& b) {
+    const PatchBC& bc = m.bc[m.bpatch[f - m.nIF]];
+    if (bc.T_code == DAS_BC_MIXED) bc_mixed<T>(mixed_of(m, f), 1.0, 0.0, m.fg[f].nod, Tc, b);
+    else bc_scalar<T>(bc.T_code, bc.T_val, bc.dT_val, m.fg[f].nod, 0.0, Tc, b);
+}
+// Gauss linear gradient of T
+template <class T, class G>
+DAS_HD void body_heat_grad(int c, const DevMeshT<G>& m, const ResParams& prm, const T* W, T* gradT) {
+    const CellGeomT<G>& cgc = m.cg[c];
+    T Tc = W[c];
+    T gT[3] = {T(0.0), T(0.0), T(0.0)};
+    for (int s = m.cf_ptr[c]; s < m.cf_ptr[c + 1]; s++) {
+        int fe = m.cf_face[s];
+        int f = fe & 0x7fffffff;
+        bool nb = fe < 0;
+        const FaceGeomT<G>& g = m.fg[f];
+        double sg = nb ? -1.0 : 1.0;
+        T Tf;
+        if (f < m.nIF) {
+            G wc = nb ? G(1.0 - g.w) : g.w;
+            Tf = wc * Tc + (1.0 - wc) * W[m.cf_other[s]];
+        } else {
+            ScalarBC<T, G> b;
+            heat_bface<T, G>(m, f, Tc, b);
+            Tf = b.xb;
+        }
+#pragma unroll
+        for (int i = 0; i < 3; i++) gT[i] += (sg * g.Sf[i]) * Tf;
+    }
+    G rV = 1.0 / cgc.V;
+#pragma unroll
+    for (int i = 0; i < 3; i++) gradT[3LL * c + i] = gT[i] * rV;
+}
+
+// TRes = (laplacian(kappa, T)) & T   (Gauss linear corrected; kappa interpolated linearly to the faces; DAResidualHeatTransferFoam.C:97-102)
+template <class T, class G>
+DAS_HD void body_heat(int c, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* gradT, T* R) {
+    const CellGeomT<G>& cgc = m.cg[c];
+    const T Tc = W[c];
+    const T kc = kappa_of<T>(prm, Tc);
+    T sum(0.0);
+    for (int s = m.cf_ptr[c]; s < m.cf_ptr[c + 1]; s++) {
+        int fe = m.cf_face[s];
+        int f = fe & 0x7fffffff;
+        bool nb = fe < 0;
+        const FaceGeomT<G>& g = m.fg[f];
+        if (f < m.nIF) {
+            const int o = m.cf_other[s];
+            const double sg = nb ? -1.0 : 1.0;
+            const T To = W[o];
+            G wc = nb ? G(1.0 - g.w) : g.w, wo = 1.0 - wc;
+            const T kf = wc * kc + wo * kappa_of<T>(prm, To);
+            T cv = g.corr[0] * (wc * gradT[3LL * c] + wo * gradT[3LL * o]) + g.corr[1] * (wc * gradT[3LL * c + 1] + wo * gradT[3LL * o + 1])
+                   + g.corr[2] * (wc * gradT[3LL * c + 2] + wo * gradT[3LL * o + 2]);
+            sum += (kf * g.magSf) * (g.nod * (To - Tc) + sg * cv);
+        } else {
+            ScalarBC<T, G> b;
+            heat_bface<T, G>(m, f, Tc, b);
+            sum += (kappa_of<T>(prm, b.xb) * g.magSf) * (b.gic * Tc + b.gbc);
+        }
+    }
+    T res = sum * (1.0 / cgc.V);
+    if (!prm.normT) res = res * cgc.V;
+    R[c] = res;
+}
+
+// the face functions of the solid, on the one-block state layout [T] (kinds and DAS_FN_ALT_BIT as body_facefn):
+//   wallHeatFlux     kappa(T_b) snGrad(T), snGrad the patch field's gic T_c + gbc (wallDistanceMethod default) or (T_b - T_c) / |C_f - C_c|
+//                    (daCustom)                                            DAFunctionWallHeatFlux.C:229-261
+//   thermalCoupling  d_f[0] T_c + d_f[1] kappa(T_b) deltaCoeff, deltaCoeff the face's delta coefficient or 1 / |C_f - C_c| (daCustom): the
+//                    functional seeds . output of a thermalCouplingOutput, discipline thermal   DAOutputThermalCoupling.C:212-241
+template <class T, class G>
+DAS_HD void body_thermal_coupling_solid(int f, const DevMeshT<G>& m, const ResParams& prm, const T* W, bool custom, T& Tnear, T& kd) {
+    const FaceGeomT<G>& g = m.fg[f];
+    const int c = m.owner[f];
+    const T Tc = W[c];
+    ScalarBC<T, G> b;
+    heat_bface<T, G>(m, f, Tc, b);
+    G delta = g.nod;
+    if (custom) {
+        const G d0 = g.Cf[0] - m.cg[c].C[0], d1 = g.Cf[1] - m.cg[c].C[1], d2 = g.Cf[2] - m.cg[c].C[2];
+        delta = 1.0 / dsqrt(d0 * d0 + d1 * d1 + d2 * d2);
+    }
+    Tnear = Tc;
+    kd = kappa_of<T>(prm, b.xb) * delta;
+}
+template <class T, class G, class DV>
+DAS_HD T body_facefn_solid(int f, const DevMeshT<G>& m, const ResParams& prm, const T* W, int kind, const DV* dir) {
+    if (DAS_FN_BASE(kind) == DAS_FN_THERMALCOUPLING) {
+        T Tnear, kd;
+        body_thermal_coupling_solid<T, G>(f, m, prm, W, DAS_FN_ALT(kind), Tnear, kd);
+        return dir[0] * Tnear + dir[1] * kd;
+    }
+    // wallHeatFlux (the host defines no other kind on this solver)
+    const FaceGeomT<G>& g = m.fg[f];
+    const int c = m.owner[f];
+    const T Tc = W[c];
+    ScalarBC<T, G> b;
+    heat_bface<T, G>(m, f, Tc, b);
+    T sn;
+    if (DAS_FN_ALT(kind)) {
+        const G d0 = g.Cf[0] - m.cg[c].C[0], d1 = g.Cf[1] - m.cg[c].C[1], d2 = g.Cf[2] - m.cg[c].C[2];
+        sn = (b.xb - Tc) / dsqrt(d0 * d0 + d1 * d1 + d2 * d2);
+    } else {
+        sn = b.gic * Tc + b.gbc;
+    }
+    return kappa_of<T>(prm, b.xb) * sn;
+}
+// body_facefn of the flow solvers, or body_facefn_solid: what the face-function kernels call (SOLID is their template argument)
+template <class T, bool RHO, bool SOLID, class G, class DV>
+DAS_HD T facefn_of(int f, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* nut, const T* gradU, int kind, const DV* dir,
+                   double gammaFn, double RFn, const double* loc = nullptr, double pRef = 0.0) {
+    if constexpr (SOLID) return body_facefn_solid<T, G, DV>(f, m, prm, W, kind, dir);
+    else return body_facefn<T, RHO>(f, m, prm, W, nut, gradU, kind, dir, gammaFn, RFn, loc, pRef);
 }
 
 // a face-integral objective as the kernels see it (k_fn_value / k_fn_tangent / k_fn_grad / k_fn_dual / k_fn_area_avg)

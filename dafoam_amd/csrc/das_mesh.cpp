@@ -237,7 +237,7 @@ void Mesh::build(const das_case_t* c) {
         DAS_CHECK(b.U_code != DAS_BC_MIXED && b.p_code != DAS_BC_MIXED && b.nuTilda_code != DAS_BC_MIXED, DAS_ERR_ARG,
                   "patch " + std::to_string(p) + ": the mixed patch field is built for T only, not for " +
                       (b.U_code == DAS_BC_MIXED ? "U" : b.p_code == DAS_BC_MIXED ? "p" : "nuTilda"));
-        if (b.T_code != DAS_BC_MIXED) continue;
+        if (b.T_code != DAS_BC_MIXED) continue;  // (DAHeatTransferFoam carries a mixed T as the flow solvers do: body_heat reads it through bc_mixed)
         DAS_CHECK(c->solver != DAS_SOLVER_SCALARTRANSPORTFOAM, DAS_ERR_ARG, "the mixed T patch field is built for the flow solvers, not for DAScalarTransportFoam");
         DAS_CHECK(patch_type[p] != DAS_PATCH_CYCLIC, DAS_ERR_ARG, "a cyclic patch cannot carry a mixed T");
         if (mixed.empty()) mixed.assign(4 * (size_t)(nF - nIF), 0.0);

@@ -19,13 +19,14 @@
 
 namespace das {
 
-template <bool RHO>
+template <bool RHO, bool SOLID = false>
 __global__ __launch_bounds__(256) void k_tc_values(DevMesh m, ResParams prm, const double* __restrict__ W, const double* nut, int nf,
                                                    const int* __restrict__ faces, int custom, double* __restrict__ out) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= nf) return;
     double Tnear, kd;
-    body_thermal_coupling<double, RHO>(faces[k], m, prm, W, nut, custom != 0, Tnear, kd);
+    if constexpr (SOLID) body_thermal_coupling_solid<double>(faces[k], m, prm, W, custom != 0, Tnear, kd);  // discipline thermal
+    else body_thermal_coupling<double, RHO>(faces[k], m, prm, W, nut, custom != 0, Tnear, kd);
     out[k] = Tnear;
     out[(long long)nf + k] = kd;
 }

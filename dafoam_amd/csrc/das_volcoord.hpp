@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void k_vc_rows_dual(DevMesh m, RowLayout L, co
 }
 // exact mode, objectives: the tangent of the per-face summand w_k q_k (force, mass flow: constant weights; moment: the arm
 // axis x (Cf - center) follows the dual face centre; area averages: the linearised functional (cN q + cA) |Sf| as in k_fn_area_avg)
-template <bool RHO>
+template <bool RHO, bool SOLID = false>
 __global__ __launch_bounds__(256) void k_fn_dual(DevMeshT<VD> m, ResParams prm, const VD* __restrict__ W, const VD* nut, const VD* gU, FaceFnView fn,
                                                  int isMoment, double a0, double a1, double a2, double c0, double c1, double c2, int areaAvg, double cN0,
                                                  double cN1, double cA0, double cA1, double* __restrict__ fv) {
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void k_fn_dual(DevMeshT<VD> m, ResParams prm, 
     } else if (fn.dir) {
         dir[0] = VD(fn.dir[3 * k]); dir[1] = VD(fn.dir[3 * k + 1]); dir[2] = VD(fn.dir[3 * k + 2]);
     }
-    const VD q = body_facefn<VD, RHO>(f, m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc, fn.pRef);
+    const VD q = facefn_of<VD, RHO, SOLID>(f, m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc, fn.pRef);
     VD v;
     if (areaAvg) v = (fn.group[k] ? (cN1 * q + cA1) : (cN0 * q + cA0)) * m.fg[f].magSf;
     else v = fn.w[k] * q;
@@ -161,14 +161,14 @@ __global__ void k_fn_moment_dir(int nf, const int* __restrict__ faces, const Fac
 // A_g = sum |Sf| over the faces of group g): the host-built weights |Sf| / A carry the metrics, so the product differentiates the
 // LINEARISED functional  fv_k = cN[g] |Sf_k| q_k + cA[g] |Sf_k|  (cN = dF/dN_g, cA = dF/dA_g at the unperturbed mesh) on the
 // perturbed metrics instead
-template <bool RHO>
+template <bool RHO, bool SOLID = false>
 __global__ __launch_bounds__(256) void k_fn_area_avg(DevMesh m, ResParams prm, const double* __restrict__ W, const double* nut, const double* gU,
                                                      FaceFnView fn, double cN0, double cN1, double cA0, double cA1, double* __restrict__ fv) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= fn.nf) return;
     double dir[3] = {0.0, 0.0, 0.0};
     const int f = fn.faces[k];
-    const double q = body_facefn<double, RHO>(f, m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc);
+    const double q = facefn_of<double, RHO, SOLID>(f, m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc);
     const double a = m.fg[f].magSf;
     fv[k] = fn.group[k] ? (cN1 * q + cA1) * a : (cN0 * q + cA0) * a;
 }

@@ -108,6 +108,8 @@ class FoamCase:
     ref_data: Dict[str, dict] = field(default_factory=dict)
     # the patches whose T is (BC_MIXED, 0.0): {patch: (refValue (size,), valueFraction (size,))}, one entry per face of the patch
     mixed_T: Dict[str, tuple] = field(default_factory=dict)
+    # DAHeatTransferFoam, constant/solidProperties: kappa(T) = sum_k kappa_coeffs[k] T^k (`kappa`: one coefficient; `kappaCoeffs`: up to 8)
+    kappa_coeffs: Optional[tuple] = None
 
 
 def hex_block(
@@ -404,7 +406,7 @@ def wall_distance_exact(mesh: PolyMesh, cell_centres, face_centres, face_areas, 
 
 def n_states(case: FoamCase) -> int:
     m = case.mesh
-    if case.solver_name == "DAScalarTransportFoam":
+    if case.solver_name in ("DAScalarTransportFoam", "DAHeatTransferFoam"):
         return m.n_cells
     if case.solver_name == "DASimpleFoam":
         return (6 if case.has_T else 5) * m.n_cells + m.n_faces
@@ -718,7 +720,7 @@ def renumber_case(case: FoamCase, seed=0) -> FoamCase:
     if case.phi is not None:
         out.phi = case.phi[face_perm] * sign
     W = case.states
-    if case.solver_name == "DAScalarTransportFoam":
+    if case.solver_name in ("DAScalarTransportFoam", "DAHeatTransferFoam"):
         out.states = W[old_of_new]
     else:  # [U | scalar cell blocks ... | phi]
         nsc = (W.size - 3 * N - F) // N
@@ -888,6 +890,18 @@ def mixed_cell_case(case: FoamCase, pyramids=(), merges=(), prism_columns=(), di
     # parent's cell values, of the size channel_case uses
     sibling = np.bincount(parent, minlength=N)[parent] > 1
     jit = np.where(sibling[:, None], 1.0 + perturb * rng.standard_normal((nC, 5)), 1.0)
+    if case.solver_name == "DAHeatTransferFoam":  # one cell state; the per-face records of a mixed patch follow the hex a new face came from
+        new.states = W[parent] * jit[:, 0]
+        new.mixed_T = {}
+        for pt_old, pt in zip(m.patches, patches):
+            if pt_old.name not in case.mixed_T:
+                continue
+            slot = np.full(N, -1)
+            slot[m.owner[pt_old.start : pt_old.start + pt_old.size]] = np.arange(pt_old.size)  # (a hex of one block has one face per patch)
+            k = slot[parent[own[pt.start : pt.start + pt.size]]]
+            assert (k >= 0).all()
+            new.mixed_T[pt.name] = tuple(np.asarray(a)[k].copy() for a in case.mixed_T[pt_old.name])
+        return new
     if case.solver_name == "DAScalarTransportFoam":  # frozen flux of the velocity field of scalar_transport_case at the new centres
         Lx = float(m.points[:, 0].max())
         Uc = np.zeros((nC, 3))
@@ -1105,6 +1119,39 @@ def with_mixed_T(case: FoamCase, patch: str, ref_value, value_fraction) -> FoamC
     c.mixed_T[patch] = (np.broadcast_to(np.asarray(ref_value, dtype=np.float64), (size,)).copy(),
                         np.broadcast_to(np.asarray(value_fraction, dtype=np.float64), (size,)).copy())
     return c
+
+
+def heat_transfer_case(nx=6, ny=5, nz=4, lengths=(1.0, 0.2, 0.1), kappa=None, kappa_coeffs=None, mapping="bump", mixed_patches=None,
+                       T_bcs=None, T_range=(300.0, 400.0), seed=0, perturb=0.02) -> FoamCase:
+    """DAHeatTransferFoam (steady conduction in a solid) on one hex_block with the usual six patches.
+    kappa: the constant conductivity; kappa_coeffs: the polynomial kappa(T) = sum_k c_k T^k (one of the two, as constant/solidProperties).
+    mapping: "bump" (bump_mapping: non-orthogonal), None (orthogonal box) or a function on the points.
+    T_bcs: {patch: ("fixedValue", value) | ("zeroGradient",)}; default inlet 400, top 300, the rest zeroGradient.
+    mixed_patches: {patch: (refValue, valueFraction)} - scalars or one entry per face, made mixed as with_mixed_T makes them.
+    The state is a smooth T between T_range[0] and T_range[1] with a seeded perturbation; the case has no phi and no y_wall."""
+    if (kappa is None) == (kappa_coeffs is None):
+        raise ValueError("heat_transfer_case: give kappa or kappa_coeffs (one of the two)")
+    if mapping == "bump":
+        mapping = bump_mapping(0.1, 0.15, lengths[0], lengths[1])
+    mesh = hex_block(nx, ny, nz, lengths, mapping, patch_types=("patch", "patch", "wall", "wall", "wall", "wall"))
+    g = _InputGeometry(mesh)
+    T_bcs = {"inlet": ("fixedValue", 400.0), "top": ("fixedValue", 300.0)} if T_bcs is None else T_bcs
+    bcs = {}
+    for p in mesh.patches:
+        ent = T_bcs.get(p.name, ("zeroGradient",))
+        if ent[0] not in ("fixedValue", "zeroGradient"):
+            raise ValueError(f"heat_transfer_case: patch {p.name}: T is fixedValue, zeroGradient or mixed (mixed_patches), not {ent[0]}")
+        bcs[p.name] = {"T": (BC_FIXED_VALUE, float(ent[1])) if ent[0] == "fixedValue" else (BC_ZERO_GRADIENT, 0.0)}
+    case = FoamCase(mesh=mesh, solver_name="DAHeatTransferFoam", bcs=bcs,
+                    kappa_coeffs=(float(kappa),) if kappa is not None else tuple(float(x) for x in kappa_coeffs))
+    rng = np.random.default_rng(seed)
+    x = g.C / np.array(lengths)
+    s = 0.5 + 0.3 * np.cos(np.pi * x[:, 0]) * (1.0 - 0.5 * x[:, 1]) + 0.15 * np.sin(2.0 * np.pi * x[:, 2] + 0.4) * x[:, 1]
+    T = T_range[0] + (T_range[1] - T_range[0]) * np.clip(s, 0.0, 1.0)
+    case.states = T * (1.0 + perturb * rng.standard_normal(T.size))
+    for nm, (ref, frac) in (mixed_patches or {}).items():
+        case = with_mixed_T(case, nm, ref, frac)
+    return case
 
 
 def turbo_channel_case(nx=7, ny=7, nz=7, omega=(60.0, 0.0, 0.0), origin=(0.0, -0.3, 0.0), transonic=False, mrf=True,

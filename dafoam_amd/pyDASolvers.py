@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import CaseStruct, check, dptr, lib
-from .meshgen import FoamCase
+from .meshgen import BC_MIXED, FoamCase
 
 
 # ----------------------------------------------------------------------------- PETSc stand-ins
@@ -304,6 +304,8 @@ class pyDASolvers:
         solver = argsAll.split()[0] if argsAll else case.solver_name
         if solver not in ("DASolvers", case.solver_name):
             raise ValueError(f"argsAll solver {solver} != case solver {case.solver_name}")
+        if case.solver_name == "DAHeatTransferFoam" and isinstance(pyOptions, dict) and pyOptions.get("fvSource"):
+            raise _capi.DASError("DAHeatTransferFoam: the fvSource option (heat sources) is not built; leave fvSource empty")
         self._case = case
         self._cs = CaseStruct(case)
         L = lib()
@@ -346,9 +348,9 @@ class pyDASolvers:
         m = self._case.mesh
         N, F = m.n_cells, m.n_faces
         layout = {"DASimpleFoam": (1, 3 if getattr(self._case, "has_T", False) else 2), "DARhoSimpleFoam": (1, 3), "DATurboFoam": (1, 3),
-                  "DAScalarTransportFoam": (0, 1)}[self._case.solver_name]
+                  "DAScalarTransportFoam": (0, 1), "DAHeatTransferFoam": (0, 1)}[self._case.solver_name]
         nvec, nscl = layout
-        has_phi = self._case.solver_name != "DAScalarTransportFoam"
+        has_phi = self._case.solver_name not in ("DAScalarTransportFoam", "DAHeatTransferFoam")
         owned = [[] for _ in range(N)]
         if has_phi:
             for f in range(F):
@@ -729,7 +731,9 @@ class pyDASolvers:
             return
         if inputType == "field":
             # run(input), then ONE forward-mode pass with a unit tangent on every cell (das_calc_dfield_product)
-            self.setSolverInput(inputName, inputType, inputSize, inputs)
+            # (DAHeatTransferFoam has no Spalart-Allmaras field to assign: nothing of it reads the input, the product is exact zeros)
+            if self._case.solver_name != "DAHeatTransferFoam":
+                self.setSolverInput(inputName, inputType, inputSize, inputs)
             e = self._field_entry(inputName)
             check(lib().das_calc_dfield_product(self._h, e["fieldName"].encode(), outputName.encode(), outputType.encode(),
                                                 dptr(np.ascontiguousarray(seeds_s, dtype=np.float64)), dptr(product)))
@@ -788,6 +792,8 @@ class pyDASolvers:
         L = lib()
         for fname, fd in (functions or {}).items():
             ftype = fd.get("type")
+            if self._case.solver_name == "DAHeatTransferFoam" and ftype not in ("wallHeatFlux", "variableVolSum"):
+                raise _capi.DASError(f"function {fname}: type {ftype} is not built for DAHeatTransferFoam (wallHeatFlux and variableVolSum of T are)")
             if ftype in ("variableVolSum", "patchMean", "variance"):
                 self._define_field_function(fname, fd)
                 continue
@@ -964,8 +970,8 @@ class pyDASolvers:
         ({"type", "patches", "components": ["forceCoupling"], "pRef"}, DAOutputForceCoupling.C:38-41) and thermalCouplingOutput
         ({"type", "patches", "components": ["thermalCoupling"]}, DAOutputThermalCoupling.C:38-53) are defined on the device.  The
         reference sorts the patches by name before anything else and reads pRef unconditionally; so does this.  The thermal output
-        reads the options `discipline` and `wallDistanceMethod`; discipline thermal is the solid solver DAHeatTransferFoam, which is
-        not built."""
+        reads the options `discipline` and `wallDistanceMethod`; discipline aero is the fluid side (the flow solvers), discipline
+        thermal the solid side (DAHeatTransferFoam)."""
         for oname, od in (outputInfo or {}).items():
             otype = od.get("type")
             if otype not in ("forceCouplingOutput", "thermalCouplingOutput"):
@@ -973,6 +979,8 @@ class pyDASolvers:
                                           "thermalCouplingOutput are)")
             thermal = otype == "thermalCouplingOutput"
             what = f"outputInfo[{oname}]"
+            if not thermal and self._case.solver_name == "DAHeatTransferFoam":
+                raise _capi.DASError(f"{what}: forceCouplingOutput needs a flow solver with a pressure field (DAHeatTransferFoam has no p)")
             if thermal:
                 flags = self._thermal_coupling_checks(what)
             elif "pRef" not in od:
@@ -987,6 +995,14 @@ class pyDASolvers:
         """What the reference's DAOutputThermalCoupling / DAInputThermalCoupling constructors read besides the patches: the options
         `wallDistanceMethod` and `discipline`; and the solver must carry T.  Returns the flags of the C entries."""
         sn = self._case.solver_name
+        if sn == "DAHeatTransferFoam":  # the solid side: [T_nearwall, kappa(T_b) / d], DAOutputThermalCoupling.C:212-241
+            wdm = self._wallDistanceMethod
+            if wdm not in ("default", "daCustom"):
+                raise _capi.DASError(f"wallDistanceMethod: {wdm} not supported! Options are: default and daCustom.")
+            if self._discipline != "thermal":
+                raise _capi.DASError(f"{what}: the thermal coupling of DAHeatTransferFoam needs discipline thermal (discipline {self._discipline} "
+                                     "is the fluid side, built for the flow solvers)")
+            return 2 if wdm == "daCustom" else 0
         if not (sn in ("DARhoSimpleFoam", "DATurboFoam") or (sn == "DASimpleFoam" and getattr(self._case, "has_T", False))):
             raise NotImplementedError(f"{what}: the thermal coupling (thermalCouplingOutput and the thermalCoupling input) is not built for "
                                       f"solvers without a T field ({sn} here; DASimpleFoam with T, DARhoSimpleFoam and DATurboFoam carry one)")
@@ -1067,6 +1083,9 @@ class pyDASolvers:
         """solvePrimal (reference pyDASolvers.pyx solvePrimal -> DASimpleFoam::solvePrimal, DASimpleFoam.C:123-185): converge
         the residuals from the current states.  Returns (fail, info) with info = dict(steps, linearIterations, res0, res,
         history); the converged states are read back with getOFFields / getStates."""
+        if self._case.solver_name == "DAHeatTransferFoam" and not any(
+                p.size > 0 and self._case.bcs.get(p.name, {}).get("T", (1, 0.0))[0] in (0, BC_MIXED) for p in self._case.mesh.patches):
+            raise _capi.DASError("DAHeatTransferFoam: no patch carries a fixedValue or mixed T - the steady conduction problem is singular")
         info4 = np.zeros(4)
         hist = np.zeros(int(maxSteps) + 2)
         rc = check(lib().das_solve_primal(self._h, int(maxSteps), float(relTol), float(absTol), dptr(info4), dptr(hist), hist.size))
@@ -1111,7 +1130,7 @@ class pyDASolvers:
         N, F = m.n_cells, m.n_faces
         names = {"DASimpleFoam": ["U", "p"] + (["T"] if getattr(self._case, "has_T", False) else []) + ["nuTilda", "phi"],
                  "DARhoSimpleFoam": ["U", "p", "T", "nuTilda", "phi"], "DATurboFoam": ["U", "p", "T", "nuTilda", "phi"],
-                 "DAScalarTransportFoam": ["T"]}[self._case.solver_name]
+                 "DAScalarTransportFoam": ["T"], "DAHeatTransferFoam": ["T"]}[self._case.solver_name]
         out, off = [], 0
         for nm in names:
             kind = "vec" if nm == "U" else ("face" if nm == "phi" else "scl")

@@ -37,6 +37,7 @@ extern "C" {
 #define DAS_SOLVER_SCALARTRANSPORTFOAM 1 /* DAScalarTransportFoam */
 #define DAS_SOLVER_RHOSIMPLEFOAM 2       /* DARhoSimpleFoam + SpalartAllmaras (perfect gas, hConst, const transport) */
 #define DAS_SOLVER_TURBOFOAM 3          /* DATurboFoam + SpalartAllmaras: SIMPLEC-consistent / transonic pEqn, "h" energy, MRF */
+#define DAS_SOLVER_HEATTRANSFERFOAM 4   /* DAHeatTransferFoam: steady conduction in a solid, one cell state T, kappa constant or a polynomial in T */
 #define DAS_IS_COMPRESSIBLE(s) ((s) == DAS_SOLVER_RHOSIMPLEFOAM || (s) == DAS_SOLVER_TURBOFOAM)
 
 /* patch types */
@@ -46,6 +47,7 @@ extern "C" {
 #define DAS_PATCH_CYCLIC 3 /* coupled pair (translational or rotational): face k of the patch pairs with face k of patch_neighbour */
 
 /* boundary-condition codes per patch and field */
+#define DAS_MAX_KAPPA_COEFFS 8
 #define DAS_BC_FIXED_VALUE 0
 #define DAS_BC_ZERO_GRADIENT 1
 #define DAS_BC_INLET_OUTLET 2
@@ -91,7 +93,7 @@ typedef struct das_case {
     double nu;
     double relax_U, relax_nuTilda, relax_T;
     double DT, deltaT;        /* DAScalarTransportFoam */
-    const double* y_wall;     /* n_cells, frozen wall distance (may be NULL for ScalarTransport) */
+    const double* y_wall;     /* n_cells, frozen wall distance (may be NULL for ScalarTransport and HeatTransfer) */
     const double* phi_frozen; /* n_faces, DAScalarTransportFoam only */
     const double* T_old;      /* n_cells, DAScalarTransportFoam only */
     /* DARhoSimpleFoam thermophysicalProperties (reference DAResidual.C:179-293): Cp [J/kg/K], molWeight [kg/kmol],
@@ -126,6 +128,10 @@ typedef struct das_case {
      * n_internal_faces, boundary-face order; the entries of other patches are not read).  NULL with such a patch: refValue 0, fraction 0. */
     const double* bc_T_mixed_ref;
     const double* bc_T_mixed_frac;
+    /* DAHeatTransferFoam, constant/solidProperties (reference DAResidualHeatTransferFoam.C:40-53,105-132): the conductivity
+     * kappa(T) = sum_k kappa_coeffs[k] T^k; `kappa` is one coefficient, `kappaCoeffs` up to DAS_MAX_KAPPA_COEFFS of them */
+    int n_kappa_coeffs;
+    double kappa_coeffs[DAS_MAX_KAPPA_COEFFS];
 } das_case_t;
 
 const char* das_last_error(void);
@@ -323,6 +329,8 @@ int das_define_face_function(das_solver_t* s, const char* name, const char* type
  *                               with the T field); w_f = |Sf| / sum |Sf| (flags & 1: byUnitArea) or |Sf|; snGrad from the patch field
  *                               (wallDistanceMethod default) or (x_b - x_c) / |C_f - C_c| (flags & 2: daCustom).  Solvers without a T
  *                               field return DAS_ERR_ARG                                    DAFunctionWallHeatFlux.C:115-304
+ *                               DAHeatTransferFoam: q_f = kappa(T_b) snGrad(T)_f, same weights and flags (:229-261) - the only face
+ *                               function of that solver, every other type returns DAS_ERR_ARG naming the type
  * flags & 8: calcRefVar, F <- (F - ref)^2, for these two types.  das_define_face_function(...) is
  * das_define_face_function_ex(..., flags = 1, ref = 0). */
 int das_define_face_function_ex(das_solver_t* s, const char* name, const char* type, const int* patch_ids, const int* patch_group, int npatch,
@@ -384,6 +392,8 @@ int das_calc_force_coupling(das_solver_t* s, const char* name, double* out, int 
  *   wallDistanceMethod daCustom (deltaCoeff = 1 / |C_f - C_c|) instead of the face's delta coefficient.  The size is
  *   das_get_output_size(name, "thermalCouplingOutput") = 2 nF.
  * das_calc_thermal_coupling   <- calcOutput(name, "thermalCouplingOutput", output): n = that size.  No atomics: the same bits on every call.
+ *   DAHeatTransferFoam (discipline thermal, :212-241): kappa / d = kappa(T_b) deltaCoeff, everything else as above; the caller checks
+ *   the discipline option (pyDASolvers: a coupling on DAHeatTransferFoam needs "thermal", one on a flow solver "aero").
  * Derivatives: outputType "thermalCouplingOutput", as for forceCouplingOutput above.  Solvers without a T field (DAScalarTransportFoam,
  * DASimpleFoam without T) and sharded solvers return DAS_ERR_ARG. */
 int das_define_thermal_coupling(das_solver_t* s, const char* name, const int* patch_ids, int npatch, int flags);
@@ -394,7 +404,8 @@ int das_calc_thermal_coupling(das_solver_t* s, const char* name, double* out, in
  * das_set_thermal_coupling_input    <- setSolverInput(name, "thermalCoupling", ...): in[k] becomes the refValue of face k and in[nF + k], the
  *   neighbour's kappa / d (nk), its valueFraction nk / (myK + nk), with myK this side's kappa / d (the second half of the output) at the
  *   current states, geometry and boundary values.  The fraction then stays as it is - a constant of the residual, of the Jacobians and of
- *   the volCoord products - until the input is set again.
+ *   the volCoord products - until the input is set again.  (DAHeatTransferFoam with a kappa that varies with T: myK reads T_b, which the
+ *   records of the moment give, so setting the same input twice does not give the same fraction twice.)
  * das_get_patch_mixed                   the refValue and valueFraction of the faces of one mixed patch, as they stand.
  * das_calc_dthermal_coupling_product <- calcJacTVecProduct(name, "thermalCoupling", inputs, outputName, outputType, seeds, product) after
  *   the input has been set: product = [d output / d input]^T seeds (n = 2 nF), outputType "residual" (seeds: one per state), "function"
