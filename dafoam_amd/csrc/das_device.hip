@@ -41,6 +41,7 @@
 #include "das_facefn.hpp"
 #include "das_forcecoupling.hpp"
 #include "das_thermalcoupling.hpp"
+#include "das_heatsource.hpp"
 #include "das_simple.hpp"
 #include "das_simple_host.hpp"
 
@@ -873,7 +874,23 @@ struct das_solver {
         }
     };
     std::map<std::string, CellFn> cellFunctions;
-    int colorRounds = 0;        // rounds of the speculative device colouring (0: another algorithm ran)
+    // heat sources of DAHeatTransferFoam (the fvSource option; das_heatsource.hpp).  The map keeps them in name order, the order of the
+    // reference's toc() walk, so the accumulation does not depend on the order of definition.
+    struct HeatSource {
+        int kind = DAS_HS_CYLINDERSMOOTH;
+        // cylinderSmooth: heatSourcePars = center(3), axis(3), radius, length, power; cylinderToCell: p1(3), p2(3), radius, |p2 - p1|, power
+        double pars[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        double eps = 0.0;
+        int snapCell = -1;         // snapCenter2Cell: the cell found at definition (the centre follows its C), -1 otherwise
+        std::vector<int> members;  // cylinderToCell: the cell set, chosen at definition and kept
+        DevBuf<unsigned char> d_member;
+        double volumeTotal = 0.0;  // Vt at the current metrics and parameters
+    };
+    std::map<std::string, HeatSource> heatSources;
+    DevBuf<double> d_src, d_hsVt;       // fvSource per cell (allocated with the first source); Vt per source + the total of the field
+    DevBuf<Dual<1>> d_hsPart, d_hsVtD;  // partial sums of either scalar type; dual sums of the parameter passes
+    double hsSourceTotal = 0.0;         // sum_c fvSource_c V_c
+    int colorRounds = 0;       // rounds of the speculative device colouring (0: another algorithm ran)
     DevBuf<double> d_betaFI, d_dBetaFI;  // `field` input betaFINuTilda and its tangent (das_set_field / das_calc_dfield_product)
     long long geomVersion = 0;  // bumped by das_update_of_mesh
     // mesh-sensitivity product (das_volcoord.hpp): point influence sets + colours (topology only: built once), device copies
@@ -933,6 +950,9 @@ static void need_init(das_solver* s) {
     DAS_CHECK(s, DAS_ERR_ARG, "null solver handle");
     DAS_CHECK(s->inited, DAS_ERR_STATE, "das_init_solver has not been called (or failed): no GPU path available");
 }
+// the fvSource field from the metrics on the device and the parameters as they stand (nothing to do without a source or a device);
+// check: wait for the totals, keep them and refuse a total volume that is zero or not finite
+static void refresh_heat_sources(das_solver* s, bool check);
 
 // sum of a small device buffer over the ranks: the native all-reduce in stream order, else the legacy host callback (single rank: nothing)
 static void rank_allreduce(das_solver* s, double* p, long long cnt, hipStream_t st) {
@@ -1218,10 +1238,14 @@ static das_mat* assemble(das_solver* s, int isPC, int mode) {
     } else {
         const double delta = s->opt.getd("adjPartDerivFDStep.State");
         if (s->d_R0.n != (size_t)n) { s->d_R0.alloc(n); s->d_Wp.alloc(n); }
-        eval_residual<double>(s->dm, s->cp, prm, s->d_W.p, s->d_R0.p, s->wk, s->d_phiF.p, s->d_Told.p, st);
+        // the heat sources do not depend on the states: the difference quotients are taken of the residual without them, so that the
+        // term does not cost the difference its low digits and the matrix has the bits it has without a source
+        DevMesh dmJ = s->dm;
+        dmJ.src = nullptr;
+        eval_residual<double>(dmJ, s->cp, prm, s->d_W.p, s->d_R0.p, s->wk, s->d_phiF.p, s->d_Told.p, st);
         for (int col = 0; col < s->nColors; col++) {
             hipLaunchKernelGGL(k_perturb, dim3(nblk(n, B)), dim3(B), 0, st, n, s->d_W.p, s->d_colors.p, s->d_scale.p, col, delta, s->d_Wp.p);
-            eval_residual<double>(s->dm, s->cp, prm, s->d_Wp.p, s->d_R.p, s->wk, s->d_phiF.p, s->d_Told.p, st);
+            eval_residual<double>(dmJ, s->cp, prm, s->d_Wp.p, s->d_R.p, s->wk, s->d_phiF.p, s->d_Told.p, st);
             const long long q0 = jc.cl_ptr[col], cnt = jc.cl_ptr[col + 1] - q0;
             if (cnt > 0)
                 hipLaunchKernelGGL(k_scatter_fd, dim3(nblk(cnt, 16)), dim3(B), 0, st, cnt, s->d_R.p, s->d_R0.p, 1.0 / delta, c.cl_cols.p + q0,
@@ -3267,6 +3291,7 @@ int das_init_solver(das_solver_t* s, int device) {
     s->d_tmp2.alloc(s->n);
     s->inited = true;
     compute_scales(s);
+    refresh_heat_sources(s, true);
     return DAS_OK;
     DAS_CATCH
 }
@@ -3303,6 +3328,7 @@ int das_update_of_mesh(das_solver_t* s, const double* points) {
         s->d_cg.upload(m.cg);
     }
     compute_scales(s);
+    refresh_heat_sources(s, true);  // Vt, the volume of a cell set and a snapped centre follow the metrics; the set and the cell stay
     return DAS_OK;
     DAS_CATCH
 }
@@ -4957,6 +4983,261 @@ static RowLayout residual_row_layout(das_solver* s) {
     for (int b = 0; b < L.nb; b++) { L.off[b] = stn.states[b].offset; L.kind[b] = (int)stn.states[b].kind; }
     return L;
 }
+// ---- heat sources of DAHeatTransferFoam (reference DAFvSourceHeatSource.C; kernels: das_heatsource.hpp) -----------------------------
+static void need_heat_source_solver(das_solver* s) {
+    DAS_CHECK(s, DAS_ERR_ARG, "null solver handle");
+    DAS_CHECK(s->cp.solver == DAS_SOLVER_HEATTRANSFERFOAM, DAS_ERR_ARG,
+              "the fvSource heat sources (and the fvSourcePar input) are built for DAHeatTransferFoam only: no fvSource on a flow solver or on DAScalarTransportFoam");
+    DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "the fvSource heat sources run on an undecomposed solver (sharded solvers are not supported)");
+}
+static das_solver::HeatSource& get_heat_source(das_solver* s, const char* name) {
+    auto it = s->heatSources.find(name ? name : "");
+    DAS_CHECK(it != s->heatSources.end(), DAS_ERR_ARG, std::string("fvSource has no heat source ") + (name ? name : "(null)"));
+    return it->second;
+}
+extern "C++" {
+template <class P>
+static HsView<P> heat_source_view(const das_solver::HeatSource& h) {
+    HsView<P> v;
+    v.kind = h.kind; v.member = h.d_member.p; v.field = nullptr;
+    for (int i = 0; i < 3; i++) { v.center[i] = P(h.pars[i]); v.axis[i] = P(h.pars[3 + i]); }
+    v.radius = P(h.pars[6]); v.length = P(h.pars[7]); v.power = P(h.pars[8]);
+    v.eps = h.eps; v.snapCell = h.snapCell;
+    return v;
+}
+// out[0] = the two-stage sum of k_hs_partial / k_hs_final over all cells
+template <class R, class P, class G>
+static void heat_source_sum(das_solver* s, const HsView<P>& v, const CellGeomT<G>* cg, const double* psi, int byV, const R* vt, R* out) {
+    const int nC = s->mesh.nC, nb = std::min(nblk(nC, 256), DAS_HS_MAX_BLOCKS);
+    if (s->d_hsPart.n < (size_t)DAS_HS_MAX_BLOCKS) s->d_hsPart.alloc(DAS_HS_MAX_BLOCKS);
+    R* part = reinterpret_cast<R*>(s->d_hsPart.p);
+    hipLaunchKernelGGL((k_hs_partial<R, P, G>), dim3(nb), dim3(256), 0, s->stream, v, nC, cg, psi, byV, vt, part);
+    hipLaunchKernelGGL((k_hs_final<R>), dim3(1), dim3(256), 0, s->stream, nb, (const R*)part, out);
+}
+}  // extern "C++"
+static void refresh_heat_sources(das_solver* s, bool check) {
+    if (s->heatSources.empty() || !s->inited) return;
+    const int nC = s->mesh.nC, K = (int)s->heatSources.size();
+    if (s->d_src.n != (size_t)nC) s->d_src.alloc(nC);
+    if (s->d_hsVt.n < (size_t)K + 1) s->d_hsVt.alloc(K + 1);
+    s->dm.src = s->d_src.p;
+    const CellGeom* cg = s->d_cg.p;
+    int k = 0;
+    for (auto& e : s->heatSources) {
+        das_solver::HeatSource& h = e.second;
+        if (h.kind == DAS_HS_CYLINDERTOCELL && h.d_member.n != (size_t)nC) {
+            std::vector<unsigned char> mask(nC, 0);
+            for (int c : h.members) mask[c] = 1;
+            h.d_member.upload(mask);
+        }
+        const HsView<double> v = heat_source_view<double>(h);
+        heat_source_sum<double, double, double>(s, v, cg, nullptr, 0, nullptr, s->d_hsVt.p + k);
+        hipLaunchKernelGGL((k_hs_apply<double, double, double>), dim3(nblk(nC, 256)), dim3(256), 0, s->stream, v, nC, cg, (const double*)(s->d_hsVt.p + k), (int)(k == 0),
+                           s->d_src.p);
+        k++;
+    }
+    HsView<double> fv{};
+    fv.kind = DAS_HS_FIELD; fv.field = s->d_src.p; fv.snapCell = -1;
+    heat_source_sum<double, double, double>(s, fv, cg, nullptr, 0, nullptr, s->d_hsVt.p + K);
+    DAS_HIP(hipGetLastError());
+    if (!check) return;
+    std::vector<double> tot(K + 1);
+    DAS_HIP(hipMemcpyAsync(tot.data(), s->d_hsVt.p, (K + 1) * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    k = 0;
+    for (auto& e : s->heatSources) {
+        DAS_CHECK(std::isfinite(tot[k]) && tot[k] != 0.0, DAS_ERR_ARG,
+                  "fvSource " + e.first + ": the total volume of the heat source is " + std::to_string(tot[k]) + " (zero or not finite): the source reaches no cell");
+        e.second.volumeTotal = tot[k++];
+    }
+    s->hsSourceTotal = tot[K];
+}
+// sum_c psi_c nrm_c dq_c / dpars[idx] of one cylinderSmooth source: one forward pass with Dual<1> parameters on the double mesh (s_c and
+// Vt are dual; the residual body is not run: dR_c / dp = dq_c / dp, times V_c in the unnormalised row).  unsnap: a snapped centre is
+// taken as the parameter it replaces, at its current place
+static double heat_source_par_pass(das_solver* s, const das_solver::HeatSource& h, int idx, const double* d_psi, bool unsnap) {
+    typedef Dual<1> D;
+    HsView<D> v = heat_source_view<D>(h);
+    if (unsnap && h.snapCell >= 0) {
+        for (int i = 0; i < 3; i++) v.center[i] = D(s->mesh.cg[h.snapCell].C[i]);
+        v.snapCell = -1;
+    }
+    D& p = idx < 3 ? v.center[idx] : (idx < 6 ? v.axis[idx - 3] : (idx == 6 ? v.radius : (idx == 7 ? v.length : v.power)));
+    p.d[0] = 1.0;
+    if (s->d_hsVtD.n < 2) s->d_hsVtD.alloc(2);
+    const int byV = make_params(s->cp, s->opt, 0).normT ? 0 : 1;
+    heat_source_sum<D, D, double>(s, v, (const CellGeom*)s->d_cg.p, nullptr, 0, nullptr, s->d_hsVtD.p);
+    heat_source_sum<D, D, double>(s, v, (const CellGeom*)s->d_cg.p, d_psi, byV, (const D*)s->d_hsVtD.p, s->d_hsVtD.p + 1);
+    DAS_HIP(hipGetLastError());
+    D r;
+    DAS_HIP(hipMemcpyAsync(&r, s->d_hsVtD.p + 1, sizeof(D), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    return r.d[0];
+}
+
+// das_define_heat_source <- one entry of the fvSource option, type heatSource (DAFvSourceHeatSource.C:30-128)
+int das_define_heat_source(das_solver_t* s, const char* name, const char* kind, const double* pars, double eps, int snapCenter2Cell) {
+    DAS_TRY
+    need_heat_source_solver(s);
+    DAS_CHECK(name && kind && pars, DAS_ERR_ARG, "fvSource: null argument");
+    const std::string nm = name, kd = kind, what = "fvSource " + nm;
+    const Mesh& m = s->mesh;
+    das_solver::HeatSource h;
+    if (kd == "cylinderToCell") {
+        // OpenFOAM's cylinderToCell on the cell centres of this moment: between the two end planes and within the radius of the axis
+        h.kind = DAS_HS_CYLINDERTOCELL;
+        const double* p1 = pars;
+        const double* p2 = pars + 3;
+        const double radius = pars[6], a[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};
+        const double aa = a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
+        DAS_CHECK(aa > 0.0 && radius > 0.0 && std::isfinite(pars[7]), DAS_ERR_ARG, what + ": cylinderToCell needs p1 != p2, radius > 0 and a finite power");
+        for (int c = 0; c < m.nC; c++) {
+            const double d[3] = {m.cg[c].C[0] - p1[0], m.cg[c].C[1] - p1[1], m.cg[c].C[2] - p1[2]};
+            const double mg = d[0] * a[0] + d[1] * a[1] + d[2] * a[2];
+            if (mg > 0.0 && mg < aa && (d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) - mg * mg / aa < radius * radius) h.members.push_back(c);
+        }
+        DAS_CHECK(!h.members.empty(), DAS_ERR_ARG, what + ": cylinderToCell selects no cell (an empty set cannot carry the power)");
+        for (int i = 0; i < 6; i++) h.pars[i] = pars[i];
+        h.pars[6] = radius; h.pars[7] = std::sqrt(aa); h.pars[8] = pars[7];
+    } else if (kd == "cylinderSmooth") {
+        h.kind = DAS_HS_CYLINDERSMOOTH;
+        for (int i = 0; i < 9; i++) h.pars[i] = pars[i];
+        h.eps = eps;
+        DAS_CHECK(eps > 0.0, DAS_ERR_ARG, what + ": cylinderSmooth needs eps > 0");
+        DAS_CHECK(pars[3] * pars[3] + pars[4] * pars[4] + pars[5] * pars[5] > 0.0, DAS_ERR_ARG, what + ": cylinderSmooth needs a non-zero axis");
+        if (snapCenter2Cell) {
+            // primitiveMesh::findCell as DAUtility::myFindCell calls it: the cells whose face planes all have the point on their inner side
+            int found = 0;
+            for (int c = 0; c < m.nC; c++) {
+                bool in = true;
+                for (int q = m.cf_ptr[c]; q < m.cf_ptr[c + 1] && in; q++) {
+                    const int fe = m.cf_face[q], f = fe & 0x7fffffff;
+                    const FaceGeom& g = m.fg[f];
+                    const double dot = (pars[0] - g.Cf[0]) * g.Sf[0] + (pars[1] - g.Cf[1]) * g.Sf[1] + (pars[2] - g.Cf[2]) * g.Sf[2];
+                    in = (fe < 0 ? -dot : dot) <= 0.0;
+                }
+                if (in) { found++; h.snapCell = c; }
+            }
+            DAS_CHECK(found == 1, DAS_ERR_ARG,
+                      what + ": snapCenter2Cell: there should be only one cell found while " + std::to_string(found)
+                          + " was returned. Please adjust center such that it is located completely within a cell in the mesh domain. The center should not be "
+                            "outside of the mesh domain or on a mesh face");
+        }
+    } else {
+        DAS_CHECK(false, DAS_ERR_ARG, what + ": source: " + kd + " not supported! Options are: cylinderToCell and cylinderSmooth!");
+    }
+    s->heatSources.erase(nm);
+    s->heatSources.emplace(nm, std::move(h));
+    refresh_heat_sources(s, true);
+    return DAS_OK;
+    DAS_CATCH
+}
+// das_set_heat_source_pars <- DAInputFvSourcePar::run (DAInputFvSourcePar.C:75-140): heatSourcePars[indices[k]] = values[k], then updateFvSource
+int das_set_heat_source_pars(das_solver_t* s, const char* name, const int* indices, int n, const double* values) {
+    DAS_TRY
+    need_heat_source_solver(s);
+    DAS_CHECK(indices && values && n >= 0, DAS_ERR_ARG, "fvSourcePar: null argument");
+    das_solver::HeatSource& h = get_heat_source(s, name);
+    DAS_CHECK(h.kind == DAS_HS_CYLINDERSMOOTH, DAS_ERR_ARG,
+              std::string("fvSourcePar: fvSource ") + name + " is a cylinderToCell source; heatSourcePars exist for cylinderSmooth sources only");
+    for (int k = 0; k < n; k++)
+        DAS_CHECK(indices[k] >= 0 && indices[k] < 9, DAS_ERR_ARG,
+                  std::string("fvSourcePar: index ") + std::to_string(indices[k]) + " of fvSource " + name + " is out of range (a heat source has 9 parameters)");
+    for (int k = 0; k < n; k++) h.pars[indices[k]] = values[k];
+    DAS_CHECK(h.pars[3] * h.pars[3] + h.pars[4] * h.pars[4] + h.pars[5] * h.pars[5] > 0.0, DAS_ERR_ARG, std::string("fvSource ") + name + ": cylinderSmooth needs a non-zero axis");
+    refresh_heat_sources(s, true);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_get_heat_source_info(das_solver_t* s, const char* name, double* pars9, double* volumeTotal, double* sourceTotal, int* snappedCell) {
+    DAS_TRY
+    need_heat_source_solver(s);
+    const das_solver::HeatSource& h = get_heat_source(s, name);
+    if (pars9) std::copy(h.pars, h.pars + 9, pars9);
+    if (volumeTotal) *volumeTotal = h.volumeTotal;
+    if (sourceTotal) *sourceTotal = s->hsSourceTotal;
+    if (snappedCell) *snappedCell = h.snapCell;
+    return DAS_OK;
+    DAS_CATCH
+}
+// the cells of a cylinderToCell source (cap entries at most are written); returns their number
+int das_get_heat_source_cells(das_solver_t* s, const char* name, int* cells, int cap) {
+    DAS_TRY
+    need_heat_source_solver(s);
+    const das_solver::HeatSource& h = get_heat_source(s, name);
+    if (cells) std::copy(h.members.begin(), h.members.begin() + std::min((size_t)std::max(cap, 0), h.members.size()), cells);
+    return (int)h.members.size();
+    DAS_CATCH
+}
+int das_get_fv_source(das_solver_t* s, double* out) {
+    DAS_TRY
+    need_heat_source_solver(s);
+    need_init(s);
+    DAS_CHECK(out, DAS_ERR_ARG, "null argument");
+    if (s->heatSources.empty()) { std::fill(out, out + s->mesh.nC, 0.0); return DAS_OK; }
+    DAS_HIP(hipMemcpyAsync(out, s->d_src.p, (size_t)s->mesh.nC * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    return DAS_OK;
+    DAS_CATCH
+}
+// das_calc_dfvsourcepar_product <- calcJacTVecProduct(name, "fvSourcePar", ...) after the input has been set: product[k] =
+// seeds . d output / d heatSourcePars[indices[k]].  No function and no coupling output reads the source: exact zeros without a pass.  The
+// first three parameters of a snapped source are not read either.
+int das_calc_dfvsourcepar_product(das_solver_t* s, const char* name, const int* indices, int n, const char* outputName, const char* outputType,
+                                  const double* seeds, double* product) {
+    DAS_TRY
+    need_heat_source_solver(s);
+    need_init(s);
+    DAS_CHECK(indices && outputType && seeds && product && n >= 0, DAS_ERR_ARG, "fvSourcePar: null argument");
+    const das_solver::HeatSource& h = get_heat_source(s, name);
+    DAS_CHECK(h.kind == DAS_HS_CYLINDERSMOOTH, DAS_ERR_ARG,
+              std::string("fvSourcePar: fvSource ") + name + " is a cylinderToCell source; heatSourcePars exist for cylinderSmooth sources only");
+    for (int k = 0; k < n; k++)
+        DAS_CHECK(indices[k] >= 0 && indices[k] < 9, DAS_ERR_ARG,
+                  std::string("fvSourcePar: index ") + std::to_string(indices[k]) + " of fvSource " + name + " is out of range (a heat source has 9 parameters)");
+    const std::string ot = outputType;
+    DAS_CHECK(ot == "residual" || ot == "function" || is_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
+    if (ot != "residual") {
+        if (is_coupling(ot)) (void)coupling_size(s, ot, outputName);
+        else if (!find_cell_function(s, outputName)) (void)get_function(s, outputName);
+        std::fill(product, product + n, 0.0);
+        return DAS_OK;
+    }
+    DevBuf<double> d_psi;
+    d_psi.upload(seeds, (size_t)s->n);
+    for (int k = 0; k < n; k++) product[k] = (h.snapCell >= 0 && indices[k] < 3) ? 0.0 : heat_source_par_pass(s, h, indices[k], d_psi.p, false);
+    return DAS_OK;
+    DAS_CATCH
+}
+
+// The volCoord product and the heat sources.  A point moves the source of EVERY cell through the total Vt, and a snapped centre moves with
+// its cell - neither fits the colouring, which lets a point reach the rows of its own influence set only.  Inside the coloured passes both
+// are therefore frozen data; what they add is rank one per source and goes onto the per-cell tangents before the gather, as
+// k_vc_cellfn_all does for divByTotalVol:
+//   beta = -(power / Vt^2) sum_c psi_c s_c nrm_c   multiplies (s_c V_c)' of every cell          (nrm_c = 1, or V_c unnormalised)
+//   gamma_j = sum_c psi_c nrm_c dq_c / dcenter_j   multiplies C_j' of the snapped cell          (the fvSourcePar pass, unsnapped)
+// view: the source with its centre where it is now and no snapped cell - the frozen form the passes evaluate
+struct HsRank1 { HsView<double> view; int snapCell; double beta, gamma[3]; };
+static void heat_source_rank1_terms(das_solver* s, const double* d_psi, int byV, std::vector<HsRank1>& terms) {
+    for (auto& e : s->heatSources) {
+        const das_solver::HeatSource& h = e.second;
+        HsRank1 r{heat_source_view<double>(h), h.snapCell, 0.0, {0.0, 0.0, 0.0}};
+        heat_source_sum<double, double, double>(s, r.view, (const CellGeom*)s->d_cg.p, d_psi, byV, nullptr, s->d_hsVt.p);
+        double S = 0.0;
+        DAS_HIP(hipMemcpyAsync(&S, s->d_hsVt.p, sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        DAS_HIP(hipStreamSynchronize(s->stream));
+        r.beta = -h.pars[8] / (h.volumeTotal * h.volumeTotal) * S;
+        if (h.snapCell >= 0) {
+            for (int j = 0; j < 3; j++) {
+                r.gamma[j] = heat_source_par_pass(s, h, j, d_psi, true);
+                r.view.center[j] = s->mesh.cg[h.snapCell].C[j];
+            }
+            r.view.snapCell = -1;
+        }
+        terms.push_back(r);
+    }
+}
+
 // the end of a product: the vector and the bad-volume flag come down, the timing goes into info4
 static void finish_volcoord(das_solver* s, const double* d_out, double* product, const char* badMessage, double t0, long long passes, double* info4) {
     das_solver::VolCoord& v = s->vc;
@@ -5024,6 +5305,18 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
         function_face_slots(m, *fn, cptr, cidx);
         d_fnPtr.upload(cptr); d_fnIdx.upload(cidx);
     }
+    // heat sources (residual rows only): the totals and a snapped centre are frozen inside the coloured passes (the dual src array carries
+    // the local tangent through C_c and V_c of the cell itself) and come back as rank-one terms - heat_source_rank1_terms
+    std::vector<HsRank1> hsTerms;
+    DevBuf<D> d_srcD, d_vtD;
+    if (!isCell && !isFn && !s->heatSources.empty()) {
+        heat_source_rank1_terms(s, d_seeds.p, prm0.normT ? 0 : 1, hsTerms);
+        std::vector<D> vt;
+        for (auto& e : s->heatSources) vt.push_back(D(e.second.volumeTotal));
+        d_vtD.upload(vt);
+        d_srcD.alloc((size_t)m.nC);
+        dmD.src = d_srcD.p;
+    }
     const double t0 = wall_seconds();
     long long passes = 0;
     for (int col = 0; col < I.nColors; col++) {
@@ -5041,8 +5334,14 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
                     hipLaunchKernelGGL(k_vc_cellfn_terms, dim3(nblk((long long)cfn->cell.size(), B)), dim3(B), 0, st, cfn->view(), (const CellGeomT<D>*)d_cgD.p,
                                        cell_function_src(s, *cfn), cellB, d_tc.p);
             } else if (!isFn) {
+                for (size_t k = 0; k < hsTerms.size(); k++)
+                    hipLaunchKernelGGL((k_hs_apply<D, double, D>), dim3(nblk(m.nC, B)), dim3(B), 0, st, hsTerms[k].view, m.nC, (const CellGeomT<D>*)d_cgD.p,
+                                       (const D*)(d_vtD.p + k), (int)(k == 0), d_srcD.p);
                 eval_residual<D, D>(dmD, s->cp, prm0, d_Wd.p, d_Rd.p, s->wk1, s->d_phiF.p, s->d_Told.p, st);
                 hipLaunchKernelGGL(k_vc_rows_dual, dim3(nblk(m.nC, B)), dim3(B), 0, st, s->dm, L, (const double*)d_seeds.p, (const D*)d_Rd.p, d_tc.p);
+                for (const HsRank1& r : hsTerms)
+                    hipLaunchKernelGGL(k_hs_vc_rank1, dim3(nblk(m.nC, B)), dim3(B), 0, st, r.view, m.nC, (const CellGeomT<D>*)d_cgD.p, r.snapCell, r.beta, r.gamma[0],
+                                       r.gamma[1], r.gamma[2], d_tc.p);
             } else {
                 const ResParams prm = s->wk1.bind(s->cp.solver, s->dm.nC, s->dm.nF, prm0);
                 const bool isLoc = DAS_FN_BASE(fn->kind) == DAS_FN_LOCATION;  // the linearised functional sum w_eff a_f; no state is read
@@ -5163,6 +5462,7 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
             v.d_fg0.release(); v.d_cg0.release(); v.d_Rp.release(); v.d_Rm.release(); v.d_seeds.release();
             v.d_X.release(); v.d_X0.release(); v.d_tc.release(); v.d_fvp.release(); v.d_fvm.release();
             if (fn) fn->uploaded = false;  // moment arms were recomputed from perturbed face centres: re-upload the host copy
+            try { refresh_heat_sources(s, false); } catch (...) {}  // the source field of the unperturbed metrics
         }
         das_solver::FaceFn* fn;
     } restore{s, (fn && fn->isMoment) ? fn : nullptr};
@@ -5182,8 +5482,26 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
         function_face_slots(m, *fn, cptr, cidx);
         v.d_fnPtr.upload(cptr); v.d_fnIdx.upload(cidx);
     }
+    std::vector<HsRank1> hsTerms;
+    DevBuf<double> d_vt0, d_tc2;
+    double sideSign = 1.0;
+    if (!isFn && !s->heatSources.empty()) {
+        heat_source_rank1_terms(s, v.d_seeds.p, prm0.normT ? 0 : 1, hsTerms);
+        std::vector<double> vt;
+        for (auto& e : s->heatSources) vt.push_back(e.second.volumeTotal);
+        d_vt0.upload(vt);
+        d_tc2.alloc((size_t)m.nC);
+    }
     auto output_pass = [&](double* Rout, double* fvOut) {
         if (!isFn) {
+            // the source field of the moved mesh with the totals and a snapped centre frozen, as in the exact mode; their rank-one terms
+            // are collected side by side (+ and -) in d_tc2
+            for (size_t k = 0; k < hsTerms.size(); k++) {
+                hipLaunchKernelGGL((k_hs_apply<double, double, double>), dim3(nblk(m.nC, B)), dim3(B), 0, st, hsTerms[k].view, m.nC, (const CellGeom*)s->d_cg.p,
+                                   (const double*)(d_vt0.p + k), (int)(k == 0), s->d_src.p);
+                hipLaunchKernelGGL(k_hs_fd_rank1, dim3(nblk(m.nC, B)), dim3(B), 0, st, hsTerms[k].view, m.nC, (const CellGeom*)s->d_cg.p, hsTerms[k].snapCell,
+                                   sideSign * hsTerms[k].beta, sideSign * hsTerms[k].gamma[0], sideSign * hsTerms[k].gamma[1], sideSign * hsTerms[k].gamma[2], d_tc2.p);
+            }
             eval_residual<double>(s->dm, s->cp, prm0, s->d_W.p, Rout, s->wk, s->d_phiF.p, s->d_Told.p, st);
             return;
         }
@@ -5208,7 +5526,9 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
         if (np == 0) continue;
         const int* pts = v.d_cpoints.p + I.cptr[col];
         for (int axis = 0; axis < 3; axis++) {
+            if (!hsTerms.empty()) DAS_HIP(hipMemsetAsync(d_tc2.p, 0, (size_t)m.nC * sizeof(double), st));
             for (int side = 0; side < 2; side++) {
+                sideSign = side == 0 ? 1.0 : -1.0;
                 hipLaunchKernelGGL(k_move_points, dim3(nblk(np, B)), dim3(B), 0, st, np, pts, (const double*)v.d_h.p, side == 0 ? 1.0 : -1.0, axis,
                                    (const double*)v.d_X0.p, v.d_X.p);
                 device_geometry(s, t, v.d_X.p);
@@ -5216,10 +5536,11 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
                 passes++;
             }
             hipLaunchKernelGGL(k_move_points, dim3(nblk(np, B)), dim3(B), 0, st, np, pts, (const double*)v.d_h.p, 0.0, axis, (const double*)v.d_X0.p, v.d_X.p);
-            if (!isFn)
+            if (!isFn) {
                 hipLaunchKernelGGL(k_vc_rows, dim3(nblk(m.nC, B)), dim3(B), 0, st, s->dm, L, (const double*)v.d_seeds.p, (const double*)v.d_Rp.p,
                                    (const double*)v.d_Rm.p, v.d_tc.p);
-            else
+                if (!hsTerms.empty()) hipLaunchKernelGGL(k_hs_add, dim3(nblk(m.nC, B)), dim3(B), 0, st, m.nC, (const double*)d_tc2.p, v.d_tc.p);
+            } else
                 hipLaunchKernelGGL(k_vc_fn_cells, dim3(nblk(m.nC, B)), dim3(B), 0, st, m.nC, (const int*)v.d_fnPtr.p, (const int*)v.d_fnIdx.p, seeds[0],
                                    (const double*)v.d_fvp.p, (const double*)v.d_fvm.p, v.d_tc.p);
             hipLaunchKernelGGL(k_vc_gather, dim3(nblk(np, 4)), dim3(256), 0, st, np, pts, (const long long*)v.d_ptr.p, (const int*)v.d_cells.p,

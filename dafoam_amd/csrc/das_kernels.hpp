@@ -8,6 +8,7 @@
 //   nutUSpaldingWallFunction calcNut/calcUTau   src/adjoint/DAMisc/nutUSpaldingWallFunctionDF/...DF.C:42-150
 //   DAResidualScalarTransportFoam::calcResiduals src/adjoint/DAResidual/DAResidualScalarTransportFoam.C:57-84
 //   DAResidualHeatTransferFoam::calcResiduals   src/adjoint/DAResidual/DAResidualHeatTransferFoam.C:97-132   (body_heat_grad / body_heat)
+//   DAFvSourceHeatSource::calcFvSource          src/adjoint/DAFvSource/DAFvSourceHeatSource.C:236-321       (body_heat_source)
 //   residual normalisation macros               src/include/DAMacroFunctions.H:28-51
 //   DAResidualRhoSimpleFoam::calcResiduals      src/adjoint/DAResidual/DAResidualRhoSimpleFoam.C:84-211   (RHO = true)
 //   DAResidualTurboFoam::calcResiduals          src/adjoint/DAResidual/DAResidualTurboFoam.C:66-233       (RHO = true, prm.turbo)
@@ -43,6 +44,9 @@ struct DevMeshT {  // G: the scalar of the metrics (double; Dual<1> in the mesh-
     const int* cyc;     // boundary face -> paired face of a cyclic pair, -1 otherwise
     // patches with a mixed T (DAS_BC_MIXED): per boundary face refValue, valueFraction and their tangents; null when no patch is mixed
     const double* mixed = nullptr;
+    // DAHeatTransferFoam with heat sources (the fvSource option): fvSource per cell [W/m^3], in the scalar of the metrics; null when no
+    // source is defined - nothing is loaded then
+    const G* src = nullptr;
 };
 typedef DevMeshT<double> DevMesh;
 // the mixed-T record of boundary face f (a mesh face index); it is read only where the patch's T_code says mixed
@@ -1428,7 +1432,34 @@ DAS_HD void body_heat_grad(int c, const DevMeshT<G>& m, const ResParams& prm, co
     for (int i = 0; i < 3; i++) gradT[3LL * c + i] = gT[i] * rV;
 }
 
-// TRes = (laplacian(kappa, T)) & T   (Gauss linear corrected; kappa interpolated linearly to the faces; DAResidualHeatTransferFoam.C:97-102)
+// the shape s_c of one cylinderSmooth heat source at the cell centre C (DAFvSourceHeatSource.C:258-293): with n = axis / |axis| and
+// c = C - center the reference takes the COMPONENT-WISE product c o n (it writes diag(c) & n) as the axial part - not the projection
+// n (c . n) - and c - c o n as the radial part; s = sA sR, each factor 1 inside and a Gaussian of the overshoot over eps outside.  The
+// two switches select: a cell that sits on the centre (A = R = 0) gives s = 1 with a zero tangent (dsqrt at 0).
+// P: the scalar of the parameters, G: of the metrics, R: of the result (Dual<1> when either of them is).
+template <class R, class P, class G>
+DAS_HD R body_heat_source(const P* center, const P* axis, const P& radius, const P& length, double eps, const G* C) {
+    const P an = dsqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
+    R a2(0.0), r2(0.0);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        const R c = R(C[i]) - R(center[i]);
+        const R ca = c * R(axis[i] / an);
+        const R cr = c - ca;
+        a2 += ca * ca;
+        r2 += cr * cr;
+    }
+    const R A = dsqrt(a2), Rr = dsqrt(r2);
+    const R halfL = R(length * 0.5), rad = R(radius);
+    const double ie2 = 1.0 / (eps * eps);
+    R s(1.0);
+    if (val(A) > val(halfL)) { const R d = A - halfL; s = dexp(-(d * d) * ie2); }
+    if (val(Rr) > val(rad)) { const R d = Rr - rad; s = s * dexp(-(d * d) * ie2); }
+    return s;
+}
+
+// TRes = (laplacian(kappa, T) + fvSource) & T   (Gauss linear corrected; kappa interpolated linearly to the faces; fvSource the heat
+// sources per unit volume, when there are any; DAResidualHeatTransferFoam.C:97-102)
 template <class T, class G>
 DAS_HD void body_heat(int c, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* gradT, T* R) {
     const CellGeomT<G>& cgc = m.cg[c];
@@ -1456,6 +1487,7 @@ DAS_HD void body_heat(int c, const DevMeshT<G>& m, const ResParams& prm, const T
         }
     }
     T res = sum * (1.0 / cgc.V);
+    if (m.src) res = res + m.src[c];
     if (!prm.normT) res = res * cgc.V;
     R[c] = res;
 }

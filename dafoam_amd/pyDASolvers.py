@@ -304,9 +304,8 @@ class pyDASolvers:
         solver = argsAll.split()[0] if argsAll else case.solver_name
         if solver not in ("DASolvers", case.solver_name):
             raise ValueError(f"argsAll solver {solver} != case solver {case.solver_name}")
-        if case.solver_name == "DAHeatTransferFoam" and isinstance(pyOptions, dict) and pyOptions.get("fvSource"):
-            raise _capi.DASError("DAHeatTransferFoam: the fvSource option (heat sources) is not built; leave fvSource empty")
         self._case = case
+        self._fvSource = self._checked_fv_source(pyOptions.get("fvSource") if isinstance(pyOptions, dict) else None)
         self._cs = CaseStruct(case)
         L = lib()
         self._h = L.das_create(self._cs.byref())
@@ -330,6 +329,7 @@ class pyDASolvers:
         self._define_functions(pyOptions.get("function") if isinstance(pyOptions, dict) else None)
         self._define_outputs(pyOptions.get("outputInfo") if isinstance(pyOptions, dict) else None)
         self._define_thermal_inputs()
+        self._define_heat_sources()
         if case.states is not None:  # FoamCase.states is always in "state" ordering (input data)
             check(lib().das_update_of_fields(self._h, dptr(np.ascontiguousarray(case.states, dtype=np.float64))))
 
@@ -388,7 +388,7 @@ class pyDASolvers:
         [type, value] pairs produced by pyDAFoam._getDefOptions, pyDAFoam.py:823-844)."""
         flat = {}
         opts = {k: (v[1] if isinstance(v, list) and len(v) == 2 and isinstance(v[0], type) else v) for k, v in pyOptions.items()}
-        _flatten("", {k: v for k, v in opts.items() if not k.startswith("amdCase") and k not in ("function", "inputInfo", "outputInfo", "primalBC")}, flat)
+        _flatten("", {k: v for k, v in opts.items() if not k.startswith("amdCase") and k not in ("function", "inputInfo", "outputInfo", "primalBC", "fvSource")}, flat)
         if flat.get("adjStateOrdering") == "cell" and getattr(self, "_perm", None) is not None:
             flat.pop("adjStateOrdering")  # handled at this boundary (permutation); the library stays in "state" ordering
         L = lib()
@@ -440,6 +440,8 @@ class pyDASolvers:
             return 2 * sum(sizes[p] for p in self._input_entry(inputName, inputType)["patches"])
         if inputType == "volCoord":  # reference DAInputVolCoord.H size() = nLocalPoints * 3
             return self.getNLocalPoints() * 3
+        if inputType == "fvSourcePar":  # reference DAInputFvSourcePar.H size() = indices.size()
+            return len(self._fv_source_par_entry(inputName)[1])
         return check(lib().das_get_input_size(self._h, inputName.encode(), inputType.encode()))
 
     # -- boundary-value inputs (reference src/adjoint/DAInput/DAInputPatchVelocity.C, DAInputPatchVar.C) ---------
@@ -510,6 +512,11 @@ class pyDASolvers:
             # DAInputThermalCoupling::run: refValue and, from the neighbour's kappa / d, the valueFraction of the mixed T patches
             self._input_entry(inputName, inputType)
             return check(lib().das_set_thermal_coupling_input(self._h, inputName.encode(), dptr(np.ascontiguousarray(inputs, dtype=np.float64)), inputSize))
+        if inputType == "fvSourcePar":
+            # DAInputFvSourcePar::run (reference DAInputFvSourcePar.C:75-140): heatSourcePars[indices] = input, then updateFvSource
+            name, idx = self._fv_source_par_entry(inputName)
+            return check(lib().das_set_heat_source_pars(self._h, name.encode(), idx.ctypes.data_as(_capi.c_int_p), idx.size,
+                                                        dptr(np.ascontiguousarray(inputs, dtype=np.float64))))
         if inputType not in ("patchVelocity", "patchVar"):
             raise _capi.DASError(f"inputType not supported on this path: {inputType}")
         field, val, _ = self._patch_input_tangents(inputName, inputType, inputs)
@@ -727,6 +734,15 @@ class pyDASolvers:
             out = np.zeros(inputSize)
             check(lib().das_calc_dthermal_coupling_product(self._h, inputName.encode(), outputName.encode(), outputType.encode(),
                                                            dptr(np.ascontiguousarray(seeds_s, dtype=np.float64)), dptr(out), inputSize))
+            product[:] = out
+            return
+        if inputType == "fvSourcePar":
+            # run(input), then one forward-mode pass per selected parameter (das_calc_dfvsourcepar_product)
+            self.setSolverInput(inputName, inputType, inputSize, inputs)
+            name, idx = self._fv_source_par_entry(inputName)
+            out = np.zeros(inputSize)
+            check(lib().das_calc_dfvsourcepar_product(self._h, name.encode(), idx.ctypes.data_as(_capi.c_int_p), idx.size, outputName.encode(),
+                                                      outputType.encode(), dptr(np.ascontiguousarray(seeds_s, dtype=np.float64)), dptr(out)))
             product[:] = out
             return
         if inputType == "field":
@@ -1040,6 +1056,92 @@ class pyDASolvers:
                     raise _capi.DASError(f"{what}: patch {p} does not carry a mixed T patch field (the thermalCoupling input writes its "
                                          "refValue and valueFraction)")
             check(lib().das_define_thermal_coupling_input(self._h, iname.encode(), ids.ctypes.data_as(_capi.c_int_p), ids.size, flags))
+
+    # -- heat sources: the fvSource option of DAHeatTransferFoam (reference DAFvSourceHeatSource.C) and the fvSourcePar input ----------
+    _HEAT_SOURCE_KEYS = {"cylinderToCell": ("p1", "p2", "radius", "power"),
+                         "cylinderSmooth": ("center", "axis", "radius", "length", "power", "eps")}
+
+    def _checked_fv_source(self, fvSource):
+        """The fvSource option as the constructor accepts it: empty anywhere; on DAHeatTransferFoam entries of type heatSource with source
+        cylinderToCell or cylinderSmooth and the keys of that source.  Everything else is refused, and every message carries the word
+        fvSource and the entry's name."""
+        fvSource = dict(fvSource or {})
+        sn = self._case.solver_name
+        for name, e in fvSource.items():
+            what = f"fvSource[{name}]"
+            if sn != "DAHeatTransferFoam":
+                raise _capi.DASError(f"{what}: the fvSource option is not built for {sn} (no momentum sources; heat sources run on DAHeatTransferFoam)")
+            if not isinstance(e, dict):
+                raise _capi.DASError(f"{what}: a dictionary is expected")
+            if e.get("type") != "heatSource":
+                raise _capi.DASError(f"{what}: type {e.get('type')} is not built (actuatorDisk, actuatorLine, actuatorPoint and uniformPressureGradient "
+                                     "are momentum sources; DAHeatTransferFoam takes type heatSource)")
+            if "source" not in e:
+                raise _capi.DASError(f"{what}: the key source is missing (cylinderToCell or cylinderSmooth)")
+            if e["source"] not in self._HEAT_SOURCE_KEYS:
+                raise _capi.DASError(f"{what}: source: {e['source']} not supported! Options are: cylinderToCell and cylinderSmooth!")
+            missing = [k for k in self._HEAT_SOURCE_KEYS[e["source"]] if k not in e]
+            if missing:
+                raise _capi.DASError(f"{what}: source {e['source']} needs the key(s) {', '.join(missing)}")
+            for k, n in (("p1", 3), ("p2", 3), ("center", 3), ("axis", 3)):
+                if k in e and k in self._HEAT_SOURCE_KEYS[e["source"]] and np.size(e[k]) != n:
+                    raise _capi.DASError(f"{what}: {k} needs {n} components")
+        return fvSource
+
+    def _define_heat_sources(self):
+        for name in sorted(self._fvSource):
+            e = self._fvSource[name]
+            if e["source"] == "cylinderToCell":
+                pars = np.array(list(e["p1"]) + list(e["p2"]) + [e["radius"], e["power"]], dtype=np.float64)
+                eps, snap = 0.0, 0
+            else:
+                pars = np.array(list(e["center"]) + list(e["axis"]) + [e["radius"], e["length"], e["power"]], dtype=np.float64)
+                eps, snap = float(e["eps"]), int(bool(e.get("snapCenter2Cell", 0)))
+            check(lib().das_define_heat_source(self._h, name.encode(), e["source"].encode(), dptr(pars), eps, snap))
+
+    def _fv_source_par_entry(self, inputName):
+        """(fvSourceName, indices) of an inputInfo entry of type fvSourcePar (reference DAInputFvSourcePar.C:38-72: all nine by default)."""
+        e = self._input_entry(inputName, "fvSourcePar")
+        name = e.get("fvSourceName")
+        if name not in self._fvSource:
+            raise _capi.DASError(f"inputInfo[{inputName}]: fvSourceName {name} is not an entry of the fvSource option")
+        if self._fvSource[name]["source"] != "cylinderSmooth":
+            raise _capi.DASError(f"inputInfo[{inputName}]: fvSource[{name}] is a {self._fvSource[name]['source']} source; the fvSourcePar input drives the "
+                                 "heatSourcePars, which exist for cylinderSmooth sources only")
+        idx = np.array(e.get("indices", list(range(9))), dtype=np.int32)
+        if idx.size and (idx.min() < 0 or idx.max() >= 9):
+            raise _capi.DASError(f"inputInfo[{inputName}]: index {int(idx.max() if idx.max() >= 9 else idx.min())} of fvSource[{name}] is out of range "
+                                 "(a heat source has 9 parameters)")
+        return name, np.ascontiguousarray(idx)
+
+    def updateFvSource(self):
+        """DAFvSource::updateFvSource: the field follows the parameters and the metrics at once here (das_set_heat_source_pars,
+        das_update_of_mesh); nothing is left to do."""
+        return None
+
+    def getFvSource(self):
+        """The fvSource field [W/m^3], one value per cell."""
+        out = np.zeros(self._case.mesh.n_cells)
+        check(lib().das_get_fv_source(self._h, dptr(out)))
+        return out
+
+    def heatSourceInfo(self, name):
+        """What the reference prints per source, and more: the parameters, volumeTotal (the total volume of the source), sourceTotal (the sum
+        of fvSource V over the whole field [W]), the snapped cell and its centre (None without snapCenter2Cell), the cells of a
+        cylinderToCell source."""
+        pars, vt, st, cell = np.zeros(9), C.c_double(0.0), C.c_double(0.0), C.c_int(-1)
+        check(lib().das_get_heat_source_info(self._h, name.encode(), dptr(pars), C.byref(vt), C.byref(st), C.byref(cell)))
+        n = check(lib().das_get_heat_source_cells(self._h, name.encode(), None, 0))
+        cells = np.zeros(n, dtype=np.int32)
+        if n:
+            check(lib().das_get_heat_source_cells(self._h, name.encode(), cells.ctypes.data_as(_capi.c_int_p), n))
+        center = None
+        if cell.value >= 0:
+            Cc = np.zeros(3 * self._case.mesh.n_cells)
+            check(lib().das_get_geometry(self._h, None, None, dptr(Cc), None, None, None, None, None))
+            center = Cc[3 * cell.value:3 * cell.value + 3].copy()
+        return dict(pars=pars, volumeTotal=vt.value, sourceTotal=st.value, snappedCell=(cell.value if cell.value >= 0 else None), snappedCenter=center,
+                    cells=cells)
 
     def getPatchMixedT(self, patchName):
         """(refValue, valueFraction) of the faces of a patch with a mixed T, as they stand on the solver."""

@@ -417,7 +417,36 @@ int das_get_patch_mixed(das_solver_t* s, int patch, double* refValue, double* va
 int das_calc_dthermal_coupling_product(das_solver_t* s, const char* inputName, const char* outputName, const char* outputType, const double* seeds,
                                        double* product, int n);
 
-/* das_calc_jac_t_vec_product <- calcJacTVecProduct(inputName,inputType,inputs,outputName,outputType,seeds,product)
+/* Heat sources of DAHeatTransferFoam: the fvSource option, entries of type heatSource (reference DAFvSourceHeatSource.C:30-321), and the
+ * fvSourcePar input (DAInputFvSourcePar.C:38-140).  TRes = laplacian(kappa, T) + fvSource (DAResidualHeatTransferFoam.C:90-102), fvSource
+ * [W/m^3] the sum of the sources in the order of their names.  The field depends on the metrics and the parameters only: it is computed when
+ * a source is defined, when parameters are set and by das_update_of_mesh, never per residual evaluation.  Two-stage sums in a fixed order,
+ * no atomics: the same bits on every call.
+ * das_define_heat_source      kind "cylinderToCell": pars = p1(3), p2(3), radius, power (8 values); the cells with 0 < d.a < a.a and
+ *   |d|^2 - (d.a)^2 / a.a < radius^2 (a = p2 - p1, d = C - p1) are chosen now and kept, q = power / (their volume, at the current metrics);
+ *   an empty set is an error.  kind "cylinderSmooth": pars = the nine heatSourcePars center(3), axis(3), radius, length, power, and eps;
+ *   q = power s / sum s V with s of :258-293 (the axial part is the component-wise product of C - center and the unit axis).
+ *   snapCenter2Cell: the one cell that contains center is found now (none or several: an error) and center is C of that cell from then on.
+ * das_set_heat_source_pars    heatSourcePars[indices[k]] = values[k] of a cylinderSmooth source, then the field again (updateFvSource).
+ * das_get_heat_source_info    the parameters (cylinderToCell: p1, p2, radius, |p2 - p1|, power), the total volume of the source, the
+ *   total sum fvSource V of the whole field [W] and the snapped cell (-1: none); any output may be NULL.
+ * das_get_heat_source_cells   the cell set of a cylinderToCell source (at most cap entries are written); returns its size.
+ * das_get_fv_source           the field, one value per cell (zeros while no source is defined).
+ * das_calc_dfvsourcepar_product <- calcJacTVecProduct(name, "fvSourcePar", ...): product[k] = seeds . d output / d heatSourcePars[indices[k]].
+ *   outputType "residual": one forward pass per index with dual-number parameters (s and the total volume are dual; the residual body is
+ *   not run, d TRes / d p = d fvSource / d p); "function" and the coupling outputs: exact zeros, nothing of them reads the source.  The
+ *   centre of a snapped source is not read: exact zeros for indices 0-2.
+ * Every other solver and a sharded solver return DAS_ERR_ARG with a message that names fvSource; so do an unknown source name, an index
+ * outside 0-8 and parameters asked of a cylinderToCell source. */
+int das_define_heat_source(das_solver_t* s, const char* name, const char* kind, const double* pars, double eps, int snapCenter2Cell);
+int das_set_heat_source_pars(das_solver_t* s, const char* name, const int* indices, int n, const double* values);
+int das_get_heat_source_info(das_solver_t* s, const char* name, double* pars9, double* volumeTotal, double* sourceTotal, int* snappedCell);
+int das_get_heat_source_cells(das_solver_t* s, const char* name, int* cells, int cap);
+int das_get_fv_source(das_solver_t* s, double* out);
+int das_calc_dfvsourcepar_product(das_solver_t* s, const char* name, const int* indices, int n, const char* outputName, const char* outputType,
+                                  const double* seeds, double* product);
+
+/* das_calc_jac_t_vec_product <-calcJacTVecProduct(inputName,inputType,inputs,outputName,outputType,seeds,product)
  *   pyDASolvers.pyx:208-235 (DASolver.C:1690-1839).  Supported pair on this path: inputType "stateVar",
  *   outputType "residual": product = D_s (dR/dW)^T seeds  (normalizeJacTVecProduct, DASolver.C:1443-1553);
  *   outputType "function" (outputName = function name, one seed): product = seed * D_s dF/dW  (mphys_dafoam.py:746-801). */
