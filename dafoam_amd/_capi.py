@@ -318,6 +318,12 @@ _SIGS = {
     "das_get_heat_source_cells": (C.c_int, [_VP, C.c_char_p, c_int_p, C.c_int]),
     "das_get_fv_source": (C.c_int, [_VP, c_double_p]),
     "das_calc_dfvsourcepar_product": (C.c_int, [_VP, C.c_char_p, c_int_p, C.c_int, C.c_char_p, C.c_char_p, c_double_p, c_double_p]),
+    "das_define_actuator_disk": (C.c_int, [_VP, C.c_char_p, C.c_char_p, c_double_p, C.c_char_p, C.c_double, C.c_int]),
+    "das_set_actuator_disk_pars": (C.c_int, [_VP, C.c_char_p, c_int_p, C.c_int, c_double_p]),
+    "das_get_actuator_disk_info": (C.c_int, [_VP, C.c_char_p, c_double_p, c_double_p, c_int_p]),
+    "das_get_actuator_disk_cells": (C.c_int, [_VP, C.c_char_p, c_int_p, C.c_int]),
+    "das_get_fv_source_vector": (C.c_int, [_VP, c_double_p]),
+    "das_calc_dactuatordiskpar_product": (C.c_int, [_VP, C.c_char_p, c_int_p, C.c_int, C.c_char_p, C.c_char_p, c_double_p, c_double_p]),
     "das_get_input_size": (C.c_int, [_VP, C.c_char_p, C.c_char_p]),
     "das_get_output_size": (C.c_int, [_VP, C.c_char_p, C.c_char_p]),
     "das_calc_jac_t_vec_product": (

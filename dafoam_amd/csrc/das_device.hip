@@ -42,6 +42,7 @@
 #include "das_forcecoupling.hpp"
 #include "das_thermalcoupling.hpp"
 #include "das_heatsource.hpp"
+#include "das_actuatordisk.hpp"
 #include "das_simple.hpp"
 #include "das_simple_host.hpp"
 
@@ -119,11 +120,12 @@ __global__ __launch_bounds__(CPB * 8) void k_grad_fp(DevMesh m, ResParams prm, c
         *dst = sum * (1.0 / m.cg[c0 + oc].V);
     }
 }
-template <class T, bool RHO, class G = double>
+// SRC: with the momentum source of the actuator disks (m.src3 set); the kernels without it are the ones of before
+template <class T, bool RHO, class G = double, bool SRC = false>
 __global__ __launch_bounds__(256) void k_cell(DevMeshT<G> m, ResParams prm, const T* __restrict__ W, const T* nut, const T* gU, const T* gP,
                                               const T* gN, const T* gH, T* R, T* rAU, T* HbyA) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < m.nC) body_cell<T, RHO>(c, m, prm, W, nut, gU, gP, gN, gH, R, rAU, HbyA, (const T*)prm.wTU);
+    if (c < m.nC) body_cell<T, RHO, G, SRC>(c, m, prm, W, nut, gU, gP, gN, gH, R, rAU, HbyA, (const T*)prm.wTU);
 }
 // Round 6: the cell pass of DASimpleFoam split the finite-volume way (das_kernels.hpp body_fcoef / body_bcoef / body_cell2): every
 // internal face evaluated ONCE by its own thread (the monolithic k_cell evaluates it from both sides inside a serial six-trip loop that
@@ -140,12 +142,12 @@ __global__ __launch_bounds__(256) void k_bcoef(DevMesh m, ResParams prm, const T
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < m.nF - m.nIF) body_bcoef<T>(b, m, prm, W, nut, gU, brec);
 }
-template <class T>
+template <class T, bool SRC = false>
 __global__ __launch_bounds__(256) void k_cell2(DevMesh m, ResParams prm, const T* __restrict__ W, const T* __restrict__ nut, const T* __restrict__ gU,
                                                const T* __restrict__ gP, const T* __restrict__ gN, const T* __restrict__ fc, const T* __restrict__ brec,
                                                T* __restrict__ R, T* __restrict__ rAU, T* __restrict__ HbyA) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < m.nC) body_cell2<T>(c, m, prm, W, nut, gU, gP, gN, fc, brec, R, rAU, HbyA);
+    if (c < m.nC) body_cell2<T, SRC>(c, m, prm, W, nut, gU, gP, gN, fc, brec, R, rAU, HbyA);
 }
 template <class T, bool RHO, class G = double>
 __global__ __launch_bounds__(256) void k_face(DevMeshT<G> m, ResParams prm, const T* __restrict__ W, const T* nut, const T* gP, const T* rAU,
@@ -321,11 +323,18 @@ static void eval_residual(const DevMeshT<G>& dm, const CaseParams& cp, const Res
                 if (wk.brec.n != (size_t)DAS_BREC_N * nBF) wk.brec.alloc((size_t)DAS_BREC_N * nBF);
                 if (dm.nIF > 0) hipLaunchKernelGGL((k_fcoef<T>), dim3(nblk(dm.nIF, B)), dim3(B), 0, st, dm, prm, W, (const T*)wk.nut.p, (const T*)wk.gU.p, (const T*)wk.gN.p, wk.fc.p);
                 if (nBF > 0) hipLaunchKernelGGL((k_bcoef<T>), dim3(nblk(nBF, B)), dim3(B), 0, st, dm, prm, W, (const T*)wk.nut.p, (const T*)wk.gU.p, wk.brec.p);
-                hipLaunchKernelGGL((k_cell2<T>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, W, (const T*)wk.nut.p, (const T*)wk.gU.p, (const T*)wk.gP.p, (const T*)wk.gN.p,
-                                   (const T*)wk.fc.p, (const T*)wk.brec.p, R, wk.rAU.p, wk.HbyA.p);
+                if (dm.src3)
+                    hipLaunchKernelGGL((k_cell2<T, true>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, W, (const T*)wk.nut.p, (const T*)wk.gU.p, (const T*)wk.gP.p,
+                                       (const T*)wk.gN.p, (const T*)wk.fc.p, (const T*)wk.brec.p, R, wk.rAU.p, wk.HbyA.p);
+                else
+                    hipLaunchKernelGGL((k_cell2<T>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, W, (const T*)wk.nut.p, (const T*)wk.gU.p, (const T*)wk.gP.p,
+                                       (const T*)wk.gN.p, (const T*)wk.fc.p, (const T*)wk.brec.p, R, wk.rAU.p, wk.HbyA.p);
             }
         }
-        if (!split)
+        if (!split && dm.src3)
+            hipLaunchKernelGGL((k_cell<T, false, G, true>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, W, wk.nut.p, wk.gU.p, wk.gP.p, wk.gN.p,
+                               (const T*)wk.gH.p, R, wk.rAU.p, wk.HbyA.p);
+        else if (!split)
             hipLaunchKernelGGL((k_cell<T, false, G>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, W, wk.nut.p, wk.gU.p, wk.gP.p, wk.gN.p,
                                (const T*)wk.gH.p, R, wk.rAU.p, wk.HbyA.p);
         hipLaunchKernelGGL((k_face<T, false, G>), dim3(nblk(dm.nF, B)), dim3(B), 0, st, dm, prm, W, wk.nut.p, wk.gP.p, wk.rAU.p, wk.HbyA.p, wk.q.p, R);
@@ -890,6 +899,21 @@ struct das_solver {
     DevBuf<double> d_src, d_hsVt;       // fvSource per cell (allocated with the first source); Vt per source + the total of the field
     DevBuf<Dual<1>> d_hsPart, d_hsVtD;  // partial sums of either scalar type; dual sums of the parameter passes
     double hsSourceTotal = 0.0;         // sum_c fvSource_c V_c
+    // actuator disks of DASimpleFoam (the fvSource option, type actuatorDisk; das_actuatordisk.hpp), in name order like the heat sources
+    struct ActuatorDisk {
+        int smooth = 1, adjustThrust = 0;
+        // the 13 actuatorDiskPars: center(3), direction(3), innerRadius, outerRadius, scale, POD, expM, expN, targetThrust
+        // (cylinderAnnulusToCell: center = (p1 + p2) / 2, direction = p2 - p1; expM, expN and targetThrust are not read)
+        double pars[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        double eps = 0.0, rotSign = 1.0;
+        std::vector<int> members;  // cylinderAnnulusToCell: the cell set, chosen at definition and kept
+        DevBuf<unsigned char> d_member;
+        double scale = 0.0, thrustSum = 0.0, torqueSum = 0.0, unitThrust = 0.0;  // at the current metrics and parameters
+    };
+    std::map<std::string, ActuatorDisk> actuatorDisks;
+    DevBuf<double> d_src3, d_adSums;  // fvSource (3 per cell, allocated with the first disk); per disk: unit sums(2), scale, sums(2)
+    DevBuf<Dual<1>> d_adPart, d_adD;  // partial sums of either scalar type; the sums and the scale of a dual pass
+    DevBuf<int> d_adBad;              // set where a cell centre sits on the axis of a disk
     int colorRounds = 0;       // rounds of the speculative device colouring (0: another algorithm ran)
     DevBuf<double> d_betaFI, d_dBetaFI;  // `field` input betaFINuTilda and its tangent (das_set_field / das_calc_dfield_product)
     long long geomVersion = 0;  // bumped by das_update_of_mesh
@@ -953,6 +977,8 @@ static void need_init(das_solver* s) {
 // the fvSource field from the metrics on the device and the parameters as they stand (nothing to do without a source or a device);
 // check: wait for the totals, keep them and refuse a total volume that is zero or not finite
 static void refresh_heat_sources(das_solver* s, bool check);
+// the same for the actuator disks of DASimpleFoam (check: also refuse a cell centre on the axis of a disk)
+static void refresh_actuator_disks(das_solver* s, bool check);
 
 // sum of a small device buffer over the ranks: the native all-reduce in stream order, else the legacy host callback (single rank: nothing)
 static void rank_allreduce(das_solver* s, double* p, long long cnt, hipStream_t st) {
@@ -3292,6 +3318,7 @@ int das_init_solver(das_solver_t* s, int device) {
     s->inited = true;
     compute_scales(s);
     refresh_heat_sources(s, true);
+    refresh_actuator_disks(s, true);
     return DAS_OK;
     DAS_CATCH
 }
@@ -3329,6 +3356,7 @@ int das_update_of_mesh(das_solver_t* s, const double* points) {
     }
     compute_scales(s);
     refresh_heat_sources(s, true);  // Vt, the volume of a cell set and a snapped centre follow the metrics; the set and the cell stay
+    refresh_actuator_disks(s, true);  // the field and an adjustThrust scale follow the metrics; a cell set stays
     return DAS_OK;
     DAS_CATCH
 }
@@ -3576,6 +3604,8 @@ static void run_simple_sweeps(das_solver* s, int nSweeps, double alphaP, double 
 int das_simple_iteration(das_solver_t* s, int nSweeps, double alphaP, double linTol, int maxLinIters, double* info3) {
     DAS_TRY
     DAS_CHECK(s && nSweeps >= 0 && alphaP > 0.0 && linTol > 0.0 && maxLinIters > 0, DAS_ERR_ARG, "das_simple_iteration: bad argument");
+    DAS_CHECK(s->actuatorDisks.empty(), DAS_ERR_ARG,
+              "das_simple_iteration: the SIMPLE sweep does not carry the fvSource actuator disks (its U equation has no source term); use das_solve_primal");
     run_simple_sweeps(s, nSweeps, alphaP, linTol, maxLinIters, info3);
     return DAS_OK;
     DAS_CATCH
@@ -5238,6 +5268,342 @@ static void heat_source_rank1_terms(das_solver* s, const double* d_psi, int byV,
     }
 }
 
+// ---- actuator disks of DASimpleFoam (reference DAFvSourceActuatorDisk.C; kernels: das_actuatordisk.hpp) -----------------------------
+static void need_actuator_disk_solver(das_solver* s) {
+    DAS_CHECK(s, DAS_ERR_ARG, "null solver handle");
+    DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM, DAS_ERR_ARG,
+              "the fvSource actuator disks are built for DASimpleFoam only: not for DARhoSimpleFoam (its fvSourceEnergy = fvSource . U is not built), DATurboFoam, "
+              "DAScalarTransportFoam or DAHeatTransferFoam");
+    DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "the fvSource actuator disks run on an undecomposed solver (sharded solvers are not supported)");
+}
+static das_solver::ActuatorDisk& get_actuator_disk(das_solver* s, const char* name) {
+    auto it = s->actuatorDisks.find(name ? name : "");
+    DAS_CHECK(it != s->actuatorDisks.end(), DAS_ERR_ARG, std::string("fvSource has no actuator disk ") + (name ? name : "(null)"));
+    return it->second;
+}
+static void check_actuator_disk_pars(const das_solver::ActuatorDisk& a, const std::string& what) {
+    const double* p = a.pars;
+    DAS_CHECK(p[3] * p[3] + p[4] * p[4] + p[5] * p[5] > 0.0, DAS_ERR_ARG, what + ": the direction (p2 - p1) must not be zero");
+    DAS_CHECK(p[7] > p[6] && p[6] >= 0.0, DAS_ERR_ARG, what + ": 0 <= innerRadius < outerRadius is needed");
+    for (int i = 0; i < 13; i++) DAS_CHECK(std::isfinite(p[i]), DAS_ERR_ARG, what + ": a parameter is not finite");
+    if (a.smooth) DAS_CHECK(a.eps > 0.0 && 2.0 * a.eps < p[7] - p[6], DAS_ERR_ARG, what + ": cylinderAnnulusSmooth needs 0 < eps < (outerRadius - innerRadius) / 2");
+}
+extern "C++" {
+template <class P>
+static AdView<P> actuator_disk_view(const das_solver::ActuatorDisk& a) {
+    AdView<P> v;
+    v.smooth = a.smooth; v.adjustThrust = a.adjustThrust; v.member = a.smooth ? nullptr : a.d_member.p;
+    for (int i = 0; i < 3; i++) { v.center[i] = P(a.pars[i]); v.direction[i] = P(a.pars[3 + i]); }
+    v.innerRadius = P(a.pars[6]); v.outerRadius = P(a.pars[7]); v.scale = P(a.pars[8]); v.POD = P(a.pars[9]);
+    v.expM = P(a.pars[10]); v.expN = P(a.pars[11]); v.targetThrust = P(a.pars[12]);
+    v.eps = a.eps; v.rotSign = a.rotSign;
+    return v;
+}
+// the parameter idx of a dual view
+static Dual<1>& actuator_disk_par(AdView<Dual<1>>& v, int idx) {
+    if (idx < 3) return v.center[idx];
+    if (idx < 6) return v.direction[idx - 3];
+    Dual<1>* rest[7] = {&v.innerRadius, &v.outerRadius, &v.scale, &v.POD, &v.expM, &v.expN, &v.targetThrust};
+    return *rest[idx - 6];
+}
+// out2 = {sum fAxial V, sum fCirc V} at the scale scale[0] (null: 1) through k_ad_partial / k_ad_final
+template <class R, class P, class G>
+static void actuator_disk_sums(das_solver* s, const AdView<P>& v, const CellGeomT<G>* cg, const R* scale, R* out2) {
+    const int nC = s->mesh.nC, nb = std::min(nblk(nC, 256), DAS_HS_MAX_BLOCKS);
+    if (s->d_adPart.n < (size_t)2 * DAS_HS_MAX_BLOCKS) s->d_adPart.alloc((size_t)2 * DAS_HS_MAX_BLOCKS);
+    R* part = reinterpret_cast<R*>(s->d_adPart.p);
+    hipLaunchKernelGGL((k_ad_partial<R, P, G>), dim3(nb), dim3(256), 0, s->stream, v, nC, cg, scale, part);
+    hipLaunchKernelGGL((k_ad_final<R>), dim3(1), dim3(256), 0, s->stream, nb, (const R*)part, out2);
+}
+// the whole field of the disks views[0..K) into src3 (3 nC); work: 5 slots per disk {unit sums(2), scale, sums(2)}; withSums: the
+// thrust and torque sums at the effective scale as well
+template <class R, class P, class G>
+static void actuator_disk_field(das_solver* s, const std::vector<AdView<P>>& views, const CellGeomT<G>* cg, R* work, R* src3, bool withSums) {
+    const int nC = s->mesh.nC;
+    if (s->d_adBad.n < 1) { s->d_adBad.alloc(1); DAS_HIP(hipMemsetAsync(s->d_adBad.p, 0, sizeof(int), s->stream)); }
+    for (size_t k = 0; k < views.size(); k++) {
+        R* w = work + 5 * k;
+        if (views[k].adjustThrust) actuator_disk_sums<R, P, G>(s, views[k], cg, (const R*)nullptr, w);
+        hipLaunchKernelGGL((k_ad_scale<R, P>), dim3(1), dim3(64), 0, s->stream, views[k], (const R*)w, w + 2);
+        hipLaunchKernelGGL((k_ad_apply<R, P, G>), dim3(nblk(nC, 256)), dim3(256), 0, s->stream, views[k], nC, cg, (const R*)(w + 2), (int)(k == 0), src3, s->d_adBad.p);
+        if (withSums) actuator_disk_sums<R, P, G>(s, views[k], cg, (const R*)(w + 2), w + 3);
+    }
+}
+}  // extern "C++"
+static void refresh_actuator_disks(das_solver* s, bool check) {
+    if (s->actuatorDisks.empty() || !s->inited) return;
+    const int nC = s->mesh.nC, K = (int)s->actuatorDisks.size();
+    if (s->d_src3.n != (size_t)3 * nC) s->d_src3.alloc((size_t)3 * nC);
+    if (s->d_adSums.n < (size_t)5 * K) s->d_adSums.alloc((size_t)5 * K);
+    DAS_HIP(hipMemsetAsync(s->d_adSums.p, 0, (size_t)5 * K * sizeof(double), s->stream));
+    s->dm.src3 = s->d_src3.p;
+    std::vector<AdView<double>> views;
+    for (auto& e : s->actuatorDisks) {
+        das_solver::ActuatorDisk& a = e.second;
+        if (!a.smooth && a.d_member.n != (size_t)nC) {
+            std::vector<unsigned char> mask(nC, 0);
+            for (int c : a.members) mask[c] = 1;
+            a.d_member.upload(mask);
+        }
+        views.push_back(actuator_disk_view<double>(a));
+    }
+    if (s->d_adBad.n < 1) s->d_adBad.alloc(1);
+    DAS_HIP(hipMemsetAsync(s->d_adBad.p, 0, sizeof(int), s->stream));
+    actuator_disk_field<double, double, double>(s, views, (const CellGeom*)s->d_cg.p, s->d_adSums.p, s->d_src3.p, true);
+    DAS_HIP(hipGetLastError());
+    if (!check) return;
+    std::vector<double> w((size_t)5 * K);
+    int bad = 0;
+    DAS_HIP(hipMemcpyAsync(w.data(), s->d_adSums.p, w.size() * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipMemcpyAsync(&bad, s->d_adBad.p, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    int k = 0;
+    for (auto& e : s->actuatorDisks) {
+        das_solver::ActuatorDisk& a = e.second;
+        a.unitThrust = w[5 * k]; a.scale = w[5 * k + 2]; a.thrustSum = w[5 * k + 3]; a.torqueSum = w[5 * k + 4];
+        DAS_CHECK(!a.adjustThrust || (std::isfinite(a.scale) && a.unitThrust != 0.0), DAS_ERR_ARG,
+                  "fvSource " + e.first + ": adjustThrust: the thrust at scale 1 is " + std::to_string(a.unitThrust) + " (zero or not finite): the disk reaches no cell");
+        k++;
+    }
+    DAS_CHECK(!bad, DAS_ERR_ARG,
+              "fvSource actuatorDisk: a cell centre sits on the axis of a disk (its radial part is exactly zero): the reference divides by zero there; move the "
+              "centre off the cell centres");
+}
+
+// das_define_actuator_disk <- one entry of the fvSource option, type actuatorDisk (DAFvSourceActuatorDisk.C:36-92 the cell set, :431-500 the
+// parameters)
+int das_define_actuator_disk(das_solver_t* s, const char* name, const char* kind, const double* pars, const char* rotDir, double eps, int adjustThrust) {
+    DAS_TRY
+    need_actuator_disk_solver(s);
+    DAS_CHECK(name && kind && pars && rotDir, DAS_ERR_ARG, "fvSource: null argument");
+    const std::string nm = name, kd = kind, rd = rotDir, what = "fvSource " + nm;
+    const Mesh& m = s->mesh;
+    das_solver::ActuatorDisk a;
+    DAS_CHECK(rd == "left" || rd == "right", DAS_ERR_ARG, what + ": rotDir not valid: " + rd + " (left or right)");
+    a.rotSign = rd == "left" ? 1.0 : -1.0;
+    if (kd == "cylinderAnnulusToCell") {
+        // pars = p1(3), p2(3), innerRadius, outerRadius, scale, POD.  OpenFOAM's cylinderAnnulusToCell on the cell centres of this moment:
+        // between the two end planes and between the two radii of the axis
+        a.smooth = 0;
+        const double* p1 = pars;
+        const double* p2 = pars + 3;
+        const double ax[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};
+        const double aa = ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2], ir2 = pars[6] * pars[6], or2 = pars[7] * pars[7];
+        for (int i = 0; i < 3; i++) { a.pars[i] = 0.5 * (p1[i] + p2[i]); a.pars[3 + i] = ax[i]; }
+        for (int i = 6; i < 10; i++) a.pars[i] = pars[i];
+        check_actuator_disk_pars(a, what);
+        for (int c = 0; c < m.nC; c++) {
+            const double d[3] = {m.cg[c].C[0] - p1[0], m.cg[c].C[1] - p1[1], m.cg[c].C[2] - p1[2]};
+            const double mg = d[0] * ax[0] + d[1] * ax[1] + d[2] * ax[2];
+            if (mg > 0.0 && mg < aa) {
+                const double d2 = (d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) - mg * mg / aa;
+                if (d2 < or2 && d2 > ir2) a.members.push_back(c);
+            }
+        }
+        DAS_CHECK(!a.members.empty(), DAS_ERR_ARG, what + ": cylinderAnnulusToCell selects no cell (an empty set carries no force)");
+    } else if (kd == "cylinderAnnulusSmooth") {
+        a.smooth = 1;
+        for (int i = 0; i < 13; i++) a.pars[i] = pars[i];
+        a.eps = eps;
+        a.adjustThrust = adjustThrust ? 1 : 0;
+        check_actuator_disk_pars(a, what);
+    } else {
+        DAS_CHECK(false, DAS_ERR_ARG, what + ": source: " + kd + " not supported! Options are: cylinderAnnulusToCell and cylinderAnnulusSmooth!");
+    }
+    // a disk that cannot be evaluated is not kept, and a refused redefinition leaves the earlier disk of that name as it was
+    auto old = s->actuatorDisks.extract(nm);
+    s->actuatorDisks.emplace(nm, std::move(a));
+    try {
+        refresh_actuator_disks(s, true);
+    } catch (...) {
+        s->actuatorDisks.erase(nm);
+        if (!old.empty()) s->actuatorDisks.insert(std::move(old));
+        if (s->actuatorDisks.empty()) s->dm.src3 = nullptr;
+        else try { refresh_actuator_disks(s, false); } catch (...) {}
+        throw;
+    }
+    return DAS_OK;
+    DAS_CATCH
+}
+// das_set_actuator_disk_pars <- DAInputFvSourcePar::run (DAInputFvSourcePar.C:75-140): actuatorDiskPars[indices[k]] = values[k], then updateFvSource
+int das_set_actuator_disk_pars(das_solver_t* s, const char* name, const int* indices, int n, const double* values) {
+    DAS_TRY
+    need_actuator_disk_solver(s);
+    DAS_CHECK(indices && values && n >= 0, DAS_ERR_ARG, "fvSourcePar: null argument");
+    das_solver::ActuatorDisk& a = get_actuator_disk(s, name);
+    DAS_CHECK(a.smooth, DAS_ERR_ARG,
+              std::string("fvSourcePar: fvSource ") + name + " is a cylinderAnnulusToCell disk; actuatorDiskPars exist for cylinderAnnulusSmooth disks only");
+    for (int k = 0; k < n; k++)
+        DAS_CHECK(indices[k] >= 0 && indices[k] < 13, DAS_ERR_ARG,
+                  std::string("fvSourcePar: index ") + std::to_string(indices[k]) + " of fvSource " + name + " is out of range (an actuator disk has 13 parameters)");
+    das_solver::ActuatorDisk trial;
+    trial.smooth = 1; trial.eps = a.eps;
+    std::copy(a.pars, a.pars + 13, trial.pars);
+    for (int k = 0; k < n; k++) trial.pars[indices[k]] = values[k];
+    check_actuator_disk_pars(trial, std::string("fvSource ") + name);
+    // parameters whose field cannot be evaluated (a cell centre on the axis, no thrust at scale 1) are not kept either
+    double before[13];
+    std::copy(a.pars, a.pars + 13, before);
+    std::copy(trial.pars, trial.pars + 13, a.pars);
+    try {
+        refresh_actuator_disks(s, true);
+    } catch (...) {
+        std::copy(before, before + 13, a.pars);
+        try { refresh_actuator_disks(s, false); } catch (...) {}
+        throw;
+    }
+    return DAS_OK;
+    DAS_CATCH
+}
+// info4 = {the effective scale, thrustSourceSum, torqueSourceSum, the thrust at scale 1 (adjustThrust; 0 otherwise)}
+int das_get_actuator_disk_info(das_solver_t* s, const char* name, double* pars13, double* info4, int* nCells) {
+    DAS_TRY
+    need_actuator_disk_solver(s);
+    const das_solver::ActuatorDisk& a = get_actuator_disk(s, name);
+    if (pars13) std::copy(a.pars, a.pars + 13, pars13);
+    if (info4) { info4[0] = a.scale; info4[1] = a.thrustSum; info4[2] = a.torqueSum; info4[3] = a.unitThrust; }
+    if (nCells) *nCells = a.smooth ? s->mesh.nC : (int)a.members.size();
+    return DAS_OK;
+    DAS_CATCH
+}
+// the cells of a cylinderAnnulusToCell disk (cap entries at most are written); returns their number (a smooth disk: 0, it has no set)
+int das_get_actuator_disk_cells(das_solver_t* s, const char* name, int* cells, int cap) {
+    DAS_TRY
+    need_actuator_disk_solver(s);
+    const das_solver::ActuatorDisk& a = get_actuator_disk(s, name);
+    if (cells) std::copy(a.members.begin(), a.members.begin() + std::min((size_t)std::max(cap, 0), a.members.size()), cells);
+    return (int)a.members.size();
+    DAS_CATCH
+}
+int das_get_fv_source_vector(das_solver_t* s, double* out) {
+    DAS_TRY
+    need_actuator_disk_solver(s);
+    need_init(s);
+    DAS_CHECK(out, DAS_ERR_ARG, "null argument");
+    if (s->actuatorDisks.empty()) { std::fill(out, out + 3 * (size_t)s->mesh.nC, 0.0); return DAS_OK; }
+    DAS_HIP(hipMemcpyAsync(out, s->d_src3.p, 3 * (size_t)s->mesh.nC * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    return DAS_OK;
+    DAS_CATCH
+}
+
+// The dual-metrics residual with NO point seeded: the metrics of the solver lifted to Dual<1> with zero tangents.  It is the vehicle of
+// fvSourcePar -> residual: the residual is affine in the source field but the factor (rAU in HbyA, phiHbyA, pRes, phiRes) depends on the
+// states, so the tangent of the field is pushed through the whole residual body rather than added to the U rows.
+struct AdDualResidual {
+    typedef Dual<1> D;
+    DevBuf<D> d_XD, d_Wd, d_Rd, d_src3D, d_work;
+    DevBuf<FaceGeomT<D>> d_fgD;
+    DevBuf<CellGeomT<D>> d_cgD;
+    DevBuf<double> d_X0, d_psi, d_part, d_out;
+    DevMeshT<D> dmD;
+    ResParams prm0;
+    void init(das_solver* s, const double* seeds) {
+        const Mesh& m = s->mesh;
+        const GeomTopo t = device_geom_topo(s);
+        hipStream_t st = s->stream;
+        const int B = 256;
+        const size_t n3 = 3 * (size_t)m.nP;
+        d_XD.alloc(n3); d_Wd.alloc((size_t)s->n); d_Rd.alloc((size_t)s->n); d_src3D.alloc(3 * (size_t)m.nC); d_work.alloc(5 * s->actuatorDisks.size());
+        d_fgD.alloc((size_t)m.nF); d_cgD.alloc((size_t)m.nC);
+        d_X0.upload(m.points.data(), n3);
+        d_psi.upload(seeds, (size_t)s->n);
+        d_part.alloc(DAS_HS_MAX_BLOCKS); d_out.alloc(1);
+        DAS_HIP(hipMemsetAsync(s->vc.d_bad.p, 0, sizeof(int), st));
+        hipLaunchKernelGGL(k_points_lift, dim3(nblk((long long)n3, B)), dim3(B), 0, st, (long long)n3, (const double*)d_X0.p, d_XD.p);
+        hipLaunchKernelGGL(k_cell_y, dim3(nblk(m.nC, B)), dim3(B), 0, st, m.nC, (const CellGeom*)s->d_cg.p, d_cgD.p);
+        hipLaunchKernelGGL(k_lift, dim3(nblk(s->n, B)), dim3(B), 0, st, s->n, s->d_W.p, d_Wd.p);
+        hipLaunchKernelGGL(k_geom_face<D>, dim3(nblk(t.nF, B)), dim3(B), 0, st, t, (const D*)d_XD.p, d_fgD.p);
+        hipLaunchKernelGGL(k_geom_cell<D>, dim3(nblk(t.nC, B)), dim3(B), 0, st, t, (const FaceGeomT<D>*)d_fgD.p, d_cgD.p, s->vc.d_bad.p);
+        hipLaunchKernelGGL(k_geom_weights<D>, dim3(nblk(t.nF, B)), dim3(B), 0, st, t, (const CellGeomT<D>*)d_cgD.p, d_fgD.p);
+        dmD.nC = m.nC; dmD.nF = m.nF; dmD.nIF = m.nIF;
+        dmD.fg = d_fgD.p; dmD.cg = d_cgD.p;
+        dmD.cf_ptr = s->dm.cf_ptr; dmD.cf_face = s->dm.cf_face; dmD.cf_other = s->dm.cf_other;
+        dmD.owner = s->dm.owner; dmD.neigh = s->dm.neigh; dmD.bpatch = s->dm.bpatch; dmD.bc = s->dm.bc; dmD.cyc = s->dm.cyc; dmD.mixed = s->dm.mixed;
+        dmD.src3 = d_src3D.p;
+        prm0 = make_params(s->cp, s->opt, 0);
+    }
+    // seeds . dR / d(parameter idx of the disk `name`); unitScale: d / d(the effective scale) instead, whatever sets it (the rank-one
+    // factor of the volCoord product)
+    double pass(das_solver* s, const std::string& name, int idx, bool unitScale) {
+        hipStream_t st = s->stream;
+        std::vector<AdView<D>> views;
+        for (auto& e : s->actuatorDisks) {
+            AdView<D> v = actuator_disk_view<D>(e.second);
+            if (e.first == name) {
+                if (unitScale) { v.adjustThrust = 0; v.scale = D(e.second.scale); v.scale.d[0] = 1.0; }
+                else actuator_disk_par(v, idx).d[0] = 1.0;
+            }
+            views.push_back(v);
+        }
+        actuator_disk_field<D, D, double>(s, views, (const CellGeom*)s->d_cg.p, d_work.p, d_src3D.p, false);
+        eval_residual<D, D>(dmD, s->cp, prm0, d_Wd.p, d_Rd.p, s->wk1, s->d_phiF.p, s->d_Told.p, st);
+        const int nb = std::min(nblk(s->n, 256), DAS_HS_MAX_BLOCKS);
+        hipLaunchKernelGGL(k_ad_dot_partial, dim3(nb), dim3(256), 0, st, (long long)s->n, (const double*)d_psi.p, (const D*)d_Rd.p, d_part.p);
+        hipLaunchKernelGGL((k_hs_final<double>), dim3(1), dim3(256), 0, st, nb, (const double*)d_part.p, d_out.p);
+        DAS_HIP(hipGetLastError());
+        double r = 0.0;
+        DAS_HIP(hipMemcpyAsync(&r, d_out.p, sizeof(double), hipMemcpyDeviceToHost, st));
+        DAS_HIP(hipStreamSynchronize(st));
+        return r;
+    }
+};
+
+// das_calc_dactuatordiskpar_product <- calcJacTVecProduct(name, "fvSourcePar", ...) after the input has been set: product[k] =
+// seeds . d output / d actuatorDiskPars[indices[k]].  No function and no coupling output reads the source: exact zeros without a pass.
+// Neither does anything read scale (index 8) with adjustThrust, or targetThrust (12) without.
+int das_calc_dactuatordiskpar_product(das_solver_t* s, const char* name, const int* indices, int n, const char* outputName, const char* outputType,
+                                      const double* seeds, double* product) {
+    DAS_TRY
+    need_actuator_disk_solver(s);
+    need_init(s);
+    DAS_CHECK(indices && outputType && seeds && product && n >= 0, DAS_ERR_ARG, "fvSourcePar: null argument");
+    const das_solver::ActuatorDisk& a = get_actuator_disk(s, name);
+    DAS_CHECK(a.smooth, DAS_ERR_ARG,
+              std::string("fvSourcePar: fvSource ") + name + " is a cylinderAnnulusToCell disk; actuatorDiskPars exist for cylinderAnnulusSmooth disks only");
+    for (int k = 0; k < n; k++)
+        DAS_CHECK(indices[k] >= 0 && indices[k] < 13, DAS_ERR_ARG,
+                  std::string("fvSourcePar: index ") + std::to_string(indices[k]) + " of fvSource " + name + " is out of range (an actuator disk has 13 parameters)");
+    const std::string ot = outputType;
+    DAS_CHECK(ot == "residual" || ot == "function" || is_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
+    if (ot != "residual") {
+        if (is_coupling(ot)) (void)coupling_size(s, ot, outputName);
+        else if (!find_cell_function(s, outputName)) (void)get_function(s, outputName);
+        std::fill(product, product + n, 0.0);
+        return DAS_OK;
+    }
+    AdDualResidual dr;
+    dr.init(s, seeds);
+    for (int k = 0; k < n; k++) {
+        const bool unread = (indices[k] == 8 && a.adjustThrust) || (indices[k] == 12 && !a.adjustThrust);
+        product[k] = unread ? 0.0 : dr.pass(s, name, indices[k], false);
+    }
+    return DAS_OK;
+    DAS_CATCH
+}
+
+// The volCoord product and the disks.  The coloured passes recompute the field from the dual (or moved) C and V with the effective scale
+// of every disk frozen; an adjustThrust disk adds the rank-one term of its total afterwards (k_ad_vc_rank1 / k_ad_fd_rank1).
+struct AdRank1 { AdView<double> view; double beta; };
+static void actuator_disk_volcoord_setup(das_solver* s, const double* seeds /* host */, std::vector<AdView<double>>& frozen, std::vector<AdRank1>& terms) {
+    std::vector<std::string> adj;
+    for (auto& e : s->actuatorDisks) {
+        AdView<double> v = actuator_disk_view<double>(e.second);
+        if (e.second.adjustThrust) adj.push_back(e.first);
+        v.adjustThrust = 0;
+        v.scale = e.second.scale;
+        frozen.push_back(v);
+    }
+    if (adj.empty()) return;
+    AdDualResidual dr;
+    dr.init(s, seeds);
+    for (const std::string& nm : adj) {
+        const das_solver::ActuatorDisk& a = s->actuatorDisks[nm];
+        const double gamma = dr.pass(s, nm, -1, true);
+        terms.push_back(AdRank1{actuator_disk_view<double>(a), -(a.scale / a.unitThrust) * gamma});
+    }
+}
+
 // the end of a product: the vector and the bad-volume flag come down, the timing goes into info4
 static void finish_volcoord(das_solver* s, const double* d_out, double* product, const char* badMessage, double t0, long long passes, double* info4) {
     das_solver::VolCoord& v = s->vc;
@@ -5317,6 +5683,17 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
         d_srcD.alloc((size_t)m.nC);
         dmD.src = d_srcD.p;
     }
+    // actuator disks (residual rows only): the effective scales are frozen inside the coloured passes; an adjustThrust disk comes back
+    // as a rank-one term - actuator_disk_volcoord_setup
+    std::vector<AdView<double>> adFrozen;
+    std::vector<AdRank1> adTerms;
+    DevBuf<D> d_src3D, d_adWork;
+    if (!isCell && !isFn && !s->actuatorDisks.empty()) {
+        actuator_disk_volcoord_setup(s, seeds, adFrozen, adTerms);
+        d_src3D.alloc(3 * (size_t)m.nC);
+        d_adWork.alloc(5 * adFrozen.size());
+        dmD.src3 = d_src3D.p;
+    }
     const double t0 = wall_seconds();
     long long passes = 0;
     for (int col = 0; col < I.nColors; col++) {
@@ -5337,8 +5714,11 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
                 for (size_t k = 0; k < hsTerms.size(); k++)
                     hipLaunchKernelGGL((k_hs_apply<D, double, D>), dim3(nblk(m.nC, B)), dim3(B), 0, st, hsTerms[k].view, m.nC, (const CellGeomT<D>*)d_cgD.p,
                                        (const D*)(d_vtD.p + k), (int)(k == 0), d_srcD.p);
+                if (!adFrozen.empty()) actuator_disk_field<D, double, D>(s, adFrozen, (const CellGeomT<D>*)d_cgD.p, d_adWork.p, d_src3D.p, false);
                 eval_residual<D, D>(dmD, s->cp, prm0, d_Wd.p, d_Rd.p, s->wk1, s->d_phiF.p, s->d_Told.p, st);
                 hipLaunchKernelGGL(k_vc_rows_dual, dim3(nblk(m.nC, B)), dim3(B), 0, st, s->dm, L, (const double*)d_seeds.p, (const D*)d_Rd.p, d_tc.p);
+                for (const AdRank1& r : adTerms)
+                    hipLaunchKernelGGL((k_ad_vc_rank1<double>), dim3(nblk(m.nC, B)), dim3(B), 0, st, r.view, m.nC, (const CellGeomT<D>*)d_cgD.p, r.beta, d_tc.p);
                 for (const HsRank1& r : hsTerms)
                     hipLaunchKernelGGL(k_hs_vc_rank1, dim3(nblk(m.nC, B)), dim3(B), 0, st, r.view, m.nC, (const CellGeomT<D>*)d_cgD.p, r.snapCell, r.beta, r.gamma[0],
                                        r.gamma[1], r.gamma[2], d_tc.p);
@@ -5463,6 +5843,7 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
             v.d_X.release(); v.d_X0.release(); v.d_tc.release(); v.d_fvp.release(); v.d_fvm.release();
             if (fn) fn->uploaded = false;  // moment arms were recomputed from perturbed face centres: re-upload the host copy
             try { refresh_heat_sources(s, false); } catch (...) {}  // the source field of the unperturbed metrics
+            try { refresh_actuator_disks(s, false); } catch (...) {}
         }
         das_solver::FaceFn* fn;
     } restore{s, (fn && fn->isMoment) ? fn : nullptr};
@@ -5492,8 +5873,21 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
         d_vt0.upload(vt);
         d_tc2.alloc((size_t)m.nC);
     }
+    // actuator disks: as in the exact mode - the scales frozen in the moved-mesh fields, the rank-one terms side by side in d_tc2
+    std::vector<AdView<double>> adFrozen;
+    std::vector<AdRank1> adTerms;
+    DevBuf<double> d_adWork;
+    if (!isFn && !s->actuatorDisks.empty()) {
+        actuator_disk_volcoord_setup(s, seeds, adFrozen, adTerms);
+        d_adWork.alloc(5 * adFrozen.size());
+        if (!adTerms.empty()) d_tc2.alloc((size_t)m.nC);
+    }
+    const bool rank1 = !hsTerms.empty() || !adTerms.empty();
     auto output_pass = [&](double* Rout, double* fvOut) {
         if (!isFn) {
+            if (!adFrozen.empty()) actuator_disk_field<double, double, double>(s, adFrozen, (const CellGeom*)s->d_cg.p, d_adWork.p, s->d_src3.p, false);
+            for (const AdRank1& r : adTerms)
+                hipLaunchKernelGGL((k_ad_fd_rank1<double>), dim3(nblk(m.nC, B)), dim3(B), 0, st, r.view, m.nC, (const CellGeom*)s->d_cg.p, sideSign * r.beta, d_tc2.p);
             // the source field of the moved mesh with the totals and a snapped centre frozen, as in the exact mode; their rank-one terms
             // are collected side by side (+ and -) in d_tc2
             for (size_t k = 0; k < hsTerms.size(); k++) {
@@ -5526,7 +5920,7 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
         if (np == 0) continue;
         const int* pts = v.d_cpoints.p + I.cptr[col];
         for (int axis = 0; axis < 3; axis++) {
-            if (!hsTerms.empty()) DAS_HIP(hipMemsetAsync(d_tc2.p, 0, (size_t)m.nC * sizeof(double), st));
+            if (rank1) DAS_HIP(hipMemsetAsync(d_tc2.p, 0, (size_t)m.nC * sizeof(double), st));
             for (int side = 0; side < 2; side++) {
                 sideSign = side == 0 ? 1.0 : -1.0;
                 hipLaunchKernelGGL(k_move_points, dim3(nblk(np, B)), dim3(B), 0, st, np, pts, (const double*)v.d_h.p, side == 0 ? 1.0 : -1.0, axis,
@@ -5539,7 +5933,7 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
             if (!isFn) {
                 hipLaunchKernelGGL(k_vc_rows, dim3(nblk(m.nC, B)), dim3(B), 0, st, s->dm, L, (const double*)v.d_seeds.p, (const double*)v.d_Rp.p,
                                    (const double*)v.d_Rm.p, v.d_tc.p);
-                if (!hsTerms.empty()) hipLaunchKernelGGL(k_hs_add, dim3(nblk(m.nC, B)), dim3(B), 0, st, m.nC, (const double*)d_tc2.p, v.d_tc.p);
+                if (rank1) hipLaunchKernelGGL(k_hs_add, dim3(nblk(m.nC, B)), dim3(B), 0, st, m.nC, (const double*)d_tc2.p, v.d_tc.p);
             } else
                 hipLaunchKernelGGL(k_vc_fn_cells, dim3(nblk(m.nC, B)), dim3(B), 0, st, m.nC, (const int*)v.d_fnPtr.p, (const int*)v.d_fnIdx.p, seeds[0],
                                    (const double*)v.d_fvp.p, (const double*)v.d_fvm.p, v.d_tc.p);
@@ -6137,6 +6531,7 @@ int das_set_owned_mask(das_solver_t* s, const unsigned char* owned) {
     DAS_TRY
     DAS_CHECK(s, DAS_ERR_ARG, "null solver handle");
     if (!owned) { s->owned.clear(); return DAS_OK; }
+    DAS_CHECK(s->actuatorDisks.empty(), DAS_ERR_ARG, "the fvSource actuator disks run on an undecomposed solver (sharded solvers are not supported)");
     s->owned.assign(owned, owned + s->n);
     if (s->inited) s->d_owned.upload(s->owned);
     return DAS_OK;

@@ -9,6 +9,7 @@
 //   DAResidualScalarTransportFoam::calcResiduals src/adjoint/DAResidual/DAResidualScalarTransportFoam.C:57-84
 //   DAResidualHeatTransferFoam::calcResiduals   src/adjoint/DAResidual/DAResidualHeatTransferFoam.C:97-132   (body_heat_grad / body_heat)
 //   DAFvSourceHeatSource::calcFvSource          src/adjoint/DAFvSource/DAFvSourceHeatSource.C:236-321       (body_heat_source)
+//   DAFvSourceActuatorDisk::calcFvSource        src/adjoint/DAFvSource/DAFvSourceActuatorDisk.C:93-429      (body_actuator_disk)
 //   residual normalisation macros               src/include/DAMacroFunctions.H:28-51
 //   DAResidualRhoSimpleFoam::calcResiduals      src/adjoint/DAResidual/DAResidualRhoSimpleFoam.C:84-211   (RHO = true)
 //   DAResidualTurboFoam::calcResiduals          src/adjoint/DAResidual/DAResidualTurboFoam.C:66-233       (RHO = true, prm.turbo)
@@ -47,6 +48,9 @@ struct DevMeshT {  // G: the scalar of the metrics (double; Dual<1> in the mesh-
     // DAHeatTransferFoam with heat sources (the fvSource option): fvSource per cell [W/m^3], in the scalar of the metrics; null when no
     // source is defined - nothing is loaded then
     const G* src = nullptr;
+    // DASimpleFoam with actuator disks (the fvSource option, type actuatorDisk): the momentum source per cell, three components
+    // interleaved, in the scalar of the metrics; null when no disk is defined - nothing is loaded then
+    const G* src3 = nullptr;
 };
 typedef DevMeshT<double> DevMesh;
 // the mixed-T record of boundary face f (a mesh face index); it is read only where the patch's T_code says mixed
@@ -454,7 +458,9 @@ DAS_HD void dev2T_scaled(const T* g, const T& nuEff, T* tau) {
 // ================================================================================ k_cell
 // per cell: U-equation (diag/off-diag/source incl. boundary coeffs), relax, URes, rAU, HbyA, the SA residual and
 // (RHO) the energy residual TRes = EEqn & he.  RHO: phi is the mass flux, muEff = mu + rho nut replaces nuEff.
-template <class T, bool RHO, class G>
+// SRC: the momentum source of the actuator disks (DevMeshT::src3) is added; a template flag, so that the instantiation without disks is the
+// code it was before the disks came, instruction for instruction
+template <class T, bool RHO, class G, bool SRC = false>
 DAS_HD void body_cell(int c, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* nut, const T* gradU, const T* gradP,
                       const T* gradN, const T* gradH, T* R, T* rAU, T* HbyA, const T* TU = nullptr) {
     const long long N = m.nC;
@@ -702,6 +708,10 @@ DAS_HD void body_cell(int c, const DevMeshT<G>& m, const ResParams& prm, const T
         src[1] -= rv * (prm.om[2] * Uc[0] - prm.om[0] * Uc[2]);
         src[2] -= rv * (prm.om[0] * Uc[1] - prm.om[1] * Uc[0]);
     }
+    if constexpr (SRC) {  // - fvSource (DAResidualSimpleFoam.C:141-147): part of the matrix source, so it reaches URes and H alike
+#pragma unroll
+        for (int k = 0; k < 3; k++) src[k] += cgc.V * m.src3[3LL * c + k];
+    }
     // fvMatrix::relax (see DESIGN.md "relax"): diagonal dominance fix-up with boundary max/min contributions
     T D = dmax(dabs(D0 + vmaxs), sumOff) * (1.0 / prm.alphaU) - vmins;
     T dD = D - D0;
@@ -883,7 +893,7 @@ DAS_HD void body_bcoef(int b, const DevMeshT<double>& m, const ResParams& prm, c
     r[12] = gn_b * bf.n.gbc - phi * bf.n.vbc;
 }
 
-template <class T>
+template <class T, bool SRC = false>
 DAS_HD void body_cell2(int c, const DevMeshT<double>& m, const ResParams& prm, const T* W, const T* nut, const T* gradU, const T* gradP, const T* gradN,
                        const T* fc, const T* brec, T* R, T* rAU, T* HbyA) {
     const long long N = m.nC, nIF = m.nIF;
@@ -930,6 +940,10 @@ DAS_HD void body_cell2(int c, const DevMeshT<double>& m, const ResParams& prm, c
     }
     D0 -= sumPhi;
     dN -= sumPhi;
+    if constexpr (SRC) {  // - fvSource, as body_cell
+#pragma unroll
+        for (int k = 0; k < 3; k++) src[k] += cgc.V * m.src3[3LL * c + k];
+    }
     T D = dmax(dabs(D0 + vmaxs), sumOff) * (1.0 / prm.alphaU) - vmins;
     T dD = D - D0;
     const double rV = 1.0 / cgc.V;
@@ -1458,7 +1472,78 @@ DAS_HD R body_heat_source(const P* center, const P* axis, const P& radius, const
     return s;
 }
 
-// TRes = (laplacian(kappa, T) + fvSource) & T   (Gauss linear corrected; kappa interpolated linearly to the faces; fvSource the heat
+// a^e with a tangent in the base and in the exponent; the exponent's needs log(a): call it with a > 0 only
+DAS_HD double ad_pow(double a, double e) { return pow(a, e); }
+template <int K>
+DAS_HD Dual<K> ad_pow(const Dual<K>& a, const Dual<K>& e) {
+    Dual<K> r;
+    r.v = pow(a.v, e.v);
+    const double ga = e.v * pow(a.v, e.v - 1.0), ge = r.v * log(a.v);
+#pragma unroll
+    for (int k = 0; k < K; k++) r.d[k] = ga * a.d[k] + ge * e.d[k];
+    return r;
+}
+
+// the momentum source of one actuator disk at the cell centre C (DAFvSourceActuatorDisk.C:93-429): with n = direction / |direction| and
+// c = C - center the reference takes the COMPONENT-WISE product c o n as the axial part (cellC2AVecE & dirNorm) - not the projection - and
+// c - c o n as the radial part r; the circumferential direction is r x n (rotDir left, rotSign +1) or n x r (right, -1), normalised.
+//   smooth == 0 (cylinderAnnulusToCell, :108-204; center = (p1 + p2) / 2, direction = p2 - p1; on the cells of the set only):
+//     rPrime = |r| / outerRadius, rStar = (rPrime - hub) / (1 - hub), hub = innerRadius / outerRadius,
+//     fAxial = rStar sqrt(1 - rStar) scale, fCirc = fAxial POD / pi / rPrime                                   (Hoekstra)
+//   smooth == 1 (cylinderAnnulusSmooth, :205-419): epsR = eps / (outerRadius - innerRadius),
+//     fR = rStar^expM (1 - rStar)^expN for epsR <= rStar <= 1 - epsR, else its value at the nearer end times exp(-(overshoot / epsR)^2),
+//     fAxial = scale fR exp(-|c o n|^2 / eps^2), fCirc = fAxial POD / pi / (rPrime + 0.01 eps / outerRadius)
+// f[0..2] = fAxial n + fCirc circ, f[3] = fAxial, f[4] = fCirc.  Returns 1 where the reference divides by zero (r = 0 or r parallel to
+// n: no circumferential direction), 0 otherwise.  scale is R: with adjustThrust it is targetThrust / sum fAxial(scale = 1) V.
+// P: the scalar of the parameters, G: of the metrics, R: of the result (Dual<1> when either of them is).
+template <class R, class P, class G>
+DAS_HD int body_actuator_disk(int smooth, const P* center, const P* direction, const P& innerRadius, const P& outerRadius, const R& scale, const P& POD,
+                              const P& expM, const P& expN, double eps, double rotSign, const G* C, R* f) {
+    const P dn = dsqrt(direction[0] * direction[0] + direction[1] * direction[1] + direction[2] * direction[2]);
+    R n[3], r[3], a2(0.0), r2(0.0);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        n[i] = R(direction[i] / dn);
+        const R c = R(C[i]) - R(center[i]);
+        const R ca = c * n[i];
+        r[i] = c - ca;
+        a2 += ca * ca;
+        r2 += r[i] * r[i];
+    }
+    R t[3] = {rotSign * (r[1] * n[2] - r[2] * n[1]), rotSign * (r[2] * n[0] - r[0] * n[2]), rotSign * (r[0] * n[1] - r[1] * n[0])};
+    const R rLen = dsqrt(r2), tLen = dsqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
+    const int degenerate = (val(rLen) == 0.0 || val(tLen) == 0.0) ? 1 : 0;
+    const R outer = R(outerRadius), inner = R(innerRadius);
+    const R rPrime = rLen / outer, hub = inner / outer;
+    const R rStar = (rPrime - hub) / (1.0 - hub);
+    R fAxial, fCirc;
+    if (!smooth) {
+        fAxial = rStar * dsqrt(1.0 - rStar) * scale;
+        fCirc = fAxial * R(POD) * (1.0 / 3.14159265358979323846) / rPrime;
+    } else {
+        const R epsR = eps / (outer - inner);
+        const R lo = epsR, hi = 1.0 - epsR, m = R(expM), e = R(expN);
+        R fR;
+        if (val(rStar) < val(lo)) {
+            const R d = rStar - lo;
+            fR = ad_pow(lo, m) * ad_pow(1.0 - lo, e) * dexp(-(d * d) / epsR / epsR);
+        } else if (val(rStar) <= val(hi)) {
+            fR = ad_pow(rStar, m) * ad_pow(1.0 - rStar, e);
+        } else {
+            const R d = rStar - hi;
+            fR = ad_pow(hi, m) * ad_pow(1.0 - hi, e) * dexp(-(d * d) / epsR / epsR);
+        }
+        fAxial = fR * scale * dexp(-a2 * (1.0 / (eps * eps)));
+        fCirc = fAxial * R(POD) * (1.0 / 3.14159265358979323846) / (rPrime + 0.01 * eps / outer);
+    }
+#pragma unroll
+    for (int i = 0; i < 3; i++) f[i] = fAxial * n[i] + fCirc * (t[i] / tLen);
+    f[3] = fAxial;
+    f[4] = fCirc;
+    return degenerate;
+}
+
+// TRes = (laplacian(kappa, T) + fvSource) & T  (Gauss linear corrected; kappa interpolated linearly to the faces; fvSource the heat
 // sources per unit volume, when there are any; DAResidualHeatTransferFoam.C:97-102)
 template <class T, class G>
 DAS_HD void body_heat(int c, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* gradT, T* R) {

@@ -384,6 +384,16 @@ def _forward_exchange(halo, w):
     return w
 
 
+def refuse_fv_source(options):
+    """A sharded solver takes no fvSource entries: the totals of a source (the adjustThrust scale, the volume of a heat source) are sums
+    over the whole mesh, and a shard holds its own cells and ghosts only."""
+    fv = (options or {}).get("fvSource")
+    if fv:
+        from ._capi import DASError
+
+        raise DASError(f"fvSource[{sorted(fv)[0]}]: sharded solvers take no fvSource entries (actuator disks and heat sources run on one undecomposed mesh)")
+
+
 class _DevPtr:
     def __init__(self, ptr, n):
         self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<f8", "data": (int(ptr), False), "version": 2}
@@ -430,6 +440,7 @@ class ShardedAdjoint:
         elif state == "prolonged":
             prolong_channel_state(case, (part.nxl, NY, NZ), co, i0=part.e0, nx_global=NX)
         self.case = case
+        refuse_fv_source(options)
         opts = dict(options)
         opts["amdDevice"] = device_index
         self.D = PYDAFOAM(options=opts, case=case)
@@ -743,6 +754,7 @@ class ShardedAdjointGeneral(ShardedAdjoint):
         self.rank, self.world = dist.get_rank(), dist.get_world_size()
         self.case, self.info = case, info
         self.key, self.owner_rank, self.owned = info["key"], info["owner_rank"], info["owned"]
+        refuse_fv_source(options)
         opts = dict(options)
         opts["amdDevice"] = device_index
         self.D = PYDAFOAM(options=opts, case=case)

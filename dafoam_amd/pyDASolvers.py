@@ -329,7 +329,7 @@ class pyDASolvers:
         self._define_functions(pyOptions.get("function") if isinstance(pyOptions, dict) else None)
         self._define_outputs(pyOptions.get("outputInfo") if isinstance(pyOptions, dict) else None)
         self._define_thermal_inputs()
-        self._define_heat_sources()
+        self._define_fv_sources()
         if case.states is not None:  # FoamCase.states is always in "state" ordering (input data)
             check(lib().das_update_of_fields(self._h, dptr(np.ascontiguousarray(case.states, dtype=np.float64))))
 
@@ -459,6 +459,9 @@ class pyDASolvers:
         """inputInfo entry of a `field` input (reference DAInputField.C:33-86): fieldName, fieldType "scalar"; cellSetName /
         vector fields are not implemented here."""
         e = self._input_entry(inputName, "field")
+        if e.get("fieldName") == "fvSource":
+            raise _capi.DASError(f"inputInfo[{inputName}]: a field input with fieldName fvSource is not built (vector field inputs are not implemented; "
+                                 "the fvSourcePar input drives the actuator disks)")
         if e.get("fieldType", "scalar") != "scalar":
             raise _capi.DASError("field input: only fieldType scalar is implemented")
         if "cellSetName" in e:
@@ -513,10 +516,10 @@ class pyDASolvers:
             self._input_entry(inputName, inputType)
             return check(lib().das_set_thermal_coupling_input(self._h, inputName.encode(), dptr(np.ascontiguousarray(inputs, dtype=np.float64)), inputSize))
         if inputType == "fvSourcePar":
-            # DAInputFvSourcePar::run (reference DAInputFvSourcePar.C:75-140): heatSourcePars[indices] = input, then updateFvSource
+            # DAInputFvSourcePar::run (reference DAInputFvSourcePar.C:75-140): heatSourcePars / actuatorDiskPars[indices] = input, then updateFvSource
             name, idx = self._fv_source_par_entry(inputName)
-            return check(lib().das_set_heat_source_pars(self._h, name.encode(), idx.ctypes.data_as(_capi.c_int_p), idx.size,
-                                                        dptr(np.ascontiguousarray(inputs, dtype=np.float64))))
+            setter = lib().das_set_actuator_disk_pars if self._is_actuator_disk(name) else lib().das_set_heat_source_pars
+            return check(setter(self._h, name.encode(), idx.ctypes.data_as(_capi.c_int_p), idx.size, dptr(np.ascontiguousarray(inputs, dtype=np.float64))))
         if inputType not in ("patchVelocity", "patchVar"):
             raise _capi.DASError(f"inputType not supported on this path: {inputType}")
         field, val, _ = self._patch_input_tangents(inputName, inputType, inputs)
@@ -741,8 +744,9 @@ class pyDASolvers:
             self.setSolverInput(inputName, inputType, inputSize, inputs)
             name, idx = self._fv_source_par_entry(inputName)
             out = np.zeros(inputSize)
-            check(lib().das_calc_dfvsourcepar_product(self._h, name.encode(), idx.ctypes.data_as(_capi.c_int_p), idx.size, outputName.encode(),
-                                                      outputType.encode(), dptr(np.ascontiguousarray(seeds_s, dtype=np.float64)), dptr(out)))
+            prod = lib().das_calc_dactuatordiskpar_product if self._is_actuator_disk(name) else lib().das_calc_dfvsourcepar_product
+            check(prod(self._h, name.encode(), idx.ctypes.data_as(_capi.c_int_p), idx.size, outputName.encode(), outputType.encode(),
+                       dptr(np.ascontiguousarray(seeds_s, dtype=np.float64)), dptr(out)))
             product[:] = out
             return
         if inputType == "field":
@@ -1069,8 +1073,13 @@ class pyDASolvers:
         sn = self._case.solver_name
         for name, e in fvSource.items():
             what = f"fvSource[{name}]"
+            if sn == "DASimpleFoam":
+                self._check_actuator_disk(what, e)
+                continue
             if sn != "DAHeatTransferFoam":
-                raise _capi.DASError(f"{what}: the fvSource option is not built for {sn} (no momentum sources; heat sources run on DAHeatTransferFoam)")
+                why = " (its fvSourceEnergy = fvSource . U is not built)" if sn == "DARhoSimpleFoam" else ""
+                raise _capi.DASError(f"{what}: the fvSource option is not built for {sn}{why} (actuator disks run on DASimpleFoam, heat sources on "
+                                     "DAHeatTransferFoam)")
             if not isinstance(e, dict):
                 raise _capi.DASError(f"{what}: a dictionary is expected")
             if e.get("type") != "heatSource":
@@ -1087,6 +1096,66 @@ class pyDASolvers:
                 if k in e and k in self._HEAT_SOURCE_KEYS[e["source"]] and np.size(e[k]) != n:
                     raise _capi.DASError(f"{what}: {k} needs {n} components")
         return fvSource
+
+    # -- actuator disks: the fvSource option of DASimpleFoam (reference DAFvSourceActuatorDisk.C) ------------------------------------------
+    _ACTUATOR_DISK_KEYS = {"cylinderAnnulusToCell": ("p1", "p2", "innerRadius", "outerRadius", "rotDir", "scale", "POD"),
+                           "cylinderAnnulusSmooth": ("center", "direction", "innerRadius", "outerRadius", "rotDir", "scale", "POD", "eps", "expM", "expN")}
+    # adjustThrust and targetThrust may be left out (0 and 0.0): the reference's own docstring example has neither
+    ACTUATOR_DISK_PAR_NAMES = ("center_x", "center_y", "center_z", "direction_x", "direction_y", "direction_z", "innerRadius", "outerRadius", "scale", "POD",
+                               "expM", "expN", "targetThrust")
+
+    def _check_actuator_disk(self, what, e):
+        """One fvSource entry on DASimpleFoam: type actuatorDisk with source cylinderAnnulusToCell or cylinderAnnulusSmooth and the keys of
+        that source.  Every message names the entry and the solver."""
+        sn = self._case.solver_name
+        if not isinstance(e, dict):
+            raise _capi.DASError(f"{what}: a dictionary is expected ({sn})")
+        t = e.get("type")
+        if t == "heatSource":
+            raise _capi.DASError(f"{what}: type heatSource is not built for {sn} (heat sources run on DAHeatTransferFoam; {sn} takes type actuatorDisk)")
+        if t != "actuatorDisk":
+            raise _capi.DASError(f"{what}: type {t} is not built for {sn} (actuatorLine, actuatorPoint and uniformPressureGradient are not implemented; "
+                                 "type actuatorDisk is)")
+        if "source" not in e:
+            raise _capi.DASError(f"{what}: the key source is missing (cylinderAnnulusToCell or cylinderAnnulusSmooth; {sn})")
+        if e["source"] not in self._ACTUATOR_DISK_KEYS:
+            raise _capi.DASError(f"{what}: source: {e['source']} not supported! Options are: cylinderAnnulusToCell and cylinderAnnulusSmooth! ({sn})")
+        missing = [k for k in self._ACTUATOR_DISK_KEYS[e["source"]] if k not in e]
+        if missing:
+            raise _capi.DASError(f"{what}: source {e['source']} needs the key(s) {', '.join(missing)} ({sn})")
+        for k in ("p1", "p2", "center", "direction"):
+            if k in self._ACTUATOR_DISK_KEYS[e["source"]] and np.size(e[k]) != 3:
+                raise _capi.DASError(f"{what}: {k} needs 3 components ({sn})")
+        if e["rotDir"] not in ("left", "right"):
+            raise _capi.DASError(f"{what}: rotDir not valid: {e['rotDir']} (left or right; {sn})")
+
+    def _define_actuator_disks(self):
+        for name in sorted(self._fvSource):
+            e = self._fvSource[name]
+            if e["source"] == "cylinderAnnulusToCell":
+                pars = np.array(list(e["p1"]) + list(e["p2"]) + [e["innerRadius"], e["outerRadius"], e["scale"], e["POD"]], dtype=np.float64)
+                eps, adjust = 0.0, 0
+            else:
+                pars = np.array(list(e["center"]) + list(e["direction"]) + [e.get(k, 0.0) for k in self.ACTUATOR_DISK_PAR_NAMES[6:]], dtype=np.float64)
+                eps, adjust = float(e["eps"]), int(bool(e.get("adjustThrust", 0)))
+            check(lib().das_define_actuator_disk(self._h, name.encode(), e["source"].encode(), dptr(pars), e["rotDir"].encode(), eps, adjust))
+
+    def actuatorDiskInfo(self, name):
+        """What the reference prints per disk, and more: the 13 actuatorDiskPars, the effective scale (the adjusted one with adjustThrust),
+        thrustSourceSum = sum fAxial V and torqueSourceSum = sum fCirc V, the thrust at scale 1, the size of the cell set and, for a
+        cylinderAnnulusToCell disk, its cells."""
+        pars, info, nc = np.zeros(13), np.zeros(4), C.c_int(0)
+        check(lib().das_get_actuator_disk_info(self._h, name.encode(), dptr(pars), dptr(info), C.byref(nc)))
+        n = check(lib().das_get_actuator_disk_cells(self._h, name.encode(), None, 0))
+        cells = np.zeros(n, dtype=np.int32)
+        if n:
+            check(lib().das_get_actuator_disk_cells(self._h, name.encode(), cells.ctypes.data_as(_capi.c_int_p), n))
+        return dict(pars=pars, scale=float(info[0]), thrustSourceSum=float(info[1]), torqueSourceSum=float(info[2]), unitThrust=float(info[3]),
+                    nCells=nc.value, cells=cells)
+
+    def _define_fv_sources(self):
+        """the entries of the fvSource option: actuator disks on DASimpleFoam, heat sources on DAHeatTransferFoam"""
+        return self._define_actuator_disks() if self._case.solver_name == "DASimpleFoam" else self._define_heat_sources()
 
     def _define_heat_sources(self):
         for name in sorted(self._fvSource):
@@ -1105,14 +1174,19 @@ class pyDASolvers:
         name = e.get("fvSourceName")
         if name not in self._fvSource:
             raise _capi.DASError(f"inputInfo[{inputName}]: fvSourceName {name} is not an entry of the fvSource option")
-        if self._fvSource[name]["source"] != "cylinderSmooth":
+        disk = self._fvSource[name].get("type") == "actuatorDisk"
+        smooth, pars, nPar, kind = ("cylinderAnnulusSmooth", "actuatorDiskPars", 13, "an actuator disk") if disk else ("cylinderSmooth", "heatSourcePars", 9, "a heat source")
+        if self._fvSource[name]["source"] != smooth:
             raise _capi.DASError(f"inputInfo[{inputName}]: fvSource[{name}] is a {self._fvSource[name]['source']} source; the fvSourcePar input drives the "
-                                 "heatSourcePars, which exist for cylinderSmooth sources only")
-        idx = np.array(e.get("indices", list(range(9))), dtype=np.int32)
-        if idx.size and (idx.min() < 0 or idx.max() >= 9):
-            raise _capi.DASError(f"inputInfo[{inputName}]: index {int(idx.max() if idx.max() >= 9 else idx.min())} of fvSource[{name}] is out of range "
-                                 "(a heat source has 9 parameters)")
+                                 f"{pars}, which exist for {smooth} sources only")
+        idx = np.array(e.get("indices", list(range(nPar))), dtype=np.int32)  # DAInputFvSourcePar.C:45-48: all 13 of a disk by default
+        if idx.size and (idx.min() < 0 or idx.max() >= nPar):
+            raise _capi.DASError(f"inputInfo[{inputName}]: index {int(idx.max() if idx.max() >= nPar else idx.min())} of fvSource[{name}] is out of range "
+                                 f"({kind} has {nPar} parameters)")
         return name, np.ascontiguousarray(idx)
+
+    def _is_actuator_disk(self, name):
+        return self._fvSource[name].get("type") == "actuatorDisk"
 
     def updateFvSource(self):
         """DAFvSource::updateFvSource: the field follows the parameters and the metrics at once here (das_set_heat_source_pars,
@@ -1120,7 +1194,12 @@ class pyDASolvers:
         return None
 
     def getFvSource(self):
-        """The fvSource field [W/m^3], one value per cell."""
+        """The fvSource field: [W/m^3], one value per cell, on DAHeatTransferFoam; the momentum source of the actuator disks [force per unit
+        volume], (nCells, 3), on DASimpleFoam."""
+        if self._case.solver_name == "DASimpleFoam":
+            out = np.zeros((self._case.mesh.n_cells, 3))
+            check(lib().das_get_fv_source_vector(self._h, dptr(out)))
+            return out
         out = np.zeros(self._case.mesh.n_cells)
         check(lib().das_get_fv_source(self._h, dptr(out)))
         return out

@@ -446,6 +446,40 @@ int das_get_fv_source(das_solver_t* s, double* out);
 int das_calc_dfvsourcepar_product(das_solver_t* s, const char* name, const int* indices, int n, const char* outputName, const char* outputType,
                                   const double* seeds, double* product);
 
+/* Actuator disks of DASimpleFoam: the fvSource option, entries of type actuatorDisk (reference DAFvSourceActuatorDisk.C:36-500), and the
+ * fvSourcePar input for them.  UEqn = div(phi, U) + ... - fvSource (DAResidualSimpleFoam.C:141-147): the source is part of the matrix
+ * source, so it reaches URes and, through H, HbyA, phiHbyA, pRes and phiRes; dR/dW changes with it.  fvSource [force per unit volume] is
+ * the sum of the disks in the order of their names.  Like the heat sources the field depends on the metrics and the parameters only: it is
+ * computed when a disk is defined, when parameters are set and by das_update_of_mesh, never per residual evaluation; two-stage sums in a
+ * fixed order, no atomics.
+ * das_define_actuator_disk     kind "cylinderAnnulusToCell": pars = p1(3), p2(3), innerRadius, outerRadius, scale, POD (10 values); the cells
+ *   with 0 < d.a < a.a and innerRadius^2 < |d|^2 - (d.a)^2 / a.a < outerRadius^2 (a = p2 - p1, d = C - p1) are chosen now and kept; an
+ *   empty set is an error.  kind "cylinderAnnulusSmooth": pars = the 13 actuatorDiskPars center(3), direction(3), innerRadius, outerRadius,
+ *   scale, POD, expM, expN, targetThrust, and eps; adjustThrust: scale = targetThrust / sum fAxial(scale = 1) V, pars[8] is not read.
+ *   rotDir "left" or "right".  The axial part of C - center is the component-wise product with the unit direction, as in the reference.
+ *   A cell centre on the axis of a disk (the reference divides by zero there) is an error, here and whenever the field is recomputed.
+ * das_set_actuator_disk_pars   actuatorDiskPars[indices[k]] = values[k] of a cylinderAnnulusSmooth disk, then the field again.
+ * das_get_actuator_disk_info   the 13 parameters (cylinderAnnulusToCell: center = (p1 + p2) / 2, direction = p2 - p1), info4 = {effective
+ *   scale, thrustSourceSum = sum fAxial V, torqueSourceSum = sum fCirc V, the thrust at scale 1 (adjustThrust)}, and the size of the cell
+ *   set (a smooth disk: all cells); any output may be NULL.
+ * das_get_actuator_disk_cells  the cell set of a cylinderAnnulusToCell disk (at most cap entries are written); returns its size.
+ * das_get_fv_source_vector     the field, three components per cell (zeros while no disk is defined).
+ * das_calc_dactuatordiskpar_product <- calcJacTVecProduct(name, "fvSourcePar", ...): product[k] = seeds . d output / d actuatorDiskPars[
+ *   indices[k]].  outputType "residual": one forward pass per index - the parameters, the field and the adjustThrust total in dual
+ *   numbers, then the whole residual once with that tangent on the source and none elsewhere (the factor rAU of H depends on the states:
+ *   the U, p and phi rows all carry it); "function" and the coupling outputs: exact zeros.  Index 8 with adjustThrust and index 12
+ *   without are not read: exact zeros.
+ * das_simple_iteration refuses while a disk is defined (the SIMPLE sweep has no source term); das_solve_primal runs with disks.
+ * Every other solver and a sharded solver return DAS_ERR_ARG with a message that names fvSource; so do an unknown disk name, an index
+ * outside 0-12 and parameters asked of a cylinderAnnulusToCell disk. */
+int das_define_actuator_disk(das_solver_t* s, const char* name, const char* kind, const double* pars, const char* rotDir, double eps, int adjustThrust);
+int das_set_actuator_disk_pars(das_solver_t* s, const char* name, const int* indices, int n, const double* values);
+int das_get_actuator_disk_info(das_solver_t* s, const char* name, double* pars13, double* info4, int* nCells);
+int das_get_actuator_disk_cells(das_solver_t* s, const char* name, int* cells, int cap);
+int das_get_fv_source_vector(das_solver_t* s, double* out);
+int das_calc_dactuatordiskpar_product(das_solver_t* s, const char* name, const int* indices, int n, const char* outputName, const char* outputType,
+                                      const double* seeds, double* product);
+
 /* das_calc_jac_t_vec_product <-calcJacTVecProduct(inputName,inputType,inputs,outputName,outputType,seeds,product)
  *   pyDASolvers.pyx:208-235 (DASolver.C:1690-1839).  Supported pair on this path: inputType "stateVar",
  *   outputType "residual": product = D_s (dR/dW)^T seeds  (normalizeJacTVecProduct, DASolver.C:1443-1553);
