@@ -10,12 +10,13 @@ import os
 
 import numpy as np
 
-from .meshgen import BC_MIXED, FoamCase
+from .meshgen import BC_MIXED, BC_TRACTION, FoamCase
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DAFOAM_AMD_LIB") or os.path.join(_HERE, "lib", "libdafoam_amd.so")  # (override: tuning builds)
 
-SOLVER_IDS = {"DASimpleFoam": 0, "DAScalarTransportFoam": 1, "DARhoSimpleFoam": 2, "DATurboFoam": 3, "DAHeatTransferFoam": 4}
+SOLVER_IDS = {"DASimpleFoam": 0, "DAScalarTransportFoam": 1, "DARhoSimpleFoam": 2, "DATurboFoam": 3, "DAHeatTransferFoam": 4,
+              "DASolidDisplacementFoam": 5}
 PATCH_TYPES = {"patch": 0, "wall": 1, "symmetry": 2, "cyclic": 3}
 
 c_double_p = C.POINTER(C.c_double)
@@ -79,6 +80,14 @@ class das_case_t(C.Structure):
         ("bc_T_mixed_frac", c_double_p),
         ("n_kappa_coeffs", C.c_int),
         ("kappa_coeffs", C.c_double * 8),
+        ("solid_rho", C.c_double),
+        ("solid_E", C.c_double),
+        ("solid_nu", C.c_double),
+        ("plane_stress", C.c_int),
+        ("bc_D_code", c_int_p),
+        ("bc_D_val", c_double_p),
+        ("bc_D_traction", c_double_p),
+        ("bc_D_pressure", c_double_p),
     ]
 
 
@@ -228,6 +237,45 @@ class CaseStruct:
             s.n_kappa_coeffs = len(coeffs)
             for i, x in enumerate(coeffs):
                 s.kappa_coeffs[i] = x
+        if case.solver_name == "DASolidDisplacementFoam":
+            # constant/mechanicalProperties (rho, E, nu: type uniform; planeStress) and the patch fields of D
+            mp = getattr(case, "mechanical", None) or {}
+            uniform = {}
+            for nm in ("rho", "E", "nu"):
+                ent = mp.get(nm)
+                if isinstance(ent, dict):
+                    if ent.get("type", "uniform") != "uniform":
+                        raise DASError(f"DASolidDisplacementFoam: mechanicalProperties {nm} of type {ent.get('type')} is not built (only uniform is)")
+                    ent = ent.get("value")
+                if ent is None:
+                    raise DASError(f"DASolidDisplacementFoam needs mechanicalProperties {nm} (a number, or type uniform with a value)")
+                uniform[nm] = float(ent)
+            rho, E, nu = uniform["rho"], uniform["E"], uniform["nu"]
+            if not rho > 0.0:
+                raise DASError(f"DASolidDisplacementFoam needs a positive rho, not {rho}")
+            if not E > 0.0:
+                raise DASError(f"DASolidDisplacementFoam needs a positive E, not {E}")
+            if not -1.0 < nu < 0.5:
+                raise DASError(f"DASolidDisplacementFoam needs nu inside (-1, 0.5), not {nu}")
+            s.solid_rho, s.solid_E, s.solid_nu, s.plane_stress = rho, E, nu, 1 if mp.get("planeStress", False) else 0
+            code = np.ones(P, dtype=np.int32)
+            val, trac, pres = np.zeros((P, 3)), np.zeros((P, 3)), np.zeros(P)
+            for i, p in enumerate(m.patches):
+                if p.type == "cyclic":
+                    raise DASError(f"DASolidDisplacementFoam: patch {p.name} is cyclic - cyclic patches are not built for D")
+                ent = case.bcs.get(p.name, {}).get("D")
+                if ent is None:
+                    continue
+                code[i] = ent[0]
+                if ent[0] == BC_TRACTION:
+                    trac[i], pres[i] = ent[1], ent[2]
+                elif ent[0] in (0, 1, 3):
+                    val[i] = ent[1] if ent[0] == 0 else 0.0
+                else:
+                    raise DASError(f"DASolidDisplacementFoam: patch {p.name}: D is fixedValue, zeroGradient, symmetry or tractionDisplacement, not code {ent[0]}")
+            k["bc_D_code"], k["bc_D_val"], k["bc_D_traction"], k["bc_D_pressure"] = code, val, trac, pres
+            s.bc_D_code = _ip(code)
+            s.bc_D_val, s.bc_D_traction, s.bc_D_pressure = _dp(val), _dp(trac), _dp(pres)
         s.simple_has_T = 1 if (case.solver_name == "DASimpleFoam" and getattr(case, "has_T", False)) else 0
 
     def byref(self):
@@ -303,6 +351,7 @@ _SIGS = {
     "das_define_location_function": (C.c_int, [_VP, C.c_char_p, C.c_char_p, c_int_p, C.c_int, c_double_p, c_double_p, C.c_double, C.c_int, C.c_double]),
     "das_define_patch_field_function": (C.c_int, [_VP, C.c_char_p, C.c_char_p, c_int_p, C.c_int, C.c_char_p, c_int_p, C.c_int, c_double_p, C.c_int, C.c_double, C.c_double]),
     "das_define_cell_function": (C.c_int, [_VP, C.c_char_p, C.c_char_p, c_int_p, C.c_int, C.c_char_p, c_int_p, C.c_int, c_double_p, C.c_int, C.c_double, C.c_double]),
+    "das_define_von_mises_function": (C.c_int, [_VP, C.c_char_p, c_int_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double]),
     "das_calc_function": (C.c_int, [_VP, C.c_char_p, c_double_p]),
     "das_define_force_coupling": (C.c_int, [_VP, C.c_char_p, c_int_p, C.c_int, C.c_double]),
     "das_calc_force_coupling": (C.c_int, [_VP, C.c_char_p, c_double_p, C.c_int]),

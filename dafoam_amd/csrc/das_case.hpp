@@ -21,8 +21,21 @@ struct CaseParams {
     // DAHeatTransferFoam: kappa(T) = sum_k kappa[k] T^k (constant/solidProperties kappa / kappaCoeffs)
     int nKappa = 0;
     double kappa[DAS_MAX_KAPPA_COEFFS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // DASolidDisplacementFoam, constant/mechanicalProperties: rho, E, nu, planeStress and the Lame coefficients per unit density; the
+    // pointer is what the traction kernel reads (device memory in the library, the host vector in the test harness)
+    double solidRho = 1.0, solidE = 0.0, solidNu = 0.0, solidMu = 0.0, solidLambda = 0.0;
+    int planeStress = 0, nTrac = 0;
+    const int* tracCells_ptr = nullptr;
     void from_case(const das_case_t* c) {
         solver = c->solver;
+        if (solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM) {
+            DAS_CHECK(c->solid_rho > 0.0, DAS_ERR_ARG, "DASolidDisplacementFoam needs a positive rho, not " + std::to_string(c->solid_rho));
+            DAS_CHECK(c->solid_E > 0.0, DAS_ERR_ARG, "DASolidDisplacementFoam needs a positive E, not " + std::to_string(c->solid_E));
+            DAS_CHECK(c->solid_nu > -1.0 && c->solid_nu < 0.5, DAS_ERR_ARG,
+                      "DASolidDisplacementFoam needs nu inside (-1, 0.5), not " + std::to_string(c->solid_nu));
+            solidRho = c->solid_rho; solidE = c->solid_E; solidNu = c->solid_nu; planeStress = c->plane_stress != 0;
+            solid_lame(solidRho, solidE, solidNu, planeStress, solidMu, solidLambda);
+        }
         if (solver == DAS_SOLVER_HEATTRANSFERFOAM) {
             DAS_CHECK(c->n_kappa_coeffs >= 1 && c->n_kappa_coeffs <= DAS_MAX_KAPPA_COEFFS, DAS_ERR_ARG,
                       "DAHeatTransferFoam needs kappa or kappaCoeffs with 1 to " + std::to_string(DAS_MAX_KAPPA_COEFFS) + " coefficients, not " +
@@ -113,6 +126,11 @@ inline ResParams make_params(const CaseParams& cp, const Options& opt, int isPC)
     p.solid = cp.solver == DAS_SOLVER_HEATTRANSFERFOAM;
     p.nKappa = cp.nKappa;
     for (int k = 0; k < DAS_MAX_KAPPA_COEFFS; k++) p.kappa[k] = cp.kappa[k];
+    p.sRho = cp.solidRho; p.sMu = cp.solidMu; p.sLam = cp.solidLambda;
+    p.normD = opt.list_has("normalizeResiduals", "DRes");
+    p.nPass = (int)opt.geti("maxCorrectBCCalls");  // read at residual time: the passes of the tractionDisplacement gradient
+    p.nTrac = cp.nTrac;
+    p.tracCells = cp.tracCells_ptr;
     for (int k = 0; k < 3; k++) { p.om[k] = cp.om[k]; p.org[k] = cp.org[k]; }
     return p;
 }

@@ -7,6 +7,7 @@
 #pragma once
 #include "das_common.hpp"
 #include "das_dual.hpp"
+#include "das_kernels.hpp"
 
 namespace das {
 
@@ -71,6 +72,41 @@ __global__ __launch_bounds__(256) void k_vc_cellfn_terms(CellFnView f, const Cel
     const int c = f.cell[t];
     const double x = cellfn_x(f, src, t);
     tc[c] += b * (f.square ? x * x : x) * cg[c].V.d[0];
+}
+
+// ---- vonMisesStressKS of DASolidDisplacementFoam (reference DAFunctionVonMisesStressKS.C): F = log(sum_t exp(coeffKS vm_t)) / coeffKS
+// over the cells of the set, vm_t = solid_von_mises of the cell gradient gradD of the residual pass (traction passes included).  The sum
+// runs max-shifted in log space through the two-stage kernels of das_facefn.hpp (k_ks_max ... k_ks_weights) on the compact array a[t].
+// a[t] = vm of cell[t]
+__global__ __launch_bounds__(256) void k_vm_terms(long long nt, const int* __restrict__ cell, ResParams prm, const double* __restrict__ gD, double scale,
+                                                  double* __restrict__ a) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < nt) a[t] = solid_von_mises<double>(prm, gD + 9LL * cell[t], scale);
+}
+// wc[cell[t]] = wt[t]: the softmax weights per cell (the caller zeroes wc; the cells of a set are distinct)
+__global__ __launch_bounds__(256) void k_vm_cell_weights(long long nt, const int* __restrict__ cell, const double* __restrict__ wt, double* __restrict__ wc) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < nt) wc[cell[t]] = wt[t];
+}
+// tc[c] = wc[c] x the tangent of vm_c (dual-number gradD: a state colour, or the dual points of the volCoord pass); 0 outside the set
+__global__ __launch_bounds__(256) void k_vm_tangent(int nC, ResParams prm, const Dual<1>* __restrict__ gD, double scale, const double* __restrict__ wc,
+                                                    double* __restrict__ tc) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= nC) return;
+    const double w = wc[c];
+    tc[c] = w == 0.0 ? 0.0 : w * solid_von_mises<Dual<1>>(prm, gD + 9LL * c, scale).d[0];
+}
+// dFdW of one colour, a gather without atomics: state j = 3 c + q of colour col receives tc of its cell and of the face neighbours -
+// vm reads D at levels 0 and 1, and the distance-2 colouring leaves one state of a colour in the stencil of a cell
+__global__ __launch_bounds__(256) void k_vm_gather(DevMesh m, const int* __restrict__ colors, int col, const double* __restrict__ tc, double seed,
+                                                   double* __restrict__ out) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= 3LL * m.nC || colors[j] != col) return;
+    const int c = (int)(j / 3);
+    double acc = tc[c];
+    for (int s = m.cf_ptr[c]; s < m.cf_ptr[c + 1]; s++)
+        if ((m.cf_face[s] & 0x7fffffff) < m.nIF) acc += tc[m.cf_other[s]];
+    out[j] = seed * acc;
 }
 
 }  // namespace das

@@ -385,6 +385,10 @@ struct PatchBC {  // per patch, small table
     int mrf_included;  // 1 = the patch rotates with the MRF zone (MRFZone includedFaces)
     int rot;           // cyclic patch with a rotation: neighbour-side vectors are multiplied by Q (forwardT)
     double Q[9];
+    // DASolidDisplacementFoam: the state D rides in the U slots (U_code / U_val / dU_val); traction and pressure of a
+    // tractionDisplacement patch (U_code == DAS_BC_TRACTION)
+    double D_trac[3];
+    double D_pres;
 };
 
 // ---- host mesh (fvMesh equivalent) ------------------------------------------------------------
@@ -402,6 +406,8 @@ struct Mesh {
     // patches with a mixed T (DAS_BC_MIXED): 4 per boundary face - refValue, valueFraction and their tangents (forward-mode seeds, zero
     // except inside the products of the thermalCoupling input); empty when no patch is mixed
     std::vector<double> mixed;
+    // DASolidDisplacementFoam: the cells that own at least one tractionDisplacement face, ascending
+    std::vector<int> trac_cells;
     // cell -> faces CSR; entry = face id | (side<<31), side 1 = this cell is the face's neighbour
     std::vector<int> cf_ptr, cf_face, cf_other;
     // cell -> cells CSR (face neighbours, ascending)

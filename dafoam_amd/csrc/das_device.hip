@@ -268,9 +268,38 @@ __global__ __launch_bounds__(256) void k_heat(DevMeshT<G> m, ResParams prm, cons
     if (c < m.nC) body_heat<T>(c, m, prm, W, gT, R);
 }
 
+// DASolidDisplacementFoam (body_solid_grad / body_solid_traction / body_solid): the Gauss gradient of D with the pass-0 boundary values
+// over all cells, the lagged tractionDisplacement passes over the compact list of the cells that own a traction face (they overwrite
+// gradD of those cells and leave the final g per traction face), then DRes; one thread per cell, no atomics
+template <class T, class G = double>
+__global__ __launch_bounds__(256) void k_solid_grad(DevMeshT<G> m, ResParams prm, const T* __restrict__ W, T* gD) {
+    int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < m.nC) body_solid_grad<T>(c, m, prm, W, gD);
+}
+template <class T, class G = double>
+__global__ __launch_bounds__(256) void k_solid_traction(DevMeshT<G> m, ResParams prm, T* gD, T* gTr) {
+    int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < prm.nTrac) body_solid_traction<T>(k, m, prm, gD, gTr);
+}
+template <class T, class G = double>
+__global__ __launch_bounds__(256) void k_solid(DevMeshT<G> m, ResParams prm, const T* __restrict__ W, const T* gD, const T* gTr, T* R) {
+    int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < m.nC) body_solid<T>(c, m, prm, W, gD, gTr, R);
+}
+// the gradient passes of DASolidDisplacementFoam into wk.gU (9 per cell) and wk.gTr (3 per boundary face)
+template <class T, class G, class WK>
+static void launch_solid_grad(const DevMeshT<G>& dm, const ResParams& prm, const T* W, WK& wk, hipStream_t st) {
+    DAS_CHECK(prm.nPass >= 1, DAS_ERR_ARG, "DASolidDisplacementFoam needs maxCorrectBCCalls >= 1, not " + std::to_string(prm.nPass));
+    const size_t nBF3 = 3 * (size_t)std::max(1, dm.nF - dm.nIF);
+    if (wk.gTr.n != nBF3) wk.gTr.alloc(nBF3);
+    hipLaunchKernelGGL((k_solid_grad<T, G>), dim3(nblk(dm.nC, 256)), dim3(256), 0, st, dm, prm, W, wk.gU.p);
+    if (prm.nTrac > 0) hipLaunchKernelGGL((k_solid_traction<T, G>), dim3(nblk(prm.nTrac, 256)), dim3(256), 0, st, dm, prm, wk.gU.p, wk.gTr.p);
+}
+
 template <class T>
 struct ResWork {
     DevBuf<T> nut, gU, gP, gN, gH, rAU, HbyA, q, gT, TU;
+    DevBuf<T> gTr;  // DASolidDisplacementFoam: the tractionDisplacement gradient, 3 per boundary face (allocated on first use)
     DevBuf<T> fc, brec;  // face / cell split of the cell pass: 6 scalars per internal face, 13 per boundary face (allocated on first use)
     void ensure(int solver, long long N, long long F) {
         if (solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(solver)) {
@@ -279,6 +308,8 @@ struct ResWork {
             }
             if (gH.n != (size_t)(3 * N)) gH.alloc(3 * N);  // compressible he / the optional T field of DASimpleFoam
             if (solver == DAS_SOLVER_TURBOFOAM && TU.n != (size_t)(3 * N)) TU.alloc(3 * N);
+        } else if (solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM) {
+            if (gU.n != (size_t)(9 * N)) gU.alloc(9 * N);  // gradD
         } else if (gT.n != (size_t)(3 * N)) gT.alloc(3 * N);
     }
     // work array referenced through ResParams (DATurboFoam)
@@ -348,6 +379,9 @@ static void eval_residual(const DevMeshT<G>& dm, const CaseParams& cp, const Res
     } else if (cp.solver == DAS_SOLVER_HEATTRANSFERFOAM) {
         hipLaunchKernelGGL((k_heat_grad<T, G>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, W, wk.gT.p);
         hipLaunchKernelGGL((k_heat<T, G>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, W, (const T*)wk.gT.p, R);
+    } else if (cp.solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM) {
+        launch_solid_grad<T, G>(dm, prm, W, wk, st);
+        hipLaunchKernelGGL((k_solid<T, G>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, W, (const T*)wk.gU.p, (const T*)wk.gTr.p, R);
     } else {
         hipLaunchKernelGGL((k_gradT<T, G>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, W, d_phiF, wk.gT.p);
         hipLaunchKernelGGL((k_T<T, G>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, W, d_phiF, d_Told, wk.gT.p, R);
@@ -794,6 +828,7 @@ struct das_solver {
     DevBuf<int> d_cf_ptr, d_cf_face, d_cf_other, d_owner, d_neigh, d_bpatch, d_cyc;
     DevBuf<PatchBC> d_bc;
     DevBuf<double> d_mixed;  // Mesh::mixed (the per-face records of the mixed T patches), when there are any
+    DevBuf<int> d_tracCells;  // Mesh::trac_cells (DASolidDisplacementFoam), when there are any
     DevBuf<double> d_phiF, d_Told;
     DevMesh dm;
     DevBuf<double> d_W, d_R, d_R0, d_Wp, d_scale, d_tmp1, d_tmp2;
@@ -877,6 +912,11 @@ struct das_solver {
         DevBuf<int> d_cell;
         DevBuf<long long> d_idx;
         DevBuf<double> d_data, d_part, d_unit;  // d_unit: betaFINuTilda = 1 while no field has been set
+        // DASolidDisplacementFoam: constSrc = variableVolSum of solid:rho (src = the uniform density, a `field`-like source no state
+        // reaches); vmKS = vonMisesStressKS over the cell set (k_vm_terms + the KS kernels of das_facefn.hpp)
+        bool constSrc = false, vmKS = false;
+        double coeffKS = 1.0;
+        DevBuf<double> d_a, d_ks, d_kpart, d_wt, d_wc;  // vm per term, {m, S}, partials, softmax weights per term and per cell
         bool uploaded = false;
         CellFnView view() const {
             return CellFnView{(long long)cell.size(), d_cell.p, d_idx.p, data.empty() ? nullptr : d_data.p, (int)square, (int)multiplyVol};
@@ -1241,7 +1281,7 @@ static das_mat* assemble(das_solver* s, int isPC, int mode) {
     // in-pattern entries of the same colour - an accepted approximation of the PRECONDITIONER matrix only, the operator
     // dRdW^T always uses the full tables
     // A user table with URes < 2 gets the reference's upwind div(pc) back (weight 0) with a warning instead of an error.
-    if (isPC && prm.convBlend > 0.0 && s->cp.solver != DAS_SOLVER_SCALARTRANSPORTFOAM && s->cp.solver != DAS_SOLVER_HEATTRANSFERFOAM && s->opt.geti("maxResConLv4JacPCMat.URes") < 2) {
+    if (isPC && prm.convBlend > 0.0 && s->cp.solver != DAS_SOLVER_SCALARTRANSPORTFOAM && s->cp.solver != DAS_SOLVER_HEATTRANSFERFOAM && s->cp.solver != DAS_SOLVER_SOLIDDISPLACEMENTFOAM && s->opt.geti("maxResConLv4JacPCMat.URes") < 2) {
         static bool warned = false;
         if (!warned) fprintf(stderr, "[dafoam_amd] warning: amd.pcUpwindBlend %.3g needs maxResConLv4JacPCMat.URes >= 2 (the second-order correction reaches two cell rings); "
                                      "the PC matrix is assembled with the upwind div(pc) (weight 0) instead\n", prm.convBlend);
@@ -3054,8 +3094,15 @@ static double device_norm2(das_solver* s, das_ksp* k, const double* x) {
 
 static int run_newton_primal(das_solver* s, int maxSteps, double relTol, double absTol, NewtonInfo& info) {
     need_init(s);
-    DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver) || s->cp.solver == DAS_SOLVER_HEATTRANSFERFOAM, DAS_ERR_ARG,
-              "the Newton primal needs a flow solver or DAHeatTransferFoam");
+    DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver) || s->cp.solver == DAS_SOLVER_HEATTRANSFERFOAM ||
+                  s->cp.solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM,
+              DAS_ERR_ARG, "the Newton primal needs a flow solver, DAHeatTransferFoam or DASolidDisplacementFoam");
+    if (s->cp.solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM) {
+        // without a fixedValue patch a rigid translation of D changes nothing: the steady elastic problem is singular
+        bool anchored = false;
+        for (int p = 0; p < (int)s->mesh.bc.size(); p++) anchored = anchored || (s->mesh.patch_size[p] > 0 && s->mesh.bc[p].U_code == DAS_BC_FIXED_VALUE);
+        DAS_CHECK(anchored, DAS_ERR_ARG, "DASolidDisplacementFoam: no patch carries a fixedValue D - the steady elastic problem is singular");
+    }
     if (s->cp.solver == DAS_SOLVER_HEATTRANSFERFOAM) {
         // pure zeroGradient boundaries leave T undetermined up to a constant: the steady conduction problem is singular
         bool anchored = false;
@@ -3220,7 +3267,7 @@ das_solver_t* das_create(const das_case_t* c) {
         s->t0_cpu = std::clock();
         s->cp.from_case(c);
         s->mesh.build(c);
-        s->opt.s["solverName"] = c->solver == DAS_SOLVER_SIMPLEFOAM ? "DASimpleFoam" : (c->solver == DAS_SOLVER_RHOSIMPLEFOAM ? "DARhoSimpleFoam" : (c->solver == DAS_SOLVER_TURBOFOAM ? "DATurboFoam" : (c->solver == DAS_SOLVER_HEATTRANSFERFOAM ? "DAHeatTransferFoam" : "DAScalarTransportFoam")));
+        s->opt.s["solverName"] = c->solver == DAS_SOLVER_SIMPLEFOAM ? "DASimpleFoam" : (c->solver == DAS_SOLVER_RHOSIMPLEFOAM ? "DARhoSimpleFoam" : (c->solver == DAS_SOLVER_TURBOFOAM ? "DATurboFoam" : (c->solver == DAS_SOLVER_HEATTRANSFERFOAM ? "DAHeatTransferFoam" : (c->solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM ? "DASolidDisplacementFoam" : "DAScalarTransportFoam"))));
         s->st_full = make_stencil(s->cp.solver, s->mesh.nC, s->mesh.nF, s->opt, false, s->cp.hasT != 0);
         s->n = s->st_full.n;
         s->h_W.assign(s->n, 0.0);
@@ -3311,6 +3358,11 @@ int das_init_solver(das_solver_t* s, int device) {
     s->dm = DevMesh{m.nC, m.nF, m.nIF, s->d_fg.p, s->d_cg.p, s->d_cf_ptr.p, s->d_cf_face.p, s->d_cf_other.p, s->d_owner.p, s->d_neigh.p,
                     s->d_bpatch.p, s->d_bc.p, s->d_cyc.p};
     if (!m.mixed.empty()) { s->d_mixed.upload(m.mixed); s->dm.mixed = s->d_mixed.p; }
+    if (!m.trac_cells.empty()) {  // DASolidDisplacementFoam: the compact list the traction passes run over
+        s->d_tracCells.upload(m.trac_cells);
+        s->cp.tracCells_ptr = s->d_tracCells.p;
+        s->cp.nTrac = (int)m.trac_cells.size();
+    }
     s->d_W.upload(s->h_W);
     s->d_R.alloc(s->n);
     s->d_tmp1.alloc(s->n);
@@ -3589,6 +3641,7 @@ extern "C++" struct SimpleDeviceOps {  // (a member template inside the C-ABI bl
 // of the last sweep.
 static void run_simple_sweeps(das_solver* s, int nSweeps, double alphaP, double linTol, int maxLin, double* info) {
     need_init(s);
+    DAS_CHECK(s->cp.solver != DAS_SOLVER_SOLIDDISPLACEMENTFOAM, DAS_ERR_ARG, "the SIMPLE sweeps are not built for DASolidDisplacementFoam (use das_solve_primal)");
     DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM && !s->cp.hasT && !s->cp.mrf && !s->cp.hasCyclic, DAS_ERR_ARG,
               "SIMPLE sweeps serve DASimpleFoam + SA without T field, MRF and cyclic pairs");
     DAS_CHECK(!s->halo.active && !s->halo_cb && s->owned.empty(), DAS_ERR_ARG, "the SIMPLE sweeps are single-rank");
@@ -3845,6 +3898,8 @@ static void launch_grad_and_faces(hipStream_t st, bool rho, const DevMeshT<G>& d
 static double ref_var_value(bool refVar, double ref, double F0) { return refVar ? (F0 - ref) * (F0 - ref) : F0; }
 static double ref_var_outer(bool refVar, double ref, double F0) { return refVar ? 2.0 * (F0 - ref) : 1.0; }
 static void need_flow_solver(das_solver* s) {
+    DAS_CHECK(s->cp.solver != DAS_SOLVER_SOLIDDISPLACEMENTFOAM, DAS_ERR_ARG,
+              "face functions and coupling outputs are not built for DASolidDisplacementFoam (variableVolSum of D is)");
     DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver), DAS_ERR_ARG, "function needs a flow solver");
 }
 // the derivative passes of a face function that is already defined: the flow solvers, and DAHeatTransferFoam (wallHeatFlux, thermal coupling)
@@ -4016,6 +4071,11 @@ static int field_var_id(das_solver* s, const char* var, bool allowField) {
     const bool hasT = DAS_IS_COMPRESSIBLE(s->cp.solver) || s->cp.hasT || s->cp.solver == DAS_SOLVER_SCALARTRANSPORTFOAM || s->cp.solver == DAS_SOLVER_HEATTRANSFERFOAM;
     const std::string supported = std::string(flow ? "U, p, nuTilda" : "") + (hasT ? (flow ? ", T" : "T") : "") + (allowField && flow ? ", betaFINuTilda" : "");
     int id = -1;
+    if (s->cp.solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM) {  // the one vector state D sits where U sits in the flow layouts
+        DAS_CHECK(v == "D" || (v == "solid:rho" && allowField), DAS_ERR_ARG,
+                  "varName " + v + " is not supported by DASolidDisplacementFoam; supported: D" + (allowField ? ", solid:rho" : ""));
+        return v == "D" ? 0 : 4;  // solid:rho: the uniform density, a source no state reaches (the slot of the `field` sources)
+    }
     if (v == "U" && flow) id = 0;
     else if (v == "p" && flow) id = 1;
     else if (v == "nuTilda" && flow) id = 2;
@@ -4072,12 +4132,15 @@ int das_define_cell_function(das_solver_t* s, const char* name, const char* type
     DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "variableVolSum / variance functions run on an undecomposed solver");
     const std::string ty = type;
     DAS_CHECK(ty == "variableVolSum" || ty == "variance", DAS_ERR_ARG, "cell function type not valid: " + ty);
+    DAS_CHECK(s->cp.solver != DAS_SOLVER_SOLIDDISPLACEMENTFOAM || ty == "variableVolSum", DAS_ERR_ARG,
+              "function type " + ty + " (function " + name + ") is not built for DASolidDisplacementFoam; variableVolSum of D is");
     const int vid = field_var_id(s, var, ty == "variableVolSum");
     check_comps(vid, comps, ncomp);
     DAS_CHECK(ty == "variance" || ncomp == 1, DAS_ERR_ARG, "variableVolSum takes one component");
     das_solver::CellFn fn;
     fn.variance = ty == "variance";
     fn.field = vid == 4;
+    fn.constSrc = fn.field && s->cp.solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM;
     fn.square = fn.variance || (flags & 1);
     fn.multiplyVol = fn.variance ? (flags & 16) != 0 : (flags & 2) != 0;
     fn.divByTotalVol = !fn.variance && (flags & 4);
@@ -4102,6 +4165,33 @@ int das_define_cell_function(das_solver_t* s, const char* name, const char* type
         for (int k = 0; k < ncells; k++) { DAS_CHECK(!seen[cells[k]], DAS_ERR_ARG, "repeated cell in the cell set"); seen[cells[k]] = 1; }
     }
     if (fn.variance && data) fn.data.assign(data, data + fn.cell.size());
+    s->functions.erase(name);
+    s->cellFunctions[name] = std::move(fn);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_define_von_mises_function(das_solver_t* s, const char* name, const int* cells, int ncells, double scale, double coeffKS, int flags, double ref) {
+    DAS_TRY
+    DAS_CHECK(s && name && cells && ncells > 0, DAS_ERR_ARG, "vonMisesStressKS: a non-empty cell set is expected");
+    DAS_CHECK(s->cp.solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM, DAS_ERR_ARG,
+              std::string("function type vonMisesStressKS (function ") + name + ") is built for DASolidDisplacementFoam only");
+    DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "vonMisesStressKS runs on an undecomposed solver (sharded solvers are not supported)");
+    DAS_CHECK(coeffKS != 0.0, DAS_ERR_ARG, std::string("coeffKS of vonMisesStressKS function ") + name + " is zero");
+    das_solver::CellFn fn;
+    fn.vmKS = true;
+    fn.coeffKS = coeffKS;
+    fn.scale = scale;
+    fn.refVar = (flags & 8) != 0;
+    fn.ref = ref;
+    std::vector<unsigned char> seen(s->mesh.nC, 0);
+    for (int k = 0; k < ncells; k++) {
+        const int c = cells[k];
+        DAS_CHECK(c >= 0 && c < s->mesh.nC, DAS_ERR_ARG, "cell index out of range");
+        DAS_CHECK(!seen[c], DAS_ERR_ARG, "repeated cell in the cell set");
+        seen[c] = 1;
+        fn.cell.push_back(c);
+        fn.idx.push_back(3LL * c);
+    }
     s->functions.erase(name);
     s->cellFunctions[name] = std::move(fn);
     return DAS_OK;
@@ -4137,15 +4227,69 @@ static das_solver::CellFn* find_cell_function(das_solver* s, const char* name) {
 // is left as it is)
 static const double* cell_function_src(das_solver* s, das_solver::CellFn& fn) {
     if (!fn.field) return s->d_W.p;
-    if (!s->cp.beta_fi.empty()) return s->d_betaFI.p;
-    if (fn.d_unit.n != (size_t)s->mesh.nC) fn.d_unit.upload(std::vector<double>(s->mesh.nC, 1.0));
+    if (!fn.constSrc && !s->cp.beta_fi.empty()) return s->d_betaFI.p;
+    if (fn.d_unit.n != (size_t)s->mesh.nC) fn.d_unit.upload(std::vector<double>(s->mesh.nC, fn.constSrc ? s->cp.solidRho : 1.0));
     return fn.d_unit.p;
 }
 static int cell_function_blocks(const das_solver::CellFn& fn) {
     return std::max(1, std::min(DAS_CELLFN_MAX_BLOCKS, nblk((long long)fn.cell.size(), 256)));
 }
+// vonMisesStressKS: gradD of the residual pass (traction passes included) into s->wk.gU, vm of the terms into fn.d_a, then the
+// max-shifted two-stage KS sum of das_facefn.hpp; {m, S} stay in fn.d_ks for the weights.  F0 = (m + log S) / coeffKS.  The reference
+// aborts when its plain sum of exponentials passes 1e200; the log-space sum has no such limit and none is imposed (wider than the reference).
+static double vm_ks_value(das_solver* s, das_solver::CellFn& fn) {
+    const long long nt = (long long)fn.cell.size();
+    DAS_CHECK(nt > 0, DAS_ERR_ARG, "vonMisesStressKS: the cell set is empty");
+    const ResParams prm = s->wk.bind(s->cp.solver, s->dm.nC, s->dm.nF, make_params(s->cp, s->opt, 0));
+    launch_solid_grad<double, double>(s->dm, prm, (const double*)s->d_W.p, s->wk, s->stream);
+    const int nb = cell_function_blocks(fn);
+    if (fn.d_ks.n != 2) fn.d_ks.alloc(2);
+    if (fn.d_kpart.n != DAS_CELLFN_MAX_BLOCKS) fn.d_kpart.alloc(DAS_CELLFN_MAX_BLOCKS);
+    if (fn.d_a.n != (size_t)nt) { fn.d_a.alloc(nt); fn.d_wt.alloc(nt); }
+    if (fn.d_wc.n != (size_t)s->mesh.nC) fn.d_wc.alloc(s->mesh.nC);
+    hipLaunchKernelGGL(k_vm_terms, dim3(nblk(nt, 256)), dim3(256), 0, s->stream, nt, (const int*)fn.d_cell.p, prm, (const double*)s->wk.gU.p, fn.scale, fn.d_a.p);
+    hipLaunchKernelGGL(k_ks_max, dim3(nb), dim3(256), 0, s->stream, nt, (const double*)fn.d_a.p, fn.coeffKS, fn.d_kpart.p);
+    hipLaunchKernelGGL(k_ks_max_final, dim3(1), dim3(256), 0, s->stream, nb, (const double*)fn.d_kpart.p, fn.d_ks.p);
+    hipLaunchKernelGGL(k_ks_expsum, dim3(nb), dim3(256), 0, s->stream, nt, (const double*)fn.d_a.p, fn.coeffKS, (const double*)fn.d_ks.p, fn.d_kpart.p);
+    hipLaunchKernelGGL(k_ks_sum_final, dim3(1), dim3(256), 0, s->stream, nb, (const double*)fn.d_kpart.p, fn.d_ks.p);
+    DAS_HIP(hipGetLastError());
+    double ms[2];
+    DAS_HIP(hipMemcpyAsync(ms, fn.d_ks.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    return (ms[0] + std::log(ms[1])) / fn.coeffKS;
+}
+// the per-cell weights g dF/dvm_c of the derivative passes into fn.d_wc (0 outside the set); g = seed x dF/dF0 of calcRefVar
+static void vm_ks_cell_weights(das_solver* s, das_solver::CellFn& fn, double seed) {
+    const double outer = seed * ref_var_outer(fn.refVar, fn.ref, vm_ks_value(s, fn));
+    const long long nt = (long long)fn.cell.size();
+    hipLaunchKernelGGL(k_ks_weights, dim3(nblk(nt, 256)), dim3(256), 0, s->stream, nt, (const double*)fn.d_a.p, fn.coeffKS, (const double*)fn.d_ks.p, outer, fn.d_wt.p);
+    DAS_HIP(hipMemsetAsync(fn.d_wc.p, 0, (size_t)s->mesh.nC * sizeof(double), s->stream));
+    hipLaunchKernelGGL(k_vm_cell_weights, dim3(nblk(nt, 256)), dim3(256), 0, s->stream, nt, (const int*)fn.d_cell.p, (const double*)fn.d_wt.p, fn.d_wc.p);
+    DAS_HIP(hipGetLastError());
+}
+// product_j = seed s_j dF/dW_j of vonMisesStressKS: per colour one dual-number gradient pass and a gather over the cell and its face
+// neighbours (k_vm_gather), no atomics
+static void vm_ks_gradient(das_solver* s, das_solver::CellFn& fn, double seed, double* product) {
+    ensure_con_dev(s, 0);
+    vm_ks_cell_weights(s, fn, 1.0);
+    const ResParams prm = s->wk1.bind(s->cp.solver, s->dm.nC, s->dm.nF, make_params(s->cp, s->opt, 0));
+    const long long n = s->n;
+    if (s->d_Wd.n != (size_t)n) { s->d_Wd.alloc(n); s->d_Rd.alloc(n); }
+    DAS_HIP(hipMemsetAsync(s->d_tmp2.p, 0, n * sizeof(double), s->stream));
+    const int B = 256;
+    for (int col = 0; col < s->nColors; col++) {
+        hipLaunchKernelGGL(k_seed<1>, dim3(nblk(n, B)), dim3(B), 0, s->stream, n, s->d_W.p, s->d_colors.p, s->d_scale.p, col, s->d_Wd.p);
+        launch_solid_grad<Dual<1>, double>(s->dm, prm, (const Dual<1>*)s->d_Wd.p, s->wk1, s->stream);
+        hipLaunchKernelGGL(k_vm_tangent, dim3(nblk(s->dm.nC, B)), dim3(B), 0, s->stream, s->dm.nC, prm, (const Dual<1>*)s->wk1.gU.p, fn.scale, (const double*)fn.d_wc.p, s->d_tmp1.p);
+        hipLaunchKernelGGL(k_vm_gather, dim3(nblk(n, B)), dim3(B), 0, s->stream, s->dm, (const int*)s->d_colors.p, col, (const double*)s->d_tmp1.p, seed, s->d_tmp2.p);
+    }
+    DAS_HIP(hipGetLastError());
+    DAS_HIP(hipMemcpyAsync(product, s->d_tmp2.p, n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
+}
 // F0 = coef sum_t w_t g(x_t) (before calcRefVar)
 static double cell_function_base_value(das_solver* s, das_solver::CellFn& fn) {
+    if (fn.vmKS) return vm_ks_value(s, fn);
     if (fn.coef == 0.0) return 0.0;
     const int nb = cell_function_blocks(fn);
     hipLaunchKernelGGL(k_cellfn_value, dim3(nb), dim3(256), 0, s->stream, fn.view(), (const CellGeom*)s->d_cg.p, cell_function_src(s, fn), fn.d_part.p);
@@ -4287,6 +4431,7 @@ static void function_gradient(das_solver* s, const char* name, double seed, doub
     need_init(s);
     if (das_solver::CellFn* cf = find_cell_function(s, name)) {  // local and analytic: one elementwise pass, no colouring
         if (cf->field) std::fill(product, product + s->n, 0.0);
+        else if (cf->vmKS) vm_ks_gradient(s, *cf, seed, product);
         else cell_function_gradient(s, *cf, seed, true, product, s->n);
         return;
     }
@@ -4592,7 +4737,7 @@ long long das_op_format_bytes(das_solver_t* s) {
 // ---- boundary-value inputs (reference DAInputPatchVelocity.C:33-135, DAInputPatchVar.C) ---------------------------
 static int bc_field_id(const char* field) {
     std::string f = field ? field : "";
-    if (f == "U") return 0;
+    if (f == "U" || f == "D") return 0;  // (D of DASolidDisplacementFoam rides in the U slots of the patch table)
     if (f == "p") return 1;
     if (f == "nuTilda") return 2;
     if (f == "T") return 3;
@@ -4678,7 +4823,9 @@ int das_calc_dbc_product(das_solver_t* s, const int* patches, int np, const char
         hipLaunchKernelGGL(k_tangent_dot, dim3(1024), dim3(256), 0, st, n, s->d_Rd.p, s->d_tmp2.p, part.p);
         hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, st, 1024LL, (const unsigned char*)nullptr, (const double*)part.p, s->d_tmp1.p);
         DAS_HIP(hipStreamSynchronize(st));  // part goes out of scope
-    } else if (!isFC && find_cell_function(s, outputName)) {  // cell-set functions read no boundary value
+    } else if (!isFC && find_cell_function(s, outputName)) {
+        // variableVolSum reads no boundary value.  vonMisesStressKS does - vm of a boundary cell follows a fixedValue D through the cell
+        // gradD - and its zero here is the convention the function layer was specified with, NOT the derivative
         product[0] = 0.0;
         return DAS_OK;
     } else if (!isFC && DAS_FN_BASE(get_function(s, outputName).kind) == DAS_FN_LOCATION) {  // geometry only
@@ -4816,7 +4963,8 @@ int das_set_field(das_solver_t* s, const char* fieldName, const double* values) 
     DAS_TRY
     DAS_CHECK(s && values, DAS_ERR_ARG, "null argument");
     check_field(fieldName);
-    DAS_CHECK(s->cp.solver != DAS_SOLVER_SCALARTRANSPORTFOAM && s->cp.solver != DAS_SOLVER_HEATTRANSFERFOAM, DAS_ERR_ARG, "betaFINuTilda needs a Spalart-Allmaras solver");
+    DAS_CHECK(s->cp.solver != DAS_SOLVER_SCALARTRANSPORTFOAM && s->cp.solver != DAS_SOLVER_HEATTRANSFERFOAM && s->cp.solver != DAS_SOLVER_SOLIDDISPLACEMENTFOAM,
+              DAS_ERR_ARG, "betaFINuTilda needs a Spalart-Allmaras solver");
     s->cp.beta_fi.assign(values, values + s->mesh.nC);
     if (s->inited) {
         DAS_HIP(hipStreamSynchronize(s->stream));
@@ -4850,7 +4998,7 @@ int das_calc_dfield_product(das_solver_t* s, const char* fieldName, const char* 
     const std::string ot = outputType;
     DAS_CHECK(ot == "residual" || ot == "function" || is_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
     const long long N = s->mesh.nC, n = s->n;
-    if (s->cp.solver == DAS_SOLVER_SCALARTRANSPORTFOAM || s->cp.solver == DAS_SOLVER_HEATTRANSFERFOAM) {
+    if (s->cp.solver == DAS_SOLVER_SCALARTRANSPORTFOAM || s->cp.solver == DAS_SOLVER_HEATTRANSFERFOAM || s->cp.solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM) {
         // no Spalart-Allmaras production term: nothing of these solvers reads the field - exact zeros (an unknown output still fails by name)
         if (is_coupling(ot)) (void)coupling_size(s, ot, outputName);
         else if (ot == "function" && !find_cell_function(s, outputName)) (void)get_function(s, outputName);
@@ -5016,6 +5164,7 @@ static RowLayout residual_row_layout(das_solver* s) {
 // ---- heat sources of DAHeatTransferFoam (reference DAFvSourceHeatSource.C; kernels: das_heatsource.hpp) -----------------------------
 static void need_heat_source_solver(das_solver* s) {
     DAS_CHECK(s, DAS_ERR_ARG, "null solver handle");
+    DAS_CHECK(s->cp.solver != DAS_SOLVER_SOLIDDISPLACEMENTFOAM, DAS_ERR_ARG, "the fvSource option is not built for DASolidDisplacementFoam");
     DAS_CHECK(s->cp.solver == DAS_SOLVER_HEATTRANSFERFOAM, DAS_ERR_ARG,
               "the fvSource heat sources (and the fvSourcePar input) are built for DAHeatTransferFoam only: no fvSource on a flow solver or on DAScalarTransportFoam");
     DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "the fvSource heat sources run on an undecomposed solver (sharded solvers are not supported)");
@@ -5271,6 +5420,7 @@ static void heat_source_rank1_terms(das_solver* s, const double* d_psi, int byV,
 // ---- actuator disks of DASimpleFoam (reference DAFvSourceActuatorDisk.C; kernels: das_actuatordisk.hpp) -----------------------------
 static void need_actuator_disk_solver(das_solver* s) {
     DAS_CHECK(s, DAS_ERR_ARG, "null solver handle");
+    DAS_CHECK(s->cp.solver != DAS_SOLVER_SOLIDDISPLACEMENTFOAM, DAS_ERR_ARG, "the fvSource option is not built for DASolidDisplacementFoam");
     DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM, DAS_ERR_ARG,
               "the fvSource actuator disks are built for DASimpleFoam only: not for DARhoSimpleFoam (its fvSourceEnergy = fvSource . U is not built), DATurboFoam, "
               "DAScalarTransportFoam or DAHeatTransferFoam");
@@ -5633,7 +5783,10 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
     // cell-set functions (variableVolSum): F0 = N / T with N = coef T sum_S w g, T = totalVol, so dF/dV_c = dF/dF0 ( [c in S, multiplyVol]
     // scale g_c / T - [divByTotalVol] F0 / T ): cellA multiplies V_c' on every cell, cellB g_c V_c' on the cells of the set
     double cellA = 0.0, cellB = 0.0;
-    if (isCell) {
+    const bool isVm = isCell && cfn->vmKS;  // vonMisesStressKS: the linearised functional sum_c w_c vm_c on the dual metrics
+    if (isVm) {
+        vm_ks_cell_weights(s, *cfn, seeds[0]);
+    } else if (isCell) {
         const double F0 = cell_function_base_value(s, *cfn);
         const double outer = seeds[0] * ref_var_outer(cfn->refVar, cfn->ref, F0);
         cellA = cfn->divByTotalVol ? -outer * F0 / cfn->totalVol : 0.0;
@@ -5705,7 +5858,11 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
             hipLaunchKernelGGL(k_geom_face<D>, dim3(nblk(t.nF, B)), dim3(B), 0, st, t, (const D*)d_XD.p, d_fgD.p);
             hipLaunchKernelGGL(k_geom_cell<D>, dim3(nblk(t.nC, B)), dim3(B), 0, st, t, (const FaceGeomT<D>*)d_fgD.p, d_cgD.p, v.d_bad.p);
             hipLaunchKernelGGL(k_geom_weights<D>, dim3(nblk(t.nF, B)), dim3(B), 0, st, t, (const CellGeomT<D>*)d_cgD.p, d_fgD.p);
-            if (isCell) {
+            if (isVm) {
+                const ResParams prm = s->wk1.bind(s->cp.solver, s->dm.nC, s->dm.nF, prm0);
+                launch_solid_grad<D, D>(dmD, prm, (const D*)d_Wd.p, s->wk1, st);
+                hipLaunchKernelGGL(k_vm_tangent, dim3(nblk(m.nC, B)), dim3(B), 0, st, m.nC, prm, (const D*)s->wk1.gU.p, cfn->scale, (const double*)cfn->d_wc.p, d_tc.p);
+            } else if (isCell) {
                 hipLaunchKernelGGL(k_vc_cellfn_all, dim3(nblk(m.nC, B)), dim3(B), 0, st, m.nC, (const CellGeomT<D>*)d_cgD.p, cellA, d_tc.p);
                 if (cellB != 0.0 && !cfn->cell.empty())
                     hipLaunchKernelGGL(k_vc_cellfn_terms, dim3(nblk((long long)cfn->cell.size(), B)), dim3(B), 0, st, cfn->view(), (const CellGeomT<D>*)d_cgD.p,

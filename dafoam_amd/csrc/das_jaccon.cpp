@@ -85,6 +85,10 @@ Stencil make_stencil(int solver, int nC, int nF, const Options& opt, bool isPC, 
         add_state("T", KIND_SCL);
         st.levels.resize(1);
         st.levels[0] = {bits({"T"}), bits({"T"}), bits({"T"})};
+    } else if (solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM) {  // DAStateInfoSolidDisplacementFoam.C: DRes <- D at levels 0, 1 and 2
+        add_state("D", KIND_VEC);
+        st.levels.resize(1);
+        st.levels[0] = {bits({"D"}), bits({"D"}), bits({"D"})};
     } else {
         throw Error(DAS_ERR_ARG, "unknown solver id");
     }

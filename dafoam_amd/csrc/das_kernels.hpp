@@ -88,6 +88,12 @@ struct ResParams {
     // DAHeatTransferFoam: kappa(T) = sum_k kappa[k] T^k, nKappa terms (kappa_of); solid = 1: the one-block state layout [T] (host-side launch switch)
     int solid, nKappa;
     double kappa[DAS_MAX_KAPPA_COEFFS];
+    // DASolidDisplacementFoam: rho and the Lame coefficients per unit density (E / rho based, solid_lame); normD: DRes is listed in
+    // normalizeResiduals; nPass: the option maxCorrectBCCalls, the lagged passes of the tractionDisplacement gradient; the compact list of
+    // the cells that own a traction face (nTrac entries; device memory in the library, the host vector in the test harness)
+    double sRho, sMu, sLam;
+    int normD, nPass, nTrac;
+    const int* tracCells;
 };
 #define DAS_TREF 298.15
 
@@ -1575,6 +1581,206 @@ DAS_HD void body_heat(int c, const DevMeshT<G>& m, const ResParams& prm, const T
     if (m.src) res = res + m.src[c];
     if (!prm.normT) res = res * cgc.V;
     R[c] = res;
+}
+
+// ================================================================================ DASolidDisplacementFoam
+// One cell vector state D, layout [D] as the U block of the flow solvers.  gradD[9 c + 3 i + j] = d_i D_j (Gauss linear).
+//   DRes = -(laplacian(2 mu + lambda, D) + div(sigmaD - (2 mu + lambda) gradD)),  sigmaD = mu twoSymm(gradD) + lambda tr(gradD) I
+//   (DEqn & D with the steady d2dt2 = 0; DAResidualSolidDisplacementFoam.C:66-76).  There is no PC variant: isPC is not read.
+// Lame coefficients per unit density, as readMechanicalPropertiesSolidDisplacement.H:133-156 computes them
+inline void solid_lame(double rho, double E, double nu, int planeStress, double& mu, double& lambda) {
+    const double Er = E / rho;
+    mu = Er / (2.0 * (1.0 + nu));
+    lambda = planeStress ? nu * Er / ((1.0 + nu) * (1.0 - nu)) : nu * Er / ((1.0 + nu) * (1.0 - 2.0 * nu));
+}
+// the D patch field of boundary face f without its lagged part: fixedValue / zeroGradient / symmetry through bc_vector; a
+// tractionDisplacement face as the freshly constructed patch field has it, gradient 0 and D_b = D_c.  nrm: the unit normal
+template <class T, class G>
+DAS_HD bool solid_bface(const DevMeshT<G>& m, int f, const T* Dc, G* nrm, VectorBC<T, G>& b) {
+    const PatchBC& bc = m.bc[m.bpatch[f - m.nIF]];
+    const FaceGeomT<G>& g = m.fg[f];
+#pragma unroll
+    for (int k = 0; k < 3; k++) nrm[k] = g.Sf[k] / g.magSf;
+    const bool trac = bc.U_code == DAS_BC_TRACTION;
+    bc_vector<T>(trac ? DAS_BC_ZERO_GRADIENT : bc.U_code, bc.U_val, bc.dU_val, g.nod, 0.0, nrm, Dc, b);
+    return trac;
+}
+// X = sigmaD - (2 mu + lambda) gradD = mu gradD^T - (mu + lambda) gradD + lambda tr(gradD) I, then acc_j += S_i X_ij
+template <class T, class G>
+DAS_HD void solid_div_term(const ResParams& prm, const T* B, const G* S, double sg, T* acc) {
+    const T ltr = prm.sLam * (B[0] + B[4] + B[8]);
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        T a(0.0);
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            T x = prm.sMu * B[3 * j + i] - (prm.sMu + prm.sLam) * B[3 * i + j];
+            if (i == j) x = x + ltr;
+            a += S[i] * x;
+        }
+        acc[j] += sg * a;
+    }
+}
+// OpenFOAM's corrected boundary gradient of a non-coupled patch: B = Gc + n (sn - n . Gc)  (gaussGrad::correctBoundaryConditions)
+template <class T, class G>
+DAS_HD void solid_bgrad(const T* Gc, const G* n, const T* sn, T* B) {
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const T d = sn[j] - (n[0] * Gc[j] + n[1] * Gc[3 + j] + n[2] * Gc[6 + j]);
+#pragma unroll
+        for (int i = 0; i < 3; i++) B[3 * i + j] = Gc[3 * i + j] + n[i] * d;
+    }
+}
+// Gauss linear gradient of D with the pass-0 boundary values (solid_bface)
+template <class T, class G>
+DAS_HD void body_solid_grad(int c, const DevMeshT<G>& m, const ResParams& prm, const T* W, T* gradD) {
+    const CellGeomT<G>& cgc = m.cg[c];
+    const T Dc[3] = {W[3LL * c], W[3LL * c + 1], W[3LL * c + 2]};
+    T gD[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) gD[i] = T(0.0);
+    for (int s = m.cf_ptr[c]; s < m.cf_ptr[c + 1]; s++) {
+        int fe = m.cf_face[s];
+        int f = fe & 0x7fffffff;
+        bool nb = fe < 0;
+        const FaceGeomT<G>& g = m.fg[f];
+        double sg = nb ? -1.0 : 1.0;
+        T Df[3];
+        if (f < m.nIF) {
+            const int o = m.cf_other[s];
+            G wc = nb ? G(1.0 - g.w) : g.w;
+#pragma unroll
+            for (int j = 0; j < 3; j++) Df[j] = wc * Dc[j] + (1.0 - wc) * W[3LL * o + j];
+        } else {
+            VectorBC<T, G> b;
+            G nrm[3];
+            solid_bface<T, G>(m, f, Dc, nrm, b);
+#pragma unroll
+            for (int j = 0; j < 3; j++) Df[j] = b.xb[j];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+            for (int j = 0; j < 3; j++) gD[3 * i + j] += (sg * g.Sf[i]) * Df[j];
+    }
+    G rV = 1.0 / cgc.V;
+#pragma unroll
+    for (int i = 0; i < 9; i++) gradD[9LL * c + i] = gD[i] * rV;
+}
+// The lagged passes of tractionDisplacement (tractionDisplacementFvPatchVectorField.C:89-117 under DASolver::updateStateBoundaryConditions)
+// for the k-th cell that owns a traction face: from g = 0 and the pass-0 gradient G0, each of the prm.nPass passes evaluates
+//   g = ((t - p n) / rho - n . (mu B^T - (mu + lambda) B) - n tr(B) lambda) / (2 mu + lambda),  B = G + n (g_prev - n . G)
+// on every traction face of the cell from the previous G and the face's own previous g, sets D_b = D_c + g / deltaCoeff and rebuilds
+// G = G0 + sum_f Sf (g / deltaCoeff) / V.  Everything stays inside the cell.  gTr: 3 per boundary face, the final g of the traction faces
+template <class T, class G>
+DAS_HD void body_solid_traction(int k, const DevMeshT<G>& m, const ResParams& prm, T* gradD, T* gTr) {
+    const int c = prm.tracCells[k];
+    const G rV = 1.0 / m.cg[c].V;
+    const double rg = 1.0 / (2.0 * prm.sMu + prm.sLam);
+    T G0[9], Gp[9], Gn[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) { G0[i] = gradD[9LL * c + i]; Gp[i] = G0[i]; }
+    for (int pass = 0; pass < prm.nPass; pass++) {  // (the host refuses maxCorrectBCCalls < 1 for this solver)
+#pragma unroll
+        for (int i = 0; i < 9; i++) Gn[i] = G0[i];
+        for (int s = m.cf_ptr[c]; s < m.cf_ptr[c + 1]; s++) {
+            const int f = m.cf_face[s] & 0x7fffffff;
+            if (f < m.nIF) continue;
+            const PatchBC& bc = m.bc[m.bpatch[f - m.nIF]];
+            if (bc.U_code != DAS_BC_TRACTION) continue;
+            const FaceGeomT<G>& g = m.fg[f];
+            T* gf = gTr + 3LL * (f - m.nIF);
+            G n[3];
+#pragma unroll
+            for (int i = 0; i < 3; i++) n[i] = g.Sf[i] / g.magSf;
+            T gp[3] = {T(0.0), T(0.0), T(0.0)};
+            if (pass > 0) { gp[0] = gf[0]; gp[1] = gf[1]; gp[2] = gf[2]; }
+            T B[9];
+            solid_bgrad<T, G>(Gp, n, gp, B);
+            const T ltr = prm.sLam * (B[0] + B[4] + B[8]);
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                T a(0.0);
+#pragma unroll
+                for (int i = 0; i < 3; i++) a += n[i] * (prm.sMu * B[3 * j + i] - (prm.sMu + prm.sLam) * B[3 * i + j]);
+                const T gj = (((bc.D_trac[j] - bc.D_pres * n[j]) * (1.0 / prm.sRho)) - a - n[j] * ltr) * rg;
+                gf[j] = gj;
+#pragma unroll
+                for (int i = 0; i < 3; i++) Gn[3 * i + j] += (g.Sf[i] * rV / g.nod) * gj;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 9; i++) Gp[i] = Gn[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 9; i++) gradD[9LL * c + i] = Gp[i];
+}
+// DRes of cell c from the final gradD and the final traction gradients gTr
+template <class T, class G>
+DAS_HD void body_solid(int c, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* gradD, const T* gTr, T* R) {
+    const CellGeomT<G>& cgc = m.cg[c];
+    const double gam = 2.0 * prm.sMu + prm.sLam;
+    const T Dc[3] = {W[3LL * c], W[3LL * c + 1], W[3LL * c + 2]};
+    T Gc[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) Gc[i] = gradD[9LL * c + i];
+    T lap[3] = {T(0.0), T(0.0), T(0.0)}, dv[3] = {T(0.0), T(0.0), T(0.0)};
+    for (int s = m.cf_ptr[c]; s < m.cf_ptr[c + 1]; s++) {
+        int fe = m.cf_face[s];
+        int f = fe & 0x7fffffff;
+        bool nb = fe < 0;
+        const FaceGeomT<G>& g = m.fg[f];
+        if (f < m.nIF) {
+            const int o = m.cf_other[s];
+            const double sg = nb ? -1.0 : 1.0;
+            G wc = nb ? G(1.0 - g.w) : g.w, wo = 1.0 - wc;
+            T Gf[9];
+#pragma unroll
+            for (int i = 0; i < 9; i++) Gf[i] = wc * Gc[i] + wo * gradD[9LL * o + i];
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                T cv = g.corr[0] * Gf[j] + g.corr[1] * Gf[3 + j] + g.corr[2] * Gf[6 + j];
+                lap[j] += (gam * g.magSf) * (g.nod * (W[3LL * o + j] - Dc[j]) + sg * cv);
+            }
+            solid_div_term<T, G>(prm, Gf, g.Sf, sg, dv);
+        } else {
+            VectorBC<T, G> b;
+            G n[3];
+            const bool trac = solid_bface<T, G>(m, f, Dc, n, b);
+            T sn[3];
+#pragma unroll
+            for (int j = 0; j < 3; j++) sn[j] = trac ? gTr[3LL * (f - m.nIF) + j] : T(b.gic[j] * Dc[j] + b.gbc[j]);
+#pragma unroll
+            for (int j = 0; j < 3; j++) lap[j] += (gam * g.magSf) * sn[j];
+            T B[9];
+            solid_bgrad<T, G>(Gc, n, sn, B);
+            solid_div_term<T, G>(prm, B, g.Sf, 1.0, dv);
+        }
+    }
+    const G rV = 1.0 / cgc.V;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        T res = -((lap[j] + dv[j]) * rV);
+        if (!prm.normD) res = res * cgc.V;
+        R[3LL * c + j] = res;
+    }
+}
+// von Mises stress of cell c, vm = scale sqrt(1.5 |dev sigma|^2), sigma = rho (mu twoSymm(gradD) + lambda tr(gradD) I)
+// (DAFunctionVonMisesStressKS.C:55-58); dev removes the trace, so lambda drops out
+template <class T>
+DAS_HD T solid_von_mises(const ResParams& prm, const T* Gc, double scale) {
+    const T tr3 = (2.0 / 3.0) * (Gc[0] + Gc[4] + Gc[8]);
+    T ss(0.0);
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            T e = Gc[3 * i + j] + Gc[3 * j + i];
+            if (i == j) e = e - tr3;
+            ss += e * e;
+        }
+    const double rm = prm.sRho * prm.sMu;
+    return scale * dsqrt(1.5 * (rm * rm) * ss);
 }
 
 // the face functions of the solid, on the one-block state layout [T] (kinds and DAS_FN_ALT_BIT as body_facefn):

@@ -30,6 +30,7 @@ Options::Options() {
     d["normalizeStates.nuTilda"] = 1.0;
     d["normalizeStates.phi"] = 1.0;
     d["normalizeStates.T"] = 1.0;
+    d["normalizeStates.D"] = 1.0;
     i["useConstrainHbyA"] = 1;
     i["adjUseColoring"] = 1;
     i["maxCorrectBCCalls"] = 2;
@@ -55,6 +56,7 @@ Options::Options() {
     i["maxResConLv4JacPCMat.phiRes"] = 1;
     i["maxResConLv4JacPCMat.URes"] = 2;
     i["maxResConLv4JacPCMat.TRes"] = 2;
+    i["maxResConLv4JacPCMat.DRes"] = 2;
     i["maxResConLv4JacPCMat.nuTildaRes"] = 2;
     d["jacLowerBounds.dRdW"] = 1.0e-30;
     d["jacLowerBounds.dRdWPC"] = 1.0e-30;
@@ -223,6 +225,23 @@ void Mesh::build(const das_case_t* c) {
         b.mrf_included = (c->mrf_active && c->patch_mrf_rotating) ? (c->patch_mrf_rotating[p] != 0) : 0;
         b.rot = 0;
         for (int k = 0; k < 9; k++) b.Q[k] = (k % 4 == 0) ? 1.0 : 0.0;
+        b.D_trac[0] = b.D_trac[1] = b.D_trac[2] = b.D_pres = 0.0;
+        if (c->solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM) {  // the one vector state D takes the U slots of the table
+            DAS_CHECK(patch_type[p] != DAS_PATCH_CYCLIC, DAS_ERR_ARG,
+                      "DASolidDisplacementFoam: patch " + std::to_string(p) + " is cyclic - cyclic patches are not built for D");
+            b.U_code = c->bc_D_code ? c->bc_D_code[p] : DAS_BC_ZERO_GRADIENT;
+            DAS_CHECK(b.U_code == DAS_BC_FIXED_VALUE || b.U_code == DAS_BC_ZERO_GRADIENT || b.U_code == DAS_BC_SYMMETRY || b.U_code == DAS_BC_TRACTION,
+                      DAS_ERR_ARG, "DASolidDisplacementFoam: patch " + std::to_string(p) + ": D is fixedValue, zeroGradient, symmetry or tractionDisplacement, not code " +
+                                       std::to_string(b.U_code));
+            for (int k = 0; k < 3; k++) {
+                b.U_val[k] = c->bc_D_val ? c->bc_D_val[3 * p + k] : 0.0;
+                b.D_trac[k] = c->bc_D_traction ? c->bc_D_traction[3 * p + k] : 0.0;
+            }
+            b.D_pres = c->bc_D_pressure ? c->bc_D_pressure[p] : 0.0;
+        } else {
+            DAS_CHECK(b.U_code != DAS_BC_TRACTION && b.p_code != DAS_BC_TRACTION && b.nuTilda_code != DAS_BC_TRACTION && b.T_code != DAS_BC_TRACTION,
+                      DAS_ERR_ARG, "patch " + std::to_string(p) + ": the tractionDisplacement patch field is built for D of DASolidDisplacementFoam only");
+        }
         if (patch_type[p] == DAS_PATCH_CYCLIC && c->patch_rotation) {
             double dev = 0;
             for (int k = 0; k < 9; k++) { b.Q[k] = c->patch_rotation[9 * p + k]; dev += std::fabs(b.Q[k] - ((k % 4 == 0) ? 1.0 : 0.0)); }
@@ -262,6 +281,15 @@ void Mesh::build(const das_case_t* c) {
     }
     build_addressing();
     compute_geometry(c->y_wall);
+    // DASolidDisplacementFoam: the cells that own at least one tractionDisplacement face, ascending (the lagged passes run over these alone)
+    trac_cells.clear();
+    if (c->solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM) {
+        std::vector<unsigned char> has(nC, 0);
+        for (int f = nIF; f < nF; f++)
+            if (bc[bface_patch[f - nIF]].U_code == DAS_BC_TRACTION) has[owner[f]] = 1;
+        for (int x = 0; x < nC; x++)
+            if (has[x]) trac_cells.push_back(x);
+    }
 }
 
 // primitiveMesh::makeFaceCentresAndAreas / makeCellCentresAndVols and surfaceInterpolation::makeWeights /

@@ -603,6 +603,8 @@ def extract_submesh(case, part, rank, G=GHOST_LAYERS):
 
     if case.solver_name == "DAHeatTransferFoam":
         raise NotImplementedError("sharded (multi-rank) DAHeatTransferFoam solvers are not built: the solid solver runs on one undecomposed mesh")
+    if case.solver_name == "DASolidDisplacementFoam":
+        raise NotImplementedError("sharded (multi-rank) DASolidDisplacementFoam solvers are not built: the solid solver runs on one undecomposed mesh")
     m = case.mesh
     N, F, nIF = m.n_cells, m.n_faces, m.n_internal_faces
     own, nei = m.owner.astype(np.int64), m.neighbour.astype(np.int64)

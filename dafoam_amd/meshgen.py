@@ -29,6 +29,7 @@ BC_INLET_OUTLET = 2
 BC_SYMMETRY = 3
 BC_CYCLIC = 4  # coupled (cyclic) patch: no patch-field coefficients, the paired cell acts as a neighbour
 BC_MIXED = 5  # T only: mixedFvPatchField with refGrad = 0 and a refValue / valueFraction per face (FoamCase.mixed_T)
+BC_TRACTION = 6  # D only: the reference's tractionDisplacement patch field, (BC_TRACTION, traction (3,), pressure)
 # nut wall treatment codes
 NUT_CALCULATED = 0
 NUT_LOWRE_WALL = 1  # nut_w = 0 (nutLowReWallFunction, reference DAField.C:1155-1218)
@@ -110,6 +111,10 @@ class FoamCase:
     mixed_T: Dict[str, tuple] = field(default_factory=dict)
     # DAHeatTransferFoam, constant/solidProperties: kappa(T) = sum_k kappa_coeffs[k] T^k (`kappa`: one coefficient; `kappaCoeffs`: up to 8)
     kappa_coeffs: Optional[tuple] = None
+    # DASolidDisplacementFoam, constant/mechanicalProperties: {"rho", "E", "nu": the uniform values (or {"type": "uniform", "value": x}),
+    # "planeStress": bool}; the patch fields of D sit in bcs as {"D": (BC_FIXED_VALUE, (3,)) | (BC_ZERO_GRADIENT, 0.0) | (BC_SYMMETRY, 0.0)
+    # | (BC_TRACTION, traction (3,), pressure)}
+    mechanical: Optional[dict] = None
 
 
 def hex_block(
@@ -408,6 +413,8 @@ def n_states(case: FoamCase) -> int:
     m = case.mesh
     if case.solver_name in ("DAScalarTransportFoam", "DAHeatTransferFoam"):
         return m.n_cells
+    if case.solver_name == "DASolidDisplacementFoam":
+        return 3 * m.n_cells
     if case.solver_name == "DASimpleFoam":
         return (6 if case.has_T else 5) * m.n_cells + m.n_faces
     if case.solver_name in ("DARhoSimpleFoam", "DATurboFoam"):
@@ -722,6 +729,8 @@ def renumber_case(case: FoamCase, seed=0) -> FoamCase:
     W = case.states
     if case.solver_name in ("DAScalarTransportFoam", "DAHeatTransferFoam"):
         out.states = W[old_of_new]
+    elif case.solver_name == "DASolidDisplacementFoam":  # [D]
+        out.states = W.reshape(N, 3)[old_of_new].ravel()
     else:  # [U | scalar cell blocks ... | phi]
         nsc = (W.size - 3 * N - F) // N
         U = W[: 3 * N].reshape(N, 3)[old_of_new]
@@ -901,6 +910,9 @@ def mixed_cell_case(case: FoamCase, pyramids=(), merges=(), prism_columns=(), di
             k = slot[parent[own[pt.start : pt.start + pt.size]]]
             assert (k >= 0).all()
             new.mixed_T[pt.name] = tuple(np.asarray(a)[k].copy() for a in case.mixed_T[pt_old.name])
+        return new
+    if case.solver_name == "DASolidDisplacementFoam":  # one cell vector state, no flux
+        new.states = (W.reshape(N, 3)[parent] * jit[:, :3]).ravel()
         return new
     if case.solver_name == "DAScalarTransportFoam":  # frozen flux of the velocity field of scalar_transport_case at the new centres
         Lx = float(m.points[:, 0].max())
@@ -1151,6 +1163,43 @@ def heat_transfer_case(nx=6, ny=5, nz=4, lengths=(1.0, 0.2, 0.1), kappa=None, ka
     case.states = T * (1.0 + perturb * rng.standard_normal(T.size))
     for nm, (ref, frac) in (mixed_patches or {}).items():
         case = with_mixed_T(case, nm, ref, frac)
+    return case
+
+
+def solid_displacement_case(nx=6, ny=5, nz=4, lengths=(1.0, 0.2, 0.1), rho=7854.0, E=2e11, nu=0.3, plane_stress=False, mapping="bump",
+                            D_bcs=None, amplitude=1e-6, seed=0, perturb=0.02) -> FoamCase:
+    """DASolidDisplacementFoam (steady linear elasticity) on one hex_block with the usual six patches.
+    rho, E, nu, plane_stress: the uniform constant/mechanicalProperties.
+    mapping: "bump" (bump_mapping: non-orthogonal), None (orthogonal box) or a function on the points.
+    D_bcs: {patch: ("fixedValue", (3,)) | ("zeroGradient",) | ("symmetry",) | ("tractionDisplacement", traction (3,), pressure)}; default
+    inlet fixedValue 0, outlet a traction with a pressure, the rest zeroGradient.
+    The state is a smooth non-zero displacement of order amplitude x lengths[0] with a seeded perturbation; the case has no phi and no y_wall."""
+    if mapping == "bump":
+        mapping = bump_mapping(0.1, 0.15, lengths[0], lengths[1])
+    mesh = hex_block(nx, ny, nz, lengths, mapping, patch_types=("patch", "patch", "wall", "wall", "wall", "wall"))
+    g = _InputGeometry(mesh)
+    D_bcs = {"inlet": ("fixedValue", (0.0, 0.0, 0.0)), "outlet": ("tractionDisplacement", (1e6, 0.0, 0.0), 1e5)} if D_bcs is None else D_bcs
+    bcs = {}
+    for p in mesh.patches:
+        ent = D_bcs.get(p.name, ("zeroGradient",))
+        if ent[0] == "fixedValue":
+            bcs[p.name] = {"D": (BC_FIXED_VALUE, tuple(float(x) for x in ent[1]))}
+        elif ent[0] == "zeroGradient":
+            bcs[p.name] = {"D": (BC_ZERO_GRADIENT, 0.0)}
+        elif ent[0] == "symmetry":
+            bcs[p.name] = {"D": (BC_SYMMETRY, 0.0)}
+        elif ent[0] == "tractionDisplacement":
+            bcs[p.name] = {"D": (BC_TRACTION, tuple(float(x) for x in ent[1]), float(ent[2]))}
+        else:
+            raise ValueError(f"solid_displacement_case: patch {p.name}: D is fixedValue, zeroGradient, symmetry or tractionDisplacement, not {ent[0]}")
+    case = FoamCase(mesh=mesh, solver_name="DASolidDisplacementFoam", bcs=bcs,
+                    mechanical={"rho": float(rho), "E": float(E), "nu": float(nu), "planeStress": bool(plane_stress)})
+    rng = np.random.default_rng(seed)
+    x = g.C / np.array(lengths)
+    D = np.stack([x[:, 0] * (1.0 + 0.3 * x[:, 1]) + 0.1 * np.sin(2.0 * np.pi * x[:, 2]),
+                  -0.3 * x[:, 1] * (0.5 + x[:, 0]) + 0.05 * np.cos(np.pi * x[:, 0]),
+                  0.2 * x[:, 2] * x[:, 0] + 0.05 * np.sin(np.pi * x[:, 1] + 0.3)], axis=1)
+    case.states = (amplitude * lengths[0] * D * (1.0 + perturb * rng.standard_normal(D.shape))).ravel()
     return case
 
 

@@ -348,9 +348,9 @@ class pyDASolvers:
         m = self._case.mesh
         N, F = m.n_cells, m.n_faces
         layout = {"DASimpleFoam": (1, 3 if getattr(self._case, "has_T", False) else 2), "DARhoSimpleFoam": (1, 3), "DATurboFoam": (1, 3),
-                  "DAScalarTransportFoam": (0, 1), "DAHeatTransferFoam": (0, 1)}[self._case.solver_name]
+                  "DAScalarTransportFoam": (0, 1), "DAHeatTransferFoam": (0, 1), "DASolidDisplacementFoam": (1, 0)}[self._case.solver_name]
         nvec, nscl = layout
-        has_phi = self._case.solver_name not in ("DAScalarTransportFoam", "DAHeatTransferFoam")
+        has_phi = self._case.solver_name not in ("DAScalarTransportFoam", "DAHeatTransferFoam", "DASolidDisplacementFoam")
         owned = [[] for _ in range(N)]
         if has_phi:
             for f in range(F):
@@ -752,7 +752,7 @@ class pyDASolvers:
         if inputType == "field":
             # run(input), then ONE forward-mode pass with a unit tangent on every cell (das_calc_dfield_product)
             # (DAHeatTransferFoam has no Spalart-Allmaras field to assign: nothing of it reads the input, the product is exact zeros)
-            if self._case.solver_name != "DAHeatTransferFoam":
+            if self._case.solver_name not in ("DAHeatTransferFoam", "DASolidDisplacementFoam"):
                 self.setSolverInput(inputName, inputType, inputSize, inputs)
             e = self._field_entry(inputName)
             check(lib().das_calc_dfield_product(self._h, e["fieldName"].encode(), outputName.encode(), outputType.encode(),
@@ -814,6 +814,20 @@ class pyDASolvers:
             ftype = fd.get("type")
             if self._case.solver_name == "DAHeatTransferFoam" and ftype not in ("wallHeatFlux", "variableVolSum"):
                 raise _capi.DASError(f"function {fname}: type {ftype} is not built for DAHeatTransferFoam (wallHeatFlux and variableVolSum of T are)")
+            if ftype == "vonMisesStressKS":
+                # DAFunctionVonMisesStressKS.C: source allCells / boxToCell, scale, coeffKS (required, as the reference reads it)
+                if self._case.solver_name != "DASolidDisplacementFoam":
+                    raise _capi.DASError(f"function {fname}: type vonMisesStressKS needs DASolidDisplacementFoam, not {self._case.solver_name}")
+                if "coeffKS" not in fd:
+                    raise _capi.DASError(f"function {fname}: vonMisesStressKS needs coeffKS")
+                cells = self._function_cells(fname, fd)
+                flags, ref = (8, float(np.atleast_1d(fd["ref"])[0])) if int(fd.get("calcRefVar", 0)) else (0, 0.0)
+                check(L.das_define_von_mises_function(self._h, fname.encode(), cells.ctypes.data_as(_capi.c_int_p), cells.size, float(fd.get("scale", 1.0)),
+                                                      float(fd["coeffKS"]), flags, ref))
+                continue
+            if self._case.solver_name == "DASolidDisplacementFoam" and not (ftype == "variableVolSum" and fd.get("varName") in ("D", "solid:rho")):
+                raise _capi.DASError(f"function {fname}: type {ftype}" + (f" of {fd.get('varName')}" if ftype == "variableVolSum" else "") +
+                                     " is not built for DASolidDisplacementFoam (vonMisesStressKS and variableVolSum of D and of solid:rho are)")
             if ftype in ("variableVolSum", "patchMean", "variance"):
                 self._define_field_function(fname, fd)
                 continue
@@ -923,7 +937,7 @@ class pyDASolvers:
         else:
             comps = [int(fd.get("index", 0))] if vtype == "vector" else [0]
         comps = np.array(comps, dtype=np.int32)
-        if (vtype == "vector") != (var == "U"):
+        if (vtype == "vector") != (var in ("U", "D")):
             raise _capi.DASError(f"function {fname}: varType {vtype} does not match varName {var}")
         flags = (int(fd.get("isSquare", 0)) and 1) | (int(fd.get("multiplyVol", 1)) and 2) | (int(fd.get("divByTotalVol", 0)) and 4)
         ref = 0.0
@@ -999,6 +1013,8 @@ class pyDASolvers:
                                           "thermalCouplingOutput are)")
             thermal = otype == "thermalCouplingOutput"
             what = f"outputInfo[{oname}]"
+            if self._case.solver_name == "DASolidDisplacementFoam":
+                raise _capi.DASError(f"{what}: {otype} is not built for DASolidDisplacementFoam (the reference has no coupling output on the solid displacement)")
             if not thermal and self._case.solver_name == "DAHeatTransferFoam":
                 raise _capi.DASError(f"{what}: forceCouplingOutput needs a flow solver with a pressure field (DAHeatTransferFoam has no p)")
             if thermal:
@@ -1267,6 +1283,9 @@ class pyDASolvers:
         if self._case.solver_name == "DAHeatTransferFoam" and not any(
                 p.size > 0 and self._case.bcs.get(p.name, {}).get("T", (1, 0.0))[0] in (0, BC_MIXED) for p in self._case.mesh.patches):
             raise _capi.DASError("DAHeatTransferFoam: no patch carries a fixedValue or mixed T - the steady conduction problem is singular")
+        if self._case.solver_name == "DASolidDisplacementFoam" and not any(
+                p.size > 0 and self._case.bcs.get(p.name, {}).get("D", (1, 0.0))[0] == 0 for p in self._case.mesh.patches):
+            raise _capi.DASError("DASolidDisplacementFoam: no patch carries a fixedValue D - the steady elastic problem is singular")
         info4 = np.zeros(4)
         hist = np.zeros(int(maxSteps) + 2)
         rc = check(lib().das_solve_primal(self._h, int(maxSteps), float(relTol), float(absTol), dptr(info4), dptr(hist), hist.size))
@@ -1278,6 +1297,8 @@ class pyDASolvers:
         pEqnSimple.H, DASpalartAllmaras::correct), on the device from the current states (das_simple_iteration); alphaP = the explicit
         pressure relaxation of fvSolution, linTol / maxLinIters = the inner solvers' settings.  Returns the inner iteration counts of the
         last sweep; the new states are read with getOFFields / getStates."""
+        if self._case.solver_name == "DASolidDisplacementFoam":
+            raise _capi.DASError("simpleIteration: the SIMPLE sweep is not built for DASolidDisplacementFoam (use solvePrimal)")
         info = np.zeros(3)
         check(lib().das_simple_iteration(self._h, int(nSweeps), float(alphaP), float(linTol), int(maxLinIters), dptr(info)))
         return dict(U=int(info[0]), p=int(info[1]), nuTilda=int(info[2]))
@@ -1311,10 +1332,10 @@ class pyDASolvers:
         N, F = m.n_cells, m.n_faces
         names = {"DASimpleFoam": ["U", "p"] + (["T"] if getattr(self._case, "has_T", False) else []) + ["nuTilda", "phi"],
                  "DARhoSimpleFoam": ["U", "p", "T", "nuTilda", "phi"], "DATurboFoam": ["U", "p", "T", "nuTilda", "phi"],
-                 "DAScalarTransportFoam": ["T"], "DAHeatTransferFoam": ["T"]}[self._case.solver_name]
+                 "DAScalarTransportFoam": ["T"], "DAHeatTransferFoam": ["T"], "DASolidDisplacementFoam": ["D"]}[self._case.solver_name]
         out, off = [], 0
         for nm in names:
-            kind = "vec" if nm == "U" else ("face" if nm == "phi" else "scl")
+            kind = "vec" if nm in ("U", "D") else ("face" if nm == "phi" else "scl")
             size = {"vec": 3 * N, "scl": N, "face": F}[kind]
             out.append((nm, kind, off, size))
             off += size

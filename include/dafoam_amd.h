@@ -38,6 +38,7 @@ extern "C" {
 #define DAS_SOLVER_RHOSIMPLEFOAM 2       /* DARhoSimpleFoam + SpalartAllmaras (perfect gas, hConst, const transport) */
 #define DAS_SOLVER_TURBOFOAM 3          /* DATurboFoam + SpalartAllmaras: SIMPLEC-consistent / transonic pEqn, "h" energy, MRF */
 #define DAS_SOLVER_HEATTRANSFERFOAM 4   /* DAHeatTransferFoam: steady conduction in a solid, one cell state T, kappa constant or a polynomial in T */
+#define DAS_SOLVER_SOLIDDISPLACEMENTFOAM 5 /* DASolidDisplacementFoam: steady linear-elastic solid, one cell vector state D, uniform rho, E, nu */
 #define DAS_IS_COMPRESSIBLE(s) ((s) == DAS_SOLVER_RHOSIMPLEFOAM || (s) == DAS_SOLVER_TURBOFOAM)
 
 /* patch types */
@@ -57,6 +58,10 @@ extern "C" {
  * x_b = f refValue + (1 - f) x_c, snGrad = f deltaCoeff (refValue - x_c) (bc_T_mixed_ref / bc_T_mixed_frac below); what the
  * thermalCoupling input of a conjugate heat transfer loop writes (reference DAInputThermalCoupling.C) */
 #define DAS_BC_MIXED 5
+/* D only: the reference's tractionDisplacement patch field (DAMisc/tractionDisplacement), a fixedGradient whose gradient
+ * g = ((t - p n) / rho - n . (mu gradD_b^T - (mu + lambda) gradD_b) - n tr(gradD_b) lambda) / (2 mu + lambda) is lagged: the residual
+ * runs the option maxCorrectBCCalls passes from g = 0 (bc_D_traction / bc_D_pressure below) */
+#define DAS_BC_TRACTION 6
 /* nut patch treatment (reference DAField.C:1155-1218, DAMisc/nutUSpaldingWallFunctionDF) */
 #define DAS_NUT_CALCULATED 0
 #define DAS_NUT_LOWRE_WALL 1
@@ -132,6 +137,19 @@ typedef struct das_case {
      * kappa(T) = sum_k kappa_coeffs[k] T^k; `kappa` is one coefficient, `kappaCoeffs` up to DAS_MAX_KAPPA_COEFFS of them */
     int n_kappa_coeffs;
     double kappa_coeffs[DAS_MAX_KAPPA_COEFFS];
+    /* DASolidDisplacementFoam, constant/mechanicalProperties (reference readMechanicalPropertiesSolidDisplacement.H): uniform density
+     * rho [kg/m^3], Young's modulus E [Pa] and Poisson's ratio nu; E is normalised by rho, mu = (E / rho) / (2 (1 + nu)),
+     * lambda = nu (E / rho) / ((1 + nu) (1 - 2 nu)), or nu (E / rho) / ((1 + nu) (1 - nu)) with plane_stress != 0.  rho <= 0, E <= 0 and
+     * nu outside (-1, 0.5) return DAS_ERR_ARG with the value in the message */
+    double solid_rho, solid_E, solid_nu;
+    int plane_stress;
+    /* per-patch tables of the state D: code (DAS_BC_FIXED_VALUE, DAS_BC_ZERO_GRADIENT, DAS_BC_SYMMETRY or DAS_BC_TRACTION), the
+     * fixedValue (3 per patch), and the traction [Pa] (3 per patch) and pressure [Pa] (1 per patch) of a tractionDisplacement patch.
+     * NULL code table: zeroGradient everywhere; NULL value tables: zeros.  A cyclic patch on this solver returns DAS_ERR_ARG */
+    const int* bc_D_code;
+    const double* bc_D_val;
+    const double* bc_D_traction;
+    const double* bc_D_pressure;
 } das_case_t;
 
 const char* das_last_error(void);
@@ -372,6 +390,14 @@ int das_define_patch_field_function(das_solver_t* s, const char* name, const cha
  * (variableVolSum; variance rejects it).  Sharded solvers (owned-cell mask) return DAS_ERR_ARG. */
 int das_define_cell_function(das_solver_t* s, const char* name, const char* type, const int* cells, int ncells, const char* var, const int* comps,
                              int ncomp, const double* data, int flags, double scale, double ref);
+/* das_define_von_mises_function <- the "function" entries of type vonMisesStressKS (DASolidDisplacementFoam only; DAFunctionVonMisesStressKS.C):
+ *   F = log(sum_c exp(coeffKS vm_c)) / coeffKS over cells[ncells], vm_c = scale sqrt(1.5 |dev sigma|^2), sigma = rho (mu twoSymm(gradD) +
+ *   lambda tr(gradD) I) with the cell gradD of the residual pass, traction passes included.  The sum runs max-shifted in log space (two
+ *   deterministic stages); the reference's abort above 1e200 is not reproduced - wider than the reference.  flags & 8: calcRefVar.
+ *   Derivatives: stateVar (reaches the face neighbours through gradD) and volCoord; patchVar, patchVelocity and field inputs give zeros.
+ *   das_define_cell_function with var "solid:rho" (variableVolSum, DASolidDisplacementFoam only) sums the uniform density: the mass, whose
+ *   state derivative is exactly zero. */
+int das_define_von_mises_function(das_solver_t* s, const char* name, const int* cells, int ncells, double scale, double coeffKS, int flags, double ref);
 int das_calc_function(das_solver_t* s, const char* name, double* value);
 /* das_define_force_coupling <- the "outputInfo" option entry {type: forceCouplingOutput, patches, pRef} consumed by DAOutputForceCoupling
  *   (reference src/adjoint/DAOutput/DAOutputForceCoupling.C): the force S_f (p_b - pRef) + S_f . devRhoReff_b of every face of the patches,
