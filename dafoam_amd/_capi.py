@@ -480,6 +480,14 @@ _SIGS = {
     "das_debug_vecpack": (C.c_int, [C.c_longlong, c_ll_p, c_int_p, c_double_p, C.c_longlong, C.c_longlong, c_int_p, c_ll_p, C.POINTER(C.c_ubyte), C.c_longlong, c_ll_p,
                                     c_double_p, c_double_p, C.c_longlong]),
     "das_debug_spmv_rows": (C.c_int, [C.c_longlong, c_int_p, C.c_longlong, c_ll_p, c_int_p, c_double_p, c_double_p, c_double_p, C.c_longlong]),
+    # test-only entries (tests/test_gpu_color_kernels.py): the colouring kernels on a caller-made pattern and kept-row list, never called
+    # by the bindings
+    "das_debug_color_firstfit": (C.c_int, [C.c_longlong, c_ll_p, c_int_p, C.c_longlong, c_ll_p, c_int_p, C.c_longlong, c_int_p, c_int_p]),
+    "das_debug_color_speculative": (C.c_int, [C.c_longlong, c_ll_p, c_int_p, C.c_longlong, c_ll_p, C.c_int, c_int_p, C.c_longlong, c_int_p, c_int_p, c_int_p,
+                                              c_int_p]),
+    "das_debug_color_spec_round": (C.c_int, [C.c_longlong, c_ll_p, c_int_p, C.c_longlong, c_ll_p, c_int_p, C.c_int, C.c_int, C.c_int, c_int_p, C.POINTER(C.c_ubyte),
+                                             c_int_p, C.c_longlong, C.POINTER(C.c_ulonglong), C.c_longlong, C.POINTER(C.c_uint), c_int_p]),
+    "das_debug_color_check": (C.c_int, [C.c_longlong, c_ll_p, c_int_p, C.c_longlong, c_ll_p, c_int_p, C.c_int, c_int_p]),
     # test-only entries (tests/test_gpu_coarse_kernels.py): the coarse space of the two-level preconditioner on caller-made structures,
     # never called by the bindings
     "das_debug_coarse_assemble": (C.c_int, [C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, c_ll_p, c_int_p, c_double_p, c_int_p, c_int_p, C.c_int, C.c_double,

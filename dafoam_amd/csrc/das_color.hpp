@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void k_color_firstfit(ColorView P) {
                     // beside this persistent kernel - measured: the first one returned after 26 s)
                     __hip_atomic_store(&P.host[0], t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     if (__hip_atomic_load(&P.host[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u) {
-                        __hip_atomic_store(&P.ctrl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        atomicCAS(&P.ctrl[1], 0u, 1u);
                         t = 0xFFFFFFFFu;
                     }
                 }
@@ -82,15 +82,21 @@ __global__ __launch_bounds__(256) void k_color_firstfit(ColorView P) {
             unsigned spins = 0;
             while (__hip_atomic_load(&P.done[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < need) {
                 __builtin_amdgcn_s_sleep(2);
-                if ((++spins & 1023u) == 0u &&
-                    (__hip_atomic_load(&P.ctrl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || spins > (1u << 24))) {
-                    __hip_atomic_store(&P.ctrl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    dead = true;
-                    break;
+                if ((++spins & 1023u) == 0u) {
+                    // a run that is over already (abort 1, overflow 2) keeps its code: an overflow that a waiting wave turned into an
+                    // abort made the host give up instead of widening the bitmaps
+                    const bool over = __hip_atomic_load(&P.ctrl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
+                    if (over || spins > (1u << 24)) {
+                        if (!over) atomicCAS(&P.ctrl[1], 0u, 1u);
+                        dead = true;
+                        break;
+                    }
                 }
             }
         }
-        if (__any(dead)) return;
+        // (a wave never leaves on its own: thread 0 draws the tickets, and without wave 0 the other waves of the workgroup would run
+        //  the last ticket again for ever, out of the watchdog's reach.  ctrl[1] is set: the next draw sends the whole workgroup home)
+        if (__any(dead)) continue;
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         // 2. forbidden set = OR of the nets' bitmaps (read past the L1 / the other XCDs' L2: agent scope)
         for (long long q = q0 + lane; q < q1; q += 64) {
@@ -101,7 +107,8 @@ __global__ __launch_bounds__(256) void k_color_firstfit(ColorView P) {
             }
         }
         __builtin_amdgcn_wave_barrier();
-        // 3. the members of the group take the smallest free colours one after the other (lane w owns word w)
+        // 3. the members of the group take the smallest free colours one after the other (lane w owns word w); columns WITHOUT a net
+        //    form a group too (their empty lists are equal) but exclude nothing, not even each other: every one takes colour 0
         unsigned long long mine = lane < W ? fbs[wave][lane] : ~0ull;
         int cs[8];
         const int mm = m < 8 ? m : 8;
@@ -112,10 +119,10 @@ __global__ __launch_bounds__(256) void k_color_firstfit(ColorView P) {
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) best = min(best, __shfl_xor(best, o, 64));
             if (best >= 64 * W) { over = true; best = 64 * W - 1; }
-            if (lane == (best >> 6)) mine |= 1ull << (best & 63);
+            if (lane == (best >> 6) && q1 > q0) mine |= 1ull << (best & 63);
             cs[i] = best;
         }
-        if (over || m > 8) { if (lane == 0) __hip_atomic_store(&P.ctrl[1], 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); return; }
+        if (over || m > 8) { if (lane == 0) __hip_atomic_store(&P.ctrl[1], 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); continue; }
         for (int i = 0; i < mm; i++) if (lane == 0) P.colors[j0 + i] = cs[i];
         // 4. publish: the colours into every net's bitmap, THEN the counters (release order)
         for (long long q = q0 + lane; q < q1; q += 64) {
@@ -135,8 +142,9 @@ __global__ __launch_bounds__(256) void k_color_firstfit(ColorView P) {
 // rows wrap around (an O-grid: the first cell of ring j+1 neighbours the LAST cells of ring j) serialises it completely
 // (measured: 63 s at 2 M cells).  The host watches the ticket counter through a side stream; when the projected run time
 // exceeds max(10 s, 1 us per column) it raises the abort flag and the caller switches to the order-independent algorithm.
+// widthOut: the bitmap words per net of the run that succeeded.
 inline int color_firstfit_run(long long n, long long nNets, const std::vector<long long>& gstartHost, const long long* d_cptr, const int* d_crow,
-                              const int* d_cpos, std::vector<int>& colors, hipStream_t st) {
+                              const int* d_cpos, std::vector<int>& colors, hipStream_t st, int* widthOut = nullptr) {
     const long long nGroups = (long long)gstartHost.size() - 1;
     DevBuf<long long> d_gstart;
     d_gstart.upload(gstartHost);
@@ -193,6 +201,7 @@ inline int color_firstfit_run(long long n, long long nNets, const std::vector<lo
         if (ctrl[1] != 0u) return 0;
         colors.resize(n);
         d_colors.download(colors.data(), n);
+        if (widthOut) *widthOut = W;
         return 1;
     }
     return 0;
@@ -383,9 +392,34 @@ __global__ __launch_bounds__(256) void k_spec_netbits(SpecView P) {
     for (int w = lane; w < P.W; w += 64) P.F[r * P.W + w] = bits[w];
 }
 
-// the rounds of the speculative colouring on device arrays: column -> nets (cptr / crow) and net -> columns (krp / kcol)
+// k_spec_conflict keeps one int per colour and wave: 4 x 64 W ints = 1 KiB of dynamic LDS per bitmap word.  A workgroup of gfx950 holds
+// 160 KiB, so no width beyond 160 words can run; the device may report less (hipDeviceAttributeMaxSharedMemoryPerBlock).
+constexpr int SPEC_MAXW = 160;
+inline size_t spec_conflict_lds(int W) { return (size_t)4 * 64 * W * sizeof(int); }
+// the widest bitmap whose k_spec_conflict fits into the LDS of a workgroup of the current device (a host-side query, no launch)
+inline int spec_max_words() {
+    int dev = 0, bytes = 0;
+    DAS_HIP(hipGetDevice(&dev));
+    DAS_HIP(hipDeviceGetAttribute(&bytes, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    hipFuncAttributes fa{};
+    DAS_HIP(hipFuncGetAttributes(&fa, (const void*)k_spec_conflict));
+    const long long room = (long long)bytes - (long long)fa.sharedSizeBytes;  // (the kernel has no static LDS: sharedSizeBytes is 0)
+    return (int)std::max<long long>(0, std::min<long long>(SPEC_MAXW, room / (long long)spec_conflict_lds(1)));
+}
+// before k_spec_conflict is launched with W words: false if the device cannot hold them, else the kernel is given the dynamic LDS it
+// asks for (above 64 KiB a launch is rejected without this, as for k_ras_apply)
+inline bool spec_conflict_prepare(int W) {
+    if (W < 1 || W > spec_max_words()) return false;
+    DAS_HIP(hipFuncSetAttribute((const void*)k_spec_conflict, hipFuncAttributeMaxDynamicSharedMemorySize, (int)spec_conflict_lds(W)));
+    return true;
+}
+
+// the rounds of the speculative colouring on device arrays: column -> nets (cptr / crow) and net -> columns (krp / kcol).  spread = -1:
+// S by the rule below (and DAS_COLOR_SPREAD); spread >= 1: S as given.  roundsOut / spreadOut / widthOut: the rounds, S and W of the run
+// that succeeded.  false: more colours than the widest bitmaps the device holds, or an invalid result - the caller falls back, loudly
 inline bool color_speculative_run(long long n, long long nKeep, long long maxNet, const long long* d_cptr, const int* d_crow, const long long* d_krp,
-                                  const int* d_kcol, std::vector<int>& colors, hipStream_t st, int* roundsOut = nullptr) {
+                                  const int* d_kcol, std::vector<int>& colors, hipStream_t st, int* roundsOut = nullptr, int spread = -1,
+                                  int* spreadOut = nullptr, int* widthOut = nullptr) {
     const bool dbg = getenv("DAS_DEBUG_TIMING") != nullptr;
     DevBuf<int> d_colors(n), d_tent(n);
     DevBuf<unsigned char> d_lose(n);
@@ -393,13 +427,16 @@ inline bool color_speculative_run(long long n, long long nKeep, long long maxNet
     // the spread of the first picks: a little above the longest net (a lower bound of the colour count)
     int S = (int)std::max<long long>(8, maxNet + maxNet / 4);
     if (const char* e = getenv("DAS_COLOR_SPREAD")) S = std::max(1, atoi(e));
-    for (int W = (int)std::max<long long>(8, ((long long)(2 * S) + 63) / 64); W <= 1024; W *= 2) {
+    if (spread >= 1) S = spread;  // (tests: a spread of the caller's, whatever the environment says)
+    if (spreadOut) *spreadOut = S;
+    // the bitmaps are widened on overflow as long as the device holds k_spec_conflict's LDS; beyond that: false, the caller's loud fallback
+    for (long long W = std::max<long long>(8, (2LL * S + 63) / 64); W <= SPEC_MAXW && spec_conflict_prepare((int)W); W *= 2) {
         DevBuf<unsigned long long> d_F((size_t)nKeep * W);
         DAS_HIP(hipMemsetAsync(d_F.p, 0, (size_t)nKeep * W * sizeof(unsigned long long), st));
         DAS_HIP(hipMemsetAsync(d_colors.p, 0xff, n * sizeof(int), st));
         DAS_HIP(hipMemsetAsync(d_tent.p, 0xff, n * sizeof(int), st));
         DAS_HIP(hipMemsetAsync(d_lose.p, 0, n, st));
-        SpecView V{n, nKeep, d_cptr, d_crow, d_krp, d_kcol, W, d_F.p, d_colors.p, d_tent.p, d_lose.p, d_ctrl.p};
+        SpecView V{n, nKeep, d_cptr, d_crow, d_krp, d_kcol, (int)W, d_F.p, d_colors.p, d_tent.p, d_lose.p, d_ctrl.p};
         const unsigned gNet = (unsigned)((nKeep + 3) / 4);
         bool overflow = false;
         unsigned left = 1u;
@@ -407,9 +444,10 @@ inline bool color_speculative_run(long long n, long long nKeep, long long maxNet
         for (; left != 0u && round < 100000; round++) {
             DAS_HIP(hipMemsetAsync(d_ctrl.p, 0, 4 * sizeof(unsigned), st));
             hipLaunchKernelGGL(k_spec_assign, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, st, V, S, (unsigned)round);
-            hipLaunchKernelGGL(k_spec_conflict, dim3(gNet), dim3(256), (size_t)4 * 64 * W * sizeof(int), st, V, 0);
+            hipLaunchKernelGGL(k_spec_conflict, dim3(gNet), dim3(256), spec_conflict_lds((int)W), st, V, 0);
             hipLaunchKernelGGL(k_spec_commit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, V);
             hipLaunchKernelGGL(k_spec_netbits, dim3(gNet), dim3(256), (size_t)4 * W * sizeof(unsigned long long), st, V);
+            DAS_HIP(hipGetLastError());  // a rejected launch must not pass for a round without conflicts
             unsigned ctrl[4] = {0, 0, 0, 0};
             DAS_HIP(hipMemcpyAsync(ctrl, d_ctrl.p, sizeof(ctrl), hipMemcpyDeviceToHost, st));
             DAS_HIP(hipStreamSynchronize(st));
@@ -420,7 +458,8 @@ inline bool color_speculative_run(long long n, long long nKeep, long long maxNet
         if (left != 0u) return false;
         // validity: every net holds pairwise different final colours
         DAS_HIP(hipMemsetAsync(d_ctrl.p, 0, 4 * sizeof(unsigned), st));
-        hipLaunchKernelGGL(k_spec_conflict, dim3(gNet), dim3(256), (size_t)4 * 64 * W * sizeof(int), st, V, 1);
+        hipLaunchKernelGGL(k_spec_conflict, dim3(gNet), dim3(256), spec_conflict_lds((int)W), st, V, 1);
+        DAS_HIP(hipGetLastError());
         unsigned ctrl[4] = {0, 0, 0, 0};
         DAS_HIP(hipMemcpyAsync(ctrl, d_ctrl.p, sizeof(ctrl), hipMemcpyDeviceToHost, st));
         DAS_HIP(hipStreamSynchronize(st));
@@ -428,7 +467,8 @@ inline bool color_speculative_run(long long n, long long nKeep, long long maxNet
         colors.resize(n);
         d_colors.download(colors.data(), n);
         if (roundsOut) *roundsOut = round;
-        if (dbg) fprintf(stderr, "[dafoam_amd]     speculative colouring: %d rounds, spread %d, %d bitmap words per net\n", round, S, W);
+        if (widthOut) *widthOut = (int)W;
+        if (dbg) fprintf(stderr, "[dafoam_amd]     speculative colouring: %d rounds, spread %d, %d bitmap words per net\n", round, S, (int)W);
         return true;
     }
     return false;

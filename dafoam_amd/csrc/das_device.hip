@@ -34,6 +34,7 @@
 #include "das_coarse.hpp"
 #include "das_coarse_debug.hpp"
 #include "das_color.hpp"
+#include "das_color_debug.hpp"
 #include "das_opmat.hpp"
 #include "das_graph.hpp"
 #include "das_volcoord.hpp"
@@ -7170,6 +7171,85 @@ int das_debug_spmv_rows(long long nrows, const int* rows, long long n, const lon
     for (long long k = 0; k < nrows; k++) DAS_CHECK(rows[k] >= 0 && rows[k] < n, DAS_ERR_ARG, who + ": row index out of range");
     DAS_GRAPH_DEVICE(who);
     debug_spmv_rows(nrows, rows, n, rowptr, col, vals, x, buf, buflen);
+    return DAS_OK;
+    DAS_CATCH
+}
+// Test-only entries (tests/test_gpu_color_kernels.py): the colouring kernels on a caller-made pattern and kept-row list; the device
+// structures are derived with the helpers the solver uses (das_color_debug.hpp).  Everything is checked on the host before anything is
+// launched.
+static void color_check_input(const std::string& who, long long n, const long long* rowptr, const int* col, long long nKeep, const long long* keep) {
+    graph_check_sizes(who, n);
+    DAS_CHECK(rowptr && col && keep, DAS_ERR_ARG, who + ": null pointer");
+    graph_check_csr(who, n, rowptr, col, n, true);
+    DAS_CHECK(rowptr[n] > 0, DAS_ERR_ARG, who + ": a pattern without entries");
+    DAS_CHECK(nKeep >= 1 && nKeep <= n, DAS_ERR_ARG, who + ": nKeep outside [1, n]");
+    std::vector<unsigned char> seen((size_t)n, 0);
+    for (long long q = 0; q < nKeep; q++) {
+        DAS_CHECK(keep[q] >= 0 && keep[q] < n, DAS_ERR_ARG, who + ": kept row out of range");
+        DAS_CHECK(!seen[keep[q]], DAS_ERR_ARG, who + ": kept row repeated");
+        seen[keep[q]] = 1;
+    }
+}
+static void color_check_width(const std::string& who, int W) {
+    DAS_CHECK(W >= 1 && W <= SPEC_MAXW, DAS_ERR_ARG, who + ": W outside 1 .. 160 (the LDS of k_spec_conflict holds no more)");
+}
+static void color_check_colors(const std::string& who, long long n, const int* colors, int W) {
+    DAS_CHECK(colors, DAS_ERR_ARG, who + ": null pointer");
+    for (long long j = 0; j < n; j++) DAS_CHECK(colors[j] >= -1 && colors[j] < 64 * W, DAS_ERR_ARG, who + ": colour outside [-1, 64 W)");
+}
+int das_debug_color_firstfit(long long n, const long long* rowptr, const int* col, long long nKeep, const long long* keep, int* colors, long long colorsLen,
+                             int* rc, int* W) {
+    DAS_TRY
+    const std::string who = "das_debug_color_firstfit";
+    color_check_input(who, n, rowptr, col, nKeep, keep);
+    DAS_CHECK(colors && rc && W, DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(colorsLen >= n, DAS_ERR_ARG, who + ": colors shorter than n");
+    DAS_GRAPH_DEVICE(who);
+    debug_color_firstfit(n, rowptr, col, nKeep, keep, colors, rc, W);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_color_speculative(long long n, const long long* rowptr, const int* col, long long nKeep, const long long* keep, int spread, int* colors,
+                                long long colorsLen, int* ok, int* rounds, int* S, int* W) {
+    DAS_TRY
+    const std::string who = "das_debug_color_speculative";
+    color_check_input(who, n, rowptr, col, nKeep, keep);
+    DAS_CHECK(colors && ok && rounds && S && W, DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(colorsLen >= n, DAS_ERR_ARG, who + ": colors shorter than n");
+    DAS_CHECK(spread == -1 || spread >= 1, DAS_ERR_ARG, who + ": the spread is -1 (the rule) or at least 1");
+    DAS_CHECK(spread <= 32 * SPEC_MAXW, DAS_ERR_ARG, who + ": a spread whose first bitmaps exceed the LDS of k_spec_conflict");
+    DAS_GRAPH_DEVICE(who);
+    debug_color_speculative(n, rowptr, col, nKeep, keep, spread, colors, ok, rounds, S, W);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_color_spec_round(long long n, const long long* rowptr, const int* col, long long nKeep, const long long* keep, const int* colorsIn, int S, int W,
+                               int round, int* tent, unsigned char* lose, int* colorsOut, long long outLen, unsigned long long* F, long long FLen,
+                               unsigned* left, int* overflow) {
+    DAS_TRY
+    const std::string who = "das_debug_color_spec_round";
+    color_check_input(who, n, rowptr, col, nKeep, keep);
+    color_check_width(who, W);
+    DAS_CHECK(S >= 1, DAS_ERR_ARG, who + ": S must be at least 1");
+    DAS_CHECK(round >= 0, DAS_ERR_ARG, who + ": negative round");
+    color_check_colors(who, n, colorsIn, W);
+    DAS_CHECK(tent && lose && colorsOut && F && left && overflow, DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(outLen >= n, DAS_ERR_ARG, who + ": tent / lose / colorsOut shorter than n");
+    DAS_CHECK(FLen >= nKeep * W, DAS_ERR_ARG, who + ": F shorter than nKeep W");
+    DAS_GRAPH_DEVICE(who);
+    debug_color_spec_round(n, rowptr, col, nKeep, keep, colorsIn, S, W, round, tent, lose, colorsOut, F, left, overflow);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_color_check(long long n, const long long* rowptr, const int* col, long long nKeep, const long long* keep, const int* colors, int W, int* invalid) {
+    DAS_TRY
+    const std::string who = "das_debug_color_check";
+    color_check_input(who, n, rowptr, col, nKeep, keep);
+    color_check_width(who, W);
+    color_check_colors(who, n, colors, W);
+    DAS_CHECK(invalid, DAS_ERR_ARG, who + ": null pointer");
+    DAS_GRAPH_DEVICE(who);
+    debug_color_check(n, rowptr, col, nKeep, keep, colors, W, invalid);
     return DAS_OK;
     DAS_CATCH
 }

@@ -847,6 +847,31 @@ int das_debug_vecpack(long long n, const long long* rowptr, const int* col, cons
 /* k_spmv_rows_to_buf: buf[k] = A[rows[k], :] . x, k < nrows; buf holds buflen >= nrows entries */
 int das_debug_spmv_rows(long long nrows, const int* rows, long long n, const long long* rowptr, const int* col, const double* vals, const double* x, double* buf,
                         long long buflen);
+/* ---- TEST-ONLY entries (tests/test_gpu_color_kernels.py): the colouring kernels (csrc/das_color.hpp) on a caller-made n x n CSR
+ * pattern (columns of a row strictly ascending) and the kept rows keep[0..nKeep) (net q = row keep[q], nKeep >= 1).  No mesh, no solver
+ * handle; everything runs on the null stream.  The structures the kernels index with (column -> nets with positions, groups, net ->
+ * columns) are derived from the pattern with the helpers THE SOLVER USES (device_transpose, device_build_nets, color_groups_from_flags,
+ * k_rows_gather).  Everything is checked on the host before anything is launched, and DAS_ERR_ARG is returned for everything
+ * das_debug_graph_nets refuses, for n >= 2^31, nKeep < 1, a colour outside [-1, 64 W), W < 1 or above what the LDS of k_spec_conflict
+ * holds (160 words at most; fewer if the device says so), S < 1, a spread that is neither -1 nor >= 1, a negative round and an output
+ * array too short for what is written. */
+/* color_firstfit_run (k_color_firstfit, the bitmaps doubled from 8 words on overflow) as the graph path of the solver runs it: *rc = 1
+ * and colors[0..n), *W = the bitmap words that sufficed; *rc = 0 (gave up) or -1 (watchdog) and nothing else.  colors holds colorsLen
+ * >= n entries */
+int das_debug_color_firstfit(long long n, const long long* rowptr, const int* col, long long nKeep, const long long* keep, int* colors, long long colorsLen,
+                             int* rc, int* W);
+/* color_speculative_run: spread = -1 is the rule of the solver (1.25 x the longest net, DAS_COLOR_SPREAD), spread >= 1 is taken as it
+ * is.  *ok = 1: colors[0..n), *rounds, *S and *W of the run that succeeded; *ok = 0: the bitmaps cannot be widened any further */
+int das_debug_color_speculative(long long n, const long long* rowptr, const int* col, long long nKeep, const long long* keep, int spread, int* colors,
+                                long long colorsLen, int* ok, int* rounds, int* S, int* W);
+/* one round from the final colours colorsIn (-1 = none): k_spec_netbits, k_spec_assign (-> tent), k_spec_conflict(0) (-> lose),
+ * k_spec_commit (-> colorsOut, *left), k_spec_netbits (-> F, nKeep x W words), *overflow = a column found no colour below 64 W.  tent,
+ * lose and colorsOut hold outLen >= n entries, F holds FLen >= nKeep W */
+int das_debug_color_spec_round(long long n, const long long* rowptr, const int* col, long long nKeep, const long long* keep, const int* colorsIn, int S, int W,
+                               int round, int* tent, unsigned char* lose, int* colorsOut, long long outLen, unsigned long long* F, long long FLen,
+                               unsigned* left, int* overflow);
+/* k_spec_conflict with check = 1 alone: *invalid = 1 if two columns of a net share a colour or a column of a net has none */
+int das_debug_color_check(long long n, const long long* rowptr, const int* col, long long nKeep, const long long* keep, const int* colors, int W, int* invalid);
 /* ---- TEST-ONLY entries (tests/test_gpu_coarse_kernels.py): the coarse space of the two-level preconditioner (csrc/das_coarse.hpp) on
  * caller-made structures, kernel by kernel.  No mesh, no solver handle; the launch sequences THE SOLVER USES run on the null stream.
  * These kernels index with what they are given, so everything is checked on the host before anything is launched, and DAS_ERR_ARG is
