@@ -120,6 +120,57 @@ class das_bilu_debug_t(C.Structure):
     ]
 
 
+class das_reg_spec_t(C.Structure):
+    """one entry of the regressionModel option (include/dafoam_amd.h); reg_spec() fills it and keeps its arrays alive"""
+    _fields_ = [
+        ("model_type", C.c_char_p),
+        ("n_inputs", C.c_int),
+        ("input_names", C.POINTER(C.c_char_p)),
+        ("input_shift", c_double_p),
+        ("input_scale", c_double_p),
+        ("output_name", C.c_char_p),
+        ("n_hidden_layers", C.c_int),
+        ("hidden_layer_neurons", c_int_p),
+        ("activation_function", C.c_char_p),
+        ("leaky_coeff", C.c_double),
+        ("n_rbfs", C.c_int),
+        ("output_shift", C.c_double),
+        ("output_scale", C.c_double),
+        ("output_upper_bound", C.c_double),
+        ("output_lower_bound", C.c_double),
+        ("default_output_value", C.c_double),
+    ]
+
+
+def reg_spec(e, with_names=True):
+    """das_reg_spec_t of a model dictionary with the reference's keys (modelType, inputNames, inputShift, inputScale, outputName,
+    hiddenLayerNeurons, activationFunction, leakyCoeff, nRBFs, outputShift, outputScale, outputUpperBound, outputLowerBound,
+    defaultOutputValue).  The arrays live as long as the returned structure."""
+    sp = das_reg_spec_t()
+    names = [str(n).encode() for n in e.get("inputNames", [])]
+    sp._names = (C.c_char_p * max(len(names), 1))(*names)
+    sp._shift = np.ascontiguousarray(e.get("inputShift", []), dtype=np.float64)
+    sp._scale = np.ascontiguousarray(e.get("inputScale", []), dtype=np.float64)
+    sp._hidden = np.ascontiguousarray(e.get("hiddenLayerNeurons", []), dtype=np.int32)
+    sp.model_type = str(e.get("modelType", "")).encode()
+    sp.n_inputs = len(names) if with_names else int(e["nInputs"] if "nInputs" in e else sp._shift.size)
+    sp.input_names = C.cast(sp._names, C.POINTER(C.c_char_p)) if with_names else None
+    sp.input_shift = sp._shift.ctypes.data_as(c_double_p)
+    sp.input_scale = sp._scale.ctypes.data_as(c_double_p)
+    sp.output_name = str(e["outputName"]).encode() if "outputName" in e else None
+    sp.n_hidden_layers = int(sp._hidden.size)
+    sp.hidden_layer_neurons = sp._hidden.ctypes.data_as(c_int_p)
+    sp.activation_function = str(e.get("activationFunction", "")).encode()
+    sp.leaky_coeff = float(e.get("leakyCoeff", 0.0))
+    sp.n_rbfs = int(e.get("nRBFs", 0))
+    sp.output_shift = float(e.get("outputShift", 0.0))
+    sp.output_scale = float(e.get("outputScale", 1.0))
+    sp.output_upper_bound = float(e.get("outputUpperBound", 1e30))
+    sp.output_lower_bound = float(e.get("outputLowerBound", -1e30))
+    sp.default_output_value = float(e.get("defaultOutputValue", 1.0))
+    return sp
+
+
 def _dp(a):
     return a.ctypes.data_as(c_double_p) if a is not None else None
 
@@ -373,6 +424,15 @@ _SIGS = {
     "das_get_actuator_disk_cells": (C.c_int, [_VP, C.c_char_p, c_int_p, C.c_int]),
     "das_get_fv_source_vector": (C.c_int, [_VP, c_double_p]),
     "das_calc_dactuatordiskpar_product": (C.c_int, [_VP, C.c_char_p, c_int_p, C.c_int, C.c_char_p, C.c_char_p, c_double_p, c_double_p]),
+    "das_define_regression_model": (C.c_int, [_VP, C.c_char_p, C.POINTER(das_reg_spec_t)]),
+    "das_get_regression_n_parameters": (C.c_int, [_VP, C.c_char_p]),
+    "das_set_regression_parameters": (C.c_int, [_VP, C.c_char_p, c_double_p, C.c_int]),
+    "das_get_regression_parameters": (C.c_int, [_VP, C.c_char_p, c_double_p, C.c_int]),
+    "das_get_regression_model_info": (C.c_int, [_VP, C.c_char_p, c_int_p, c_int_p, c_int_p]),
+    "das_get_regression_features": (C.c_int, [_VP, C.c_char_p, c_double_p, c_double_p, c_ll_p]),
+    "das_calc_dregressionpar_product": (C.c_int, [_VP, C.c_char_p, C.c_char_p, C.c_char_p, c_double_p, c_double_p]),
+    "das_debug_reg_forward": (C.c_int, [C.POINTER(das_reg_spec_t), c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, C.POINTER(C.c_ubyte)]),
+    "das_debug_reg_backward": (C.c_int, [C.POINTER(das_reg_spec_t), c_double_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),
     "das_get_input_size": (C.c_int, [_VP, C.c_char_p, C.c_char_p]),
     "das_get_output_size": (C.c_int, [_VP, C.c_char_p, C.c_char_p]),
     "das_calc_jac_t_vec_product": (

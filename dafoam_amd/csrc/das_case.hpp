@@ -4,6 +4,8 @@
 
 namespace das {
 
+struct RegSet;
+
 struct CaseParams {
     int solver = DAS_SOLVER_SIMPLEFOAM;
     double nu = 1.5e-5, relax_U = 0.7, relax_nuTilda = 0.7, relax_T = 1.0, DT = 0.01, deltaT = 1.0;
@@ -18,6 +20,10 @@ struct CaseParams {
     std::vector<double> beta_fi;
     const double* betaFI_ptr = nullptr;
     const double* dBetaFI_ptr = nullptr;
+    // regression models of DASimpleFoam (das_regression.hpp): the active models, null = none - then every code path is the one without
+    // the option; regSeed: the dual pass of das_calc_dregressionpar_product (unit tangent on beta after the bounds)
+    const RegSet* reg = nullptr;
+    int regSeed = 0;
     // DAHeatTransferFoam: kappa(T) = sum_k kappa[k] T^k (constant/solidProperties kappa / kappaCoeffs)
     int nKappa = 0;
     double kappa[DAS_MAX_KAPPA_COEFFS] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -103,7 +109,7 @@ inline ResParams make_params(const CaseParams& cp, const Options& opt, int isPC)
     p.hasT = cp.hasT;
     p.gradFaceParallel = (int)opt.geti_or("amd.gradFaceParallel", 1);
     // the face / cell split of the cell pass (body_fcoef + body_bcoef + body_cell2) serves DASimpleFoam + SA without T field, MRF and cyclic pairs
-    p.cellFaceSplit = (int)opt.geti_or("amd.cellFaceSplit", 0) && cp.solver == DAS_SOLVER_SIMPLEFOAM && !cp.hasT && !cp.mrf && !cp.hasCyclic;
+    p.cellFaceSplit = (int)opt.geti_or("amd.cellFaceSplit", 0) && cp.solver == DAS_SOLVER_SIMPLEFOAM && !cp.hasT && !cp.mrf && !cp.hasCyclic && !cp.reg;
     p.Cp = cp.Cp;
     p.Rgas = 8314.47 / cp.molWeight;  // Foam::constant::thermodynamic::RR / molWeight
     p.mu = cp.mu;
@@ -123,6 +129,7 @@ inline ResParams make_params(const CaseParams& cp, const Options& opt, int isPC)
     p.wTU = nullptr;
     p.betaFI = cp.betaFI_ptr;
     p.dBetaFI = cp.dBetaFI_ptr;
+    p.betaReg = nullptr;  // set by the residual evaluation once k_reg_forward has written the array of the pass
     p.solid = cp.solver == DAS_SOLVER_HEATTRANSFERFOAM;
     p.nKappa = cp.nKappa;
     for (int k = 0; k < DAS_MAX_KAPPA_COEFFS; k++) p.kappa[k] = cp.kappa[k];

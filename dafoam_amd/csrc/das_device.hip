@@ -44,6 +44,7 @@
 #include "das_thermalcoupling.hpp"
 #include "das_heatsource.hpp"
 #include "das_actuatordisk.hpp"
+#include "das_regression.hpp"
 #include "das_simple.hpp"
 #include "das_simple_host.hpp"
 
@@ -302,6 +303,7 @@ struct ResWork {
     DevBuf<T> nut, gU, gP, gN, gH, rAU, HbyA, q, gT, TU;
     DevBuf<T> gTr;  // DASolidDisplacementFoam: the tractionDisplacement gradient, 3 per boundary face (allocated on first use)
     DevBuf<T> fc, brec;  // face / cell split of the cell pass: 6 scalars per internal face, 13 per boundary face (allocated on first use)
+    DevBuf<T> beta;      // regression models: betaFINuTilda per cell as k_reg_forward wrote it (allocated on first use)
     void ensure(int solver, long long N, long long F) {
         if (solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(solver)) {
             if (nut.n != (size_t)N) {
@@ -320,6 +322,16 @@ struct ResWork {
         return prm;
     }
 };
+
+// one k_reg_forward launch (das_regression.hpp); its LDS follows the model: the parameters and two activation columns per thread
+template <class T, class G>
+static void launch_reg_forward(const RegView& v, int nC, const CellGeomT<G>* cg, const ResParams& prm, const T* W, const T* gU, const T* gP, const double* featIn,
+                               int seed, T* beta, double* featOut, unsigned char* maskOut, hipStream_t st) {
+    const size_t lds = reg_forward_lds<T>(v);
+    if (lds > 64 * 1024) { DAS_HIP(hipFuncSetAttribute((const void*)k_reg_forward<T, G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); }
+    hipLaunchKernelGGL((k_reg_forward<T, G>), dim3(nblk(nC, DAS_REG_FWD_THREADS)), dim3(DAS_REG_FWD_THREADS), lds, st, v, nC, cg, prm, W, gU, gP, featIn, seed, beta,
+                       featOut, maskOut);
+}
 
 // the gradient launch of DASimpleFoam: face-parallel k_grad_fp where it applies (no T field, double metrics, amd.gradFaceParallel), else k_grad
 template <class T, class G>
@@ -342,10 +354,16 @@ static void launch_grad_simple(const DevMeshT<G>& dm, const ResParams& prm, cons
 template <class T, class G = double>
 static void eval_residual(const DevMeshT<G>& dm, const CaseParams& cp, const ResParams& prm_in, const T* W, T* R, ResWork<T>& wk,
                           const double* d_phiF, const double* d_Told, hipStream_t st) {
-    const ResParams prm = wk.bind(cp.solver, dm.nC, dm.nF, prm_in);
+    ResParams prm = wk.bind(cp.solver, dm.nC, dm.nF, prm_in);
     const int B = 256;
     if (cp.solver == DAS_SOLVER_SIMPLEFOAM) {
         launch_grad_simple<T, G>(dm, prm, W, wk, st);
+        if (cp.reg) {  // regression models: betaFINuTilda of this pass, in its scalar; one launch per model, the last one wins
+            if (wk.beta.n != (size_t)dm.nC) wk.beta.alloc(dm.nC);
+            for (int k = 0; k < cp.reg->n; k++)
+                launch_reg_forward<T, G>(cp.reg->v[k], dm.nC, dm.cg, prm, W, (const T*)wk.gU.p, (const T*)wk.gP.p, nullptr, cp.regSeed, wk.beta.p, nullptr, nullptr, st);
+            prm.betaReg = wk.beta.p;
+        }
         bool split = false;
         if constexpr (std::is_same<G, double>::value) {
             if (prm.cellFaceSplit) {
@@ -955,6 +973,25 @@ struct das_solver {
     DevBuf<double> d_src3, d_adSums;  // fvSource (3 per cell, allocated with the first disk); per disk: unit sums(2), scale, sums(2)
     DevBuf<Dual<1>> d_adPart, d_adD;  // partial sums of either scalar type; the sums and the scale of a dual pass
     DevBuf<int> d_adBad;              // set where a cell centre sits on the axis of a disk
+    // regression models of DASimpleFoam (the regressionModel option; das_regression.hpp) in the order of their definition, the order of
+    // the option dictionary: the last one to write betaFINuTilda wins.  regSet is what CaseParams::reg points at while one is defined.
+    struct RegModel {
+        std::string name, type;
+        std::vector<std::string> inputs;
+        RegView v;
+        std::vector<double> par;
+        DevBuf<double> d_par;
+    };
+    std::vector<std::unique_ptr<RegModel>> regModels;
+    RegSet regSet;
+    DevBuf<double> d_regFeat, d_regBeta, d_regPart, d_regOut;  // features and output of one model (read-back), partials and result of the backward kernel
+    DevBuf<unsigned char> d_regMask;
+    bool reg_needs_p() const {  // pGradStream and PSoSS read grad(p): nuTildaRes then depends on p at levels 0 and 1
+        for (const auto& m : regModels)
+            for (int k = 0; k < m->v.nIn; k++)
+                if (m->v.feat[k] == DAS_REG_PGRADSTREAM || m->v.feat[k] == DAS_REG_PSOSS) return true;
+        return false;
+    }
     int colorRounds = 0;       // rounds of the speculative device colouring (0: another algorithm ran)
     DevBuf<double> d_betaFI, d_dBetaFI;  // `field` input betaFINuTilda and its tangent (das_set_field / das_calc_dfield_product)
     long long geomVersion = 0;  // bumped by das_update_of_mesh
@@ -1020,6 +1057,8 @@ static void need_init(das_solver* s) {
 static void refresh_heat_sources(das_solver* s, bool check);
 // the same for the actuator disks of DASimpleFoam (check: also refuse a cell centre on the axis of a disk)
 static void refresh_actuator_disks(das_solver* s, bool check);
+// the views of the regression models (das_solver::regSet) from the models as they stand, their parameters on the device once there is one
+static void reg_sync(das_solver* s);
 
 // sum of a small device buffer over the ranks: the native all-reduce in stream order, else the legacy host callback (single rank: nothing)
 static void rank_allreduce(das_solver* s, double* p, long long cnt, hipStream_t st) {
@@ -1100,8 +1139,8 @@ static long long cell_chain_depth(const Mesh& m) {
 static void ensure_coloring(das_solver* s, const int* preset = nullptr) {
     if (s->colored && !preset) return;
     double t = wall_seconds();
-    s->st_full = make_stencil(s->cp.solver, s->mesh.nC, s->mesh.nF, s->opt, false, s->cp.hasT != 0);
-    s->st_pc = make_stencil(s->cp.solver, s->mesh.nC, s->mesh.nF, s->opt, true, s->cp.hasT != 0);
+    s->st_full = make_stencil(s->cp.solver, s->mesh.nC, s->mesh.nF, s->opt, false, s->cp.hasT != 0, s->reg_needs_p());
+    s->st_pc = make_stencil(s->cp.solver, s->mesh.nC, s->mesh.nF, s->opt, true, s->cp.hasT != 0, s->reg_needs_p());
     double t1 = wall_seconds();
     s->con_full.build(s->mesh, s->st_full);
     s->con_pc.build(s->mesh, s->st_pc);
@@ -3269,7 +3308,7 @@ das_solver_t* das_create(const das_case_t* c) {
         s->cp.from_case(c);
         s->mesh.build(c);
         s->opt.s["solverName"] = c->solver == DAS_SOLVER_SIMPLEFOAM ? "DASimpleFoam" : (c->solver == DAS_SOLVER_RHOSIMPLEFOAM ? "DARhoSimpleFoam" : (c->solver == DAS_SOLVER_TURBOFOAM ? "DATurboFoam" : (c->solver == DAS_SOLVER_HEATTRANSFERFOAM ? "DAHeatTransferFoam" : (c->solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM ? "DASolidDisplacementFoam" : "DAScalarTransportFoam"))));
-        s->st_full = make_stencil(s->cp.solver, s->mesh.nC, s->mesh.nF, s->opt, false, s->cp.hasT != 0);
+        s->st_full = make_stencil(s->cp.solver, s->mesh.nC, s->mesh.nF, s->opt, false, s->cp.hasT != 0, s->reg_needs_p());
         s->n = s->st_full.n;
         s->h_W.assign(s->n, 0.0);
         compute_scales(s.get());
@@ -3372,6 +3411,7 @@ int das_init_solver(das_solver_t* s, int device) {
     compute_scales(s);
     refresh_heat_sources(s, true);
     refresh_actuator_disks(s, true);
+    if (!s->regModels.empty()) reg_sync(s);
     return DAS_OK;
     DAS_CATCH
 }
@@ -3660,6 +3700,8 @@ int das_simple_iteration(das_solver_t* s, int nSweeps, double alphaP, double lin
     DAS_CHECK(s && nSweeps >= 0 && alphaP > 0.0 && linTol > 0.0 && maxLinIters > 0, DAS_ERR_ARG, "das_simple_iteration: bad argument");
     DAS_CHECK(s->actuatorDisks.empty(), DAS_ERR_ARG,
               "das_simple_iteration: the SIMPLE sweep does not carry the fvSource actuator disks (its U equation has no source term); use das_solve_primal");
+    DAS_CHECK(s->regModels.empty(), DAS_ERR_ARG,
+              "das_simple_iteration: the SIMPLE sweep does not evaluate the regressionModel (its nuTilda equation reads no betaFINuTilda); use das_solve_primal");
     run_simple_sweeps(s, nSweeps, alphaP, linTol, maxLinIters, info3);
     return DAS_OK;
     DAS_CATCH
@@ -4082,6 +4124,9 @@ static int field_var_id(das_solver* s, const char* var, bool allowField) {
     else if (v == "nuTilda" && flow) id = 2;
     else if (v == "T" && hasT) id = 3;
     else if (v == "betaFINuTilda" && flow && allowField) id = 4;
+    DAS_CHECK(!(id == 4 && !s->regModels.empty()), DAS_ERR_ARG,
+              "varName betaFINuTilda: a regressionModel is active and writes betaFINuTilda from the states in every residual evaluation; an objective over it "
+              "would depend on the states, which is not built");
     DAS_CHECK(id >= 0, DAS_ERR_ARG, "varName " + v + " is not supported by this solver; supported: " + supported);
     return id;
 }
@@ -4966,6 +5011,7 @@ int das_set_field(das_solver_t* s, const char* fieldName, const double* values) 
     check_field(fieldName);
     DAS_CHECK(s->cp.solver != DAS_SOLVER_SCALARTRANSPORTFOAM && s->cp.solver != DAS_SOLVER_HEATTRANSFERFOAM && s->cp.solver != DAS_SOLVER_SOLIDDISPLACEMENTFOAM,
               DAS_ERR_ARG, "betaFINuTilda needs a Spalart-Allmaras solver");
+    DAS_CHECK(s->regModels.empty(), DAS_ERR_ARG, "field input betaFINuTilda: a regressionModel is active and would overwrite the field in every residual evaluation");
     s->cp.beta_fi.assign(values, values + s->mesh.nC);
     if (s->inited) {
         DAS_HIP(hipStreamSynchronize(s->stream));
@@ -4996,6 +5042,7 @@ int das_calc_dfield_product(das_solver_t* s, const char* fieldName, const char* 
     need_init(s);
     DAS_CHECK(outputType && seeds && product, DAS_ERR_ARG, "null argument");
     check_field(fieldName);
+    DAS_CHECK(s->regModels.empty(), DAS_ERR_ARG, "field input betaFINuTilda: a regressionModel is active and overwrites the field in every residual evaluation");
     const std::string ot = outputType;
     DAS_CHECK(ot == "residual" || ot == "function" || is_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
     const long long N = s->mesh.nC, n = s->n;
@@ -5155,7 +5202,7 @@ static void function_face_slots(const Mesh& m, const das_solver::FaceFn& fn, std
 }
 // where the residual rows of each state block start (k_vc_rows / k_vc_rows_dual)
 static RowLayout residual_row_layout(das_solver* s) {
-    const Stencil stn = make_stencil(s->cp.solver, s->mesh.nC, s->mesh.nF, s->opt, false, s->cp.hasT != 0);
+    const Stencil stn = make_stencil(s->cp.solver, s->mesh.nC, s->mesh.nF, s->opt, false, s->cp.hasT != 0, s->reg_needs_p());
     DAS_CHECK(stn.states.size() <= 8, DAS_ERR_INTERNAL, "more than 8 state blocks");
     RowLayout L{};
     L.nb = (int)stn.states.size();
@@ -6685,10 +6732,285 @@ int das_ksp_end(das_solver_t* s, das_ksp_t* ksp) {
 }
 void das_ksp_destroy(das_ksp_t* k) { delete k; }
 
+// ---- regression models of DASimpleFoam (reference DARegression.C, DAInputRegressionPar.C; kernels: das_regression.hpp) ---------------
+// the option entry -> the view the kernels read (par stays null); every refusal names what it refuses
+static RegView reg_view_from_spec(const std::string& what, const das_reg_spec_t* sp, bool needNames, std::vector<std::string>* names) {
+    DAS_CHECK(sp && sp->model_type, DAS_ERR_ARG, what + ": null model description");
+    RegView v;
+    memset(&v, 0, sizeof(v));
+    const std::string mt = sp->model_type;
+    DAS_CHECK(mt != "externalTensorFlow", DAS_ERR_ARG,
+              what + ": modelType externalTensorFlow is not built (the model runs in a Python callback outside the residual pass); neuralNetwork and radialBasisFunction are");
+    DAS_CHECK(mt == "neuralNetwork" || mt == "radialBasisFunction", DAS_ERR_ARG,
+              what + ": modelType " + mt + " not supported. Options are: neuralNetwork and radialBasisFunction");
+    v.type = mt == "neuralNetwork" ? DAS_REG_NN : DAS_REG_RBF;
+    DAS_CHECK(sp->n_inputs >= 1 && sp->n_inputs <= DAS_REG_MAX_INPUTS, DAS_ERR_ARG,
+              what + ": " + std::to_string(sp->n_inputs) + " inputNames; 1 to DAS_REG_MAX_INPUTS = " + std::to_string(DAS_REG_MAX_INPUTS) + " are supported");
+    v.nIn = sp->n_inputs;
+    DAS_CHECK(sp->input_shift && sp->input_scale, DAS_ERR_ARG, what + ": inputShift and inputScale are needed, one value per inputName");
+    static const char* const kNames[] = {"VoS", "PoD", "chiSA", "pGradStream", "PSoSS", "SCurv", "UOrth"};
+    for (int k = 0; k < v.nIn; k++) {
+        v.shift[k] = sp->input_shift[k];
+        v.scale[k] = sp->input_scale[k];
+        if (!needNames && !sp->input_names) continue;
+        DAS_CHECK(sp->input_names && sp->input_names[k], DAS_ERR_ARG, what + ": null inputName");
+        const std::string in = sp->input_names[k];
+        DAS_CHECK(!(in.size() > 3 && in.compare(in.size() - 3, 3, "_dt") == 0), DAS_ERR_ARG,
+                  what + ": inputName " + in + " is a time derivative; the *_dt features are not built (the solvers here are steady)");
+        DAS_CHECK(in != "KoU2" && in != "ReWall" && in != "TauoK", DAS_ERR_ARG,
+                  what + ": inputName " + in + " needs the turbulent kinetic energy k, which the Spalart-Allmaras model does not carry; it is not built");
+        DAS_CHECK(in != "CoP", DAS_ERR_ARG, what + ": inputName CoP needs a face interpolation of nuTilda outside the stencil of nuTildaRes; it is not built");
+        int id = -1;
+        for (int q = 0; q < 7; q++) if (in == kNames[q]) id = q;
+        DAS_CHECK(id >= 0, DAS_ERR_ARG, what + ": inputName " + in + " not supported. Options are: VoS, PoD, chiSA, pGradStream, PSoSS, SCurv, UOrth");
+        v.feat[k] = id;
+        if (names) names->push_back(in);
+    }
+    if (needNames || sp->output_name)
+        DAS_CHECK(sp->output_name && std::string(sp->output_name) == "betaFINuTilda", DAS_ERR_ARG,
+                  what + ": outputName " + (sp->output_name ? sp->output_name : "(null)") + " is not built; betaFINuTilda is");
+    if (v.type == DAS_REG_NN) {
+        DAS_CHECK(sp->n_hidden_layers >= 1 && sp->n_hidden_layers <= DAS_REG_MAX_LAYERS && sp->hidden_layer_neurons, DAS_ERR_ARG,
+                  what + ": " + std::to_string(sp->n_hidden_layers) + " hidden layers; 1 to DAS_REG_MAX_LAYERS = " + std::to_string(DAS_REG_MAX_LAYERS) + " are supported");
+        v.nLayers = sp->n_hidden_layers;
+        for (int l = 0; l < v.nLayers; l++) {
+            DAS_CHECK(sp->hidden_layer_neurons[l] >= 1 && sp->hidden_layer_neurons[l] <= DAS_REG_MAX_WIDTH, DAS_ERR_ARG,
+                      what + ": hiddenLayerNeurons " + std::to_string(sp->hidden_layer_neurons[l]) + "; 1 to DAS_REG_MAX_WIDTH = " + std::to_string(DAS_REG_MAX_WIDTH) +
+                          " neurons per layer are supported");
+            v.width[l] = sp->hidden_layer_neurons[l];
+        }
+        const std::string af = sp->activation_function ? sp->activation_function : "";
+        DAS_CHECK(af == "sigmoid" || af == "tanh" || af == "relu", DAS_ERR_ARG, what + ": activationFunction " + af + " not valid. Options are: sigmoid, tanh, and relu");
+        v.act = af == "sigmoid" ? DAS_REG_SIGMOID : (af == "tanh" ? DAS_REG_TANH : DAS_REG_RELU);
+        v.leaky = v.act == DAS_REG_RELU ? sp->leaky_coeff : 0.0;
+    } else {
+        DAS_CHECK(sp->n_rbfs >= 1 && sp->n_rbfs <= DAS_REG_MAX_RBFS, DAS_ERR_ARG,
+                  what + ": nRBFs " + std::to_string(sp->n_rbfs) + "; 1 to DAS_REG_MAX_RBFS = " + std::to_string(DAS_REG_MAX_RBFS) + " are supported");
+        v.nRBF = sp->n_rbfs;
+    }
+    v.nPar = reg_n_parameters(v);
+    DAS_CHECK(v.nPar <= DAS_REG_MAX_PARAMS, DAS_ERR_ARG,
+              what + ": " + std::to_string(v.nPar) + " parameters; at most DAS_REG_MAX_PARAMS = " + std::to_string(DAS_REG_MAX_PARAMS) + " are supported");
+    // the LDS of the two kernels follows the model: what a workgroup may hold bounds it, here and not at the first launch
+    const size_t ldsB = reg_backward_lds(v), ldsF = reg_forward_lds<Dual<1>>(v);
+    DAS_CHECK(ldsB <= DAS_REG_MAX_LDS && ldsF <= DAS_REG_MAX_LDS, DAS_ERR_ARG,
+              what + ": the model needs " + std::to_string(std::max(ldsB, ldsF)) + " bytes of LDS per workgroup (inputs + 2 x hidden neurons + 1 rows of " +
+                  std::to_string(DAS_REG_BWD_TILE * sizeof(double)) + " bytes in the backward kernel); at most DAS_REG_MAX_LDS = " + std::to_string(DAS_REG_MAX_LDS) +
+                  " are supported");
+    v.outShift = sp->output_shift; v.outScale = sp->output_scale;
+    v.upper = sp->output_upper_bound; v.lower = sp->output_lower_bound; v.dflt = sp->default_output_value;
+    return v;
+}
+static void need_regression_solver(das_solver* s) {
+    DAS_CHECK(s, DAS_ERR_ARG, "null solver handle");
+    DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM, DAS_ERR_ARG,
+              "the regressionModel option is built for DASimpleFoam only: not for " + s->opt.gets("solverName"));
+    DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "the regression models run on an undecomposed solver (sharded solvers are not supported)");
+}
+static das_solver::RegModel& get_regression_model(das_solver* s, const char* name, int* index = nullptr) {
+    for (size_t k = 0; k < s->regModels.size(); k++)
+        if (name && s->regModels[k]->name == name) { if (index) *index = (int)k; return *s->regModels[k]; }
+    throw Error(DAS_ERR_ARG, std::string("regressionModel has no model ") + (name ? name : "(null)"));
+}
+static void reg_sync(das_solver* s) {
+    s->regSet.n = (int)s->regModels.size();
+    for (int k = 0; k < s->regSet.n; k++) {
+        das_solver::RegModel& m = *s->regModels[k];
+        if (s->inited) { DAS_HIP(hipStreamSynchronize(s->stream)); m.d_par.upload(m.par); }
+        m.v.par = m.d_par.p;
+        s->regSet.v[k] = m.v;
+    }
+    s->cp.reg = s->regSet.n ? &s->regSet : nullptr;
+    s->opEpoch++;
+}
+int das_define_regression_model(das_solver_t* s, const char* name, const das_reg_spec_t* spec) {
+    DAS_TRY
+    need_regression_solver(s);
+    DAS_CHECK(name && *name, DAS_ERR_ARG, "regressionModel: a model needs a name");
+    const std::string what = std::string("regressionModel ") + name;
+    std::unique_ptr<das_solver::RegModel> m(new das_solver::RegModel);
+    m->v = reg_view_from_spec(what, spec, true, &m->inputs);
+    m->name = name;
+    m->type = spec->model_type;
+    m->par.assign(m->v.nPar, 0.0);
+    DAS_CHECK(s->cp.beta_fi.empty(), DAS_ERR_ARG, what + ": a `field` input betaFINuTilda has been set; the model would overwrite it in every residual evaluation");
+    for (const auto& e : s->cellFunctions)
+        DAS_CHECK(!e.second.field, DAS_ERR_ARG,
+                  what + ": the objective " + e.first + " reads betaFINuTilda; with a model active it would depend on the states, which is not built");
+    const bool hadP = s->reg_needs_p();
+    int at = -1;
+    for (size_t k = 0; k < s->regModels.size(); k++) if (s->regModels[k]->name == name) at = (int)k;
+    DAS_CHECK(at >= 0 || (int)s->regModels.size() < DAS_REG_MAX_MODELS, DAS_ERR_ARG,
+              what + ": at most DAS_REG_MAX_MODELS = " + std::to_string(DAS_REG_MAX_MODELS) + " models are supported");
+    if (at >= 0) s->regModels[at] = std::move(m);
+    else s->regModels.push_back(std::move(m));
+    reg_sync(s);
+    if (s->reg_needs_p() != hadP) s->colored = false;  // the connectivity of nuTildaRes changed: new patterns, new colours
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_get_regression_n_parameters(das_solver_t* s, const char* name) {
+    DAS_TRY
+    need_regression_solver(s);
+    return get_regression_model(s, name).v.nPar;
+    DAS_CATCH
+}
+int das_set_regression_parameters(das_solver_t* s, const char* name, const double* values, int n) {
+    DAS_TRY
+    need_regression_solver(s);
+    das_solver::RegModel& m = get_regression_model(s, name);
+    DAS_CHECK(values && n == m.v.nPar, DAS_ERR_ARG,
+              std::string("regressionPar ") + name + ": " + std::to_string(n) + " values given, the model has " + std::to_string(m.v.nPar) + " parameters");
+    m.par.assign(values, values + n);
+    reg_sync(s);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_get_regression_parameters(das_solver_t* s, const char* name, double* values, int n) {
+    DAS_TRY
+    need_regression_solver(s);
+    const das_solver::RegModel& m = get_regression_model(s, name);
+    DAS_CHECK(values && n == m.v.nPar, DAS_ERR_ARG,
+              std::string("regressionPar ") + name + ": room for " + std::to_string(n) + " values, the model has " + std::to_string(m.v.nPar) + " parameters");
+    std::copy(m.par.begin(), m.par.end(), values);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_get_regression_model_info(das_solver_t* s, const char* name, int* nParameters, int* nInputs, int* modelType) {
+    DAS_TRY
+    need_regression_solver(s);
+    const das_solver::RegModel& m = get_regression_model(s, name);
+    if (nParameters) *nParameters = m.v.nPar;
+    if (nInputs) *nInputs = m.v.nIn;
+    if (modelType) *modelType = m.v.type;
+    return DAS_OK;
+    DAS_CATCH
+}
+// the three counts of a mask array: the two-stage fixed-order sum
+static void reg_fail_counts(int nC, const unsigned char* d_mask, DevBuf<double>& d_part, long long* fail3, hipStream_t st) {
+    const int nb = (int)std::min<long long>(nblk(nC, 256), 256);
+    if (d_part.n < 3 * (size_t)nb + 3) d_part.alloc(3 * (size_t)nb + 3);
+    hipLaunchKernelGGL(k_reg_count, dim3(nb), dim3(256), 0, st, nC, d_mask, d_part.p);
+    hipLaunchKernelGGL(k_reg_count_final, dim3(1), dim3(256), 0, st, nb, (const double*)d_part.p, d_part.p + 3 * (size_t)nb);
+    DAS_HIP(hipGetLastError());
+    double h[3];
+    DAS_HIP(hipMemcpyAsync(h, d_part.p + 3 * (size_t)nb, sizeof(h), hipMemcpyDeviceToHost, st));
+    DAS_HIP(hipStreamSynchronize(st));
+    for (int q = 0; q < 3; q++) fail3[q] = (long long)h[q];
+}
+int das_get_regression_features(das_solver_t* s, const char* name, double* features, double* output, long long* fail3) {
+    DAS_TRY
+    need_regression_solver(s);
+    need_init(s);
+    const das_solver::RegModel& m = get_regression_model(s, name);
+    const int nC = s->mesh.nC;
+    hipStream_t st = s->stream;
+    const ResParams prm = s->wk.bind(s->cp.solver, nC, s->mesh.nF, make_params(s->cp, s->opt, 0));
+    launch_grad_simple<double, double>(s->dm, prm, s->d_W.p, s->wk, st);
+    if (s->d_regFeat.n != (size_t)nC * m.v.nIn) s->d_regFeat.alloc((size_t)nC * m.v.nIn);
+    if (s->d_regBeta.n != (size_t)nC) { s->d_regBeta.alloc(nC); s->d_regMask.alloc(nC); }
+    launch_reg_forward<double, double>(m.v, nC, s->dm.cg, prm, s->d_W.p, (const double*)s->wk.gU.p, (const double*)s->wk.gP.p, nullptr, 0, s->d_regBeta.p,
+                                       s->d_regFeat.p, s->d_regMask.p, st);
+    DAS_HIP(hipGetLastError());
+    DAS_HIP(hipStreamSynchronize(st));
+    if (features) s->d_regFeat.download(features, (size_t)nC * m.v.nIn);
+    if (output) s->d_regBeta.download(output, nC);
+    if (fail3) reg_fail_counts(nC, s->d_regMask.p, s->d_regPart, fail3, st);
+    return DAS_OK;
+    DAS_CATCH
+}
+// out[k] = sum_c g[c] d beta_c / d theta_k on the device: k_reg_backward over a grid fixed by nC, then the partials in their order
+static void launch_reg_backward(const RegView& v, int nC, const CellGeom* cg, const ResParams& prm, const double* W, const double* gU, const double* gP,
+                                const double* featIn, const double* g, DevBuf<double>& d_part, double* d_out, hipStream_t st) {
+    const int nb = (int)std::min<long long>(nblk(nC, DAS_REG_BWD_TILE), DAS_REG_BWD_MAX_BLOCKS);
+    if (d_part.n < (size_t)nb * v.nPar) d_part.alloc((size_t)nb * v.nPar);
+    const size_t lds = reg_backward_lds(v);
+    if (lds > 64 * 1024) { DAS_HIP(hipFuncSetAttribute((const void*)k_reg_backward, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); }
+    hipLaunchKernelGGL(k_reg_backward, dim3(nb), dim3(DAS_REG_BWD_THREADS), lds, st, v, nC, cg, prm, W, gU, gP, featIn, g, d_part.p);
+    hipLaunchKernelGGL(k_reg_backward_final, dim3(nblk(v.nPar, 256)), dim3(256), 0, st, nb, v.nPar, (const double*)d_part.p, d_out);
+    DAS_HIP(hipGetLastError());
+}
+int das_calc_dregressionpar_product(das_solver_t* s, const char* name, const char* outputName, const char* outputType, const double* seeds, double* product) {
+    DAS_TRY
+    need_regression_solver(s);
+    need_init(s);
+    DAS_CHECK(outputType && seeds && product, DAS_ERR_ARG, "null argument");
+    int at = -1;
+    const das_solver::RegModel& m = get_regression_model(s, name, &at);
+    const std::string ot = outputType;
+    DAS_CHECK(ot == "residual" || ot == "function" || is_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
+    if (ot != "residual") {  // no function and no coupling output reads the production term: exact zeros (an unknown output still fails by name)
+        if (is_coupling(ot)) (void)coupling_size(s, ot, outputName);
+        else if (!find_cell_function(s, outputName)) (void)get_function(s, outputName);
+        std::fill(product, product + m.v.nPar, 0.0);
+        return DAS_OK;
+    }
+    if (at + 1 != (int)s->regModels.size()) {  // a later model overwrites this one's output: the residual does not see it
+        std::fill(product, product + m.v.nPar, 0.0);
+        return DAS_OK;
+    }
+    hipStream_t st = s->stream;
+    const int B = 256;
+    const long long N = s->mesh.nC, n = s->n;
+    // step 1: g_c = seeds . dR / d beta_c - one dual pass, the unit tangent set by k_reg_forward after the bounds (zero on clipped cells)
+    struct Restore { das_solver* s; ~Restore() { s->cp.regSeed = 0; } } restore{s};
+    s->cp.regSeed = 1;
+    const ResParams prm = make_params(s->cp, s->opt, 0);
+    if (s->d_Wd.n != (size_t)n) { s->d_Wd.alloc(n); s->d_Rd.alloc(n); }
+    hipLaunchKernelGGL(k_lift, dim3(nblk(n, B)), dim3(B), 0, st, n, s->d_W.p, s->d_Wd.p);  // states carry no tangent
+    eval_residual<Dual<1>>(s->dm, s->cp, prm, s->d_Wd.p, s->d_Rd.p, s->wk1, s->d_phiF.p, s->d_Told.p, st);
+    DAS_HIP(hipMemcpyAsync(s->d_tmp2.p, seeds, n * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_field_product, dim3(nblk(N, B)), dim3(B), 0, st, N, (long long)prm.offN * N, s->d_Rd.p, s->d_tmp2.p, s->d_tmp1.p);
+    // step 2: the reverse pass through the model at the same states (the gradients in double)
+    const ResParams prmD = s->wk.bind(s->cp.solver, N, s->mesh.nF, prm);
+    launch_grad_simple<double, double>(s->dm, prmD, s->d_W.p, s->wk, st);
+    if (s->d_regOut.n < (size_t)m.v.nPar) s->d_regOut.alloc(m.v.nPar);
+    launch_reg_backward(m.v, (int)N, s->dm.cg, prmD, s->d_W.p, s->wk.gU.p, s->wk.gP.p, nullptr, s->d_tmp1.p, s->d_regPart, s->d_regOut.p, st);
+    DAS_HIP(hipMemcpyAsync(product, s->d_regOut.p, m.v.nPar * sizeof(double), hipMemcpyDeviceToHost, st));
+    DAS_HIP(hipStreamSynchronize(st));
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_reg_forward(const das_reg_spec_t* spec, const double* par, int nPar, int nCells, const double* features, double* beta, unsigned char* mask) {
+    DAS_TRY
+    RegView v = reg_view_from_spec("das_debug_reg_forward", spec, false, nullptr);
+    DAS_CHECK(par && features && beta && nCells >= 1 && nPar == v.nPar, DAS_ERR_ARG,
+              "das_debug_reg_forward: bad argument (the model has " + std::to_string(v.nPar) + " parameters)");
+    DevBuf<double> d_par, d_feat, d_beta((size_t)nCells);
+    DevBuf<unsigned char> d_mask((size_t)nCells);
+    d_par.upload(par, nPar);
+    d_feat.upload(features, (size_t)nCells * v.nIn);
+    v.par = d_par.p;
+    launch_reg_forward<double, double>(v, nCells, nullptr, ResParams{}, nullptr, nullptr, nullptr, d_feat.p, 0, d_beta.p, nullptr, d_mask.p, 0);
+    DAS_HIP(hipGetLastError());
+    DAS_HIP(hipDeviceSynchronize());
+    d_beta.download(beta, nCells);
+    if (mask) d_mask.download(mask, nCells);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_reg_backward(const das_reg_spec_t* spec, const double* par, int nPar, int nCells, const double* features, const double* g, double* out) {
+    DAS_TRY
+    RegView v = reg_view_from_spec("das_debug_reg_backward", spec, false, nullptr);
+    DAS_CHECK(par && features && g && out && nCells >= 1 && nPar == v.nPar, DAS_ERR_ARG,
+              "das_debug_reg_backward: bad argument (the model has " + std::to_string(v.nPar) + " parameters)");
+    DevBuf<double> d_par, d_feat, d_g, d_part, d_out((size_t)nPar);
+    d_par.upload(par, nPar);
+    d_feat.upload(features, (size_t)nCells * v.nIn);
+    d_g.upload(g, nCells);
+    v.par = d_par.p;
+    launch_reg_backward(v, nCells, nullptr, ResParams{}, nullptr, nullptr, nullptr, d_feat.p, d_g.p, d_part, d_out.p, 0);
+    DAS_HIP(hipDeviceSynchronize());
+    d_out.download(out, nPar);
+    return DAS_OK;
+    DAS_CATCH
+}
+
 int das_set_owned_mask(das_solver_t* s, const unsigned char* owned) {
     DAS_TRY
     DAS_CHECK(s, DAS_ERR_ARG, "null solver handle");
     if (!owned) { s->owned.clear(); return DAS_OK; }
+    DAS_CHECK(s->regModels.empty(), DAS_ERR_ARG, "the regression models run on an undecomposed solver (sharded solvers are not supported)");
     DAS_CHECK(s->actuatorDisks.empty(), DAS_ERR_ARG, "the fvSource actuator disks run on an undecomposed solver (sharded solvers are not supported)");
     s->owned.assign(owned, owned + s->n);
     if (s->inited) s->d_owned.upload(s->owned);

@@ -22,7 +22,7 @@
 
 namespace das {
 
-Stencil make_stencil(int solver, int nC, int nF, const Options& opt, bool isPC, bool simpleHasT) {
+Stencil make_stencil(int solver, int nC, int nF, const Options& opt, bool isPC, bool simpleHasT, bool regNeedsP) {
     Stencil st;
     auto add_state = [&](const char* nm, StateKind k) {
         StateDef s;
@@ -55,6 +55,7 @@ Stencil make_stencil(int solver, int nC, int nF, const Options& opt, bool isPC, 
         st.levels[2] = {bits({"U", "T", "nuTilda", "phi"}), bits({"T", "nuTilda"}), bits({"T"})};      // TRes
         st.levels[3] = {bits({"U", "nuTilda", "phi"}), bits({"U", "nuTilda"}), bits({"nuTilda"})};    // nuTildaRes
         st.levels[4] = {bits({"U", "p", "nuTilda", "phi"}), bits({"U", "p", "nuTilda"}), bits({"U"})};  // phiRes
+        if (regNeedsP) { st.levels[3][0] |= bits({"p"}); st.levels[3][1] |= bits({"p"}); }  // as below
     } else if (solver == DAS_SOLVER_SIMPLEFOAM) {
         // order: volVector, volScalar, model, surfaceScalar (reference DAIndex.C:43-63)
         add_state("U", KIND_VEC);
@@ -67,6 +68,10 @@ Stencil make_stencil(int solver, int nC, int nF, const Options& opt, bool isPC, 
                         bits({"U"})};                                                                // pRes
         st.levels[2] = {bits({"U", "nuTilda", "phi"}), bits({"U", "nuTilda"}), bits({"nuTilda"})};    // nuTildaRes
         st.levels[3] = {bits({"U", "p", "nuTilda", "phi"}), bits({"U", "p", "nuTilda"}), bits({"U"})};  // phiRes
+        // a regression model with pGradStream or PSoSS among its inputs reads grad(p) of the cell: betaFINuTilda, and with it nuTildaRes,
+        // depends on p at levels 0 and 1.  (The reference applies dRdW^T by AD and never extends its table; an assembled, coloured
+        // operator must hold the entry.)  Without such a feature the table is the one above.
+        if (regNeedsP) { st.levels[2][0] |= bits({"p"}); st.levels[2][1] |= bits({"p"}); }
     } else if (DAS_IS_COMPRESSIBLE(solver)) {  // DAStateInfoTurboFoam.C:82-119 carries the same level table
         // DAStateInfoRhoSimpleFoam.C:40-47,79-116 and the compressible SA table DASpalartAllmaras.C:364-383
         add_state("U", KIND_VEC);

@@ -85,6 +85,9 @@ struct ResParams {
     // `field` input betaFINuTilda (per cell; null = 1) and its tangent (null = 0)
     const double* betaFI;
     const double* dBetaFI;
+    // regression models (das_regression.hpp): betaFINuTilda per cell as k_reg_forward wrote it in this pass, typed by the kernel's scalar
+    // like wTU; where it is set it replaces the betaFI read, null = no model
+    const void* betaReg;
     // DAHeatTransferFoam: kappa(T) = sum_k kappa[k] T^k, nKappa terms (kappa_of); solid = 1: the one-block state layout [T] (host-side launch switch)
     int solid, nKappa;
     double kappa[DAS_MAX_KAPPA_COEFFS];
@@ -166,6 +169,32 @@ template <class T>
 DAS_HD T fv1_of(const T& chi) {
     T chi3 = chi * chi * chi;
     return chi3 / (chi3 + SA_CV1 * SA_CV1 * SA_CV1);
+}
+// the SA source functions of one cell (DASpalartAllmaras.C:124-178): chi, fv1, fv2, Stilda and fw from nuTilda, nu, gradU (g[3 i + j] =
+// d_i U_j) and the wall distance y; body_cell, body_cell2 and the PoD feature of the regression models (das_regression.hpp) share them
+template <class T, class G>
+DAS_HD void sa_stilda_fw(const T& nc, const T& nu_c, const T* g, const G& y, T& Stilda, T& fw) {
+    const G k2y2 = (SA_KAPPA * y) * (SA_KAPPA * y);
+    T chi = nc / nu_c;
+    T fv1 = fv1_of<T>(chi);
+    T fv2 = 1.0 - chi / (1.0 + chi * fv1);
+    T w01 = 0.5 * (g[1] - g[3]), w02 = 0.5 * (g[2] - g[6]), w12 = 0.5 * (g[5] - g[7]);
+    T Omega = 1.4142135623730951 * dsqrt(2.0 * (w01 * w01 + w02 * w02 + w12 * w12));
+    Stilda = dmax(Omega + fv2 * nc / k2y2, SA_CS * Omega);
+    T r = dmin(nc / (dmax(Stilda, DAS_SMALL) * k2y2), 10.0);
+    T r2 = r * r, r6 = r2 * r2 * r2;
+    T gg = r + SA_CW2 * (r6 - r);
+    T g2 = gg * gg, g6 = g2 * g2 * g2;
+    const double cw36 = SA_CW3 * SA_CW3 * SA_CW3 * SA_CW3 * SA_CW3 * SA_CW3;
+    fw = gg * dpow((1.0 + cw36) / (g6 + cw36), 1.0 / 6.0);
+}
+// betaFINuTilda of cell c: the field-inversion multiplier of the production term (reference DASpalartAllmaras.C:445-485, betaFINuTilda_).
+// With a regression model active it is what k_reg_forward wrote in this pass (prm.betaReg, in the scalar of the pass); else the `field`
+// input (1 unless set, DAInputField.C) with its tangent, the seed of calcJacTVecProduct(field -> residual)
+template <class T>
+DAS_HD T beta_fi_of(const ResParams& prm, int c) {
+    if (prm.betaReg) return ((const T*)prm.betaReg)[c];
+    return prm.betaFI ? MkSeed<T>::make(prm.betaFI[c], prm.dBetaFI ? prm.dBetaFI[c] : 0.0) : T(1.0);
 }
 
 // ---- patch-field coefficients: x_b = vic*x_c + vbc ; snGrad_b = gic*x_c + gbc ---------------------
@@ -743,23 +772,10 @@ DAS_HD void body_cell(int c, const DevMeshT<G>& m, const ResParams& prm, const T
     }
     // ---- SA source terms (DASpalartAllmaras.C:124-178,445-485)
     const G y = cgc.y;
-    const G k2y2 = (SA_KAPPA * y) * (SA_KAPPA * y);
-    T chi = nc / nu_c;
-    T fv1 = fv1_of<T>(chi);
-    T fv2 = 1.0 - chi / (1.0 + chi * fv1);
-    T w01 = 0.5 * (gUc[1] - gUc[3]), w02 = 0.5 * (gUc[2] - gUc[6]), w12 = 0.5 * (gUc[5] - gUc[7]);
-    T Omega = 1.4142135623730951 * dsqrt(2.0 * (w01 * w01 + w02 * w02 + w12 * w12));
-    T Stilda = dmax(Omega + fv2 * nc / k2y2, SA_CS * Omega);
-    T r = dmin(nc / (dmax(Stilda, DAS_SMALL) * k2y2), 10.0);
-    T r2 = r * r, r6 = r2 * r2 * r2;
-    T gg = r + SA_CW2 * (r6 - r);
-    T g2 = gg * gg, g6 = g2 * g2 * g2;
-    const double cw36 = SA_CW3 * SA_CW3 * SA_CW3 * SA_CW3 * SA_CW3 * SA_CW3;
-    T fw = gg * dpow((1.0 + cw36) / (g6 + cw36), 1.0 / 6.0);
+    T Stilda, fw;
+    sa_stilda_fw<T, G>(nc, nu_c, gUc, y, Stilda, fw);
     T convdiff = ((dN + bdN) * nc + offN - sN - bsN) * rV;
-    // betaFINuTilda: the field-inversion multiplier of the production term (reference DASpalartAllmaras.C:445-485, betaFINuTilda_;
-    // 1 unless a `field` input sets it, DAInputField.C); its tangent is the seed of calcJacTVecProduct(field -> residual)
-    const T betaFI = prm.betaFI ? MkSeed<T>::make(prm.betaFI[c], prm.dBetaFI ? prm.dBetaFI[c] : 0.0) : T(1.0);
+    const T betaFI = beta_fi_of<T>(prm, c);
     T nres = convdiff - rho_c * ((SA_CB2 / SA_SIGMA) * (gNc[0] * gNc[0] + gNc[1] * gNc[1] + gNc[2] * gNc[2]) + SA_CB1 * Stilda * nc * betaFI)
              + SA_CW1 * rho_c * fw * nc / (y * y) * nc;
     if (!prm.normN) nres = nres * cgc.V;
@@ -969,21 +985,10 @@ DAS_HD void body_cell2(int c, const DevMeshT<double>& m, const ResParams& prm, c
     // ---- SA source terms (as body_cell)
     const T gNc[3] = {gradN[3LL * c], gradN[3LL * c + 1], gradN[3LL * c + 2]};
     const double y = cgc.y;
-    const double k2y2 = (SA_KAPPA * y) * (SA_KAPPA * y);
-    T chi = nc / T(prm.nu);
-    T fv1 = fv1_of<T>(chi);
-    T fv2 = 1.0 - chi / (1.0 + chi * fv1);
-    T w01 = 0.5 * (gradU[9LL * c + 1] - gradU[9LL * c + 3]), w02 = 0.5 * (gradU[9LL * c + 2] - gradU[9LL * c + 6]), w12 = 0.5 * (gradU[9LL * c + 5] - gradU[9LL * c + 7]);
-    T Omega = 1.4142135623730951 * dsqrt(2.0 * (w01 * w01 + w02 * w02 + w12 * w12));
-    T Stilda = dmax(Omega + fv2 * nc / k2y2, SA_CS * Omega);
-    T r = dmin(nc / (dmax(Stilda, DAS_SMALL) * k2y2), 10.0);
-    T r2 = r * r, r6 = r2 * r2 * r2;
-    T gg = r + SA_CW2 * (r6 - r);
-    T g2 = gg * gg, g6 = g2 * g2 * g2;
-    const double cw36 = SA_CW3 * SA_CW3 * SA_CW3 * SA_CW3 * SA_CW3 * SA_CW3;
-    T fw = gg * dpow((1.0 + cw36) / (g6 + cw36), 1.0 / 6.0);
+    T Stilda, fw;
+    sa_stilda_fw<T, double>(nc, T(prm.nu), gradU + 9LL * c, y, Stilda, fw);
     T convdiff = ((dN + bdN) * nc + offN - sN - bsN) * rV;
-    const T betaFI = prm.betaFI ? MkSeed<T>::make(prm.betaFI[c], prm.dBetaFI ? prm.dBetaFI[c] : 0.0) : T(1.0);
+    const T betaFI = beta_fi_of<T>(prm, c);
     T nres = convdiff - ((SA_CB2 / SA_SIGMA) * (gNc[0] * gNc[0] + gNc[1] * gNc[1] + gNc[2] * gNc[2]) + SA_CB1 * Stilda * nc * betaFI)
              + SA_CW1 * fw * nc / (y * y) * nc;
     if (!prm.normN) nres = nres * cgc.V;

@@ -388,6 +388,10 @@ def refuse_fv_source(options):
     """A sharded solver takes no fvSource entries: the totals of a source (the adjustThrust scale, the volume of a heat source) are sums
     over the whole mesh, and a shard holds its own cells and ghosts only."""
     fv = (options or {}).get("fvSource")
+    if ((options or {}).get("regressionModel") or {}).get("active"):
+        from ._capi import DASError
+
+        raise DASError("regressionModel: sharded solvers take no regression models (they run on one undecomposed mesh)")
     if fv:
         from ._capi import DASError
 

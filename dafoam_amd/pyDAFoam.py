@@ -36,8 +36,7 @@ class Error(Exception):
 class DAOPTION(object):
     """The reference's option surface: every DAOPTION attribute of dafoam/pyDAFoam.py:59-661 with its name, nesting and
     default value (line numbers in the comments; tests/test_reference_pins.py parses the reference file with `ast` and
-    compares).  Options of subsystems outside the adjoint hot path (mesh quality checks, FFD output, regression models,
-    ...) are accepted and carried so that existing runScripts construct unchanged; the hot path reads the ones marked *."""
+    compares).  Options of subsystems outside the adjoint hot path (mesh quality checks, FFD output, ...) are accepted and carried so that existing runScripts construct unchanged; the hot path reads the ones marked *."""
 
     def __init__(self):
         self.solverName = "DASimpleFoam"  # * :76
@@ -71,7 +70,7 @@ class DAOPTION(object):
         self.useConstrainHbyA = True  # * :433
         self.forceMeshWaveFrozen = True  # * :437 (the wall distance is always frozen here)
         self.useDdtCorr = False  # :441
-        self.regressionModel = {"active": False}  # :450
+        self.regressionModel = {"active": False}  # * :450
         self.useMeanStates = False  # :486
         self.solveLinearFunctionName = "None"  # :494
         self.printDAOptions = True  # :497
@@ -467,6 +466,11 @@ class PYDAFOAM(object):
         self.solver.readStateVars(timeVal, 0)
         if self.solverAD is not self.solver:
             self.solverAD.readStateVars(timeVal, 0)
+
+    def regressionModelInfo(self, name):
+        """nParameters, nInputs, modelType and the fail counts of a model of the regressionModel option (pyDASolvers.regressionModelInfo); the
+        reference's getNRegressionParameters(modelName) is its nParameters."""
+        return self.solver.regressionModelInfo(name)
 
     def getResiduals(self):
         """pyDAFoam.py:2121-2130"""

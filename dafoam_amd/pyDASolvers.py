@@ -330,6 +330,7 @@ class pyDASolvers:
         self._define_outputs(pyOptions.get("outputInfo") if isinstance(pyOptions, dict) else None)
         self._define_thermal_inputs()
         self._define_fv_sources()
+        self._define_regression_models(pyOptions.get("regressionModel") if isinstance(pyOptions, dict) else None)
         if case.states is not None:  # FoamCase.states is always in "state" ordering (input data)
             check(lib().das_update_of_fields(self._h, dptr(np.ascontiguousarray(case.states, dtype=np.float64))))
 
@@ -388,7 +389,7 @@ class pyDASolvers:
         [type, value] pairs produced by pyDAFoam._getDefOptions, pyDAFoam.py:823-844)."""
         flat = {}
         opts = {k: (v[1] if isinstance(v, list) and len(v) == 2 and isinstance(v[0], type) else v) for k, v in pyOptions.items()}
-        _flatten("", {k: v for k, v in opts.items() if not k.startswith("amdCase") and k not in ("function", "inputInfo", "outputInfo", "primalBC", "fvSource")}, flat)
+        _flatten("", {k: v for k, v in opts.items() if not k.startswith("amdCase") and k not in ("function", "inputInfo", "outputInfo", "primalBC", "fvSource", "regressionModel")}, flat)
         if flat.get("adjStateOrdering") == "cell" and getattr(self, "_perm", None) is not None:
             flat.pop("adjStateOrdering")  # handled at this boundary (permutation); the library stays in "state" ordering
         L = lib()
@@ -442,6 +443,8 @@ class pyDASolvers:
             return self.getNLocalPoints() * 3
         if inputType == "fvSourcePar":  # reference DAInputFvSourcePar.H size() = indices.size()
             return len(self._fv_source_par_entry(inputName)[1])
+        if inputType == "regressionPar":  # reference DAInputRegressionPar.H size() = nParameters(modelName); the entry is keyed by the model name
+            return self._regression_par_entry(inputName)
         return check(lib().das_get_input_size(self._h, inputName.encode(), inputType.encode()))
 
     # -- boundary-value inputs (reference src/adjoint/DAInput/DAInputPatchVelocity.C, DAInputPatchVar.C) ---------
@@ -520,6 +523,10 @@ class pyDASolvers:
             name, idx = self._fv_source_par_entry(inputName)
             setter = lib().das_set_actuator_disk_pars if self._is_actuator_disk(name) else lib().das_set_heat_source_pars
             return check(setter(self._h, name.encode(), idx.ctypes.data_as(_capi.c_int_p), idx.size, dptr(np.ascontiguousarray(inputs, dtype=np.float64))))
+        if inputType == "regressionPar":
+            # DAInputRegressionPar::run (reference DAInputRegressionPar.C:48-62): parameters[modelName] = input; the next residual sees them
+            self._regression_par_entry(inputName)
+            return check(lib().das_set_regression_parameters(self._h, inputName.encode(), dptr(np.ascontiguousarray(inputs, dtype=np.float64)), inputSize))
         if inputType not in ("patchVelocity", "patchVar"):
             raise _capi.DASError(f"inputType not supported on this path: {inputType}")
         field, val, _ = self._patch_input_tangents(inputName, inputType, inputs)
@@ -747,6 +754,14 @@ class pyDASolvers:
             prod = lib().das_calc_dactuatordiskpar_product if self._is_actuator_disk(name) else lib().das_calc_dfvsourcepar_product
             check(prod(self._h, name.encode(), idx.ctypes.data_as(_capi.c_int_p), idx.size, outputName.encode(), outputType.encode(),
                        dptr(np.ascontiguousarray(seeds_s, dtype=np.float64)), dptr(out)))
+            product[:] = out
+            return
+        if inputType == "regressionPar":
+            # run(input), then one dual pass for seeds . dR / d beta per cell and the reverse pass through the model (das_calc_dregressionpar_product)
+            self.setSolverInput(inputName, inputType, inputSize, inputs)
+            out = np.zeros(inputSize)
+            check(lib().das_calc_dregressionpar_product(self._h, inputName.encode(), outputName.encode(), outputType.encode(),
+                                                        dptr(np.ascontiguousarray(seeds_s, dtype=np.float64)), dptr(out)))
             product[:] = out
             return
         if inputType == "field":
@@ -1168,6 +1183,81 @@ class pyDASolvers:
             check(lib().das_get_actuator_disk_cells(self._h, name.encode(), cells.ctypes.data_as(_capi.c_int_p), n))
         return dict(pars=pars, scale=float(info[0]), thrustSourceSum=float(info[1]), torqueSourceSum=float(info[2]), unitThrust=float(info[3]),
                     nCells=nc.value, cells=cells)
+
+    # -- regression models: the regressionModel option of DASimpleFoam (reference DARegression.C) and the regressionPar input -----------------
+    _REGRESSION_KEYS = ("modelType", "inputNames", "outputName", "inputShift", "inputScale", "outputShift", "outputScale", "outputUpperBound",
+                        "outputLowerBound", "defaultOutputValue")
+
+    def _define_regression_models(self, opt):
+        """The regressionModel option (reference DARegression.C:34-147): {"active": ..., modelName: {...}, ...}.  Inactive or absent: nothing
+        is defined and nothing changes.  The models are defined in the order of the dictionary; every refusal names the model and the key."""
+        self._regressionModels = []
+        if not isinstance(opt, dict) or not opt.get("active"):
+            return
+        sn = self._case.solver_name
+        if sn != "DASimpleFoam":
+            raise _capi.DASError(f"regressionModel: the option is built for DASimpleFoam only, not for {sn}")
+        # (a variableVolSum objective over betaFINuTilda is refused by das_define_regression_model itself: the functions are defined by now)
+        for iname, e in self._inputInfo.items():
+            if e.get("type") == "field" and e.get("fieldName") == "betaFINuTilda":
+                raise _capi.DASError(f"regressionModel: inputInfo[{iname}] is a field input on betaFINuTilda; the model would overwrite it in every residual "
+                                     "evaluation")
+        for name, e in opt.items():
+            if name == "active":
+                continue
+            what = f"regressionModel[{name}]"
+            if not isinstance(e, dict):
+                raise _capi.DASError(f"{what}: a dictionary is expected")
+            missing = [k for k in self._REGRESSION_KEYS if k not in e]
+            if missing:
+                raise _capi.DASError(f"{what}: the key(s) {', '.join(missing)} are missing")
+            n = len(e["inputNames"])
+            for k in ("inputShift", "inputScale"):
+                if np.size(e[k]) != n:
+                    raise _capi.DASError(f"{what}: inputNames has different sizes than {k} ({n} names, {np.size(e[k])} values)")
+            if e["modelType"] == "neuralNetwork":
+                for k in ("hiddenLayerNeurons", "activationFunction"):
+                    if k not in e:
+                        raise _capi.DASError(f"{what}: modelType neuralNetwork needs the key {k}")
+            elif e["modelType"] == "radialBasisFunction" and "nRBFs" not in e:
+                raise _capi.DASError(f"{what}: modelType radialBasisFunction needs the key nRBFs")
+            sp = _capi.reg_spec(e)
+            check(lib().das_define_regression_model(self._h, name.encode(), C.byref(sp)))
+            self._regressionModels.append(name)
+
+    def _regression_par_entry(self, inputName):
+        """The parameter count of the model an inputInfo entry of type regressionPar drives: the entry is keyed by the MODEL name
+        (reference DAInputRegressionPar.C:48)."""
+        self._input_entry(inputName, "regressionPar")
+        if inputName not in self._regressionModels:
+            raise _capi.DASError(f"inputInfo[{inputName}]: type regressionPar, but regressionModel has no active model {inputName} (the entry is keyed by "
+                                 f"the model name; models: {', '.join(self._regressionModels) or 'none'})")
+        return check(lib().das_get_regression_n_parameters(self._h, inputName.encode()))
+
+    def regressionModelInfo(self, name):
+        """nParameters, nInputs and modelType of a model and, once the solver is initialised, the number of cells whose output was NaN, Inf
+        and out of bounds at the current states (the reference's fail flag: any of them non-zero)."""
+        nPar, nIn, mt = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(lib().das_get_regression_model_info(self._h, name.encode(), C.byref(nPar), C.byref(nIn), C.byref(mt)))
+        fail = np.zeros(3, dtype=np.int64)
+        if self._inited:
+            check(lib().das_get_regression_features(self._h, name.encode(), None, None, fail.ctypes.data_as(_capi.c_ll_p)))
+        return dict(nParameters=nPar.value, nInputs=nIn.value, modelType=("neuralNetwork", "radialBasisFunction")[mt.value], nNaN=int(fail[0]),
+                    nInf=int(fail[1]), nBounded=int(fail[2]), fail=int(fail.any()))
+
+    def getRegressionFeatures(self, name):
+        """(features (nCells, nInputs), output (nCells,)) of a model at the current states: what the reference's writeFeatures writes."""
+        nIn = C.c_int(0)
+        check(lib().das_get_regression_model_info(self._h, name.encode(), None, C.byref(nIn), None))
+        n = self._case.mesh.n_cells
+        feat, out = np.zeros((n, nIn.value)), np.zeros(n)
+        check(lib().das_get_regression_features(self._h, name.encode(), dptr(feat), dptr(out), None))
+        return feat, out
+
+    def getRegressionParameters(self, name):
+        out = np.zeros(check(lib().das_get_regression_n_parameters(self._h, name.encode())))
+        check(lib().das_get_regression_parameters(self._h, name.encode(), dptr(out), out.size))
+        return out
 
     def _define_fv_sources(self):
         """the entries of the fvSource option: actuator disks on DASimpleFoam, heat sources on DAHeatTransferFoam"""

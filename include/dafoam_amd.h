@@ -506,6 +506,57 @@ int das_get_fv_source_vector(das_solver_t* s, double* out);
 int das_calc_dactuatordiskpar_product(das_solver_t* s, const char* name, const int* indices, int n, const char* outputName, const char* outputType,
                                       const double* seeds, double* product);
 
+/* Regression models of DASimpleFoam: the regressionModel option and the regressionPar input (reference DARegression.C:164-773,
+ * DAInputRegressionPar.C).  A neural network or a sum of radial basis functions is evaluated in every cell from local flow features and
+ * writes betaFINuTilda as part of every residual evaluation (kernels: csrc/das_regression.hpp): the residual, dRdW^T (assembled, coloured),
+ * every product and the Newton primal see it.  The models run in the order of their definition; the last one wins.
+ * das_define_regression_model    one entry of the option.  model_type "neuralNetwork" | "radialBasisFunction"; input_names out of VoS, PoD,
+ *   chiSA, pGradStream, PSoSS, SCurv, UOrth, each followed by (f + input_shift) * input_scale; output_name "betaFINuTilda";
+ *   activation_function "sigmoid" | "tanh" | "relu" (with leaky_coeff).  Caps, refused by name: DAS_REG_MAX_INPUTS 8, DAS_REG_MAX_LAYERS 6
+ *   hidden layers, DAS_REG_MAX_WIDTH 32 neurons per layer, DAS_REG_MAX_RBFS 64, DAS_REG_MAX_PARAMS 4096, DAS_REG_MAX_MODELS 4, and DAS_REG_MAX_LDS 160 KB per workgroup of either kernel
+ *   (backward: inputs + 2 x hidden neurons + 1 rows of 512 bytes).
+ *   Refused by name as well: externalTensorFlow, the features KoU2, ReWall, TauoK, CoP and every *_dt, another output_name, another
+ *   solver, a sharded solver, a `field` input or a variableVolSum objective on betaFINuTilda and das_simple_iteration while a model is
+ *   defined.  The parameters start at zero, as in the reference.  A model of the same name is replaced.
+ *   pGradStream or PSoSS among the inputs of any model: nuTildaRes lists p at levels 0 and 1 and the colouring is done again.
+ * das_get_regression_n_parameters  the parameter count (DARegression::nParameters), or a negative error code.
+ * das_set/get_regression_parameters  the parameter vector in the reference's order (n must be the count); setting bumps the operator epoch.
+ * das_get_regression_model_info  nParameters, nInputs, modelType (0 network, 1 RBF); any output may be NULL.
+ * das_get_regression_features    at the current states: the features (nCells x nInputs, shifted and scaled), the model's output after the
+ *   bounds (nCells) and fail3 = the number of cells that were NaN, Inf and out of bounds (the reference's fail flag is "any of them
+ *   non-zero"); any output may be NULL.
+ * das_calc_dregressionpar_product <- calcJacTVecProduct(name, "regressionPar", ...): product[k] = seeds . d output / d parameter k.
+ *   "residual": one dual-number residual pass with a unit tangent on betaFINuTilda of every cell that kept its value (g_c = seeds . dR /
+ *   d beta_c), then the hand-written reverse pass through the model, reduced over cells x parameters in a fixed order (no atomics, the
+ *   same bits on every call).  "function" and the coupling outputs: exact zeros.  A model whose output a later model overwrites: zeros.
+ * das_debug_reg_forward / _backward  TEST ONLY: k_reg_forward / k_reg_backward on caller-supplied features (nCells x n_inputs) with no
+ *   mesh; forward gives beta (after the bounds) and the mask per cell (bit 0 NaN, 1 Inf, 2 bounded); backward gives
+ *   out[k] = sum_c g[c] d beta_c / d parameter k without the bounds (the caller zeroes g on the cells it wants masked). */
+typedef struct das_reg_spec {
+    const char* model_type;
+    int n_inputs;
+    const char* const* input_names; /* may be NULL in the debug entries */
+    const double* input_shift;
+    const double* input_scale;
+    const char* output_name;
+    int n_hidden_layers;
+    const int* hidden_layer_neurons;
+    const char* activation_function;
+    double leaky_coeff;
+    int n_rbfs;
+    double output_shift, output_scale, output_upper_bound, output_lower_bound, default_output_value;
+} das_reg_spec_t;
+int das_define_regression_model(das_solver_t* s, const char* name, const das_reg_spec_t* spec);
+int das_get_regression_n_parameters(das_solver_t* s, const char* name);
+int das_set_regression_parameters(das_solver_t* s, const char* name, const double* values, int n);
+int das_get_regression_parameters(das_solver_t* s, const char* name, double* values, int n);
+int das_get_regression_model_info(das_solver_t* s, const char* name, int* nParameters, int* nInputs, int* modelType);
+int das_get_regression_features(das_solver_t* s, const char* name, double* features, double* output, long long* fail3);
+int das_calc_dregressionpar_product(das_solver_t* s, const char* name, const char* outputName, const char* outputType, const double* seeds,
+                                    double* product);
+int das_debug_reg_forward(const das_reg_spec_t* spec, const double* par, int nPar, int nCells, const double* features, double* beta, unsigned char* mask);
+int das_debug_reg_backward(const das_reg_spec_t* spec, const double* par, int nPar, int nCells, const double* features, const double* g, double* out);
+
 /* das_calc_jac_t_vec_product <-calcJacTVecProduct(inputName,inputType,inputs,outputName,outputType,seeds,product)
  *   pyDASolvers.pyx:208-235 (DASolver.C:1690-1839).  Supported pair on this path: inputType "stateVar",
  *   outputType "residual": product = D_s (dR/dW)^T seeds  (normalizeJacTVecProduct, DASolver.C:1443-1553);
