@@ -403,6 +403,8 @@ _SIGS = {
     "das_define_patch_field_function": (C.c_int, [_VP, C.c_char_p, C.c_char_p, c_int_p, C.c_int, C.c_char_p, c_int_p, C.c_int, c_double_p, C.c_int, C.c_double, C.c_double]),
     "das_define_cell_function": (C.c_int, [_VP, C.c_char_p, C.c_char_p, c_int_p, C.c_int, C.c_char_p, c_int_p, C.c_int, c_double_p, C.c_int, C.c_double, C.c_double]),
     "das_define_von_mises_function": (C.c_int, [_VP, C.c_char_p, c_int_p, C.c_int, C.c_double, C.c_double, C.c_int, C.c_double]),
+    "das_define_mesh_quality_function": (C.c_int, [_VP, C.c_char_p, C.c_char_p, C.c_double, C.c_int, C.c_double]),
+    "das_define_residual_norm_function": (C.c_int, [_VP, C.c_char_p, C.POINTER(C.c_char_p), c_double_p, C.c_int, C.c_char_p, C.c_int, C.c_double]),
     "das_calc_function": (C.c_int, [_VP, C.c_char_p, c_double_p]),
     "das_define_force_coupling": (C.c_int, [_VP, C.c_char_p, c_int_p, C.c_int, C.c_double]),
     "das_calc_force_coupling": (C.c_int, [_VP, C.c_char_p, c_double_p, C.c_int]),

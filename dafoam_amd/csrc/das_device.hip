@@ -40,6 +40,7 @@
 #include "das_volcoord.hpp"
 #include "das_cellfn.hpp"
 #include "das_facefn.hpp"
+#include "das_meshquality.hpp"
 #include "das_forcecoupling.hpp"
 #include "das_thermalcoupling.hpp"
 #include "das_heatsource.hpp"
@@ -942,6 +943,20 @@ struct das_solver {
         }
     };
     std::map<std::string, CellFn> cellFunctions;
+    struct MeshFn {  // a function over the whole mesh (das_meshquality.hpp): meshQualityKS, or residualNorm
+        std::string name;
+        bool residualNorm = false, refVar = false;
+        double ref = 0.0;
+        int metric = DAS_MQ_ORTHO;  // meshQualityKS
+        double coeffKS = 1.0;
+        double w[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // residualNorm: the weight of every residual block, in the order of the row layout
+        bool l1 = false;
+        // d_a: a_f per face / the term per row; d_w: the softmax weights per face; d_ks = {m, S} of the last value, d_kpart = the block
+        // partials; d_X: the points of xGeom (faceSkewness reads them)
+        DevBuf<double> d_a, d_w, d_ks, d_kpart, d_X;
+        long long xGeom = -1;
+    };
+    std::map<std::string, MeshFn> meshFunctions;
     // heat sources of DAHeatTransferFoam (the fvSource option; das_heatsource.hpp).  The map keeps them in name order, the order of the
     // reference's toc() walk, so the accumulation does not depend on the order of definition.
     struct HeatSource {
@@ -4001,6 +4016,7 @@ static void register_face_function(das_solver* s, const char* name, das_solver::
     DAS_CHECK(!needFaces || !fn.faces.empty(), DAS_ERR_ARG, "the patches of function " + std::string(name) + " have no faces");
     build_function_geometry(s, fn);
     s->cellFunctions.erase(name);
+    s->meshFunctions.erase(name);
     s->functions[name] = std::move(fn);
 }
 
@@ -4212,6 +4228,7 @@ int das_define_cell_function(das_solver_t* s, const char* name, const char* type
     }
     if (fn.variance && data) fn.data.assign(data, data + fn.cell.size());
     s->functions.erase(name);
+    s->meshFunctions.erase(name);
     s->cellFunctions[name] = std::move(fn);
     return DAS_OK;
     DAS_CATCH
@@ -4239,6 +4256,7 @@ int das_define_von_mises_function(das_solver_t* s, const char* name, const int* 
         fn.idx.push_back(3LL * c);
     }
     s->functions.erase(name);
+    s->meshFunctions.erase(name);
     s->cellFunctions[name] = std::move(fn);
     return DAS_OK;
     DAS_CATCH
@@ -4458,10 +4476,164 @@ static void function_effective_weights(das_solver* s, das_solver::FaceFn& fn) {
     for (size_t k = 0; k < w.size(); k++) w[k] = fn.w0[k] * c[fn.group[k]];
     fn.d_weff.upload(w);
 }
+// ---- meshQualityKS and residualNorm (reference DAFunctionMeshQualityKS.C, DAFunctionResidualNorm.C; kernels: das_meshquality.hpp) ----
+static GeomTopo device_geom_topo(das_solver* s);
+static RowLayout residual_row_layout(das_solver* s);
+static das_solver::MeshFn* find_mesh_function(das_solver* s, const char* name) {
+    auto it = s->meshFunctions.find(name ? name : "");
+    return it == s->meshFunctions.end() ? nullptr : &it->second;
+}
+static void need_mesh_function_solver(das_solver* s, const std::string& type, const char* name) {
+    DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM || DAS_IS_COMPRESSIBLE(s->cp.solver) || s->cp.solver == DAS_SOLVER_SCALARTRANSPORTFOAM, DAS_ERR_ARG,
+              "function type " + type + " (function " + name + ") is built for DASimpleFoam, DARhoSimpleFoam, DATurboFoam and DAScalarTransportFoam");
+    DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, type + " function " + name + " runs on an undecomposed solver (sharded solvers are not supported)");
+}
+static void register_mesh_function(das_solver* s, const char* name, das_solver::MeshFn&& fn) {
+    fn.name = name;
+    s->functions.erase(name);
+    s->cellFunctions.erase(name);
+    s->meshFunctions.erase(name);
+    s->meshFunctions.emplace(name, std::move(fn));
+}
+// meshQualityKS: the KS aggregate of a per-face mesh-quality metric over ALL faces.  flags & 8: calcRefVar.  No scale is applied (the
+// reference's calcFunction multiplies by none).  Cyclic patches are refused: OpenFOAM treats their faces as coupled, with the neighbour's
+// centre, which body_mesh_quality does not.
+int das_define_mesh_quality_function(das_solver_t* s, const char* name, const char* metric, double coeffKS, int flags, double ref) {
+    DAS_TRY
+    DAS_CHECK(s && name && metric, DAS_ERR_ARG, "bad argument");
+    need_mesh_function_solver(s, "meshQualityKS", name);
+    const std::string mt = metric;
+    DAS_CHECK(mt == "faceOrthogonality" || mt == "nonOrthoAngle" || mt == "faceSkewness", DAS_ERR_ARG,
+              "metric not valid! Options: faceOrthogonality, nonOrthoAngle, or faceSkewness");
+    DAS_CHECK(coeffKS != 0.0, DAS_ERR_ARG, std::string("coeffKS of meshQualityKS function ") + name + " is zero");
+    for (int p = 0; p < s->mesh.nPatch; p++)
+        DAS_CHECK(s->mesh.patch_type[p] != DAS_PATCH_CYCLIC, DAS_ERR_ARG,
+                  std::string("meshQualityKS function ") + name + ": the mesh has cyclic patches, whose faces OpenFOAM treats as coupled; that is not built");
+    das_solver::MeshFn fn;
+    fn.metric = mt == "faceOrthogonality" ? DAS_MQ_ORTHO : mt == "nonOrthoAngle" ? DAS_MQ_NONORTHO : DAS_MQ_SKEW;
+    fn.coeffKS = coeffKS;
+    fn.refVar = (flags & 8) != 0;
+    fn.ref = ref;
+    register_mesh_function(s, name, std::move(fn));
+    return DAS_OK;
+    DAS_CATCH
+}
+// residualNorm: resNames[k] = "<state>Res" with weights[k]; every residual block of the solver must be among them, other names are
+// ignored (the reference's unit test passes TRes to a case without T).  resMode L2Norm | L1Norm.  flags & 8: calcRefVar.  No scale.
+int das_define_residual_norm_function(das_solver_t* s, const char* name, const char* const* resNames, const double* weights, int nw, const char* resMode,
+                                      int flags, double ref) {
+    DAS_TRY
+    DAS_CHECK(s && name && resMode && (nw == 0 || (resNames && weights)) && nw >= 0, DAS_ERR_ARG, "bad argument");
+    need_mesh_function_solver(s, "residualNorm", name);
+    const std::string md = resMode;
+    DAS_CHECK(md == "L2Norm" || md == "L1Norm", DAS_ERR_ARG, "resMode not supported! options are L2Norm or L1Norm (function " + std::string(name) + ": " + md + ")");
+    const Stencil stn = make_stencil(s->cp.solver, s->mesh.nC, s->mesh.nF, s->opt, false, s->cp.hasT != 0, s->reg_needs_p());
+    DAS_CHECK(stn.states.size() <= 8, DAS_ERR_INTERNAL, "more than 8 state blocks");
+    das_solver::MeshFn fn;
+    fn.residualNorm = true;
+    fn.l1 = md == "L1Norm";
+    for (size_t b = 0; b < stn.states.size(); b++) {
+        const std::string res = stn.states[b].name + "Res";
+        int at = -1;
+        for (int k = 0; k < nw; k++) if (res == resNames[k]) at = k;
+        DAS_CHECK(at >= 0, DAS_ERR_ARG, std::string("residualNorm function ") + name + ": resWeight has no entry for " + res);
+        fn.w[b] = weights[at];
+    }
+    fn.refVar = (flags & 8) != 0;
+    fn.ref = ref;
+    register_mesh_function(s, name, std::move(fn));
+    return DAS_OK;
+    DAS_CATCH
+}
+static int mesh_function_blocks(long long n) { return std::max(1, std::min(DAS_FACEFN_MAX_BLOCKS, nblk(n, 256))); }
+// a_f of all faces at the current metrics -> fn.d_a, then the max-shifted two-stage KS sum; {m, S} stay in fn.d_ks for k_ks_weights.
+// F0 = (m + log S) / coeffKS.  The reference aborts when its plain sum of exponentials passes 1e200; the log-space sum has no such limit
+// and none is imposed (as for vonMisesStressKS).
+static double mesh_quality_value(das_solver* s, das_solver::MeshFn& fn) {
+    DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, std::string(fn.residualNorm ? "residualNorm" : "meshQualityKS") + " function " + fn.name + " runs on an undecomposed solver (sharded solvers are not supported)");
+    const Mesh& m = s->mesh;
+    const GeomTopo t = device_geom_topo(s);
+    const long long nF = m.nF;
+    if (fn.xGeom != s->geomVersion) { fn.d_X.upload(m.points.data(), 3 * (size_t)m.nP); fn.xGeom = s->geomVersion; }
+    if (fn.d_a.n != (size_t)nF) { fn.d_a.alloc(nF); fn.d_w.alloc(nF); }
+    if (fn.d_ks.n != 2) { fn.d_ks.alloc(2); fn.d_kpart.alloc(DAS_FACEFN_MAX_BLOCKS); }
+    const int nb = mesh_function_blocks(nF);
+    hipLaunchKernelGGL(k_mq_metric<double>, dim3(nblk(nF, 256)), dim3(256), 0, s->stream, t, (const double*)fn.d_X.p, (const FaceGeom*)s->d_fg.p,
+                       (const CellGeom*)s->d_cg.p, fn.metric, (const double*)nullptr, fn.d_a.p);
+    hipLaunchKernelGGL(k_ks_max, dim3(nb), dim3(256), 0, s->stream, nF, (const double*)fn.d_a.p, fn.coeffKS, fn.d_kpart.p);
+    hipLaunchKernelGGL(k_ks_max_final, dim3(1), dim3(256), 0, s->stream, nb, (const double*)fn.d_kpart.p, fn.d_ks.p);
+    hipLaunchKernelGGL(k_ks_expsum, dim3(nb), dim3(256), 0, s->stream, nF, (const double*)fn.d_a.p, fn.coeffKS, (const double*)fn.d_ks.p, fn.d_kpart.p);
+    hipLaunchKernelGGL(k_ks_sum_final, dim3(1), dim3(256), 0, s->stream, nb, (const double*)fn.d_kpart.p, fn.d_ks.p);
+    DAS_HIP(hipGetLastError());
+    double ms[2];
+    DAS_HIP(hipMemcpyAsync(ms, fn.d_ks.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    return (ms[0] + std::log(ms[1])) / fn.coeffKS;
+}
+// the per-face weights seed dF/da_f of the volCoord product -> fn.d_w (the softmax of the base mesh; calcRefVar's outer derivative included)
+static void mesh_quality_weights(das_solver* s, das_solver::MeshFn& fn, double seed) {
+    const double outer = seed * ref_var_outer(fn.refVar, fn.ref, mesh_quality_value(s, fn));
+    const long long nF = s->mesh.nF;
+    hipLaunchKernelGGL(k_ks_weights, dim3(nblk(nF, 256)), dim3(256), 0, s->stream, nF, (const double*)fn.d_a.p, fn.coeffKS, (const double*)fn.d_ks.p, outer, fn.d_w.p);
+    DAS_HIP(hipGetLastError());
+}
+static RnRows residual_norm_rows(das_solver* s, const das_solver::MeshFn& fn) {
+    const RowLayout L = residual_row_layout(s);
+    RnRows r{};
+    r.nb = L.nb;
+    for (int b = 0; b < L.nb; b++) { r.off[b] = L.off[b]; r.kind[b] = L.kind[b]; r.w[b] = fn.w[b]; }
+    r.nC = s->mesh.nC; r.nF = s->mesh.nF; r.nIF = s->mesh.nIF;
+    r.l1 = fn.l1 ? 1 : 0;
+    return r;
+}
+// F0 of residualNorm on the residual das_calc_residuals returns at the current states (isPC 0, normalizeResiduals as configured); the
+// residual stays in s->d_R for k_rn_seeds
+static double residual_norm_value(das_solver* s, das_solver::MeshFn& fn) {
+    DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, std::string(fn.residualNorm ? "residualNorm" : "meshQualityKS") + " function " + fn.name + " runs on an undecomposed solver (sharded solvers are not supported)");
+    const long long n = s->n;
+    const ResParams prm = make_params(s->cp, s->opt, 0);
+    eval_residual<double>(s->dm, s->cp, prm, s->d_W.p, s->d_R.p, s->wk, s->d_phiF.p, s->d_Told.p, s->stream);
+    if (fn.d_a.n != (size_t)n) fn.d_a.alloc(n);
+    if (fn.d_ks.n != 2) { fn.d_ks.alloc(2); fn.d_kpart.alloc(DAS_FACEFN_MAX_BLOCKS); }
+    const int nb = mesh_function_blocks(n);
+    hipLaunchKernelGGL(k_rn_terms, dim3(nblk(n, 256)), dim3(256), 0, s->stream, n, residual_norm_rows(s, fn), (const double*)s->d_R.p, fn.d_a.p);
+    hipLaunchKernelGGL(k_rn_partial, dim3(nb), dim3(256), 0, s->stream, n, (const double*)fn.d_a.p, fn.d_kpart.p);
+    hipLaunchKernelGGL(k_ks_sum_final, dim3(1), dim3(256), 0, s->stream, nb, (const double*)fn.d_kpart.p, fn.d_ks.p);
+    DAS_HIP(hipGetLastError());
+    double sum = 0.0;
+    DAS_HIP(hipMemcpyAsync(&sum, fn.d_ks.p + 1, sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    return fn.l1 ? sum : std::sqrt(sum);
+}
+// d_g[i] = seed dF/dR_i at the current states (device array of s->n entries): the seeds of the  input -> residual  products
+static void residual_norm_seeds(das_solver* s, das_solver::MeshFn& fn, double seed, double* d_g) {
+    const double F0 = residual_norm_value(s, fn);
+    DAS_CHECK(fn.l1 || F0 != 0.0, DAS_ERR_ARG, "residualNorm function " + fn.name + ": the L2Norm is zero, where it has no derivative");
+    const double coef = seed * ref_var_outer(fn.refVar, fn.ref, F0);
+    hipLaunchKernelGGL(k_rn_seeds, dim3(nblk(s->n, 256)), dim3(256), 0, s->stream, (long long)s->n, residual_norm_rows(s, fn), (const double*)s->d_R.p, F0, coef, d_g);
+    DAS_HIP(hipGetLastError());
+}
+// The product of a residualNorm function from any input is the existing  input -> residual  product with the seeds g = seed dF/dR:
+// (ot, seeds) become ("residual", g).  g is formed on the device and comes down once (the product entries take host seeds).
+static void residual_norm_redirect(das_solver* s, const char* outputName, std::string& ot, const double*& seeds, std::vector<double>& g) {
+    if (ot != "function") return;
+    das_solver::MeshFn* mf = find_mesh_function(s, outputName);
+    if (!mf || !mf->residualNorm) return;
+    g.resize(s->n);
+    residual_norm_seeds(s, *mf, seeds[0], s->d_tmp2.p);
+    DAS_HIP(hipMemcpyAsync(g.data(), s->d_tmp2.p, s->n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    DAS_HIP(hipStreamSynchronize(s->stream));
+    ot = "residual";
+    seeds = g.data();
+}
 int das_calc_function(das_solver_t* s, const char* name, double* value) {
     DAS_TRY
     need_init(s);
     DAS_CHECK(value, DAS_ERR_ARG, "null output");
+    if (das_solver::MeshFn* mf = find_mesh_function(s, name)) {
+        *value = ref_var_value(mf->refVar, mf->ref, mf->residualNorm ? residual_norm_value(s, *mf) : mesh_quality_value(s, *mf));
+        return DAS_OK;
+    }
     if (das_solver::CellFn* cf = find_cell_function(s, name)) {
         *value = ref_var_value(cf->refVar, cf->ref, cell_function_base_value(s, *cf));
         return DAS_OK;
@@ -4475,6 +4647,11 @@ static void face_function_gradient(das_solver* s, das_solver::FaceFn& fn, double
 // product_j = seed * s_j dF/dW_j : coloured forward-mode gradient of the objective (one k_grad + one k_force per colour)
 static void function_gradient(das_solver* s, const char* name, double seed, double* product) {
     need_init(s);
+    if (das_solver::MeshFn* mf = find_mesh_function(s, name)) {  // meshQualityKS reads the points alone: dF/dW = 0 exactly, no pass
+        DAS_CHECK(!mf->residualNorm, DAS_ERR_INTERNAL, "residualNorm takes the residual product");
+        std::fill(product, product + s->n, 0.0);
+        return;
+    }
     if (das_solver::CellFn* cf = find_cell_function(s, name)) {  // local and analytic: one elementwise pass, no colouring
         if (cf->field) std::fill(product, product + s->n, 0.0);
         else if (cf->vmKS) vm_ks_gradient(s, *cf, seed, product);
@@ -4836,7 +5013,9 @@ int das_calc_dbc_product(das_solver_t* s, const int* patches, int np, const char
     DAS_CHECK(tangent && outputType && seeds && product, DAS_ERR_ARG, "null argument");
     check_patches(s, patches, np);
     const int fid = bc_field_id(field);
-    const std::string ot = outputType;
+    std::string ot = outputType;
+    std::vector<double> rnSeeds;  // a residualNorm function: the residual product with the seeds dF/dR
+    residual_norm_redirect(s, outputName, ot, seeds, rnSeeds);
     const bool isFC = is_coupling(ot);
     DAS_CHECK(ot == "residual" || ot == "function" || isFC, DAS_ERR_ARG, "outputType not supported on this path: " + ot);
     if (isFC) (void)coupling_size(s, ot, outputName);  // an unknown name fails before the patch table is touched
@@ -4874,7 +5053,7 @@ int das_calc_dbc_product(das_solver_t* s, const int* patches, int np, const char
         // gradD - and its zero here is the convention the function layer was specified with, NOT the derivative
         product[0] = 0.0;
         return DAS_OK;
-    } else if (!isFC && DAS_FN_BASE(get_function(s, outputName).kind) == DAS_FN_LOCATION) {  // geometry only
+    } else if (!isFC && (find_mesh_function(s, outputName) || DAS_FN_BASE(get_function(s, outputName).kind) == DAS_FN_LOCATION)) {  // geometry only
         product[0] = 0.0;
         return DAS_OK;
     } else {
@@ -4912,7 +5091,9 @@ int das_calc_dthermal_coupling_product(das_solver_t* s, const char* inputName, c
     DAS_TRY
     need_init(s);
     DAS_CHECK(outputType && seeds && product, DAS_ERR_ARG, "null argument");
-    const std::string ot = outputType;
+    std::string ot = outputType;
+    std::vector<double> rnSeeds;  // a residualNorm function: the residual product with the seeds dF/dR
+    residual_norm_redirect(s, outputName, ot, seeds, rnSeeds);
     const bool isFC = ot == "thermalCouplingOutput";
     DAS_CHECK(ot == "residual" || ot == "function" || isFC, DAS_ERR_ARG, "outputType not supported on this path: " + ot);
     das_solver::ThermalCoupling& tc = get_thermal_coupling(s, inputName, true, true);
@@ -4922,7 +5103,7 @@ int das_calc_dthermal_coupling_product(das_solver_t* s, const char* inputName, c
     if (isFC) (void)coupling_size(s, ot, outputName);
     std::fill(product, product + n, 0.0);
     if (ot == "function") {  // cell-set functions and location read no boundary value of T
-        if (find_cell_function(s, outputName)) return DAS_OK;
+        if (find_cell_function(s, outputName) || find_mesh_function(s, outputName)) return DAS_OK;
         if (DAS_FN_BASE(get_function(s, outputName).kind) == DAS_FN_LOCATION) return DAS_OK;
     }
     hipStream_t st = s->stream;
@@ -5043,13 +5224,15 @@ int das_calc_dfield_product(das_solver_t* s, const char* fieldName, const char* 
     DAS_CHECK(outputType && seeds && product, DAS_ERR_ARG, "null argument");
     check_field(fieldName);
     DAS_CHECK(s->regModels.empty(), DAS_ERR_ARG, "field input betaFINuTilda: a regressionModel is active and overwrites the field in every residual evaluation");
-    const std::string ot = outputType;
+    std::string ot = outputType;
+    std::vector<double> rnSeeds;  // a residualNorm function: the residual product with the seeds dF/dR
+    residual_norm_redirect(s, outputName, ot, seeds, rnSeeds);
     DAS_CHECK(ot == "residual" || ot == "function" || is_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
     const long long N = s->mesh.nC, n = s->n;
     if (s->cp.solver == DAS_SOLVER_SCALARTRANSPORTFOAM || s->cp.solver == DAS_SOLVER_HEATTRANSFERFOAM || s->cp.solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM) {
         // no Spalart-Allmaras production term: nothing of these solvers reads the field - exact zeros (an unknown output still fails by name)
         if (is_coupling(ot)) (void)coupling_size(s, ot, outputName);
-        else if (ot == "function" && !find_cell_function(s, outputName)) (void)get_function(s, outputName);
+        else if (ot == "function" && !find_cell_function(s, outputName) && !find_mesh_function(s, outputName)) (void)get_function(s, outputName);
         std::fill(product, product + N, 0.0);
         return DAS_OK;
     }
@@ -5060,7 +5243,7 @@ int das_calc_dfield_product(das_solver_t* s, const char* fieldName, const char* 
     }
     if (ot == "function") {
         das_solver::CellFn* cf = find_cell_function(s, outputName);
-        if (!cf) (void)get_function(s, outputName);  // the patch-integral functions do not see the production term
+        if (!cf && !find_mesh_function(s, outputName)) (void)get_function(s, outputName);  // the patch-integral functions do not see the production term
         if (cf && cf->field) cell_function_gradient(s, *cf, seeds[0], false, product, N);  // dF/dbeta_c, unscaled like the field itself
         else std::fill(product, product + N, 0.0);
         return DAS_OK;
@@ -5422,11 +5605,13 @@ int das_calc_dfvsourcepar_product(das_solver_t* s, const char* name, const int* 
     for (int k = 0; k < n; k++)
         DAS_CHECK(indices[k] >= 0 && indices[k] < 9, DAS_ERR_ARG,
                   std::string("fvSourcePar: index ") + std::to_string(indices[k]) + " of fvSource " + name + " is out of range (a heat source has 9 parameters)");
-    const std::string ot = outputType;
+    std::string ot = outputType;
+    std::vector<double> rnSeeds;  // a residualNorm function: the residual product with the seeds dF/dR
+    residual_norm_redirect(s, outputName, ot, seeds, rnSeeds);
     DAS_CHECK(ot == "residual" || ot == "function" || is_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
     if (ot != "residual") {
         if (is_coupling(ot)) (void)coupling_size(s, ot, outputName);
-        else if (!find_cell_function(s, outputName)) (void)get_function(s, outputName);
+        else if (!find_cell_function(s, outputName) && !find_mesh_function(s, outputName)) (void)get_function(s, outputName);
         std::fill(product, product + n, 0.0);
         return DAS_OK;
     }
@@ -5762,11 +5947,13 @@ int das_calc_dactuatordiskpar_product(das_solver_t* s, const char* name, const i
     for (int k = 0; k < n; k++)
         DAS_CHECK(indices[k] >= 0 && indices[k] < 13, DAS_ERR_ARG,
                   std::string("fvSourcePar: index ") + std::to_string(indices[k]) + " of fvSource " + name + " is out of range (an actuator disk has 13 parameters)");
-    const std::string ot = outputType;
+    std::string ot = outputType;
+    std::vector<double> rnSeeds;  // a residualNorm function: the residual product with the seeds dF/dR
+    residual_norm_redirect(s, outputName, ot, seeds, rnSeeds);
     DAS_CHECK(ot == "residual" || ot == "function" || is_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
     if (ot != "residual") {
         if (is_coupling(ot)) (void)coupling_size(s, ot, outputName);
-        else if (!find_cell_function(s, outputName)) (void)get_function(s, outputName);
+        else if (!find_cell_function(s, outputName) && !find_mesh_function(s, outputName)) (void)get_function(s, outputName);
         std::fill(product, product + n, 0.0);
         return DAS_OK;
     }
@@ -5816,7 +6003,7 @@ static void finish_volcoord(das_solver* s, const double* d_out, double* product,
 
 // exact mode of the product (amd.volCoordMode "dual", the default): Dual<1> points -> Dual<1> metrics -> Dual<1> residual
 static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool areaAvg, const double* cN, const double* cA, const double* seeds,
-                                  double* product, double* info4, das_solver::CellFn* cfn = nullptr) {
+                                  double* product, double* info4, das_solver::CellFn* cfn = nullptr, das_solver::MeshFn* mq = nullptr) {
     typedef Dual<1> D;
     const Mesh& m = s->mesh;
     das_solver::VolCoord& v = s->vc;
@@ -5826,8 +6013,11 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
     const int B = 256;
     const long long n = s->n;
     const size_t n3 = 3 * (size_t)m.nP;
-    const bool isFn = fn != nullptr, isCell = cfn != nullptr;
+    const bool isFn = fn != nullptr, isCell = cfn != nullptr, isMq = mq != nullptr;
     const bool rho = DAS_IS_COMPRESSIBLE(s->cp.solver);
+    // meshQualityKS: the linearised functional sum_f w_f a_f, w = seed x the softmax weights of the base mesh; k_mq_metric<Dual<1>> stores
+    // w_f a_f' per face (d_fvd), k_mq_owner_gather adds the faces a cell owns into d_tc
+    if (isMq) mesh_quality_weights(s, *mq, seeds[0]);
     // cell-set functions (variableVolSum): F0 = N / T with N = coef T sum_S w g, T = totalVol, so dF/dV_c = dF/dF0 ( [c in S, multiplyVol]
     // scale g_c / T - [divByTotalVol] F0 / T ): cellA multiplies V_c' on every cell, cellB g_c V_c' on the cells of the set
     double cellA = 0.0, cellB = 0.0;
@@ -5859,7 +6049,9 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
     ResParams prm0 = make_params(s->cp, s->opt, 0);
     RowLayout L{};
     int nf = 0;
-    if (isCell) {
+    if (isMq) {
+        d_fvd.alloc((size_t)m.nF);
+    } else if (isCell) {
     } else if (!isFn) {
         L = residual_row_layout(s);
         d_Rd.alloc((size_t)n);
@@ -5876,7 +6068,7 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
     // the local tangent through C_c and V_c of the cell itself) and come back as rank-one terms - heat_source_rank1_terms
     std::vector<HsRank1> hsTerms;
     DevBuf<D> d_srcD, d_vtD;
-    if (!isCell && !isFn && !s->heatSources.empty()) {
+    if (!isMq && !isCell && !isFn && !s->heatSources.empty()) {
         heat_source_rank1_terms(s, d_seeds.p, prm0.normT ? 0 : 1, hsTerms);
         std::vector<D> vt;
         for (auto& e : s->heatSources) vt.push_back(D(e.second.volumeTotal));
@@ -5889,7 +6081,7 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
     std::vector<AdView<double>> adFrozen;
     std::vector<AdRank1> adTerms;
     DevBuf<D> d_src3D, d_adWork;
-    if (!isCell && !isFn && !s->actuatorDisks.empty()) {
+    if (!isMq && !isCell && !isFn && !s->actuatorDisks.empty()) {
         actuator_disk_volcoord_setup(s, seeds, adFrozen, adTerms);
         d_src3D.alloc(3 * (size_t)m.nC);
         d_adWork.alloc(5 * adFrozen.size());
@@ -5906,7 +6098,11 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
             hipLaunchKernelGGL(k_geom_face<D>, dim3(nblk(t.nF, B)), dim3(B), 0, st, t, (const D*)d_XD.p, d_fgD.p);
             hipLaunchKernelGGL(k_geom_cell<D>, dim3(nblk(t.nC, B)), dim3(B), 0, st, t, (const FaceGeomT<D>*)d_fgD.p, d_cgD.p, v.d_bad.p);
             hipLaunchKernelGGL(k_geom_weights<D>, dim3(nblk(t.nF, B)), dim3(B), 0, st, t, (const CellGeomT<D>*)d_cgD.p, d_fgD.p);
-            if (isVm) {
+            if (isMq) {
+                hipLaunchKernelGGL(k_mq_metric<D>, dim3(nblk(t.nF, B)), dim3(B), 0, st, t, (const D*)d_XD.p, (const FaceGeomT<D>*)d_fgD.p, (const CellGeomT<D>*)d_cgD.p,
+                                   mq->metric, (const double*)mq->d_w.p, d_fvd.p);
+                hipLaunchKernelGGL(k_mq_owner_gather, dim3(nblk(m.nC, B)), dim3(B), 0, st, m.nC, t.cf_ptr, t.cf_face, (const double*)d_fvd.p, d_tc.p);
+            } else if (isVm) {
                 const ResParams prm = s->wk1.bind(s->cp.solver, s->dm.nC, s->dm.nF, prm0);
                 launch_solid_grad<D, D>(dmD, prm, (const D*)d_Wd.p, s->wk1, st);
                 hipLaunchKernelGGL(k_vm_tangent, dim3(nblk(m.nC, B)), dim3(B), 0, st, m.nC, prm, (const D*)s->wk1.gU.p, cfn->scale, (const double*)cfn->d_wc.p, d_tc.p);
@@ -5956,7 +6152,9 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
     DAS_TRY
     need_init(s);
     DAS_CHECK(outputType && seeds && product, DAS_ERR_ARG, "null argument");
-    const std::string ot = outputType;
+    std::string ot = outputType;
+    std::vector<double> rnSeeds;  // a residualNorm function: the residual product with the seeds dF/dR
+    residual_norm_redirect(s, outputName, ot, seeds, rnSeeds);
     DAS_CHECK(ot == "residual" || ot == "function" || is_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
     DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "the volCoord product runs on an undecomposed mesh (sharded solvers: use calcVolCoordDirectionalProduct)");
     if (is_coupling(ot)) {
@@ -5974,6 +6172,13 @@ int das_calc_dvolcoord_product(das_solver_t* s, const char* outputName, const ch
     const Mesh& m = s->mesh;
     const bool isFn = ot == "function";
     if (isFn) {
+        if (das_solver::MeshFn* mf = find_mesh_function(s, outputName)) {  // meshQualityKS: the softmax-weighted face tangents on the dual metrics
+            DAS_CHECK(s->opt.gets_or("amd.volCoordMode", "dual") == "dual", DAS_ERR_ARG,
+                      "the volCoord product of meshQualityKS function " + mf->name + " needs amd.volCoordMode dual (fd is not implemented for it)");
+            ensure_point_influence(s);
+            volcoord_product_dual(s, nullptr, false, nullptr, nullptr, seeds, product, info4, nullptr, mf);
+            return DAS_OK;
+        }
         if (das_solver::CellFn* cf = find_cell_function(s, outputName)) {
             DAS_CHECK(!cf->variance, DAS_ERR_ARG, std::string("volCoord input is not supported for the variance function ") + outputName);
             ensure_point_influence(s);
@@ -6175,7 +6380,10 @@ int das_calc_jac_t_vec_product(das_solver_t* s, const char* inputName, const cha
     need_init(s);
     DAS_CHECK(inputType && outputType && inputs && seeds && product, DAS_ERR_ARG, "null argument");
     DAS_CHECK(std::string(inputType) == "stateVar", DAS_ERR_ARG, "calcJacTVecProduct: only stateVar inputs are implemented on the GPU path");
-    if (std::string(outputType) == "function") {
+    // a residualNorm function: dR/dW^T g with the seeds g = seed dF/dR formed on the device at the assigned states (k_rn_seeds)
+    das_solver::MeshFn* rn = std::string(outputType) == "function" ? find_mesh_function(s, outputName) : nullptr;
+    if (rn && !rn->residualNorm) rn = nullptr;
+    if (!rn && std::string(outputType) == "function") {
         // dFdW^T * seed, state-scaled (reference DASolver.C:1690-1839 with DAOutputFunction, normalizeJacTVecProduct :1443-1553)
         s->h_W.assign(inputs, inputs + s->n);
         s->d_W.upload(s->h_W);
@@ -6191,7 +6399,7 @@ int das_calc_jac_t_vec_product(das_solver_t* s, const char* inputName, const cha
         face_function_gradient(s, coupling_functional(s, ot, outputName, seeds), 1.0, product);
         return DAS_OK;
     }
-    DAS_CHECK(std::string(outputType) == "residual", DAS_ERR_ARG,
+    DAS_CHECK(rn || std::string(outputType) == "residual", DAS_ERR_ARG,
               "calcJacTVecProduct: only (stateVar -> residual | function | forceCouplingOutput | thermalCouplingOutput) is implemented on the GPU path");
     // DAInputStateVar::run assigns the inputs to the states (reference DASolver.C:1690-1839)
     // the operator initializedRdWTMatrixFree built is reused when it was assembled at these very states (the reference
@@ -6202,7 +6410,11 @@ int das_calc_jac_t_vec_product(das_solver_t* s, const char* inputName, const cha
     s->d_W.upload(s->h_W);
     std::unique_ptr<das_mat> A;
     if (!reuse) A.reset(assemble(s, 0, 1));
-    DAS_HIP(hipMemcpyAsync(s->d_tmp1.p, seeds, s->n * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    if (rn) {
+        residual_norm_seeds(s, *rn, seeds[0], s->d_tmp1.p);
+    } else {
+        DAS_HIP(hipMemcpyAsync(s->d_tmp1.p, seeds, s->n * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    }
     spmv(s, reuse ? s->op->m : A->m, s->d_tmp1.p, s->d_tmp2.p);
     DAS_HIP(hipMemcpyAsync(product, s->d_tmp2.p, s->n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     DAS_HIP(hipStreamSynchronize(s->stream));
@@ -6937,11 +7149,13 @@ int das_calc_dregressionpar_product(das_solver_t* s, const char* name, const cha
     DAS_CHECK(outputType && seeds && product, DAS_ERR_ARG, "null argument");
     int at = -1;
     const das_solver::RegModel& m = get_regression_model(s, name, &at);
-    const std::string ot = outputType;
+    std::string ot = outputType;
+    std::vector<double> rnSeeds;  // a residualNorm function: the residual product with the seeds dF/dR
+    residual_norm_redirect(s, outputName, ot, seeds, rnSeeds);
     DAS_CHECK(ot == "residual" || ot == "function" || is_coupling(ot), DAS_ERR_ARG, "outputType not supported on this path: " + ot);
     if (ot != "residual") {  // no function and no coupling output reads the production term: exact zeros (an unknown output still fails by name)
         if (is_coupling(ot)) (void)coupling_size(s, ot, outputName);
-        else if (!find_cell_function(s, outputName)) (void)get_function(s, outputName);
+        else if (!find_cell_function(s, outputName) && !find_mesh_function(s, outputName)) (void)get_function(s, outputName);
         std::fill(product, product + m.v.nPar, 0.0);
         return DAS_OK;
     }

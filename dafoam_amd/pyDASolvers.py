@@ -822,7 +822,8 @@ class pyDASolvers:
     def _define_functions(self, functions):
         """"function" option dict (reference pyDAFoam.py DAOPTION.function): the patch-integral types force (directionMode
         fixedDirection), moment, massFlowRate, totalPressure, totalTemperatureRatio, totalPressureRatio, wallHeatFlux and
-        location are on this path, as are the field-valued variableVolSum, patchMean and variance."""
+        location are on this path, as are the field-valued variableVolSum, patchMean and variance and the whole-mesh meshQualityKS and
+        residualNorm."""
         names = [p.name for p in self._case.mesh.patches]
         L = lib()
         for fname, fd in (functions or {}).items():
@@ -845,6 +846,9 @@ class pyDASolvers:
                                      " is not built for DASolidDisplacementFoam (vonMisesStressKS and variableVolSum of D and of solid:rho are)")
             if ftype in ("variableVolSum", "patchMean", "variance"):
                 self._define_field_function(fname, fd)
+                continue
+            if ftype in ("meshQualityKS", "residualNorm"):
+                self._define_mesh_function(fname, fd)
                 continue
             if ftype not in ("force", "moment", "massFlowRate", "totalPressure", "totalTemperatureRatio", "totalPressureRatio", "wallHeatFlux",
                              "location"):
@@ -912,6 +916,23 @@ class pyDASolvers:
         center = np.ascontiguousarray(fd.get("center", [0.0, 0.0, 0.0]), dtype=np.float64)
         check(lib().das_define_location_function(self._h, fname.encode(), str(fd["mode"]).encode(), ids.ctypes.data_as(_capi.c_int_p), ids.size,
                                                  dptr(axis), dptr(center), float(fd.get("coeffKS", 1.0)), flags, ref))
+
+    def _define_mesh_function(self, fname, fd):
+        """meshQualityKS (DAFunctionMeshQualityKS.C: coeffKS and metric are required; includeProcPatches means nothing without processor
+        patches) and residualNorm (DAFunctionResidualNorm.C: resWeight is required, resMode L2Norm by default).  Neither applies scale."""
+        flags, ref = (8, float(np.atleast_1d(fd["ref"])[0])) if int(fd.get("calcRefVar", 0)) else (0, 0.0)
+        if fd["type"] == "meshQualityKS":
+            for key in ("coeffKS", "metric"):
+                if key not in fd:
+                    raise _capi.DASError(f"function {fname}: meshQualityKS needs {key}")
+            check(lib().das_define_mesh_quality_function(self._h, fname.encode(), str(fd["metric"]).encode(), float(fd["coeffKS"]), flags, ref))
+            return
+        if not isinstance(fd.get("resWeight"), dict):
+            raise _capi.DASError(f"function {fname}: residualNorm needs the dictionary resWeight")
+        names = [str(k).encode() for k in fd["resWeight"]]
+        weights = np.array([float(w) for w in fd["resWeight"].values()], dtype=np.float64)
+        check(lib().das_define_residual_norm_function(self._h, fname.encode(), (C.c_char_p * len(names))(*names), dptr(weights), len(names),
+                                                      str(fd.get("resMode", "L2Norm")).encode(), flags, ref))
 
     def _function_cells(self, fname, fd):
         """cellSources of a cell-set function (DAFunction.C): "allCells", or "boxToCell" = the cells whose centre lies in the

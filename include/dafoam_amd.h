@@ -364,6 +364,19 @@ int das_define_face_function_ex(das_solver_t* s, const char* name, const char* t
  * softmax weights through the dual-point metrics. */
 int das_define_location_function(das_solver_t* s, const char* name, const char* mode, const int* patch_ids, int npatch, const double* axis,
                                  const double* center, double coeffKS, int flags, double ref);
+/* das_define_mesh_quality_function <- {type: meshQualityKS, coeffKS, metric} (DAFunctionMeshQualityKS.C): log(sum exp(coeffKS a_f)) / coeffKS
+ * over ALL faces of the mesh, internal and boundary; metric "faceOrthogonality" | "nonOrthoAngle" | "faceSkewness" (restated from OpenFOAM's
+ * polyMeshTools, csrc/das_meshquality.hpp).  Log-space sum, deterministic, no 1e200 abort; no scale is applied.  flags & 8: calcRefVar.
+ * Undecomposed DASimpleFoam, DARhoSimpleFoam, DATurboFoam and DAScalarTransportFoam; a mesh with cyclic patches is refused.  State,
+ * boundary-value and field derivatives are exactly zero; das_calc_dvolcoord_product (amd.volCoordMode dual) carries the softmax weights
+ * through the dual points and metrics. */
+int das_define_mesh_quality_function(das_solver_t* s, const char* name, const char* metric, double coeffKS, int flags, double ref);
+/* das_define_residual_norm_function <- {type: residualNorm, resWeight, resMode} (DAFunctionResidualNorm.C) on the residual das_calc_residuals
+ * returns (isPC 0): resMode "L2Norm" sqrt(sum w_i^2 R_i^2) | "L1Norm" sum |w_i R_i|, where the internal faces of phiRes add w^2 R^2 in either
+ * mode as in the reference.  resNames[k] = "<state>Res" carries weights[k]; every residual of the solver must be named, other names are
+ * ignored.  flags & 8: calcRefVar.  No scale.  Every product entry treats such a function as the residual output seeded with dF/dR. */
+int das_define_residual_norm_function(das_solver_t* s, const char* name, const char* const* resNames, const double* weights, int nw,
+                                      const char* resMode, int flags, double ref);
 /* das_define_patch_field_function <- the boundary-value entries of the "function" option dict (flow solvers):
  *   type "patchMean"  area average of component comps[0] of the boundary value of var, * scale   DAFunctionPatchMean.C:36-110
  *        "variance"   mode surface: sum w_f scale (b_f,i - d_f,i)^2 / W over the faces and the components comps[ncomp],
