@@ -16,7 +16,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DAFOAM_AMD_LIB") or os.path.join(_HERE, "lib", "libdafoam_amd.so")  # (override: tuning builds)
 
 SOLVER_IDS = {"DASimpleFoam": 0, "DAScalarTransportFoam": 1, "DARhoSimpleFoam": 2, "DATurboFoam": 3, "DAHeatTransferFoam": 4,
-              "DASolidDisplacementFoam": 5}
+              "DASolidDisplacementFoam": 5, "DAPimpleFoam": 6}
+DDT_SCHEMES = {"Euler": 0, "backward": 1}  # system/fvSchemes ddtSchemes.default of DAPimpleFoam
 PATCH_TYPES = {"patch": 0, "wall": 1, "symmetry": 2, "cyclic": 3}
 
 c_double_p = C.POINTER(C.c_double)
@@ -88,6 +89,7 @@ class das_case_t(C.Structure):
         ("bc_D_val", c_double_p),
         ("bc_D_traction", c_double_p),
         ("bc_D_pressure", c_double_p),
+        ("ddt_scheme", C.c_int),
     ]
 
 
@@ -327,7 +329,15 @@ class CaseStruct:
             k["bc_D_code"], k["bc_D_val"], k["bc_D_traction"], k["bc_D_pressure"] = code, val, trac, pres
             s.bc_D_code = _ip(code)
             s.bc_D_val, s.bc_D_traction, s.bc_D_pressure = _dp(val), _dp(trac), _dp(pres)
-        s.simple_has_T = 1 if (case.solver_name == "DASimpleFoam" and getattr(case, "has_T", False)) else 0
+        s.simple_has_T = 1 if (case.solver_name in ("DASimpleFoam", "DAPimpleFoam") and getattr(case, "has_T", False)) else 0
+        if case.solver_name == "DAPimpleFoam":
+            scheme = getattr(case, "ddt_scheme", "Euler")
+            if scheme not in DDT_SCHEMES:  # DASolver::getDdtSchemeOrder (DASolver.H:254-279)
+                raise DASError(f"ddtScheme {scheme} not supported! Options: steadyState, Euler, or backward"
+                               + (" (DAPimpleFoam is unsteady: Euler or backward)" if scheme == "steadyState" else ""))
+            if getattr(case, "simple_consistent", False):
+                raise DASError("DAPimpleFoam: simple_consistent is not built")
+            s.ddt_scheme = DDT_SCHEMES[scheme]
 
     def byref(self):
         return C.byref(self.struct)
@@ -384,6 +394,8 @@ _SIGS = {
     "das_op_export": (C.c_int, [_VP, c_ll_p, c_int_p, c_double_p]),
     "das_calc_drdwold_t_psi": (C.c_int, [_VP, C.c_int, c_double_p, c_double_p]),
     "das_set_old_time_fields": (C.c_int, [_VP, c_double_p, c_double_p]),
+    "das_set_old_time_states": (C.c_int, [_VP, c_double_p, c_double_p, C.c_int]),
+    "das_set_time_index": (C.c_int, [_VP, C.c_int]),
     "das_calc_jac_vec_product": (C.c_int, [_VP, c_double_p, c_double_p]),
     "das_set_patch_value": (C.c_int, [_VP, c_int_p, C.c_int, C.c_char_p, c_double_p]),
     "das_get_patch_value": (C.c_int, [_VP, C.c_int, C.c_char_p, c_double_p]),

@@ -32,8 +32,34 @@ struct CaseParams {
     double solidRho = 1.0, solidE = 0.0, solidNu = 0.0, solidMu = 0.0, solidLambda = 0.0;
     int planeStress = 0, nTrac = 0;
     const int* tracCells_ptr = nullptr;
+    // DAPimpleFoam: DASimpleFoam's layout, stencils and kernels with the fvm::ddt terms of body_cell and relax(1.0).  `solver` reads
+    // DAS_SOLVER_SIMPLEFOAM with pimple = 1, so every path written for that layout serves it; what it cannot serve is refused by name.
+    // ddtScheme: 0 Euler, 1 backward; timeIndex: the step the residual is evaluated at (backward below 2 is Euler); W0 / W00: what the
+    // kernels read (device memory in the library, the host vectors in the test harness)
+    int pimple = 0, ddtScheme = 0, timeIndex = 1;
+    const double* W0_ptr = nullptr;
+    const double* W00_ptr = nullptr;
+    // the ddt coefficients (c, c0, c00) of the time index as it stands: backwardDdtScheme with deltaT0 = deltaT; below index 2 its deltaT0 is
+    // GREAT and the three round to exactly 1, 1, 0
+    void ddt_coeffs(double& c, double& c0, double& c00) const {
+        const bool second = ddtScheme == 1 && timeIndex >= 2;
+        c = second ? 1.5 : 1.0;
+        c0 = second ? 2.0 : 1.0;
+        c00 = second ? 0.5 : 0.0;
+    }
     void from_case(const das_case_t* c) {
         solver = c->solver;
+        if (solver == DAS_SOLVER_PIMPLEFOAM) {
+            solver = DAS_SOLVER_SIMPLEFOAM;
+            pimple = 1;
+            DAS_CHECK(c->ddt_scheme == 0 || c->ddt_scheme == 1, DAS_ERR_ARG, "DAPimpleFoam: ddt_scheme is 0 (Euler) or 1 (backward), not " + std::to_string(c->ddt_scheme));
+            DAS_CHECK(c->deltaT > 0.0, DAS_ERR_ARG, "DAPimpleFoam needs a positive deltaT, not " + std::to_string(c->deltaT));
+            DAS_CHECK(!c->simple_has_T, DAS_ERR_ARG, "DAPimpleFoam: the T field is not built");
+            DAS_CHECK(!c->mrf_active, DAS_ERR_ARG, "DAPimpleFoam: MRF is not built");
+            for (int p = 0; p < c->n_patches; p++)
+                DAS_CHECK(c->patch_type[p] != DAS_PATCH_CYCLIC, DAS_ERR_ARG, "DAPimpleFoam: cyclic patches are not built");
+            ddtScheme = c->ddt_scheme;
+        }
         if (solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM) {
             DAS_CHECK(c->solid_rho > 0.0, DAS_ERR_ARG, "DASolidDisplacementFoam needs a positive rho, not " + std::to_string(c->solid_rho));
             DAS_CHECK(c->solid_E > 0.0, DAS_ERR_ARG, "DASolidDisplacementFoam needs a positive E, not " + std::to_string(c->solid_E));
@@ -89,7 +115,7 @@ struct CaseParams {
 inline ResParams make_params(const CaseParams& cp, const Options& opt, int isPC) {
     ResParams p;
     p.nu = cp.nu;
-    p.alphaU = cp.relax_U;
+    p.alphaU = cp.pimple ? 1.0 : cp.relax_U;  // DAPimpleFoam: UEqn.relax(1.0), whatever fvSolution says
     p.alphaN = cp.relax_nuTilda;
     p.DT = cp.DT;
     p.deltaT = cp.deltaT;
@@ -109,7 +135,7 @@ inline ResParams make_params(const CaseParams& cp, const Options& opt, int isPC)
     p.hasT = cp.hasT;
     p.gradFaceParallel = (int)opt.geti_or("amd.gradFaceParallel", 1);
     // the face / cell split of the cell pass (body_fcoef + body_bcoef + body_cell2) serves DASimpleFoam + SA without T field, MRF and cyclic pairs
-    p.cellFaceSplit = (int)opt.geti_or("amd.cellFaceSplit", 0) && cp.solver == DAS_SOLVER_SIMPLEFOAM && !cp.hasT && !cp.mrf && !cp.hasCyclic && !cp.reg;
+    p.cellFaceSplit = (int)opt.geti_or("amd.cellFaceSplit", 0) && cp.solver == DAS_SOLVER_SIMPLEFOAM && !cp.hasT && !cp.mrf && !cp.hasCyclic && !cp.reg && !cp.pimple;
     p.Cp = cp.Cp;
     p.Rgas = 8314.47 / cp.molWeight;  // Foam::constant::thermodynamic::RR / molWeight
     p.mu = cp.mu;
@@ -139,6 +165,10 @@ inline ResParams make_params(const CaseParams& cp, const Options& opt, int isPC)
     p.nTrac = cp.nTrac;
     p.tracCells = cp.tracCells_ptr;
     for (int k = 0; k < 3; k++) { p.om[k] = cp.om[k]; p.org[k] = cp.org[k]; }
+    p.ddt = cp.pimple;
+    cp.ddt_coeffs(p.ddtC, p.ddtC0, p.ddtC00);
+    p.W0 = cp.W0_ptr;
+    p.W00 = cp.W00_ptr;
     return p;
 }
 

@@ -124,11 +124,18 @@ __global__ __launch_bounds__(CPB * 8) void k_grad_fp(DevMesh m, ResParams prm, c
     }
 }
 // SRC: with the momentum source of the actuator disks (m.src3 set); the kernels without it are the ones of before
-template <class T, bool RHO, class G = double, bool SRC = false>
+// DDT: with the fvm::ddt terms of DAPimpleFoam (prm.ddt, prm.W0 / prm.W00 set); the same holds
+template <class T, bool RHO, class G = double, bool SRC = false, bool DDT = false>
 __global__ __launch_bounds__(256) void k_cell(DevMeshT<G> m, ResParams prm, const T* __restrict__ W, const T* nut, const T* gU, const T* gP,
                                               const T* gN, const T* gH, T* R, T* rAU, T* HbyA) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < m.nC) body_cell<T, RHO, G, SRC>(c, m, prm, W, nut, gU, gP, gN, gH, R, rAU, HbyA, (const T*)prm.wTU);
+    if (c < m.nC) body_cell<T, RHO, G, SRC, DDT>(c, m, prm, W, nut, gU, gP, gN, gH, R, rAU, HbyA, (const T*)prm.wTU);
+}
+// DAPimpleFoam: s o [dR/dW0]^T psi or s o [dR/dW00]^T psi (body_drdwold); one thread per cell, the p and phi entries are the caller's zeros
+__global__ __launch_bounds__(256) void k_drdwold(DevMesh m, ResParams prm, double coef, const double* __restrict__ rAU, const double* __restrict__ psi,
+                                                 const double* __restrict__ scale, double* __restrict__ out) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < m.nC) body_drdwold(c, m, prm, coef, rAU, psi, scale, out);
 }
 // Round 6: the cell pass of DASimpleFoam split the finite-volume way (das_kernels.hpp body_fcoef / body_bcoef / body_cell2): every
 // internal face evaluated ONCE by its own thread (the monolithic k_cell evaluates it from both sides inside a serial six-trip loop that
@@ -382,7 +389,11 @@ static void eval_residual(const DevMeshT<G>& dm, const CaseParams& cp, const Res
                                        (const T*)wk.gN.p, (const T*)wk.fc.p, (const T*)wk.brec.p, R, wk.rAU.p, wk.HbyA.p);
             }
         }
-        if (!split && dm.src3)
+        if (prm.ddt) {  // DAPimpleFoam (no split path, no disks)
+            DAS_CHECK(prm.W0 && (prm.ddtC00 == 0.0 || prm.W00), DAS_ERR_STATE, "DAPimpleFoam: the old-time states have not been set (setOldTimeStates)");
+            hipLaunchKernelGGL((k_cell<T, false, G, false, true>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, W, wk.nut.p, wk.gU.p, wk.gP.p, wk.gN.p,
+                               (const T*)wk.gH.p, R, wk.rAU.p, wk.HbyA.p);
+        } else if (!split && dm.src3)
             hipLaunchKernelGGL((k_cell<T, false, G, true>), dim3(nblk(dm.nC, B)), dim3(B), 0, st, dm, prm, W, wk.nut.p, wk.gU.p, wk.gP.p, wk.gN.p,
                                (const T*)wk.gH.p, R, wk.rAU.p, wk.HbyA.p);
         else if (!split)
@@ -850,6 +861,12 @@ struct das_solver {
     DevBuf<double> d_mixed;  // Mesh::mixed (the per-face records of the mixed T patches), when there are any
     DevBuf<int> d_tracCells;  // Mesh::trac_cells (DASolidDisplacementFoam), when there are any
     DevBuf<double> d_phiF, d_Told;
+    DevBuf<double> d_W0, d_W00;  // DAPimpleFoam: the old-time state vectors (das_set_old_time_states)
+    std::vector<double> h_W0, h_W00;
+    // rAU of the last old-time product and what it was computed at: the two levels of one adjoint step share one residual pass
+    DevBuf<double> d_rAUold;
+    std::vector<double> rAUold_states;
+    long long rAUold_epoch = -1, rAUold_geom = -1;
     DevMesh dm;
     DevBuf<double> d_W, d_R, d_R0, d_Wp, d_scale, d_tmp1, d_tmp2;
     DevBuf<int> d_colors;
@@ -3322,7 +3339,7 @@ das_solver_t* das_create(const das_case_t* c) {
         s->t0_cpu = std::clock();
         s->cp.from_case(c);
         s->mesh.build(c);
-        s->opt.s["solverName"] = c->solver == DAS_SOLVER_SIMPLEFOAM ? "DASimpleFoam" : (c->solver == DAS_SOLVER_RHOSIMPLEFOAM ? "DARhoSimpleFoam" : (c->solver == DAS_SOLVER_TURBOFOAM ? "DATurboFoam" : (c->solver == DAS_SOLVER_HEATTRANSFERFOAM ? "DAHeatTransferFoam" : (c->solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM ? "DASolidDisplacementFoam" : "DAScalarTransportFoam"))));
+        s->opt.s["solverName"] = c->solver == DAS_SOLVER_PIMPLEFOAM ? "DAPimpleFoam" : c->solver == DAS_SOLVER_SIMPLEFOAM ? "DASimpleFoam" : (c->solver == DAS_SOLVER_RHOSIMPLEFOAM ? "DARhoSimpleFoam" : (c->solver == DAS_SOLVER_TURBOFOAM ? "DATurboFoam" : (c->solver == DAS_SOLVER_HEATTRANSFERFOAM ? "DAHeatTransferFoam" : (c->solver == DAS_SOLVER_SOLIDDISPLACEMENTFOAM ? "DASolidDisplacementFoam" : "DAScalarTransportFoam"))));
         s->st_full = make_stencil(s->cp.solver, s->mesh.nC, s->mesh.nF, s->opt, false, s->cp.hasT != 0, s->reg_needs_p());
         s->n = s->st_full.n;
         s->h_W.assign(s->n, 0.0);
@@ -3410,6 +3427,8 @@ int das_init_solver(das_solver_t* s, int device) {
     s->d_bc.upload(m.bc);
     if (!s->cp.phi_frozen.empty()) s->d_phiF.upload(s->cp.phi_frozen);
     if (!s->cp.T_old.empty()) s->d_Told.upload(s->cp.T_old);
+    if (!s->h_W0.empty()) { s->d_W0.upload(s->h_W0); s->cp.W0_ptr = s->d_W0.p; }
+    if (!s->h_W00.empty()) { s->d_W00.upload(s->h_W00); s->cp.W00_ptr = s->d_W00.p; }
     s->dm = DevMesh{m.nC, m.nF, m.nIF, s->d_fg.p, s->d_cg.p, s->d_cf_ptr.p, s->d_cf_face.p, s->d_cf_other.p, s->d_owner.p, s->d_neigh.p,
                     s->d_bpatch.p, s->d_bc.p, s->d_cyc.p};
     if (!m.mixed.empty()) { s->d_mixed.upload(m.mixed); s->dm.mixed = s->d_mixed.p; }
@@ -3713,6 +3732,7 @@ static void run_simple_sweeps(das_solver* s, int nSweeps, double alphaP, double 
 int das_simple_iteration(das_solver_t* s, int nSweeps, double alphaP, double linTol, int maxLinIters, double* info3) {
     DAS_TRY
     DAS_CHECK(s && nSweeps >= 0 && alphaP > 0.0 && linTol > 0.0 && maxLinIters > 0, DAS_ERR_ARG, "das_simple_iteration: bad argument");
+    DAS_CHECK(!s->cp.pimple, DAS_ERR_ARG, "DAPimpleFoam: simpleIteration is not built (the SIMPLE sweep is steady); use das_solve_primal per time step");
     DAS_CHECK(s->actuatorDisks.empty(), DAS_ERR_ARG,
               "das_simple_iteration: the SIMPLE sweep does not carry the fvSource actuator disks (its U equation has no source term); use das_solve_primal");
     DAS_CHECK(s->regModels.empty(), DAS_ERR_ARG,
@@ -3900,6 +3920,37 @@ int das_calc_drdwold_t_psi(das_solver_t* s, int oldTimeLevel, const double* psi,
     DAS_CHECK(psi && out, DAS_ERR_ARG, "null argument");
     DAS_CHECK(oldTimeLevel == 1 || oldTimeLevel == 2, DAS_ERR_ARG, "oldTimeLevel must be 1 (W0) or 2 (W00)");
     const long long n = s->n;
+    if (s->cp.pimple) {
+        double c, c0, c00;
+        s->cp.ddt_coeffs(c, c0, c00);
+        const double coef = (oldTimeLevel == 1 ? c0 : -c00) / s->cp.deltaT;
+        if (coef == 0.0) {  // Euler, or backward below time index 2: no W00 in the residual
+            std::fill(out, out + n, 0.0);
+            return DAS_OK;
+        }
+        // rAU of the current states: one residual pass (its R goes to the scratch), kept for as long as the states, the geometry, the
+        // options and the old-time states stand - level 2 of an adjoint step reuses the pass of level 1; then the gather
+        hipStream_t st = s->stream;
+        ResParams prm = make_params(s->cp, s->opt, 0);
+        const bool kept = s->d_rAUold.n == (size_t)s->dm.nC && s->rAUold_epoch == s->opEpoch && s->rAUold_geom == s->geomVersion &&
+                          s->rAUold_states.size() == s->h_W.size() && std::memcmp(s->rAUold_states.data(), s->h_W.data(), n * sizeof(double)) == 0;
+        if (!kept) {
+            eval_residual<double>(s->dm, s->cp, prm, s->d_W.p, s->d_tmp2.p, s->wk, s->d_phiF.p, s->d_Told.p, st);
+            if (s->d_rAUold.n != (size_t)s->dm.nC) s->d_rAUold.alloc(s->dm.nC);
+            DAS_HIP(hipMemcpyAsync(s->d_rAUold.p, s->wk.rAU.p, (size_t)s->dm.nC * sizeof(double), hipMemcpyDeviceToDevice, st));
+            s->rAUold_states = s->h_W;
+            s->rAUold_epoch = s->opEpoch;
+            s->rAUold_geom = s->geomVersion;
+        }
+        DAS_HIP(hipMemcpyAsync(s->d_tmp1.p, psi, n * sizeof(double), hipMemcpyHostToDevice, st));
+        DAS_HIP(hipMemsetAsync(s->d_tmp2.p, 0, n * sizeof(double), st));
+        hipLaunchKernelGGL(k_drdwold, dim3(nblk(s->dm.nC, 256)), dim3(256), 0, st, s->dm, prm, coef, (const double*)s->d_rAUold.p, (const double*)s->d_tmp1.p,
+                           (const double*)s->d_scale.p, s->d_tmp2.p);
+        DAS_HIP(hipGetLastError());
+        DAS_HIP(hipMemcpyAsync(out, s->d_tmp2.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        DAS_HIP(hipStreamSynchronize(st));
+        return DAS_OK;
+    }
     if (s->cp.solver != DAS_SOLVER_SCALARTRANSPORTFOAM || oldTimeLevel == 2) {
         std::fill(out, out + n, 0.0);  // steady residuals / Euler scheme: no W00 dependence
         return DAS_OK;
@@ -3913,6 +3964,36 @@ int das_calc_drdwold_t_psi(das_solver_t* s, int oldTimeLevel, const double* psi,
     hipLaunchKernelGGL(k_mul, dim3(nblk(n, 256)), dim3(256), 0, s->stream, n, s->d_tmp2.p, s->d_tmp1.p);
     DAS_HIP(hipMemcpyAsync(out, s->d_tmp1.p, n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     DAS_HIP(hipStreamSynchronize(s->stream));
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_set_old_time_states(das_solver_t* s, const double* W0, const double* W00, int timeIndex) {
+    DAS_TRY
+    DAS_CHECK(s, DAS_ERR_ARG, "null solver handle");
+    DAS_CHECK(s->cp.pimple, DAS_ERR_ARG, "old-time states only exist for DAPimpleFoam");
+    DAS_CHECK(W0, DAS_ERR_ARG, "null W0");
+    DAS_CHECK(timeIndex >= 1, DAS_ERR_ARG, "timeIndex counts the time steps from 1, not " + std::to_string(timeIndex));
+    DAS_CHECK(W00 || !(s->cp.ddtScheme == 1 && timeIndex >= 2), DAS_ERR_ARG, "the backward scheme at time index " + std::to_string(timeIndex) + " needs W00");
+    s->cp.timeIndex = timeIndex;
+    s->h_W0.assign(W0, W0 + s->n);
+    if (W00) s->h_W00.assign(W00, W00 + s->n);
+    if (s->inited) {
+        s->d_W0.upload(s->h_W0); s->cp.W0_ptr = s->d_W0.p;
+        if (W00) { s->d_W00.upload(s->h_W00); s->cp.W00_ptr = s->d_W00.p; }
+    }
+    s->opEpoch++;
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_set_time_index(das_solver_t* s, int timeIndex) {
+    DAS_TRY
+    DAS_CHECK(s, DAS_ERR_ARG, "null solver handle");
+    DAS_CHECK(s->cp.pimple, DAS_ERR_ARG, "the time index only selects ddt coefficients for DAPimpleFoam");
+    DAS_CHECK(timeIndex >= 1, DAS_ERR_ARG, "timeIndex counts the time steps from 1, not " + std::to_string(timeIndex));
+    if (s->cp.timeIndex != timeIndex) {
+        s->cp.timeIndex = timeIndex;
+        s->opEpoch++;
+    }
     return DAS_OK;
     DAS_CATCH
 }
@@ -5654,6 +5735,7 @@ static void heat_source_rank1_terms(das_solver* s, const double* d_psi, int byV,
 static void need_actuator_disk_solver(das_solver* s) {
     DAS_CHECK(s, DAS_ERR_ARG, "null solver handle");
     DAS_CHECK(s->cp.solver != DAS_SOLVER_SOLIDDISPLACEMENTFOAM, DAS_ERR_ARG, "the fvSource option is not built for DASolidDisplacementFoam");
+    DAS_CHECK(!s->cp.pimple, DAS_ERR_ARG, "DAPimpleFoam: fvSource is not built");
     DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM, DAS_ERR_ARG,
               "the fvSource actuator disks are built for DASimpleFoam only: not for DARhoSimpleFoam (its fvSourceEnergy = fvSource . U is not built), DATurboFoam, "
               "DAScalarTransportFoam or DAHeatTransferFoam");
@@ -7015,6 +7097,7 @@ static RegView reg_view_from_spec(const std::string& what, const das_reg_spec_t*
 }
 static void need_regression_solver(das_solver* s) {
     DAS_CHECK(s, DAS_ERR_ARG, "null solver handle");
+    DAS_CHECK(!s->cp.pimple, DAS_ERR_ARG, "DAPimpleFoam: regressionModel is not built");
     DAS_CHECK(s->cp.solver == DAS_SOLVER_SIMPLEFOAM, DAS_ERR_ARG,
               "the regressionModel option is built for DASimpleFoam only: not for " + s->opt.gets("solverName"));
     DAS_CHECK(s->owned.empty(), DAS_ERR_ARG, "the regression models run on an undecomposed solver (sharded solvers are not supported)");

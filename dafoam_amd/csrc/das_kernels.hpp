@@ -97,6 +97,14 @@ struct ResParams {
     double sRho, sMu, sLam;
     int normD, nPass, nTrac;
     const int* tracCells;
+    // DAPimpleFoam (appended, so that every field above keeps its offset): ddt = 1: the fvm::ddt terms of body_cell are on (host-side
+    // launch switch); ddtC, ddtC0, ddtC00: the coefficients of the new, old and old-old value (Euler 1, 1, 0; backward at constant deltaT
+    // 1.5, 2, 0.5; backward below time index 2 is Euler); W0, W00: the old-time state vectors in the layout of W, plain doubles in every
+    // pass (W00 is not read where ddtC00 is 0)
+    int ddt;
+    double ddtC, ddtC0, ddtC00;
+    const double* W0;
+    const double* W00;
 };
 #define DAS_TREF 298.15
 
@@ -495,7 +503,11 @@ DAS_HD void dev2T_scaled(const T* g, const T& nuEff, T* tau) {
 // (RHO) the energy residual TRes = EEqn & he.  RHO: phi is the mass flux, muEff = mu + rho nut replaces nuEff.
 // SRC: the momentum source of the actuator disks (DevMeshT::src3) is added; a template flag, so that the instantiation without disks is the
 // code it was before the disks came, instruction for instruction
-template <class T, bool RHO, class G, bool SRC = false>
+// DDT: DAPimpleFoam (DAResidualPimpleFoam.C:94-227, DASpalartAllmaras.C:453): fvm::ddt(U) and fvm::ddt(nuTilda) enter the two matrices - the
+// diagonal gains c V / deltaT, the source V / deltaT (c0 x0 - c00 x00) - before relax, so the dominance fix-up, A and H all see them;
+// a template flag like SRC, for the same reason.  OLD: the scalar of the old-time arrays behind prm.W0 / prm.W00 - double in every kernel
+// of the library; the host test harness alone instantiates Dual<1> for the dot-product identity of the hand-written old-time product
+template <class T, bool RHO, class G, bool SRC = false, bool DDT = false, class OLD = double>
 DAS_HD void body_cell(int c, const DevMeshT<G>& m, const ResParams& prm, const T* W, const T* nut, const T* gradU, const T* gradP,
                       const T* gradN, const T* gradH, T* R, T* rAU, T* HbyA, const T* TU = nullptr) {
     const long long N = m.nC;
@@ -746,6 +758,24 @@ DAS_HD void body_cell(int c, const DevMeshT<G>& m, const ResParams& prm, const T
     if constexpr (SRC) {  // - fvSource (DAResidualSimpleFoam.C:141-147): part of the matrix source, so it reaches URes and H alike
 #pragma unroll
         for (int k = 0; k < 3; k++) src[k] += cgc.V * m.src3[3LL * c + k];
+    }
+    if constexpr (DDT) {  // + fvm::ddt: old values carry no tangent; W00 is read only where the scheme has a second old level
+        const G vdt = cgc.V / prm.deltaT;
+        D0 += prm.ddtC * vdt;
+        dN += prm.ddtC * vdt;
+        const long long jn = prm.offN * N + c;
+        const OLD* W0 = (const OLD*)prm.W0;
+        OLD oldU[3] = {prm.ddtC0 * W0[3LL * c], prm.ddtC0 * W0[3LL * c + 1], prm.ddtC0 * W0[3LL * c + 2]};
+        OLD oldN = prm.ddtC0 * W0[jn];
+        if (prm.ddtC00 != 0.0) {
+            const OLD* W00 = (const OLD*)prm.W00;
+#pragma unroll
+            for (int k = 0; k < 3; k++) oldU[k] -= prm.ddtC00 * W00[3LL * c + k];
+            oldN -= prm.ddtC00 * W00[jn];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; k++) src[k] += vdt * oldU[k];
+        sN += vdt * oldN;
     }
     // fvMatrix::relax (see DESIGN.md "relax"): diagonal dominance fix-up with boundary max/min contributions
     T D = dmax(dabs(D0 + vmaxs), sumOff) * (1.0 / prm.alphaU) - vmins;
@@ -1139,6 +1169,61 @@ DAS_HD void body_pres(int c, const DevMeshT<G>& m, const ResParams& prm, const T
     if (RHO) s = -s;
     if (prm.normP) s = s * (1.0 / m.cg[c].V);
     R[prm.offP * N + c] = s;
+}
+
+// ================================================================================ k_drdwold
+// DAPimpleFoam: out = s o [dR/dW0]^T psi (coef = c0 / deltaT) or s o [dR/dW00]^T psi (coef = -c00 / deltaT) for cell c, written by hand.
+// The old-time values sit in the matrix source of the U and nuTilda equations, so
+//   d URes_k(c) / d U0_k(c) = -coef (x V where URes is not normalised),  d nuTildaRes(c) / d nuTilda0(c) likewise,
+//   d HbyA_k(c) / d U0_k(c) = rAU(c) coef,
+// and HbyA reaches phiRes and pRes through the linear map phiHbyA_f = L_f(HbyA) of body_face and body_pres (q_f = flux - phiHbyA_f,
+// phiRes_f = phiHbyA_f - flux - phi_f, pRes_c = sum +-q_f).  Transposed: face f weighs dL_f / dHbyA(c) with
+//   lambda_f = psi_phi(f) [/ |S_f|] - (psi_p(owner) [/ V] - psi_p(neighbour) [/ V]),
+// dL_f / dHbyA(c) = w_c S_f on an internal face; S_f on a boundary face, S_f - n (n . S_f) behind the symmetry transform and nothing where
+// constrainHbyA puts the fixed value in place of the extrapolated one.  One thread per cell gathers over its face list as body_cell does:
+// no atomics, the same bits on every call.  p and phi have no old-time term: their entries are the caller's zeros.  (No MRF, no cyclic
+// pairs, incompressible: DAPimpleFoam refuses the rest.)
+DAS_HD void body_drdwold(int c, const DevMeshT<double>& m, const ResParams& prm, double coef, const double* rAU, const double* psi, const double* scale,
+                         double* out) {
+    const long long N = m.nC;
+    const CellGeomT<double>& cgc = m.cg[c];
+    const double lp_c = prm.normP ? psi[prm.offP * N + c] * (1.0 / cgc.V) : psi[prm.offP * N + c];
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int s = m.cf_ptr[c]; s < m.cf_ptr[c + 1]; s++) {
+        const int fe = m.cf_face[s];
+        const int f = fe & 0x7fffffff;
+        const bool nb = fe < 0;
+        const FaceGeomT<double>& g = m.fg[f];
+        double lam = psi[prm.offPhi * N + f];
+        if (prm.normPhi) lam = lam * (1.0 / g.magSf);
+        if (f < m.nIF) {
+            const int o = m.cf_other[s];
+            const double lp_o = prm.normP ? psi[prm.offP * N + o] * (1.0 / m.cg[o].V) : psi[prm.offP * N + o];
+            lam -= nb ? lp_o - lp_c : lp_c - lp_o;
+            const double wl = nb ? 1.0 - g.w : g.w;
+#pragma unroll
+            for (int k = 0; k < 3; k++) acc[k] += lam * (wl * g.Sf[k]);
+        } else {
+            lam -= lp_c;
+            const PatchBC& bc = m.bc[m.bpatch[f - m.nIF]];
+            if (prm.constrainHbyA && bc.U_code == DAS_BC_FIXED_VALUE) continue;
+            if (bc.U_code == DAS_BC_SYMMETRY) {
+                const double n[3] = {g.Sf[0] / g.magSf, g.Sf[1] / g.magSf, g.Sf[2] / g.magSf};
+                const double ns = n[0] * g.Sf[0] + n[1] * g.Sf[1] + n[2] * g.Sf[2];
+#pragma unroll
+                for (int k = 0; k < 3; k++) acc[k] += lam * (g.Sf[k] - n[k] * ns);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 3; k++) acc[k] += lam * g.Sf[k];
+            }
+        }
+    }
+    const double rA = rAU[c];
+    const double vU = prm.normU ? 1.0 : cgc.V, vN = prm.normN ? 1.0 : cgc.V;
+#pragma unroll
+    for (int k = 0; k < 3; k++) out[3LL * c + k] = scale[3LL * c + k] * (coef * (rA * acc[k] - vU * psi[3LL * c + k]));
+    const long long jn = prm.offN * N + c;
+    out[jn] = scale[jn] * (coef * (-vN * psi[jn]));
 }
 
 // ================================================================================ force objective

@@ -609,6 +609,8 @@ def extract_submesh(case, part, rank, G=GHOST_LAYERS):
         raise NotImplementedError("sharded (multi-rank) DAHeatTransferFoam solvers are not built: the solid solver runs on one undecomposed mesh")
     if case.solver_name == "DASolidDisplacementFoam":
         raise NotImplementedError("sharded (multi-rank) DASolidDisplacementFoam solvers are not built: the solid solver runs on one undecomposed mesh")
+    if case.solver_name == "DAPimpleFoam":
+        raise NotImplementedError("sharded (multi-rank) DAPimpleFoam solvers are not built: the old-time states and the time-accurate adjoint run on one undecomposed mesh")
     m = case.mesh
     N, F, nIF = m.n_cells, m.n_faces, m.n_internal_faces
     own, nei = m.owner.astype(np.int64), m.neighbour.astype(np.int64)

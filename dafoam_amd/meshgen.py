@@ -115,6 +115,10 @@ class FoamCase:
     # "planeStress": bool}; the patch fields of D sit in bcs as {"D": (BC_FIXED_VALUE, (3,)) | (BC_ZERO_GRADIENT, 0.0) | (BC_SYMMETRY, 0.0)
     # | (BC_TRACTION, traction (3,), pressure)}
     mechanical: Optional[dict] = None
+    # DAPimpleFoam: system/fvSchemes ddtSchemes.default ("Euler" | "backward"; deltaT above is the constant time step) and the number of
+    # time steps solvePrimal marches (endTime / deltaT)
+    ddt_scheme: str = "Euler"
+    n_steps: int = 1
 
 
 def hex_block(
@@ -415,7 +419,7 @@ def n_states(case: FoamCase) -> int:
         return m.n_cells
     if case.solver_name == "DASolidDisplacementFoam":
         return 3 * m.n_cells
-    if case.solver_name == "DASimpleFoam":
+    if case.solver_name in ("DASimpleFoam", "DAPimpleFoam"):
         return (6 if case.has_T else 5) * m.n_cells + m.n_faces
     if case.solver_name in ("DARhoSimpleFoam", "DATurboFoam"):
         return 6 * m.n_cells + m.n_faces
@@ -520,6 +524,15 @@ def channel_case(
             phi[sl] = 0.0
     phi[:nIF] *= 1.0 + perturb * rng.standard_normal(nIF)
     case.states = np.concatenate([U.ravel(), p, nuT, phi])
+    return case
+
+
+def pimple_case(nx=7, ny=7, nz=7, ddt_scheme="Euler", deltaT=0.01, n_steps=6, **kw) -> FoamCase:
+    """DAPimpleFoam + SA: channel_case with the solver name, the ddt scheme ("Euler" | "backward"), the constant time step and the
+    number of steps (reference tests/runRegTests_DAPimpleFoam.py).  The states are the start of the march."""
+    case = channel_case(nx, ny, nz, **kw)
+    case.solver_name = "DAPimpleFoam"
+    case.ddt_scheme, case.deltaT, case.n_steps = ddt_scheme, float(deltaT), int(n_steps)
     return case
 
 

@@ -531,6 +531,14 @@ class PYDAFOAM(object):
         normalised initial residual, DASolver.C:188).  The failure flag follows
         DASolver::checkPrimalFailure (DASolver.C:2722-2760): fail when primalMaxRes / primalMinResTol > primalMinResTolDiff."""
         tol = float(self.getOption("primalMinResTol"))
+        if getattr(self.solver, "_pimple", False):
+            # DAPimpleFoam: case.n_steps time steps, each converged primalMinResTol below its own first residual (the start of a step is
+            # the step before: no fixed reference norm fits every step); the series stays in memory (pyDASolvers.getTimeInstance)
+            rc, self.primalInfo = self.solver.solvePrimal(maxSteps=maxSteps, relTol=tol, absTol=0.0)
+            self.primalMaxRes = max(i["res"] / max(i["res0"], 1e-300) for i in self.primalInfo["timeSteps"])
+            self.primalInfo["primalMaxRes"] = self.primalMaxRes
+            self.primalFail = int(rc != 0 and self.primalMaxRes / tol > float(self.getOption("primalMinResTolDiff")))
+            return self.primalFail
         ref = getattr(self, "_primalResRef", None)
         user_ref = float(self.getOption("amdPrimalResRef") or 0.0)
         if user_ref > 0.0:
@@ -632,6 +640,72 @@ class PYDAFOAM(object):
         self.solverAD.destroydRdWTMatrixFree()
         self.nSolveAdjoints += 1
         return self.vec2Array(psi), fail
+
+    def solveUnsteadyAdjoint(self, functionNames, inputs):
+        """The time-accurate adjoint of DAPimpleFoam: the backward loop of DAFoamSolver.solve_linear for unsteady solvers
+        (dafoam/mphys/mphys_dafoam.py:1538-1672) over the series solvePrimal kept in memory, from the last time step to the first.
+        `functionNames`: the functions of one output, summed (the first one's timeOp gives dFScaling, as in the reference);
+        `inputs`: {inputName: values} for entries of the inputInfo option.  Per step: states and old-time states of the step; right-hand
+        side dFdW . scaling - dRdW0^T psi(n+1) - dRdW00^T psi(n+2); the adjoint solve; totals += dFdX . scaling - dRdX^T psi; the two
+        old-time products for the steps before.  Krylov only; the preconditioner is rebuilt every unsteadyAdjoint.PCMatUpdateInterval
+        steps through calcdRdWT(1) (calcPCMatWithFvMatrix is not built).  Returns (totals, fail)."""
+        s = self.solverAD
+        if not getattr(s, "_pimple", False):
+            raise Error("solveUnsteadyAdjoint needs DAPimpleFoam, not %s" % self.getOption("solverName"))
+        if self.getOption("adjEqnSolMethod") != "Krylov":
+            raise Error("solveUnsteadyAdjoint: adjEqnSolMethod %s is not built (Krylov is)" % self.getOption("adjEqnSolMethod"))
+        functionNames = [functionNames] if isinstance(functionNames, str) else list(functionNames)
+        inputInfo = self.getOption("inputInfo")
+        nSteps, order = int(self._case.n_steps), s.getDdtSchemeOrder()
+        interval = max(1, int(self.getOption("unsteadyAdjoint").get("PCMatUpdateInterval", 1)))
+        n = self.getNLocalAdjointStates()
+        if self.getOption("adjUseColoring") and self.runColoring:
+            self.solver.runColoring(cacheDir=self.getOption("amdColoringDir") or None)
+            self.runColoring = False
+        totals = {k: np.zeros_like(np.asarray(v, dtype=np.float64)) for k, v in inputs.items()}
+        dRdW0TPsi, dRdW00TPsi, dRdW00TPsiBuffer = np.zeros(n), np.zeros(n), np.zeros(n)
+        tmp, seed = np.zeros(n), np.ones(1)
+        psi = Vec(n)
+        fail, ksp, pcMat = 0, None, None
+        for step in range(nSteps, 0, -1):
+            s._set_time_instance(step)
+            W = self.getStates()
+            dFScaling = s.getdFScaling(functionNames[0], step - 1)
+            dFdW = np.zeros(n)
+            for fn in functionNames:
+                s.calcJacTVecProduct("states", "stateVar", W, fn, "function", seed, tmp)
+                dFdW += tmp * dFScaling
+            dFdW -= dRdW0TPsi
+            if order == 2:
+                dFdW -= dRdW00TPsi
+                dRdW00TPsi[:] = dRdW00TPsiBuffer
+            if ksp is None or (nSteps - step) % interval == 0:
+                pcMat = Mat().create()
+                s.calcdRdWT(1, pcMat)
+                ksp = KSP().create()
+                s.createMLRKSPMatrixFree(pcMat, ksp)
+            s.initializedRdWTMatrixFree()
+            psi.set(0)
+            fail = s.solveLinearEqn(ksp, self.array2Vec(dFdW), psi)
+            s.destroydRdWTMatrixFree()
+            if fail > 0:
+                break
+            psiArray = self.vec2Array(psi)
+            for name, x in inputs.items():
+                x = np.ascontiguousarray(x, dtype=np.float64)
+                itype = inputInfo[name]["type"]
+                dFdX, t1, dRdXTPsi = np.zeros_like(x), np.zeros_like(x), np.zeros_like(x)
+                for fn in functionNames:
+                    s.calcJacTVecProduct(name, itype, x, fn, "function", seed, t1)
+                    dFdX += t1 * dFScaling
+                s.calcJacTVecProduct(name, itype, x, "residual", "residual", psiArray, dRdXTPsi)
+                totals[name] += dFdX - dRdXTPsi
+            s.calcdRdWOldTPsiAD(1, psiArray, dRdW0TPsi)
+            if order == 2:
+                s.calcdRdWOldTPsiAD(2, psiArray, dRdW00TPsiBuffer)
+        s._set_time_instance(nSteps)  # the fields are left at the end time, as the reference leaves them
+        self.nSolveAdjoints += 1
+        return totals, fail
 
     def _updateKSPTolerances(self, psi, dFdW, ksp):
         """dynAdjustTol (reference DAFoamSolver._updateKSPTolerances, mphys_dafoam.py:576-611): converge gmresRelTol

@@ -305,6 +305,9 @@ class pyDASolvers:
         if solver not in ("DASolvers", case.solver_name):
             raise ValueError(f"argsAll solver {solver} != case solver {case.solver_name}")
         self._case = case
+        self._pimple = case.solver_name == "DAPimpleFoam"
+        if self._pimple:
+            self._pimple_checks(pyOptions if isinstance(pyOptions, dict) else {})
         self._fvSource = self._checked_fv_source(pyOptions.get("fvSource") if isinstance(pyOptions, dict) else None)
         self._cs = CaseStruct(case)
         L = lib()
@@ -348,7 +351,7 @@ class pyDASolvers:
         (volVector, volScalar, model) followed by the phi of the faces it owns (DAIndex.C:602-651)."""
         m = self._case.mesh
         N, F = m.n_cells, m.n_faces
-        layout = {"DASimpleFoam": (1, 3 if getattr(self._case, "has_T", False) else 2), "DARhoSimpleFoam": (1, 3), "DATurboFoam": (1, 3),
+        layout = {"DASimpleFoam": (1, 3 if getattr(self._case, "has_T", False) else 2), "DAPimpleFoam": (1, 2), "DARhoSimpleFoam": (1, 3), "DATurboFoam": (1, 3),
                   "DAScalarTransportFoam": (0, 1), "DAHeatTransferFoam": (0, 1), "DASolidDisplacementFoam": (1, 0)}[self._case.solver_name]
         nvec, nscl = layout
         has_phi = self._case.solver_name not in ("DAScalarTransportFoam", "DAHeatTransferFoam", "DASolidDisplacementFoam")
@@ -417,7 +420,7 @@ class pyDASolvers:
     def getNLocalAdjointBoundaryStates(self):
         m = self._case.mesh
         nb = m.n_faces - m.n_internal_faces
-        return {"DASimpleFoam": 6 if getattr(self._case, "has_T", False) else 5, "DARhoSimpleFoam": 6, "DATurboFoam": 6}.get(self._case.solver_name, 1) * nb
+        return {"DASimpleFoam": 6 if getattr(self._case, "has_T", False) else 5, "DAPimpleFoam": 5, "DARhoSimpleFoam": 6, "DATurboFoam": 6}.get(self._case.solver_name, 1) * nb
 
     def getNLocalCells(self):
         return int(lib().das_get_n_local_cells(self._h))
@@ -813,6 +816,21 @@ class pyDASolvers:
         tmp = np.zeros(len(psi)) if self._perm is not None else dRdWOldTPsi
         check(lib().das_calc_drdwold_t_psi(self._h, int(oldTimeLevel), dptr(np.ascontiguousarray(self._to_state(psi))), dptr(tmp)))
         self._from_state(tmp, dRdWOldTPsi)
+
+    def setOldTimeStates(self, W0, W00=None, timeIndex=None):
+        """DAPimpleFoam: the state vectors of the two old time levels (the ordering of getOFFields) onto the device, with the time index
+        the residual is evaluated at (default: the one of setTime).  W00 may be None where the scheme is Euler or timeIndex < 2.  Every
+        residual, Jacobian and product evaluated afterwards is R(W; W0, W00)."""
+        if not self._pimple:
+            raise _capi.DASError(f"setOldTimeStates: old-time states only exist for DAPimpleFoam, not for {self._case.solver_name}")
+        n = self.getNLocalAdjointStates()
+        if np.size(W0) != n or (W00 is not None and np.size(W00) != n):
+            raise _capi.DASError(f"setOldTimeStates: the old-time state vectors need {n} entries")
+        ti = int(getattr(self, "_timeIndex", 1) if timeIndex is None else timeIndex)
+        self._timeIndex = ti
+        w0 = np.ascontiguousarray(self._to_state(np.asarray(W0, dtype=np.float64)))
+        w00 = None if W00 is None else np.ascontiguousarray(self._to_state(np.asarray(W00, dtype=np.float64)))
+        check(lib().das_set_old_time_states(self._h, dptr(w0), dptr(w00) if w00 is not None else None, ti))
 
     def setOldTimeFields(self, phi=None, T_old=None):
         check(lib().das_set_old_time_fields(self._h, dptr(np.ascontiguousarray(phi)) if phi is not None else None,
@@ -1397,11 +1415,103 @@ class pyDASolvers:
         if self._case.solver_name == "DASolidDisplacementFoam" and not any(
                 p.size > 0 and self._case.bcs.get(p.name, {}).get("D", (1, 0.0))[0] == 0 for p in self._case.mesh.patches):
             raise _capi.DASError("DASolidDisplacementFoam: no patch carries a fixedValue D - the steady elastic problem is singular")
+        if self._pimple:
+            return self._solve_primal_unsteady(maxSteps, relTol, absTol)
         info4 = np.zeros(4)
         hist = np.zeros(int(maxSteps) + 2)
         rc = check(lib().das_solve_primal(self._h, int(maxSteps), float(relTol), float(absTol), dptr(info4), dptr(hist), hist.size))
         nst = int(info4[0])
         return rc, dict(steps=nst, linearIterations=int(info4[1]), res0=float(info4[2]), res=float(info4[3]), history=hist[: nst + 1].copy())
+
+    # -- DAPimpleFoam: what is refused, the marching primal, the time operators and the time-accurate adjoint ------------------------------
+    # the patch-integral types an incompressible solver without a T field can evaluate, and variableVolSum
+    _PIMPLE_FUNCTIONS = ("force", "moment", "massFlowRate", "totalPressure", "location", "variableVolSum")
+
+    def _pimple_checks(self, opt):
+        """What DAPimpleFoam does not build is refused by name before anything is created."""
+        case = self._case
+        if getattr(case, "has_T", False):
+            raise _capi.DASError("DAPimpleFoam: the T field is not built")
+        if getattr(case, "mrf", None):
+            raise _capi.DASError("DAPimpleFoam: MRF is not built")
+        if any(p.type == "cyclic" for p in case.mesh.patches):
+            raise _capi.DASError("DAPimpleFoam: cyclic patches are not built")
+        if getattr(case, "simple_consistent", False):
+            raise _capi.DASError("DAPimpleFoam: simple_consistent is not built")
+        if case.ddt_scheme not in _capi.DDT_SCHEMES:
+            raise _capi.DASError(f"ddtScheme {case.ddt_scheme} not supported! Options: steadyState, Euler, or backward")
+        if opt.get("fvSource"):
+            raise _capi.DASError(f"fvSource[{sorted(opt['fvSource'])[0]}]: the fvSource option is not built for DAPimpleFoam")
+        if opt.get("regressionModel") and (opt["regressionModel"].get("active", True) if isinstance(opt["regressionModel"], dict) else True):
+            raise _capi.DASError("regressionModel: the option is not built for DAPimpleFoam")
+        if opt.get("outputInfo"):
+            raise _capi.DASError(f"outputInfo[{sorted(opt['outputInfo'])[0]}]: coupling outputs are not built for DAPimpleFoam")
+        for nm, e in (opt.get("inputInfo") or {}).items():
+            if isinstance(e, dict) and e.get("type") in ("forceCoupling", "thermalCoupling", "thermalCouplingInput"):
+                raise _capi.DASError(f"inputInfo[{nm}]: coupling inputs ({e.get('type')}) are not built for DAPimpleFoam")
+        if (opt.get("dynamicMesh") or {}).get("active"):
+            raise _capi.DASError("DAPimpleFoam: dynamicMesh is not built")
+        if opt.get("runFPAdj") or opt.get("adjEqnSolMethod", "Krylov") != "Krylov":
+            raise _capi.DASError("DAPimpleFoam: runFPAdj / adjEqnSolMethod fixedPoint is not built (the time-accurate adjoint is Krylov only)")
+        for fname, fd in (opt.get("function") or {}).items():
+            if fd.get("type") not in self._PIMPLE_FUNCTIONS:
+                raise _capi.DASError(f"function {fname}: type {fd.get('type')} is not built for DAPimpleFoam (the patch-integral types and variableVolSum are)")
+            if fd.get("timeOp", "final") not in ("final", "average"):
+                raise _capi.DASError(f"function {fname}: timeOp {fd.get('timeOp')} is not built for DAPimpleFoam (final and average are)")
+        self._functionDefs = {k: dict(v) for k, v in (opt.get("function") or {}).items()}
+
+    def _time_op_range(self, functionName):
+        """(timeOp, startIdx, endIdx) over the list of the marched steps: DASolver::getTimeOpRange (DASolver.C:404-422) - final: the
+        whole list; average: the trailing window max(2, round(nStepsFrac (listEnd + 1))), nStepsFrac 0.2 unless the function sets it."""
+        fd = self._functionDefs.get(functionName)
+        if fd is None:
+            raise _capi.DASError(f"functionName {functionName} not found!")
+        op = fd.get("timeOp", "final")
+        end = int(self._case.n_steps) - 1
+        start = 0
+        if op == "average":
+            window = max(2, int(np.floor(float(fd.get("nStepsFrac", 0.2)) * (end + 1) + 0.5)))  # Foam::round: half away from zero
+            start = max(0, end - window + 1)
+        return op, start, end
+
+    def getTimeInstance(self, n):
+        """The states of time index n of the marched series (0: the start), the ordering of getOFFields."""
+        series = getattr(self, "_series", None)
+        if series is None or not 0 <= int(n) < len(series):
+            raise _capi.DASError(f"getTimeInstance: time index {n} is not in the marched series (solvePrimal first)")
+        return series[int(n)].copy()
+
+    def _set_time_instance(self, n):
+        """states and old-time states of time index n >= 1 from the series; before the start the flow is taken as steady: W(-1) = W(0)"""
+        ser = self._series
+        self.setOldTimeStates(ser[n - 1], ser[max(n - 2, 0)], n)  # one upload, with the index
+        self.setTime(n * self.getDeltaT(), n)
+        self.updateOFFields(ser[n])
+
+    def _solve_primal_unsteady(self, maxSteps, relTol, absTol):
+        """n_steps time steps, each the Newton solve of R(W; W0, W00) = 0 started from the step before; the series stays in memory"""
+        n = self.getNLocalAdjointStates()
+        W = np.zeros(n)
+        self.getOFFields(W)
+        self._series = [W.copy()]
+        self._functionTimeSteps = {k: [] for k in self._functionDefs}
+        infos, rc_all = [], 0
+        for step in range(1, int(self._case.n_steps) + 1):
+            self.setOldTimeStates(self._series[step - 1], self._series[max(step - 2, 0)], step)  # one upload, with the index
+            self.setTime(step * self.getDeltaT(), step)
+            info4 = np.zeros(4)
+            hist = np.zeros(int(maxSteps) + 2)
+            rc = check(lib().das_solve_primal(self._h, int(maxSteps), float(relTol), float(absTol), dptr(info4), dptr(hist), hist.size))
+            rc_all = max(rc_all, rc)
+            self.getOFFields(W)
+            self._series.append(W.copy())
+            for k in self._functionTimeSteps:
+                self._functionTimeSteps[k].append(self.calcFunction(k))
+            nst = int(info4[0])
+            infos.append(dict(steps=nst, linearIterations=int(info4[1]), res0=float(info4[2]), res=float(info4[3]), history=hist[: nst + 1].copy()))
+        last = infos[-1]
+        return rc_all, dict(steps=sum(i["steps"] for i in infos), linearIterations=sum(i["linearIterations"] for i in infos), res0=infos[0]["res0"],
+                            res=max(i["res"] for i in infos), history=last["history"], timeSteps=infos)
 
     def simpleIteration(self, nSweeps=1, alphaP=0.3, linTol=1e-12, maxLinIters=20000):
         """nSweeps iterations of the reference's own primal loop, SIMPLE (DASimpleFoam::solvePrimal, DASimpleFoam.C:123-185: UEqnSimple.H,
@@ -1442,6 +1552,7 @@ class pyDASolvers:
         m = self._case.mesh
         N, F = m.n_cells, m.n_faces
         names = {"DASimpleFoam": ["U", "p"] + (["T"] if getattr(self._case, "has_T", False) else []) + ["nuTilda", "phi"],
+                 "DAPimpleFoam": ["U", "p", "nuTilda", "phi"],
                  "DARhoSimpleFoam": ["U", "p", "T", "nuTilda", "phi"], "DATurboFoam": ["U", "p", "T", "nuTilda", "phi"],
                  "DAScalarTransportFoam": ["T"], "DAHeatTransferFoam": ["T"], "DASolidDisplacementFoam": ["D"]}[self._case.solver_name]
         out, off = [], 0
@@ -1606,6 +1717,8 @@ class pyDASolvers:
     # time bookkeeping of the steady solvers (pyDASolvers.pyx:358,400-410,464): iterations play the role of time
     def setTime(self, time, timeIndex):
         self._time, self._timeIndex = float(time), int(timeIndex)
+        if self._pimple:  # the ddt coefficients follow the time index (backward below 2 is Euler); the old states on the device stay
+            check(lib().das_set_time_index(self._h, int(timeIndex)))
 
     def getDeltaT(self):
         return float(getattr(self._case, "deltaT", 1.0))
@@ -1620,16 +1733,41 @@ class pyDASolvers:
         return float(getattr(self, "_prevPrimalSolTime", getattr(self, "_time", 0.0)))
 
     def getDdtSchemeOrder(self):
-        """1 (Euler) for the unsteady scalar transport residual, the steady solvers have no time derivative (DASolver::getDdtSchemeOrder)."""
+        """1 (Euler) for the unsteady scalar transport residual, the steady solvers have no time derivative (DASolver::getDdtSchemeOrder);
+        DAPimpleFoam: 1 for Euler, 2 for backward."""
+        if self._pimple:
+            return 2 if self._case.ddt_scheme == "backward" else 1
         return 1
 
     def getdFScaling(self, functionName, timeIdx=-1):
-        """DASolver::getdFScaling: the weight of a time instance in a time-averaged objective; 1 for steady solvers."""
-        return 1.0
+        """DASolver::getdFScaling: the weight of a time instance in a time-averaged objective; 1 for steady solvers.  DAPimpleFoam: the
+        function's timeOp (final | average with nStepsFrac) over the marched series, timeIdx = time index - 1 (DASolver.C:454-482):
+        average - 1 / window inside the trailing window, 0 before it; final - 1 at the last step and 0 before it.  DATimeOpFinal::dFScaling
+        returns 1 at every index of the list, which is the derivative of the SUM over the steps, not of the final value (measured on the
+        6-step channel of tests/test_gpu_pimple.py: 0.2227 = 6 x the average's 0.0371, against central differences 0.00116); what is built
+        here is the derivative of what DATimeOpFinal::compute returns."""
+        if not self._pimple:
+            return 1.0
+        op, i0, i1 = self._time_op_range(functionName)
+        if not i0 <= int(timeIdx) <= i1:
+            return 0.0
+        if op == "final":
+            return 1.0 if int(timeIdx) == i1 else 0.0
+        return 1.0 / (i1 - i0 + 1)
 
     def getTimeOpFuncVal(self, functionName):
-        """DASolver::getTimeOpFuncVal: the time-operated (final / averaged) objective; steady solvers: the value at the current states."""
-        return self.calcFunction(functionName)
+        """DASolver::getTimeOpFuncVal: the time-operated (final / averaged) objective; steady solvers: the value at the current states.
+        DAPimpleFoam: DATimeOpFinal / DATimeOpAverage over the function values of the marched series (DASolver.C:424-451)."""
+        if not self._pimple:
+            return self.calcFunction(functionName)
+        op, i0, i1 = self._time_op_range(functionName)
+        vals = self._functionTimeSteps[functionName]
+        if op == "final":
+            return float(vals[i1])
+        avg = 0.0
+        for i in range(i0, i1 + 1):
+            avg += vals[i]
+        return float(avg / (i1 - i0 + 1))
 
     def updateBoundaryConditions(self, fieldName, fieldType):
         """pyDASolvers.pyx:364: boundary values are re-evaluated inline by every kernel from the states - nothing is stored."""

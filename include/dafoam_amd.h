@@ -39,6 +39,10 @@ extern "C" {
 #define DAS_SOLVER_TURBOFOAM 3          /* DATurboFoam + SpalartAllmaras: SIMPLEC-consistent / transonic pEqn, "h" energy, MRF */
 #define DAS_SOLVER_HEATTRANSFERFOAM 4   /* DAHeatTransferFoam: steady conduction in a solid, one cell state T, kappa constant or a polynomial in T */
 #define DAS_SOLVER_SOLIDDISPLACEMENTFOAM 5 /* DASolidDisplacementFoam: steady linear-elastic solid, one cell vector state D, uniform rho, E, nu */
+/* DAPimpleFoam + SpalartAllmaras: the unsteady incompressible solver.  DASimpleFoam's states [U | p | nuTilda | phi] and stencils; the
+ * residual carries fvm::ddt(U) and fvm::ddt(nuTilda) (ddt_scheme Euler or backward at the constant deltaT) and UEqn.relax(1.0).  No T
+ * field, MRF or cyclic patches: das_create returns NULL with the reason */
+#define DAS_SOLVER_PIMPLEFOAM 6
 #define DAS_IS_COMPRESSIBLE(s) ((s) == DAS_SOLVER_RHOSIMPLEFOAM || (s) == DAS_SOLVER_TURBOFOAM)
 
 /* patch types */
@@ -150,6 +154,8 @@ typedef struct das_case {
     const double* bc_D_val;
     const double* bc_D_traction;
     const double* bc_D_pressure;
+    /* DAPimpleFoam, system/fvSchemes ddtSchemes.default: 0 Euler, 1 backward (deltaT above is its constant time step) */
+    int ddt_scheme;
 } das_case_t;
 
 const char* das_last_error(void);
@@ -296,7 +302,17 @@ int das_op_export(das_solver_t* s, long long* rowptr, int* colidx, double* vals)
  *     D_s (dR/dW_old)^T psi for oldTimeLevel 1 (W0) or 2 (W00).  Euler ddt: dR/dT0 = -1/deltaT (per-volume residual),
  *     level 2 and steady solvers give zero.
  * das_set_old_time_fields: frozen flux and old-time temperature of the current time step (the reference re-reads them
- *     from disk, readStateVars DASolver.C:3193). */
+ *     from disk, readStateVars DASolver.C:3193).
+ * DAPimpleFoam: das_set_old_time_states puts the full state vectors of the two old time levels (n states each, "state" ordering) on
+ *     the device and sets the time index the residual is evaluated at; W00 may be NULL where the scheme is Euler or timeIndex < 2 (it
+ *     is not read there).  Every residual, Jacobian and product evaluated afterwards is R(W; W0, W00).  das_calc_drdwold_t_psi then
+ *     gives D_s (dR/dW0)^T psi (level 1) and D_s (dR/dW00)^T psi (level 2; exact zeros for Euler and below time index 2) from one
+ *     hand-written gather kernel: the diagonal of the U and nuTilda rows plus rAU c0 / deltaT times the transpose of the map
+ *     HbyA -> (pRes, phiRes); bitwise the same on every call. */
+int das_set_old_time_states(das_solver_t* s, const double* W0, const double* W00 /* or NULL */, int timeIndex);
+/* das_set_time_index <- setTime(time, timeIndex) for DAPimpleFoam: the time index alone (it selects the ddt coefficients: backward
+ *     below 2 is Euler); the old-time states on the device stay.  A residual that then needs W00 and has none returns DAS_ERR_STATE. */
+int das_set_time_index(das_solver_t* s, int timeIndex);
 int das_calc_drdwold_t_psi(das_solver_t* s, int oldTimeLevel, const double* psi, double* out);
 int das_set_old_time_fields(das_solver_t* s, const double* phi_frozen /* n_faces or NULL */, const double* T_old /* n_cells or NULL */);
 
