@@ -562,6 +562,23 @@ _SIGS = {
     "das_debug_color_spec_round": (C.c_int, [C.c_longlong, c_ll_p, c_int_p, C.c_longlong, c_ll_p, c_int_p, C.c_int, C.c_int, C.c_int, c_int_p, C.POINTER(C.c_ubyte),
                                              c_int_p, C.c_longlong, C.POINTER(C.c_ulonglong), C.c_longlong, C.POINTER(C.c_uint), c_int_p]),
     "das_debug_color_check": (C.c_int, [C.c_longlong, c_ll_p, c_int_p, C.c_longlong, c_ll_p, c_int_p, C.c_int, c_int_p]),
+    # test-only entries (tests/test_gpu_reduce_kernels.py): the reductions of the objective functions and the two gathers on caller-made
+    # arrays, never called by the bindings
+    "das_debug_reduce_ks": (C.c_int, [C.c_longlong, c_double_p, C.c_double, C.c_double, c_double_p, C.c_longlong, c_double_p, c_double_p, C.c_longlong, c_double_p,
+                                      C.c_longlong, c_int_p]),
+    "das_debug_reduce_group_sum": (C.c_int, [C.c_longlong, C.POINTER(C.c_ubyte), c_double_p, c_double_p, C.c_longlong]),
+    "das_debug_reduce_tangent_dot": (C.c_int, [C.c_longlong, c_double_p, c_double_p, c_double_p, C.c_longlong, c_double_p, C.c_longlong, c_int_p]),
+    "das_debug_reduce_ad_dot": (C.c_int, [C.c_longlong, c_double_p, c_double_p, c_double_p, C.c_longlong, c_double_p, C.c_longlong, c_int_p]),
+    "das_debug_reduce_sv_dot": (C.c_int, [C.c_longlong, c_double_p, c_double_p, c_double_p, C.c_longlong, c_double_p, C.c_longlong, c_int_p]),
+    "das_debug_reduce_cellfn": (C.c_int, [C.c_longlong, c_int_p, c_ll_p, c_double_p, C.c_int, C.c_int, C.c_longlong, c_double_p, C.c_longlong, c_double_p, C.c_double,
+                                          c_double_p, C.c_longlong, c_double_p, C.c_longlong, c_double_p, C.c_double, c_double_p, C.c_longlong, c_int_p]),
+    "das_debug_reduce_rn": (C.c_int, [C.c_longlong, C.c_int, c_ll_p, c_int_p, c_double_p, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int, c_double_p, c_double_p,
+                                      C.c_longlong, c_double_p, C.c_longlong, c_double_p, C.c_longlong, C.c_double, C.c_double, c_double_p, C.c_longlong, c_int_p]),
+    "das_debug_reduce_hs_sum": (C.c_int, [C.c_int, C.c_int, c_double_p, C.POINTER(C.c_ubyte), c_double_p, c_double_p, C.c_int, C.c_double, c_double_p, c_double_p,
+                                          C.c_longlong, c_double_p, C.c_longlong, c_int_p]),
+    "das_debug_reduce_final": (C.c_int, [C.c_int, C.c_int, C.c_int, c_double_p, C.c_longlong, c_double_p, C.c_longlong]),
+    "das_debug_reduce_owner_gather": (C.c_int, [C.c_int, c_int_p, c_int_p, C.c_longlong, c_double_p, c_double_p, C.c_longlong]),
+    "das_debug_reduce_vm_gather": (C.c_int, [C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, C.c_int, c_double_p, C.c_double, c_double_p, C.c_longlong]),
     # test-only entries (tests/test_gpu_coarse_kernels.py): the coarse space of the two-level preconditioner on caller-made structures,
     # never called by the bindings
     "das_debug_coarse_assemble": (C.c_int, [C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, c_ll_p, c_int_p, c_double_p, c_int_p, c_int_p, C.c_int, C.c_double,

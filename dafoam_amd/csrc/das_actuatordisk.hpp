@@ -80,6 +80,24 @@ __global__ __launch_bounds__(256) void k_ad_dot_partial(long long n, const doubl
     acc = hs_block_sum<double>(acc);
     if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
+// ---- launch helpers: the grid arithmetic, once (hs_blocks of das_heatsource.hpp).  part holds 2 DAS_HS_MAX_BLOCKS entries of R for the
+// pair of sums, DAS_HS_MAX_BLOCKS doubles for the dot product; n >= 1
+template <class R>
+static void launch_ad_final(hipStream_t st, int nb, const R* part, R* out2) {
+    hipLaunchKernelGGL((k_ad_final<R>), dim3(1), dim3(256), 0, st, nb, part, out2);
+}
+template <class R, class P, class G>
+static void launch_ad_sums(hipStream_t st, const AdView<P>& v, int nC, const CellGeomT<G>* cg, const R* scale, R* part, R* out2) {
+    const int nb = hs_blocks(nC);
+    hipLaunchKernelGGL((k_ad_partial<R, P, G>), dim3(nb), dim3(256), 0, st, v, nC, cg, scale, part);
+    launch_ad_final<R>(st, nb, (const R*)part, out2);
+}
+// out[0] = sum_i psi_i Rd_i.d[0]
+static void launch_ad_dot(hipStream_t st, long long n, const double* psi, const Dual<1>* Rd, double* part, double* out) {
+    const int nb = hs_blocks(n);
+    hipLaunchKernelGGL(k_ad_dot_partial, dim3(nb), dim3(256), 0, st, n, psi, Rd, part);
+    launch_hs_final<double>(st, nb, (const double*)part, out);
+}
 // volCoord product: what the coloured passes cannot see of an adjustThrust disk - the total S = sum fAxial(scale = 1) V moves with every
 // cell.  beta = - (scale / S) (seeds . dR / dscale) multiplies (fAxial_1 V)' of every cell, on the per-cell tangent array.
 // exact mode: the tangents of the dual metrics

@@ -59,6 +59,18 @@ __global__ __launch_bounds__(256) void k_cellfn_grad(CellFnView f, const CellGeo
     const double dx = f.square ? 2.0 * cellfn_x(f, src, t) : 1.0;
     out[i] = g * (f.mv ? cg[f.cell[t]].V : 1.0) * dx * (sc ? sc[i] : 1.0);
 }
+// ---- launch helpers: the grid arithmetic, once.  part holds DAS_CELLFN_MAX_BLOCKS entries -----------------------------------------------
+static inline int cellfn_blocks(long long nt) { return std::max(1, std::min(DAS_CELLFN_MAX_BLOCKS, nblk(nt, 256))); }
+// out[0] = coef sum_t w_t g(x_t); part[0 .. cellfn_blocks(f.nt)) = the per-workgroup sums
+static void launch_cellfn_value(hipStream_t st, const CellFnView& f, const CellGeom* cg, const double* src, double coef, double* part, double* out) {
+    const int nb = cellfn_blocks(f.nt);
+    hipLaunchKernelGGL(k_cellfn_value, dim3(nb), dim3(256), 0, st, f, cg, src, part);
+    hipLaunchKernelGGL(k_cellfn_sum, dim3(1), dim3(256), 0, st, nb, (const double*)part, coef, out);
+}
+// f.nt > 0; the caller zeroes out
+static void launch_cellfn_grad(hipStream_t st, const CellFnView& f, const CellGeom* cg, const double* src, const double* sc, double g, double* out) {
+    hipLaunchKernelGGL(k_cellfn_grad, dim3(nblk(f.nt, 256)), dim3(256), 0, st, f, cg, src, sc, g, out);
+}
 // volCoord product (dual-point pass): per-cell tangent t_c = a V_c'  (the -N/T^2 part of divByTotalVol over all cells; a = 0 clears)
 __global__ __launch_bounds__(256) void k_vc_cellfn_all(int nC, const CellGeomT<Dual<1>>* __restrict__ cg, double a, double* __restrict__ tc) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -107,6 +119,10 @@ __global__ __launch_bounds__(256) void k_vm_gather(DevMesh m, const int* __restr
     for (int s = m.cf_ptr[c]; s < m.cf_ptr[c + 1]; s++)
         if ((m.cf_face[s] & 0x7fffffff) < m.nIF) acc += tc[m.cf_other[s]];
     out[j] = seed * acc;
+}
+// reads m.nC, m.nIF, m.cf_ptr, m.cf_face, m.cf_other
+static void launch_vm_gather(hipStream_t st, const DevMesh& m, const int* colors, int col, const double* tc, double seed, double* out) {
+    hipLaunchKernelGGL(k_vm_gather, dim3(nblk(3LL * m.nC, 256)), dim3(256), 0, st, m, colors, col, tc, seed, out);
 }
 
 }  // namespace das

@@ -46,6 +46,8 @@
 #include "das_heatsource.hpp"
 #include "das_actuatordisk.hpp"
 #include "das_regression.hpp"
+#include "das_reduce.hpp"
+#include "das_reduce_debug.hpp"
 #include "das_simple.hpp"
 #include "das_simple_host.hpp"
 
@@ -182,22 +184,7 @@ __global__ __launch_bounds__(256) void k_fn_value(DevMesh m, ResParams prm, cons
     if (fn.dir) { dir[0] = fn.dir[3 * k]; dir[1] = fn.dir[3 * k + 1]; dir[2] = fn.dir[3 * k + 2]; }
     fv[k] = fn.w[k] * facefn_of<double, RHO, SOLID>(fn.faces[k], m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc, fn.pRef);
 }
-// out2[g] = sum of fv[k] over the entries of group g (group == nullptr: everything is group 0); one workgroup, fixed order
-__global__ __launch_bounds__(256) void k_group_sum(long long cnt, const unsigned char* __restrict__ group, const double* __restrict__ fv, double* __restrict__ out2) {
-    __shared__ double sh[2][256];
-    double a0 = 0.0, a1 = 0.0;
-    for (long long k = threadIdx.x; k < cnt; k += 256) {
-        const double v = fv[k];
-        if (group && group[k]) a1 += v; else a0 += v;
-    }
-    sh[0][threadIdx.x] = a0; sh[1][threadIdx.x] = a1;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { sh[0][threadIdx.x] += sh[0][threadIdx.x + o]; sh[1][threadIdx.x] += sh[1][threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { out2[0] = sh[0][0]; out2[1] = sh[1][0]; }
-}
+// (the group sum of the per-face summands: k_group_sum, das_reduce.hpp)
 // tangent of the objective for seeded boundary values (dF/d(BC value), one forward pass): per-face summands
 template <bool RHO, bool SOLID = false>
 __global__ __launch_bounds__(256) void k_fn_tangent(DevMesh m, ResParams prm, const Dual<1>* __restrict__ W, const Dual<1>* nut, const Dual<1>* gU,
@@ -208,19 +195,6 @@ __global__ __launch_bounds__(256) void k_fn_tangent(DevMesh m, ResParams prm, co
     if (fn.dir) { dir[0] = fn.dir[3 * k]; dir[1] = fn.dir[3 * k + 1]; dir[2] = fn.dir[3 * k + 2]; }
     Dual<1> v = facefn_of<Dual<1>, RHO, SOLID>(fn.faces[k], m, prm, W, nut, gU, fn.kind, dir, fn.gammaFn, fn.RFn, fn.loc, fn.pRef);
     fv[k] = seed * fn.w[k] * v.d[0];
-}
-// part[b] = sum over the block's rows of psi_i * dR_i  (dR = tangent part of a dual residual); k_group_sum adds the parts
-__global__ __launch_bounds__(256) void k_tangent_dot(long long n, const Dual<1>* __restrict__ R, const double* __restrict__ psi, double* __restrict__ part) {
-    __shared__ double sh[256];
-    double acc = 0.0;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) acc += psi[i] * R[i].d[0];
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
 }
 // the derivative of q_f w.r.t. the (unique) state of colour `col` in the stencil of face f (cell c and its face
 // neighbours: U, p, (T), nuTilda) is accumulated into dFdW
@@ -3606,16 +3580,8 @@ __global__ __launch_bounds__(256) void k_simple_correct(long long N, int offP, c
     const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (c < N) body_sv_correct(c, N, offP, HbyA, rAU, gradP, pRel, Wn);
 }
-// small vector kernels of the inner Krylov solvers (host scalars; the sweeps are the reference's primal, not the fast path)
-__global__ __launch_bounds__(256) void k_sv_dot(long long n, const double* __restrict__ a, const double* __restrict__ b, double* __restrict__ part) {
-    __shared__ double sh[256];
-    double acc = 0.0;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) acc += a[i] * b[i];
-    sh[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o]; __syncthreads(); }
-    if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
-}
+// small vector kernels of the inner Krylov solvers (host scalars; the sweeps are the reference's primal, not the fast path); their dot
+// product is k_sv_dot of das_reduce.hpp
 __global__ __launch_bounds__(256) void k_sv_lin(long long n, double* y, double a, const double* x, double b, const double* z) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) body_sv_lin(i, y, a, x, b, z);
@@ -3652,13 +3618,11 @@ __global__ __launch_bounds__(256) void k_sv_bound(long long n, const double* x, 
 // device storage of one run of sweeps: the vectors of SimpleVecs and the partial sums of the dot product
 struct SimpleWork {
     std::vector<DevBuf<double>> store;
-    DevBuf<double> part{512}, red{2};
+    DevBuf<double> part{DAS_SV_DOT_MAX_BLOCKS}, red{2};
     double* take(long long cnt) { store.emplace_back((size_t)cnt); return store.back().p; }
 };
 static double sv_dot(hipStream_t st, SimpleWork& w, long long n, const double* a, const double* b) {
-    const int nb = (int)std::min<long long>(512, (n + 255) / 256);
-    hipLaunchKernelGGL(k_sv_dot, dim3(nb), dim3(256), 0, st, n, a, b, w.part.p);
-    hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, st, (long long)nb, (const unsigned char*)nullptr, (const double*)w.part.p, w.red.p);
+    launch_sv_dot(st, n, a, b, w.part.p, w.red.p);
     double h[2];
     DAS_HIP(hipMemcpyAsync(h, w.red.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
     DAS_HIP(hipStreamSynchronize(st));
@@ -4376,9 +4340,6 @@ static const double* cell_function_src(das_solver* s, das_solver::CellFn& fn) {
     if (fn.d_unit.n != (size_t)s->mesh.nC) fn.d_unit.upload(std::vector<double>(s->mesh.nC, fn.constSrc ? s->cp.solidRho : 1.0));
     return fn.d_unit.p;
 }
-static int cell_function_blocks(const das_solver::CellFn& fn) {
-    return std::max(1, std::min(DAS_CELLFN_MAX_BLOCKS, nblk((long long)fn.cell.size(), 256)));
-}
 // vonMisesStressKS: gradD of the residual pass (traction passes included) into s->wk.gU, vm of the terms into fn.d_a, then the
 // max-shifted two-stage KS sum of das_facefn.hpp; {m, S} stay in fn.d_ks for the weights.  F0 = (m + log S) / coeffKS.  The reference
 // aborts when its plain sum of exponentials passes 1e200; the log-space sum has no such limit and none is imposed (wider than the reference).
@@ -4387,16 +4348,12 @@ static double vm_ks_value(das_solver* s, das_solver::CellFn& fn) {
     DAS_CHECK(nt > 0, DAS_ERR_ARG, "vonMisesStressKS: the cell set is empty");
     const ResParams prm = s->wk.bind(s->cp.solver, s->dm.nC, s->dm.nF, make_params(s->cp, s->opt, 0));
     launch_solid_grad<double, double>(s->dm, prm, (const double*)s->d_W.p, s->wk, s->stream);
-    const int nb = cell_function_blocks(fn);
     if (fn.d_ks.n != 2) fn.d_ks.alloc(2);
-    if (fn.d_kpart.n != DAS_CELLFN_MAX_BLOCKS) fn.d_kpart.alloc(DAS_CELLFN_MAX_BLOCKS);
+    if (fn.d_kpart.n != DAS_FACEFN_MAX_BLOCKS) fn.d_kpart.alloc(DAS_FACEFN_MAX_BLOCKS);
     if (fn.d_a.n != (size_t)nt) { fn.d_a.alloc(nt); fn.d_wt.alloc(nt); }
     if (fn.d_wc.n != (size_t)s->mesh.nC) fn.d_wc.alloc(s->mesh.nC);
     hipLaunchKernelGGL(k_vm_terms, dim3(nblk(nt, 256)), dim3(256), 0, s->stream, nt, (const int*)fn.d_cell.p, prm, (const double*)s->wk.gU.p, fn.scale, fn.d_a.p);
-    hipLaunchKernelGGL(k_ks_max, dim3(nb), dim3(256), 0, s->stream, nt, (const double*)fn.d_a.p, fn.coeffKS, fn.d_kpart.p);
-    hipLaunchKernelGGL(k_ks_max_final, dim3(1), dim3(256), 0, s->stream, nb, (const double*)fn.d_kpart.p, fn.d_ks.p);
-    hipLaunchKernelGGL(k_ks_expsum, dim3(nb), dim3(256), 0, s->stream, nt, (const double*)fn.d_a.p, fn.coeffKS, (const double*)fn.d_ks.p, fn.d_kpart.p);
-    hipLaunchKernelGGL(k_ks_sum_final, dim3(1), dim3(256), 0, s->stream, nb, (const double*)fn.d_kpart.p, fn.d_ks.p);
+    launch_ks_reduce(s->stream, nt, (const double*)fn.d_a.p, fn.coeffKS, fn.d_kpart.p, fn.d_ks.p);
     DAS_HIP(hipGetLastError());
     double ms[2];
     DAS_HIP(hipMemcpyAsync(ms, fn.d_ks.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -4407,7 +4364,7 @@ static double vm_ks_value(das_solver* s, das_solver::CellFn& fn) {
 static void vm_ks_cell_weights(das_solver* s, das_solver::CellFn& fn, double seed) {
     const double outer = seed * ref_var_outer(fn.refVar, fn.ref, vm_ks_value(s, fn));
     const long long nt = (long long)fn.cell.size();
-    hipLaunchKernelGGL(k_ks_weights, dim3(nblk(nt, 256)), dim3(256), 0, s->stream, nt, (const double*)fn.d_a.p, fn.coeffKS, (const double*)fn.d_ks.p, outer, fn.d_wt.p);
+    launch_ks_weights(s->stream, nt, (const double*)fn.d_a.p, fn.coeffKS, (const double*)fn.d_ks.p, outer, fn.d_wt.p);
     DAS_HIP(hipMemsetAsync(fn.d_wc.p, 0, (size_t)s->mesh.nC * sizeof(double), s->stream));
     hipLaunchKernelGGL(k_vm_cell_weights, dim3(nblk(nt, 256)), dim3(256), 0, s->stream, nt, (const int*)fn.d_cell.p, (const double*)fn.d_wt.p, fn.d_wc.p);
     DAS_HIP(hipGetLastError());
@@ -4426,7 +4383,7 @@ static void vm_ks_gradient(das_solver* s, das_solver::CellFn& fn, double seed, d
         hipLaunchKernelGGL(k_seed<1>, dim3(nblk(n, B)), dim3(B), 0, s->stream, n, s->d_W.p, s->d_colors.p, s->d_scale.p, col, s->d_Wd.p);
         launch_solid_grad<Dual<1>, double>(s->dm, prm, (const Dual<1>*)s->d_Wd.p, s->wk1, s->stream);
         hipLaunchKernelGGL(k_vm_tangent, dim3(nblk(s->dm.nC, B)), dim3(B), 0, s->stream, s->dm.nC, prm, (const Dual<1>*)s->wk1.gU.p, fn.scale, (const double*)fn.d_wc.p, s->d_tmp1.p);
-        hipLaunchKernelGGL(k_vm_gather, dim3(nblk(n, B)), dim3(B), 0, s->stream, s->dm, (const int*)s->d_colors.p, col, (const double*)s->d_tmp1.p, seed, s->d_tmp2.p);
+        launch_vm_gather(s->stream, s->dm, (const int*)s->d_colors.p, col, (const double*)s->d_tmp1.p, seed, s->d_tmp2.p);
     }
     DAS_HIP(hipGetLastError());
     DAS_HIP(hipMemcpyAsync(product, s->d_tmp2.p, n * sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -4436,9 +4393,7 @@ static void vm_ks_gradient(das_solver* s, das_solver::CellFn& fn, double seed, d
 static double cell_function_base_value(das_solver* s, das_solver::CellFn& fn) {
     if (fn.vmKS) return vm_ks_value(s, fn);
     if (fn.coef == 0.0) return 0.0;
-    const int nb = cell_function_blocks(fn);
-    hipLaunchKernelGGL(k_cellfn_value, dim3(nb), dim3(256), 0, s->stream, fn.view(), (const CellGeom*)s->d_cg.p, cell_function_src(s, fn), fn.d_part.p);
-    hipLaunchKernelGGL(k_cellfn_sum, dim3(1), dim3(256), 0, s->stream, nb, (const double*)fn.d_part.p, fn.coef, s->d_tmp1.p);
+    launch_cellfn_value(s->stream, fn.view(), (const CellGeom*)s->d_cg.p, cell_function_src(s, fn), fn.coef, fn.d_part.p, s->d_tmp1.p);
     DAS_HIP(hipGetLastError());
     double v = 0.0;
     DAS_HIP(hipMemcpyAsync(&v, s->d_tmp1.p, sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -4454,8 +4409,8 @@ static void cell_function_gradient(das_solver* s, das_solver::CellFn& fn, double
     const double g = seed * cell_function_outer(s, fn) * fn.coef;
     DAS_HIP(hipMemsetAsync(s->d_tmp2.p, 0, len * sizeof(double), s->stream));
     if (g != 0.0 && !fn.cell.empty())
-        hipLaunchKernelGGL(k_cellfn_grad, dim3(nblk((long long)fn.cell.size(), 256)), dim3(256), 0, s->stream, fn.view(), (const CellGeom*)s->d_cg.p,
-                           cell_function_src(s, fn), stateScaled ? (const double*)s->d_scale.p : (const double*)nullptr, g, s->d_tmp2.p);
+        launch_cellfn_grad(s->stream, fn.view(), (const CellGeom*)s->d_cg.p, cell_function_src(s, fn),
+                           stateScaled ? (const double*)s->d_scale.p : (const double*)nullptr, g, s->d_tmp2.p);
     DAS_HIP(hipGetLastError());
     DAS_HIP(hipMemcpyAsync(out, s->d_tmp2.p, len * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     DAS_HIP(hipStreamSynchronize(s->stream));
@@ -4490,7 +4445,7 @@ static void function_sums(das_solver* s, das_solver::FaceFn& fn, double S[2]) {
             hipLaunchKernelGGL((k_fn_value<decltype(R)::value, decltype(R)::solid>), dim3(nblk(nf, B)), dim3(B), 0, s->stream, s->dm, prm, s->d_W.p, s->wk.nut.p, s->wk.gU.p, fn.view(fn.d_w0.p), fn.d_fv.p);
         });
     }
-    hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, s->stream, (long long)nf, (const unsigned char*)fn.d_group.p, (const double*)fn.d_fv.p, s->d_tmp1.p);
+    launch_group_sum(s->stream, (long long)nf, (const unsigned char*)fn.d_group.p, (const double*)fn.d_fv.p, s->d_tmp1.p);
     DAS_HIP(hipGetLastError());
     DAS_HIP(hipMemcpyAsync(S, s->d_tmp1.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
     DAS_HIP(hipStreamSynchronize(s->stream));
@@ -4502,12 +4457,8 @@ static double location_ks_value(das_solver* s, das_solver::FaceFn& fn) {
     double unused[2];
     function_sums(s, fn, unused);  // a_f -> fn.d_fv
     const long long nf = (long long)fn.faces.size();
-    const int nb = std::max(1, std::min(DAS_FACEFN_MAX_BLOCKS, nblk(nf, 256)));
     if (fn.d_ks.n != 2) { fn.d_ks.alloc(2); fn.d_kpart.alloc(DAS_FACEFN_MAX_BLOCKS); }
-    hipLaunchKernelGGL(k_ks_max, dim3(nb), dim3(256), 0, s->stream, nf, (const double*)fn.d_fv.p, fn.coeffKS, fn.d_kpart.p);
-    hipLaunchKernelGGL(k_ks_max_final, dim3(1), dim3(256), 0, s->stream, nb, (const double*)fn.d_kpart.p, fn.d_ks.p);
-    hipLaunchKernelGGL(k_ks_expsum, dim3(nb), dim3(256), 0, s->stream, nf, (const double*)fn.d_fv.p, fn.coeffKS, (const double*)fn.d_ks.p, fn.d_kpart.p);
-    hipLaunchKernelGGL(k_ks_sum_final, dim3(1), dim3(256), 0, s->stream, nb, (const double*)fn.d_kpart.p, fn.d_ks.p);
+    launch_ks_reduce(s->stream, nf, (const double*)fn.d_fv.p, fn.coeffKS, fn.d_kpart.p, fn.d_ks.p);
     DAS_HIP(hipGetLastError());
     double ms[2];
     DAS_HIP(hipMemcpyAsync(ms, fn.d_ks.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -4530,7 +4481,7 @@ static void function_effective_weights(das_solver* s, das_solver::FaceFn& fn) {
         const double outer = ref_var_outer(fn.refVar, fn.ref, F0);
         const long long nf = (long long)fn.faces.size();
         if (fn.ks) {
-            hipLaunchKernelGGL(k_ks_weights, dim3(nblk(nf, 256)), dim3(256), 0, s->stream, nf, (const double*)fn.d_fv.p, fn.coeffKS, (const double*)fn.d_ks.p, outer, fn.d_weff.p);
+            launch_ks_weights(s->stream, nf, (const double*)fn.d_fv.p, fn.coeffKS, (const double*)fn.d_ks.p, outer, fn.d_weff.p);
             DAS_HIP(hipGetLastError());
         } else {
             fn.d_weff.upload(std::vector<double>(fn.w0.size(), outer));
@@ -4626,7 +4577,6 @@ int das_define_residual_norm_function(das_solver_t* s, const char* name, const c
     return DAS_OK;
     DAS_CATCH
 }
-static int mesh_function_blocks(long long n) { return std::max(1, std::min(DAS_FACEFN_MAX_BLOCKS, nblk(n, 256))); }
 // a_f of all faces at the current metrics -> fn.d_a, then the max-shifted two-stage KS sum; {m, S} stay in fn.d_ks for k_ks_weights.
 // F0 = (m + log S) / coeffKS.  The reference aborts when its plain sum of exponentials passes 1e200; the log-space sum has no such limit
 // and none is imposed (as for vonMisesStressKS).
@@ -4638,13 +4588,9 @@ static double mesh_quality_value(das_solver* s, das_solver::MeshFn& fn) {
     if (fn.xGeom != s->geomVersion) { fn.d_X.upload(m.points.data(), 3 * (size_t)m.nP); fn.xGeom = s->geomVersion; }
     if (fn.d_a.n != (size_t)nF) { fn.d_a.alloc(nF); fn.d_w.alloc(nF); }
     if (fn.d_ks.n != 2) { fn.d_ks.alloc(2); fn.d_kpart.alloc(DAS_FACEFN_MAX_BLOCKS); }
-    const int nb = mesh_function_blocks(nF);
     hipLaunchKernelGGL(k_mq_metric<double>, dim3(nblk(nF, 256)), dim3(256), 0, s->stream, t, (const double*)fn.d_X.p, (const FaceGeom*)s->d_fg.p,
                        (const CellGeom*)s->d_cg.p, fn.metric, (const double*)nullptr, fn.d_a.p);
-    hipLaunchKernelGGL(k_ks_max, dim3(nb), dim3(256), 0, s->stream, nF, (const double*)fn.d_a.p, fn.coeffKS, fn.d_kpart.p);
-    hipLaunchKernelGGL(k_ks_max_final, dim3(1), dim3(256), 0, s->stream, nb, (const double*)fn.d_kpart.p, fn.d_ks.p);
-    hipLaunchKernelGGL(k_ks_expsum, dim3(nb), dim3(256), 0, s->stream, nF, (const double*)fn.d_a.p, fn.coeffKS, (const double*)fn.d_ks.p, fn.d_kpart.p);
-    hipLaunchKernelGGL(k_ks_sum_final, dim3(1), dim3(256), 0, s->stream, nb, (const double*)fn.d_kpart.p, fn.d_ks.p);
+    launch_ks_reduce(s->stream, nF, (const double*)fn.d_a.p, fn.coeffKS, fn.d_kpart.p, fn.d_ks.p);
     DAS_HIP(hipGetLastError());
     double ms[2];
     DAS_HIP(hipMemcpyAsync(ms, fn.d_ks.p, 2 * sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -4655,7 +4601,7 @@ static double mesh_quality_value(das_solver* s, das_solver::MeshFn& fn) {
 static void mesh_quality_weights(das_solver* s, das_solver::MeshFn& fn, double seed) {
     const double outer = seed * ref_var_outer(fn.refVar, fn.ref, mesh_quality_value(s, fn));
     const long long nF = s->mesh.nF;
-    hipLaunchKernelGGL(k_ks_weights, dim3(nblk(nF, 256)), dim3(256), 0, s->stream, nF, (const double*)fn.d_a.p, fn.coeffKS, (const double*)fn.d_ks.p, outer, fn.d_w.p);
+    launch_ks_weights(s->stream, nF, (const double*)fn.d_a.p, fn.coeffKS, (const double*)fn.d_ks.p, outer, fn.d_w.p);
     DAS_HIP(hipGetLastError());
 }
 static RnRows residual_norm_rows(das_solver* s, const das_solver::MeshFn& fn) {
@@ -4676,10 +4622,7 @@ static double residual_norm_value(das_solver* s, das_solver::MeshFn& fn) {
     eval_residual<double>(s->dm, s->cp, prm, s->d_W.p, s->d_R.p, s->wk, s->d_phiF.p, s->d_Told.p, s->stream);
     if (fn.d_a.n != (size_t)n) fn.d_a.alloc(n);
     if (fn.d_ks.n != 2) { fn.d_ks.alloc(2); fn.d_kpart.alloc(DAS_FACEFN_MAX_BLOCKS); }
-    const int nb = mesh_function_blocks(n);
-    hipLaunchKernelGGL(k_rn_terms, dim3(nblk(n, 256)), dim3(256), 0, s->stream, n, residual_norm_rows(s, fn), (const double*)s->d_R.p, fn.d_a.p);
-    hipLaunchKernelGGL(k_rn_partial, dim3(nb), dim3(256), 0, s->stream, n, (const double*)fn.d_a.p, fn.d_kpart.p);
-    hipLaunchKernelGGL(k_ks_sum_final, dim3(1), dim3(256), 0, s->stream, nb, (const double*)fn.d_kpart.p, fn.d_ks.p);
+    launch_rn_sum(s->stream, n, residual_norm_rows(s, fn), (const double*)s->d_R.p, fn.d_a.p, fn.d_kpart.p, fn.d_ks.p);
     DAS_HIP(hipGetLastError());
     double sum = 0.0;
     DAS_HIP(hipMemcpyAsync(&sum, fn.d_ks.p + 1, sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -4691,7 +4634,7 @@ static void residual_norm_seeds(das_solver* s, das_solver::MeshFn& fn, double se
     const double F0 = residual_norm_value(s, fn);
     DAS_CHECK(fn.l1 || F0 != 0.0, DAS_ERR_ARG, "residualNorm function " + fn.name + ": the L2Norm is zero, where it has no derivative");
     const double coef = seed * ref_var_outer(fn.refVar, fn.ref, F0);
-    hipLaunchKernelGGL(k_rn_seeds, dim3(nblk(s->n, 256)), dim3(256), 0, s->stream, (long long)s->n, residual_norm_rows(s, fn), (const double*)s->d_R.p, F0, coef, d_g);
+    launch_rn_seeds(s->stream, (long long)s->n, residual_norm_rows(s, fn), (const double*)s->d_R.p, F0, coef, d_g);
     DAS_HIP(hipGetLastError());
 }
 // The product of a residualNorm function from any input is the existing  input -> residual  product with the seeds g = seed dF/dR:
@@ -5125,9 +5068,8 @@ int das_calc_dbc_product(das_solver_t* s, const int* patches, int np, const char
     if (ot == "residual") {
         eval_residual<Dual<1>>(s->dm, s->cp, prm, s->d_Wd.p, s->d_Rd.p, s->wk1, s->d_phiF.p, s->d_Told.p, st);
         DAS_HIP(hipMemcpyAsync(s->d_tmp2.p, seeds, n * sizeof(double), hipMemcpyHostToDevice, st));
-        DevBuf<double> part(1024);
-        hipLaunchKernelGGL(k_tangent_dot, dim3(1024), dim3(256), 0, st, n, s->d_Rd.p, s->d_tmp2.p, part.p);
-        hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, st, 1024LL, (const unsigned char*)nullptr, (const double*)part.p, s->d_tmp1.p);
+        DevBuf<double> part(DAS_TANGENT_DOT_BLOCKS);
+        launch_tangent_dot(st, n, (const Dual<1>*)s->d_Rd.p, (const double*)s->d_tmp2.p, part.p, s->d_tmp1.p);
         DAS_HIP(hipStreamSynchronize(st));  // part goes out of scope
     } else if (!isFC && find_cell_function(s, outputName)) {
         // variableVolSum reads no boundary value.  vonMisesStressKS does - vm of a boundary cell follows a fixedValue D through the cell
@@ -5149,7 +5091,7 @@ int das_calc_dbc_product(das_solver_t* s, const int* patches, int np, const char
         launch_grad_and_faces(st, rho, s->dm, prm, (const Dual<1>*)s->d_Wd.p, s->wk1, true, [&](auto R) {
             hipLaunchKernelGGL((k_fn_tangent<decltype(R)::value, decltype(R)::solid>), dim3(nblk(nf, B)), dim3(B), 0, st, s->dm, prm, s->d_Wd.p, s->wk1.nut.p, s->wk1.gU.p, fn.view(fn.d_weff.p), fnSeed, fn.d_fv.p);
         });
-        hipLaunchKernelGGL(k_group_sum, dim3(1), dim3(256), 0, st, (long long)nf, (const unsigned char*)nullptr, (const double*)fn.d_fv.p, s->d_tmp1.p);
+        launch_group_sum(st, (long long)nf, nullptr, (const double*)fn.d_fv.p, s->d_tmp1.p);
     }
     DAS_HIP(hipGetLastError());
     DAS_HIP(hipMemcpyAsync(product, s->d_tmp1.p, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -5499,11 +5441,8 @@ static HsView<P> heat_source_view(const das_solver::HeatSource& h) {
 // out[0] = the two-stage sum of k_hs_partial / k_hs_final over all cells
 template <class R, class P, class G>
 static void heat_source_sum(das_solver* s, const HsView<P>& v, const CellGeomT<G>* cg, const double* psi, int byV, const R* vt, R* out) {
-    const int nC = s->mesh.nC, nb = std::min(nblk(nC, 256), DAS_HS_MAX_BLOCKS);
     if (s->d_hsPart.n < (size_t)DAS_HS_MAX_BLOCKS) s->d_hsPart.alloc(DAS_HS_MAX_BLOCKS);
-    R* part = reinterpret_cast<R*>(s->d_hsPart.p);
-    hipLaunchKernelGGL((k_hs_partial<R, P, G>), dim3(nb), dim3(256), 0, s->stream, v, nC, cg, psi, byV, vt, part);
-    hipLaunchKernelGGL((k_hs_final<R>), dim3(1), dim3(256), 0, s->stream, nb, (const R*)part, out);
+    launch_hs_sum<R, P, G>(s->stream, v, s->mesh.nC, cg, psi, byV, vt, reinterpret_cast<R*>(s->d_hsPart.p), out);
 }
 }  // extern "C++"
 static void refresh_heat_sources(das_solver* s, bool check) {
@@ -5774,11 +5713,8 @@ static Dual<1>& actuator_disk_par(AdView<Dual<1>>& v, int idx) {
 // out2 = {sum fAxial V, sum fCirc V} at the scale scale[0] (null: 1) through k_ad_partial / k_ad_final
 template <class R, class P, class G>
 static void actuator_disk_sums(das_solver* s, const AdView<P>& v, const CellGeomT<G>* cg, const R* scale, R* out2) {
-    const int nC = s->mesh.nC, nb = std::min(nblk(nC, 256), DAS_HS_MAX_BLOCKS);
     if (s->d_adPart.n < (size_t)2 * DAS_HS_MAX_BLOCKS) s->d_adPart.alloc((size_t)2 * DAS_HS_MAX_BLOCKS);
-    R* part = reinterpret_cast<R*>(s->d_adPart.p);
-    hipLaunchKernelGGL((k_ad_partial<R, P, G>), dim3(nb), dim3(256), 0, s->stream, v, nC, cg, scale, part);
-    hipLaunchKernelGGL((k_ad_final<R>), dim3(1), dim3(256), 0, s->stream, nb, (const R*)part, out2);
+    launch_ad_sums<R, P, G>(s->stream, v, s->mesh.nC, cg, scale, reinterpret_cast<R*>(s->d_adPart.p), out2);
 }
 // the whole field of the disks views[0..K) into src3 (3 nC); work: 5 slots per disk {unit sums(2), scale, sums(2)}; withSums: the
 // thrust and torque sums at the effective scale as well
@@ -6003,9 +5939,7 @@ struct AdDualResidual {
         }
         actuator_disk_field<D, D, double>(s, views, (const CellGeom*)s->d_cg.p, d_work.p, d_src3D.p, false);
         eval_residual<D, D>(dmD, s->cp, prm0, d_Wd.p, d_Rd.p, s->wk1, s->d_phiF.p, s->d_Told.p, st);
-        const int nb = std::min(nblk(s->n, 256), DAS_HS_MAX_BLOCKS);
-        hipLaunchKernelGGL(k_ad_dot_partial, dim3(nb), dim3(256), 0, st, (long long)s->n, (const double*)d_psi.p, (const D*)d_Rd.p, d_part.p);
-        hipLaunchKernelGGL((k_hs_final<double>), dim3(1), dim3(256), 0, st, nb, (const double*)d_part.p, d_out.p);
+        launch_ad_dot(st, (long long)s->n, (const double*)d_psi.p, (const D*)d_Rd.p, d_part.p, d_out.p);
         DAS_HIP(hipGetLastError());
         double r = 0.0;
         DAS_HIP(hipMemcpyAsync(&r, d_out.p, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -6183,7 +6117,7 @@ static void volcoord_product_dual(das_solver* s, das_solver::FaceFn* fn, bool ar
             if (isMq) {
                 hipLaunchKernelGGL(k_mq_metric<D>, dim3(nblk(t.nF, B)), dim3(B), 0, st, t, (const D*)d_XD.p, (const FaceGeomT<D>*)d_fgD.p, (const CellGeomT<D>*)d_cgD.p,
                                    mq->metric, (const double*)mq->d_w.p, d_fvd.p);
-                hipLaunchKernelGGL(k_mq_owner_gather, dim3(nblk(m.nC, B)), dim3(B), 0, st, m.nC, t.cf_ptr, t.cf_face, (const double*)d_fvd.p, d_tc.p);
+                launch_mq_owner_gather(st, m.nC, t.cf_ptr, t.cf_face, (const double*)d_fvd.p, d_tc.p);
             } else if (isVm) {
                 const ResParams prm = s->wk1.bind(s->cp.solver, s->dm.nC, s->dm.nF, prm0);
                 launch_solid_grad<D, D>(dmD, prm, (const D*)d_Wd.p, s->wk1, st);
@@ -7869,6 +7803,165 @@ int das_debug_color_check(long long n, const long long* rowptr, const int* col, 
     DAS_CHECK(invalid, DAS_ERR_ARG, who + ": null pointer");
     DAS_GRAPH_DEVICE(who);
     debug_color_check(n, rowptr, col, nKeep, keep, colors, W, invalid);
+    return DAS_OK;
+    DAS_CATCH
+}
+// Test-only entries (tests/test_gpu_reduce_kernels.py): the reductions of the objective functions and the two gathers on caller-made
+// arrays through the launch helpers the solver uses (das_reduce_debug.hpp).  Everything is checked on the host before anything is launched.
+#define DAS_REDUCE_MAX_N (1LL << 31)
+int das_debug_reduce_ks(long long n, double* a, double k, double outer, double* ms, long long msLen, double* pmax, double* psum, long long partLen, double* w,
+                        long long wLen, int* nb) {
+    DAS_TRY
+    const std::string who = "das_debug_reduce_ks";
+    DAS_CHECK(n >= 1 && n < DAS_REDUCE_MAX_N, DAS_ERR_ARG, who + ": n outside [1, 2^31) (an empty set has no KS aggregate)");
+    DAS_CHECK(a && ms && pmax && psum && w && nb, DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(msLen >= 2 && partLen >= DAS_FACEFN_MAX_BLOCKS && wLen >= n, DAS_ERR_ARG, who + ": ms shorter than 2, a partial array shorter than 1024 or w shorter than n");
+    DAS_GRAPH_DEVICE(who);
+    debug_reduce_ks(n, a, k, outer, ms, msLen, pmax, psum, partLen, w, wLen, nb);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_reduce_group_sum(long long cnt, unsigned char* group, double* fv, double* out2, long long outLen) {
+    DAS_TRY
+    const std::string who = "das_debug_reduce_group_sum";
+    DAS_CHECK(cnt >= 0 && cnt < DAS_REDUCE_MAX_N, DAS_ERR_ARG, who + ": cnt outside [0, 2^31)");
+    DAS_CHECK(fv && out2, DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(outLen >= 2, DAS_ERR_ARG, who + ": out2 shorter than 2");
+    DAS_GRAPH_DEVICE(who);
+    debug_reduce_group_sum(cnt, group, fv, out2, outLen);
+    return DAS_OK;
+    DAS_CATCH
+}
+static void reduce_check_dot(const std::string& who, long long n, long long nMin, const void* a, const void* b, const void* part, long long partLen, long long partMin,
+                             const void* out, long long outLen, long long outMin, const int* nb) {
+    DAS_CHECK(n >= nMin && n < DAS_REDUCE_MAX_N, DAS_ERR_ARG, who + ": n out of range");
+    DAS_CHECK(a && b && part && out && nb, DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(partLen >= partMin && outLen >= outMin, DAS_ERR_ARG, who + ": the partial array or the output is too short");
+}
+int das_debug_reduce_tangent_dot(long long n, double* R, double* psi, double* part, long long partLen, double* out2, long long outLen, int* nb) {
+    DAS_TRY
+    const std::string who = "das_debug_reduce_tangent_dot";
+    reduce_check_dot(who, n, 0, R, psi, part, partLen, DAS_TANGENT_DOT_BLOCKS, out2, outLen, 2, nb);
+    DAS_GRAPH_DEVICE(who);
+    debug_reduce_dual_dot(0, n, R, psi, part, partLen, out2, outLen, nb);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_reduce_ad_dot(long long n, double* R, double* psi, double* part, long long partLen, double* out, long long outLen, int* nb) {
+    DAS_TRY
+    const std::string who = "das_debug_reduce_ad_dot";
+    reduce_check_dot(who, n, 1, R, psi, part, partLen, DAS_HS_MAX_BLOCKS, out, outLen, 1, nb);
+    DAS_GRAPH_DEVICE(who);
+    debug_reduce_dual_dot(1, n, R, psi, part, partLen, out, outLen, nb);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_reduce_sv_dot(long long n, double* a, double* b, double* part, long long partLen, double* out2, long long outLen, int* nb) {
+    DAS_TRY
+    const std::string who = "das_debug_reduce_sv_dot";
+    reduce_check_dot(who, n, 1, a, b, part, partLen, DAS_SV_DOT_MAX_BLOCKS, out2, outLen, 2, nb);
+    DAS_GRAPH_DEVICE(who);
+    debug_reduce_sv_dot(n, a, b, part, partLen, out2, outLen, nb);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_reduce_cellfn(long long nt, int* cell, long long* idx, double* data, int square, int mv, long long nCells, const double* V, long long nSrc, double* src,
+                            double coef, double* part, long long partLen, double* out, long long outLen, double* sc, double g, double* grad, long long gradLen, int* nb) {
+    DAS_TRY
+    const std::string who = "das_debug_reduce_cellfn";
+    DAS_CHECK(nt >= 1 && nt < DAS_REDUCE_MAX_N && nCells >= 1 && nCells < DAS_REDUCE_MAX_N && nSrc >= 1 && nSrc < DAS_REDUCE_MAX_N, DAS_ERR_ARG, who + ": sizes outside [1, 2^31)");
+    DAS_CHECK(cell && idx && V && src && part && out && grad && nb, DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(partLen >= DAS_CELLFN_MAX_BLOCKS && outLen >= 1 && gradLen >= nSrc, DAS_ERR_ARG, who + ": part shorter than 1024, out empty or grad shorter than nSrc");
+    std::vector<unsigned char> seen((size_t)nSrc, 0);
+    for (long long t = 0; t < nt; t++) {
+        DAS_CHECK(cell[t] >= 0 && cell[t] < nCells, DAS_ERR_ARG, who + ": cell out of range");
+        DAS_CHECK(idx[t] >= 0 && idx[t] < nSrc, DAS_ERR_ARG, who + ": idx out of range");
+        DAS_CHECK(!seen[idx[t]], DAS_ERR_ARG, who + ": idx repeated (the terms of a function address distinct entries)");
+        seen[idx[t]] = 1;
+    }
+    DAS_GRAPH_DEVICE(who);
+    debug_reduce_cellfn(nt, cell, idx, data, square, mv, nCells, V, nSrc, src, coef, part, partLen, out, outLen, sc, g, grad, gradLen, nb);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_reduce_rn(long long n, int nblocks, const long long* off, const int* kind, const double* w, long long nC, long long nF, long long nIF, int l1, double* R,
+                        double* term, long long termLen, double* part, long long partLen, double* ms, long long msLen, double F, double coef, double* g, long long gLen,
+                        int* nb) {
+    DAS_TRY
+    const std::string who = "das_debug_reduce_rn";
+    DAS_CHECK(n >= 1 && n < DAS_REDUCE_MAX_N, DAS_ERR_ARG, who + ": n outside [1, 2^31)");
+    DAS_CHECK(nblocks >= 0 && nblocks <= 8, DAS_ERR_ARG, who + ": 0 to 8 residual blocks");
+    DAS_CHECK(off && kind && w && R && term && part && ms && g && nb, DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(nC >= 0 && nF >= 0 && nIF >= 0 && nIF <= nF && nC < DAS_REDUCE_MAX_N && nF < DAS_REDUCE_MAX_N, DAS_ERR_ARG, who + ": bad nC / nF / nIF");
+    DAS_CHECK(termLen >= n && gLen >= n && partLen >= DAS_FACEFN_MAX_BLOCKS && msLen >= 2, DAS_ERR_ARG, who + ": an output array is too short");
+    DAS_CHECK(l1 || F != 0.0, DAS_ERR_ARG, who + ": the L2Norm seeds divide by F");
+    RnRows r{};
+    r.nb = nblocks;
+    for (int b = 0; b < nblocks; b++) {
+        DAS_CHECK(kind[b] == KIND_VEC || kind[b] == KIND_SCL || kind[b] == KIND_FACE, DAS_ERR_ARG, who + ": kind is 0 (vector), 1 (scalar) or 2 (face)");
+        r.off[b] = off[b]; r.kind[b] = kind[b]; r.w[b] = w[b];
+    }
+    r.nC = nC; r.nF = nF; r.nIF = nIF;
+    r.l1 = l1 ? 1 : 0;
+    DAS_GRAPH_DEVICE(who);
+    debug_reduce_rn(n, r, R, term, termLen, part, partLen, ms, msLen, F, coef, g, gLen, nb);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_reduce_hs_sum(int kind, int nC, const double* V, unsigned char* member, double* field, double* psi, int byV, double power, double* vt, double* part,
+                            long long partLen, double* out, long long outLen, int* nb) {
+    DAS_TRY
+    const std::string who = "das_debug_reduce_hs_sum";
+    DAS_CHECK(kind == DAS_HS_FIELD || kind == DAS_HS_CYLINDERTOCELL, DAS_ERR_ARG, who + ": kind is 0 (cylinderToCell) or 2 (field): the kinds that read volumes only");
+    DAS_CHECK(nC >= 1, DAS_ERR_ARG, who + ": nC must be positive");
+    DAS_CHECK(V && part && out && nb && (kind == DAS_HS_FIELD ? field != nullptr : member != nullptr), DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(!vt || psi, DAS_ERR_ARG, who + ": vt is read only with psi");
+    DAS_CHECK(partLen >= DAS_HS_MAX_BLOCKS && outLen >= 1, DAS_ERR_ARG, who + ": part shorter than 1024 or out empty");
+    DAS_GRAPH_DEVICE(who);
+    debug_reduce_hs_sum(kind, nC, V, member, field, psi, byV, power, vt, part, partLen, out, outLen, nb);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_reduce_final(int pair, int dual, int nb, double* part, long long partLen, double* out, long long outLen) {
+    DAS_TRY
+    const std::string who = "das_debug_reduce_final";
+    DAS_CHECK(nb >= 1 && nb <= DAS_HS_MAX_BLOCKS, DAS_ERR_ARG, who + ": nb outside 1 .. 1024");
+    DAS_CHECK(part && out, DAS_ERR_ARG, who + ": null pointer");
+    const long long per = (dual ? 2 : 1), cnt = (pair ? 2 : 1);
+    DAS_CHECK(partLen >= cnt * per * nb && outLen >= cnt * per && partLen % per == 0 && outLen % per == 0, DAS_ERR_ARG, who + ": part or out too short (or an odd count of dual halves)");
+    DAS_GRAPH_DEVICE(who);
+    if (dual) debug_reduce_final<Dual<1>>(pair, nb, part, partLen, out, outLen);
+    else debug_reduce_final<double>(pair, nb, part, partLen, out, outLen);
+    return DAS_OK;
+    DAS_CATCH
+}
+static void reduce_check_cell_faces(const std::string& who, int nC, const int* cf_ptr, const int* cf_face) {
+    DAS_CHECK(nC >= 1, DAS_ERR_ARG, who + ": nC must be positive");
+    DAS_CHECK(cf_ptr && cf_face, DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(cf_ptr[0] == 0, DAS_ERR_ARG, who + ": cf_ptr[0] != 0");
+    for (int c = 0; c < nC; c++) DAS_CHECK(cf_ptr[c + 1] >= cf_ptr[c], DAS_ERR_ARG, who + ": decreasing cf_ptr");
+}
+int das_debug_reduce_owner_gather(int nC, int* cf_ptr, int* cf_face, long long nFt, double* ft, double* tc, long long tcLen) {
+    DAS_TRY
+    const std::string who = "das_debug_reduce_owner_gather";
+    reduce_check_cell_faces(who, nC, cf_ptr, cf_face);
+    DAS_CHECK(ft && tc && nFt >= 1 && tcLen >= nC, DAS_ERR_ARG, who + ": null pointer, no face values or tc shorter than nC");
+    for (int s = 0; s < cf_ptr[nC]; s++) DAS_CHECK(cf_face[s] < nFt, DAS_ERR_ARG, who + ": face out of range");
+    DAS_GRAPH_DEVICE(who);
+    debug_reduce_owner_gather(nC, cf_ptr, cf_face, nFt, ft, tc, tcLen);
+    return DAS_OK;
+    DAS_CATCH
+}
+int das_debug_reduce_vm_gather(int nC, int nIF, int* cf_ptr, int* cf_face, int* cf_other, int* colors, int col, double* tc, double seed, double* out, long long outLen) {
+    DAS_TRY
+    const std::string who = "das_debug_reduce_vm_gather";
+    reduce_check_cell_faces(who, nC, cf_ptr, cf_face);
+    DAS_CHECK(cf_other && colors && tc && out, DAS_ERR_ARG, who + ": null pointer");
+    DAS_CHECK(nIF >= 0 && outLen >= 3LL * nC, DAS_ERR_ARG, who + ": negative nIF or out shorter than 3 nC");
+    for (int s = 0; s < cf_ptr[nC]; s++)
+        if ((cf_face[s] & 0x7fffffff) < nIF) DAS_CHECK(cf_other[s] >= 0 && cf_other[s] < nC, DAS_ERR_ARG, who + ": neighbour of an internal face out of range");
+    DAS_GRAPH_DEVICE(who);
+    debug_reduce_vm_gather(nC, nIF, cf_ptr, cf_face, cf_other, colors, col, tc, seed, out, outLen);
     return DAS_OK;
     DAS_CATCH
 }

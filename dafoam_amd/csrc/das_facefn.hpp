@@ -65,4 +65,31 @@ __global__ __launch_bounds__(256) void k_ks_weights(long long n, const double* _
     if (t < n) w[t] = outer * exp(k * a[t] - ms[0]) / ms[1];
 }
 
+// ---- launch helpers: the grid arithmetic of the KS reduction, once.  part holds DAS_FACEFN_MAX_BLOCKS entries, ms two ({m, S}) --------
+static inline int ks_blocks(long long n) { return std::max(1, std::min(DAS_FACEFN_MAX_BLOCKS, nblk(n, 256))); }
+// ms[0] = max_t k a_t; part[0 .. ks_blocks(n)) = the per-workgroup maxima
+static void launch_ks_max(hipStream_t st, long long n, const double* a, double k, double* part, double* ms) {
+    const int nb = ks_blocks(n);
+    hipLaunchKernelGGL(k_ks_max, dim3(nb), dim3(256), 0, st, n, a, k, part);
+    hipLaunchKernelGGL(k_ks_max_final, dim3(1), dim3(256), 0, st, nb, (const double*)part, ms);
+}
+// ms[1] = the fixed-order sum of nb partials (the second stage of the exponential sum and of residualNorm)
+static void launch_ks_sum_final(hipStream_t st, int nb, const double* part, double* ms) {
+    hipLaunchKernelGGL(k_ks_sum_final, dim3(1), dim3(256), 0, st, nb, part, ms);
+}
+// ms[1] = sum_t exp(k a_t - ms[0]); part[0 .. ks_blocks(n)) = the per-workgroup sums
+static void launch_ks_expsum(hipStream_t st, long long n, const double* a, double k, double* part, double* ms) {
+    const int nb = ks_blocks(n);
+    hipLaunchKernelGGL(k_ks_expsum, dim3(nb), dim3(256), 0, st, n, a, k, (const double*)ms, part);
+    launch_ks_sum_final(st, nb, part, ms);
+}
+// the whole sequence: {m, S} -> ms through one partial buffer
+static void launch_ks_reduce(hipStream_t st, long long n, const double* a, double k, double* part, double* ms) {
+    launch_ks_max(st, n, a, k, part, ms);
+    launch_ks_expsum(st, n, a, k, part, ms);
+}
+static void launch_ks_weights(hipStream_t st, long long n, const double* a, double k, const double* ms, double outer, double* w) {
+    hipLaunchKernelGGL(k_ks_weights, dim3(nblk(n, 256)), dim3(256), 0, st, n, a, k, ms, outer, w);
+}
+
 }  // namespace das

@@ -89,6 +89,19 @@ __global__ __launch_bounds__(256) void k_hs_final(int nb, const R* __restrict__ 
     acc = hs_block_sum<R>(acc);
     if (threadIdx.x == 0) out[0] = acc;
 }
+// ---- launch helpers: the grid arithmetic, once.  part holds DAS_HS_MAX_BLOCKS entries of R; n >= 1 -------------------------------------
+static inline int hs_blocks(long long n) { return std::min(nblk(n, 256), DAS_HS_MAX_BLOCKS); }
+template <class R>
+static void launch_hs_final(hipStream_t st, int nb, const R* part, R* out) {
+    hipLaunchKernelGGL((k_hs_final<R>), dim3(1), dim3(256), 0, st, nb, part, out);
+}
+// out[0] = the two-stage sum over all cells; part[0 .. hs_blocks(nC)) = the per-workgroup sums
+template <class R, class P, class G>
+static void launch_hs_sum(hipStream_t st, const HsView<P>& v, int nC, const CellGeomT<G>* cg, const double* psi, int byV, const R* vt, R* part, R* out) {
+    const int nb = hs_blocks(nC);
+    hipLaunchKernelGGL((k_hs_partial<R, P, G>), dim3(nb), dim3(256), 0, st, v, nC, cg, psi, byV, vt, part);
+    launch_hs_final<R>(st, nb, (const R*)part, out);
+}
 // src[c] (+)= power s_c / vt[0]: the first source stores, the later ones add
 template <class R, class P, class G>
 __global__ __launch_bounds__(256) void k_hs_apply(HsView<P> v, int nC, const CellGeomT<G>* __restrict__ cg, const R* __restrict__ vt, int first, R* __restrict__ src) {

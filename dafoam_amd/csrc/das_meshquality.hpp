@@ -24,6 +24,9 @@
 #include "das_geom.hpp"
 #include "das_jaccon.hpp"
 #include "das_kernels.hpp"
+#ifdef __HIPCC__
+#include "das_facefn.hpp"
+#endif
 
 namespace das {
 
@@ -171,6 +174,20 @@ __global__ __launch_bounds__(256) void k_rn_partial(long long n, const double* _
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+// ---- launch helpers (ks_blocks, launch_ks_sum_final: das_facefn.hpp).  part holds DAS_FACEFN_MAX_BLOCKS entries, ms two ----------------
+// term[i] = the term of row i, ms[1] = their fixed-order sum; part[0 .. ks_blocks(n)) = the per-workgroup sums
+static void launch_rn_sum(hipStream_t st, long long n, const RnRows& r, const double* R, double* term, double* part, double* ms) {
+    const int nb = ks_blocks(n);
+    hipLaunchKernelGGL(k_rn_terms, dim3(nblk(n, 256)), dim3(256), 0, st, n, r, R, term);
+    hipLaunchKernelGGL(k_rn_partial, dim3(nb), dim3(256), 0, st, n, (const double*)term, part);
+    launch_ks_sum_final(st, nb, part, ms);
+}
+static void launch_rn_seeds(hipStream_t st, long long n, const RnRows& r, const double* R, double F, double coef, double* g) {
+    hipLaunchKernelGGL(k_rn_seeds, dim3(nblk(n, 256)), dim3(256), 0, st, n, r, R, F, coef, g);
+}
+static void launch_mq_owner_gather(hipStream_t st, int nC, const int* cf_ptr, const int* cf_face, const double* ft, double* tc) {
+    hipLaunchKernelGGL(k_mq_owner_gather, dim3(nblk(nC, 256)), dim3(256), 0, st, nC, cf_ptr, cf_face, ft, tc);
 }
 
 #endif  // __HIPCC__

@@ -952,6 +952,49 @@ int das_debug_color_spec_round(long long n, const long long* rowptr, const int* 
                                unsigned* left, int* overflow);
 /* k_spec_conflict with check = 1 alone: *invalid = 1 if two columns of a net share a colour or a column of a net has none */
 int das_debug_color_check(long long n, const long long* rowptr, const int* col, long long nKeep, const long long* keep, const int* colors, int W, int* invalid);
+/* ---- TEST-ONLY entries (tests/test_gpu_reduce_kernels.py): the two-stage fixed-order reductions the objective functions end in, and
+ * the two gathers without atomics, on caller-made arrays.  No mesh, no solver handle; each entry runs THE LAUNCH HELPER THE SOLVER RUNS
+ * (csrc/das_facefn.hpp, das_cellfn.hpp, das_meshquality.hpp, das_heatsource.hpp, das_actuatordisk.hpp, das_reduce.hpp) on the null
+ * stream.  Every array that is not const - input or output - is uploaded whole and downloaded whole: the caller finds its inputs as
+ * the device left them and puts sentinels behind the written range of an output (its length is an argument).  *nb = the workgroups of
+ * the first stage: the first *nb entries of a partial array are written.  Everything is checked on the host before anything is
+ * launched; DAS_ERR_ARG for a null pointer (where null is not named as allowed), a size outside its range (n < 2^31), an index a
+ * kernel would read out of range with, and an array too short. */
+/* launch_ks_max, launch_ks_expsum, launch_ks_weights: ms = {m, S} (msLen >= 2), pmax / psum = the partials of the two stages (partLen >=
+ * 1024 each), w[t] = outer exp(k a_t - m) / S (wLen >= n); n >= 1 */
+int das_debug_reduce_ks(long long n, double* a, double k, double outer, double* ms, long long msLen, double* pmax, double* psum, long long partLen, double* w,
+                        long long wLen, int* nb);
+/* launch_group_sum: out2[g] = the sum of fv over group g (group null: all in group 0); cnt >= 0, outLen >= 2 */
+int das_debug_reduce_group_sum(long long cnt, unsigned char* group, double* fv, double* out2, long long outLen);
+/* launch_tangent_dot: out2[0] = sum_i psi_i R[2 i + 1] (R: n dual numbers {value, tangent}), all 1024 partials written; n >= 0, partLen
+ * >= 1024, outLen >= 2 */
+int das_debug_reduce_tangent_dot(long long n, double* R, double* psi, double* part, long long partLen, double* out2, long long outLen, int* nb);
+/* launch_ad_dot: the same product through k_ad_dot_partial + k_hs_final; n >= 1, partLen >= 1024, outLen >= 1 */
+int das_debug_reduce_ad_dot(long long n, double* R, double* psi, double* part, long long partLen, double* out, long long outLen, int* nb);
+/* launch_sv_dot: out2[0] = a . b; n >= 1, partLen >= 512, outLen >= 2 */
+int das_debug_reduce_sv_dot(long long n, double* a, double* b, double* part, long long partLen, double* out2, long long outLen, int* nb);
+/* launch_cellfn_value: out[0] = coef sum_t w_t g(src[idx_t] - data_t) (data null: 0; w_t = V[cell_t] with mv, g = x^2 with square);
+ * launch_cellfn_grad with the factor g and the scales sc (nSrc entries, or null) into grad, whose first nSrc entries the entry zeroes
+ * (gradLen >= nSrc).  idx entries are distinct; partLen >= 1024 */
+int das_debug_reduce_cellfn(long long nt, int* cell, long long* idx, double* data, int square, int mv, long long nCells, const double* V, long long nSrc, double* src,
+                            double coef, double* part, long long partLen, double* out, long long outLen, double* sc, double g, double* grad, long long gradLen, int* nb);
+/* launch_rn_sum, launch_rn_seeds on nblocks <= 8 residual blocks {off, kind (0 vector 3 nC, 1 scalar nC, 2 face nF), w}: term[i]
+ * (termLen >= n), ms[1] = their sum (msLen >= 2, ms[0] untouched), g[i] = coef dF/dR_i at the given F (gLen >= n; L2Norm: F != 0) */
+int das_debug_reduce_rn(long long n, int nblocks, const long long* off, const int* kind, const double* w, long long nC, long long nF, long long nIF, int l1, double* R,
+                        double* term, long long termLen, double* part, long long partLen, double* ms, long long msLen, double F, double coef, double* g, long long gLen,
+                        int* nb);
+/* launch_hs_sum<double> for kind 0 (cylinderToCell: member[nC]) and 2 (field[nC]) on cells of volume V[c]: psi null: sum s V; else
+ * sum (vt ? power s / vt[0] : s) psi (byV ? V : 1); partLen >= 1024 */
+int das_debug_reduce_hs_sum(int kind, int nC, const double* V, unsigned char* member, double* field, double* psi, int byV, double power, double* vt, double* part,
+                            long long partLen, double* out, long long outLen, int* nb);
+/* the second stages on caller-made partials, 1 <= nb <= 1024: pair = 0 launch_hs_final (nb entries -> out[0]), pair = 1 launch_ad_final
+ * (nb pairs -> out[0], out[1]); dual = 1: every entry is a dual number {value, tangent}, two doubles */
+int das_debug_reduce_final(int pair, int dual, int nb, double* part, long long partLen, double* out, long long outLen);
+/* launch_mq_owner_gather: tc[c] = the sum of ft over the faces cell c owns (cf_face >= 0) in the order of its list; ft holds nFt entries */
+int das_debug_reduce_owner_gather(int nC, int* cf_ptr, int* cf_face, long long nFt, double* ft, double* tc, long long tcLen);
+/* launch_vm_gather: out[j] = seed (tc[c] + sum of tc over the neighbours across internal faces), c = j / 3, for the states j < 3 nC
+ * with colors[j] == col; every other entry of out is left as it is (outLen >= 3 nC) */
+int das_debug_reduce_vm_gather(int nC, int nIF, int* cf_ptr, int* cf_face, int* cf_other, int* colors, int col, double* tc, double seed, double* out, long long outLen);
 /* ---- TEST-ONLY entries (tests/test_gpu_coarse_kernels.py): the coarse space of the two-level preconditioner (csrc/das_coarse.hpp) on
  * caller-made structures, kernel by kernel.  No mesh, no solver handle; the launch sequences THE SOLVER USES run on the null stream.
  * These kernels index with what they are given, so everything is checked on the host before anything is launched, and DAS_ERR_ARG is
